@@ -94,10 +94,34 @@ def test_bench_record_graph_form_on_one_gpu():
     import subprocess
     import sys
     r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--record-graphs", "--steps", "11", "--warmup", "3", "--batch", "32",
-                        "--no-cpu", "--no-extra"], capture_output=True, text=True, timeout=600)
+                        "--full", "--no-cpu", "--no-extra"], capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stdout + r.stderr
     j = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
     assert j["checked"] and j["value"] > 0 and j["config"]["steps_per_graph"] == 4 and j["steps"] == 11
+
+
+@pytest.mark.parametrize("streams", ["1", "2"])
+def test_bench_plain_run_times_steps_and_dumps_the_last_outputs(tmp_path, streams):
+    """A plain bench run (no --full) times exactly --steps steps in one region and, with --dump-outputs, writes the outputs of the
+    last timed step: every shard's seeded inputs through the numpy oracle give the same maps and boxes."""
+    import json
+    import subprocess
+    import sys
+    from oracle import vt_oracle_np as onp
+    from vittracker_amd import synth
+    B, d = 8, tmp_path / "out"
+    r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", "7", "--warmup", "2", "--batch", str(B),
+                        "--streams", streams, "--dump-outputs", str(d)], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
+    j = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+    assert j["steps"] == 7 and j["regions"]["n"] == 1 and j["ms_per_step"] > 0 and j["value"] > 0 and not j["checked"]
+    sd = synth.synth_state_dict(0, len_z=16, len_x=64)
+    refs = [onp.forward(sd, *synth.synth_inputs(1000 * k, B, 64, 128)) for k in range(int(streams))]
+    for k, tol in (("score_map", 1e-4), ("size_map", 1e-4), ("offset_map", 1e-4), ("pred_boxes", 1e-5), ("hann_boxes", 1e-5), ("conf", 1e-4)):
+        got = np.load(d / (k + ".npy"))
+        want = np.concatenate([ref[k].reshape((B,) + got.shape[1:]) for ref in refs])
+        assert got.dtype == np.float32 and got.shape[0] == B * int(streams), (k, got.dtype, got.shape)
+        assert float(np.abs(got - want).max()) < tol, k
 
 
 @pytest.mark.parametrize("streams", ["1", "2"])
@@ -110,7 +134,7 @@ def test_bench_force_gather_runs_the_rccl_leg_on_one_gpu(streams):
     import subprocess
     import sys
     r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--force-gather", "--streams", streams, "--steps", "43",
-                        "--warmup", "9", "--no-cpu", "--no-extra"], capture_output=True, text=True, timeout=900)
+                        "--warmup", "9", "--full", "--no-cpu", "--no-extra"], capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     j = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
     assert j["checked"] and j["value"] > 0 and j["n_gpus"] == 1 and j["steps"] == 43
@@ -125,7 +149,7 @@ def test_force_gather_form_is_as_fast_as_the_plain_form():
     import sys
 
     def run(extra):
-        r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--steps", "400", "--warmup", "50", "--no-cpu", "--no-extra"] + extra,
+        r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--steps", "400", "--warmup", "50", "--full", "--no-cpu", "--no-extra"] + extra,
                            capture_output=True, text=True, timeout=900)
         assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
         return json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])["value"]
@@ -144,7 +168,7 @@ def test_record_graph_form_is_as_fast_as_the_plain_form():
     import sys
 
     def run(extra):
-        r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--steps", "400", "--warmup", "50", "--no-cpu", "--no-extra"] + extra,
+        r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--steps", "400", "--warmup", "50", "--full", "--no-cpu", "--no-extra"] + extra,
                            capture_output=True, text=True, timeout=600)
         assert r.returncode == 0, r.stdout + r.stderr
         return json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])["value"]

@@ -244,6 +244,32 @@ def test_bench_refuses_diagnostic_switches():
     assert r.returncode != 0 and "refuses to run" in (r.stdout + r.stderr)
 
 
+def test_bench_dump_outputs_writes_every_field_and_samples_above_the_limit(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: every output field as float32 .npy, the shards concatenated along the batch; above the size limit
+    the same seeded frames of every field, the same in every run, with their indices beside them."""
+    import types
+    import torch
+    import bench
+    B, F = 40, 8
+    g = torch.Generator().manual_seed(0)
+    shapes = {"score_map": (B, 1, F, F), "size_map": (B, 2, F, F), "offset_map": (B, 2, F, F), "pred_boxes": (B, 4), "hann_boxes": (B, 4)}
+    o = types.SimpleNamespace(conf=torch.arange(B, dtype=torch.float32), **{k: torch.rand(s, generator=g) for k, s in shapes.items()})
+    bench.dump_outputs(str(tmp_path / "all"), [o, o])
+    for k in bench.DUMP_FIELDS:
+        got = np.load(tmp_path / "all" / (k + ".npy"))
+        assert got.dtype == np.float32 and np.array_equal(got, np.concatenate([getattr(o, k).numpy()] * 2)), k
+    assert not (tmp_path / "all" / "sample_frames.npy").exists()
+    per_frame = 4 * (5 * F * F + 9)
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 10 * per_frame)
+    for run in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / run), [o, o])
+    idx = np.load(tmp_path / "a" / "sample_frames.npy")
+    assert np.array_equal(idx, np.load(tmp_path / "b" / "sample_frames.npy")) and 0 < len(idx) < 10 and len(set(idx)) == len(idx)
+    assert sum(os.path.getsize(p) for p in (tmp_path / "a").iterdir()) < 10 * per_frame + 1024 * 7        # + the .npy headers
+    np.testing.assert_array_equal(np.load(tmp_path / "a" / "conf.npy"), np.concatenate([np.arange(B)] * 2)[idx.astype(int)])
+    np.testing.assert_array_equal(np.load(tmp_path / "a" / "score_map.npy"), np.load(tmp_path / "b" / "score_map.npy"))
+
+
 def test_build_ostrack_config_surface():
     from vittracker_amd import config
     from vittracker_amd.model_vitb import build_ostrack

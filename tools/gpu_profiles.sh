@@ -75,4 +75,4 @@ print(json.dumps(res,indent=1)[:3000])
 P
 find $O -name "*counter_collection.csv" -size +2000k -delete
 cd $R
-timeout 1200 python bench.py > $O/r${N}_bench.json 2> $O/r${N}_bench.err; tail -c 600 $O/r${N}_bench.json
+timeout 1200 python bench.py --full > $O/r${N}_bench.json 2> $O/r${N}_bench.err; tail -c 600 $O/r${N}_bench.json

@@ -10,8 +10,8 @@
 #   tests           the whole -m gpu suite
 #   quick48         parity subset + per-stage times of the vit_48 path (G128, G256)
 #   ab48 [names]    tools/ab_stages.py against build_variants/*.so
-#   bench           python bench.py (the driver's line) -> bench.json
-#   bench_noextra   python bench.py --no-extra
+#   bench           python bench.py --full (the full line) -> bench.json
+#   bench_noextra   python bench.py --full --no-extra
 #   race            tools/race_check.py at G128 and G256
 #   trackstep       tracking/track_batch_demo.py --batch 256 at both geometries
 #   generic         tests/test_gpu_generic.py
@@ -76,9 +76,9 @@ P
     ab48)
       timeout 1500 python tools/ab_stages.py > $O/ab.txt 2>&1; cat $O/ab.txt ;;
     bench)
-      timeout 1500 python bench.py > $O/bench.json 2> $O/bench.err; tail -c 1500 $O/bench.err; head -c 2500 $O/bench.json ;;
+      timeout 1500 python bench.py --full > $O/bench.json 2> $O/bench.err; tail -c 1500 $O/bench.err; head -c 2500 $O/bench.json ;;
     bench_noextra)
-      timeout 600 python bench.py --no-extra > $O/bench.json 2> $O/bench.err; head -c 2500 $O/bench.json ;;
+      timeout 600 python bench.py --full --no-extra > $O/bench.json 2> $O/bench.err; head -c 2500 $O/bench.json ;;
     race)
       timeout 600 python tools/race_check.py > $O/g128.txt 2>&1; tail -3 $O/g128.txt
       timeout 600 python tools/race_check.py --geom G256 --B 256 > $O/g256.txt 2>&1; tail -3 $O/g256.txt ;;
