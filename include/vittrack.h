@@ -104,7 +104,9 @@ void vt_destroy(vt_model* m);
 int vt_load_weights(vt_model* m, const vt_tensor* tensors, int32_t n);
 
 /* Overrides the motion window (default: hann2d(F), lib/test/utils/hann.py:6-16, computed at
- * vt_create).  host_window: F*F floats. */
+ * vt_create with libm cosf, which may differ from the reference's torch float32 window by a few
+ * ulps, e.g. at F = 14, 16 and 24; vittracker_amd.native.Model uploads the torch window at
+ * construction).  host_window: F*F floats. */
 int vt_set_window(vt_model* m, const float* host_window);
 
 /* OstrackDist.forward(z, x) + CenterPredictor.forward + the tracker's windowed cal_bbox

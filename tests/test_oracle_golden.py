@@ -3,7 +3,8 @@
 The fixtures were produced by running the reference model code itself
 (tests/golden/make_golden.py); these tests are what makes the oracle trustworthy before it is
 used to judge the HIP kernels.  Tolerances: the oracle and the reference both compute in fp32
-but in different summation orders, so maps agree to ~1e-5 absolute; bboxes must be identical up
+but in different summation orders; each sits about 2e-6 from the fp64 truth on activations and
+3e-7 to 2e-6 on the maps, and TOL = 2e-5 holds the pair with headroom.  bboxes must be identical up
 to that noise because every fixture's argmax margin is >= 1e-3.
 """
 import numpy as np
@@ -40,12 +41,12 @@ def test_numpy_oracle_matches_reference(path):
 
 @pytest.mark.parametrize("path", golden_files(), ids=lambda p: p.split("/")[-1][:-4])
 def test_fp64_truth_brackets_reference(path):
-    """The float64 run of the oracle is the yardstick: the reference's fp32 output sits within
-    ~1e-5 of it, which is the noise floor any fp32 implementation (ours included) shares."""
+    """The float64 run of the oracle is the yardstick: the reference's fp32 maps sit 3e-7 to 2.1e-6 from it (measured over
+    the fixtures), the noise floor any fp32 implementation shares; tests/fp32_budget.py holds the kernels to a multiple of it."""
     g, sd, z, x = load_case(path)
     out = onp.forward(sd, z, x, dtype=np.float64)
     for k in ("score_map", "size_map", "offset_map"):
-        assert np.abs(out[k] - g[k]).max() < TOL, k
+        assert np.abs(out[k] - g[k]).max() < 5e-6, k
 
 
 @pytest.mark.parametrize("path", golden_files()[:3], ids=lambda p: p.split("/")[-1][:-4])

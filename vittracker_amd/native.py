@@ -215,6 +215,9 @@ class Model:
         self.max_batch = max_batch
         self.template_size, self.search_size = template_size, search_size
         self._graphs = weakref.WeakSet()
+        # the reference's torch float32 window, bit for bit (vt_create's libm one differs by ulps at F = 14, 16, 24)
+        from .host_ops import hann2d
+        self.set_window(hann2d((self.feat_sz, self.feat_sz)).numpy())
 
     def live_graphs(self) -> int:
         return sum(1 for g in self._graphs if g._valid)
