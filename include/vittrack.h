@@ -208,6 +208,44 @@ int vt_track_step(vt_model* m, const uint8_t* frames, int32_t H, int32_t W, doub
  * vit_dist.py:107-111 overwrites self.state), which stays the default; vt_update_state[_record] are not affected. */
 int vt_set_open_loop(vt_model* m, int32_t on);
 
+/* --- batches of frames of different sizes: one descriptor per sequence -------------------------------------------------------
+ * The reference runs one tracker per sequence and worker process (lib/test/evaluation/running.py:105-112), so every sequence brings
+ * its own frame size.  The dense entry points above take ONE (B,H,W,3) buffer with ONE H, W; the *_frames twins below take a (B,)
+ * table of descriptors instead, in device memory or device-mapped pinned host memory.  The kernels read the table when they run: a
+ * graph captured on it stays valid when the caller rewrites its contents (pointers, sizes) between replays.
+ *   data:  HWC uint8, device memory or device-mapped pinned host memory, 4-byte aligned
+ *   pitch: bytes between rows, >= 3*W (0 = 3*W); the frame is [data, data + pitch*(H-1) + 3*W), nothing outside it is read
+ * A descriptor with a null `data`, H or W < 1, a misaligned `data` or pitch < 3*W is treated as a too-small box (processing_utils.py:
+ * 33-34 raises): NaN resize factor, zero (uint8) or NaN (fp32) patch, nothing read through it; the other sequences are unaffected. */
+typedef struct vt_frame {
+    const uint8_t* data;
+    int32_t H, W;
+    int64_t pitch;
+} vt_frame;
+
+/* vt_crop with a frame table: sample_target(image_b, state_b, factor, output_sz) + Preprocessor.process per sequence
+ * (lib/train/data/processing_utils.py:12-79; lib/test/tracker/data_utils.py:11-17), each sequence b on frames_dev[b] with its own
+ * H, W and pitch.  Results equal vt_crop of that frame alone (B = 1), bit for bit. */
+int vt_crop_frames(vt_model* m, const vt_frame* frames_dev, const double* states_dev, double factor, int32_t out_size,
+                   const float* mean3, const float* std3, int32_t B, void* stream, float* crops_dev, double* resize_factor_dev);
+/* vt_crop_u8 with a frame table (sample_target alone, processing_utils.py:12-79): as vt_crop_frames, the uint8 (B,T,T,3) patch. */
+int vt_crop_u8_frames(vt_model* m, const vt_frame* frames_dev, const double* states_dev, double factor, int32_t out_size, int32_t B,
+                      void* stream, uint8_t* patch_dev, double* resize_factor_dev);
+/* vt_track_step with a frame table (lib/test/tracker/vit_dist.py:87-148 per sequence, one tracker per sequence as
+ * lib/test/evaluation/running.py:105-112 runs them): the crop of vt_crop[_u8]_frames, the network on the cached template, and the
+ * tail with clip_box (lib/utils/box_ops.py:97-106) against frames_dev[b].H / W of each sequence.  Same routes (uint8 patch / fp32
+ * crop), open loop and models as vt_track_step; a batch of equal frames gives vt_track_step's records bit for bit. */
+int vt_track_step_frames(vt_model* m, const vt_frame* frames_dev, double* states_dev, double factor, const float* mean3,
+                         const float* std3, int32_t B, void* stream, float* crops_dev, double* resize_factor_dev, const vt_outputs* out,
+                         int32_t margin, double* record);
+/* Restart single sequences (Vit_dist.initialize, lib/test/tracker/vit_dist.py:52-65, for slots whose sequence ended while the
+ * others go on): rewrite the template cache rows of slots[0..n) from z_dev (n,3,Tz,Tz), under the form batch the cache was written
+ * with -- afterwards a slot's rows are exactly what vt_set_template would have written for that template at that slot, bit for bit.
+ * Rows of every other slot are untouched; captured graphs stay valid (they read the cache by address).  slots: HOST array, each in
+ * [0, cached frames) and none twice (else VT_ERR_ARG).  VT_ERR_STATE without a cache, or when the form batch changed since it was
+ * written.  Not capturable (it stages through model scratch and copies the rows into place). */
+int vt_set_template_slots(vt_model* m, const float* z_dev, const int32_t* slots, int32_t n, void* stream);
+
 /* --- hipGraph: the whole track() device step captured once, replayed per frame -------------- */
 int vt_graph_capture(vt_model* m, const float* z_dev, const float* x_dev, int32_t B,
                      const vt_outputs* out, vt_graph** g);

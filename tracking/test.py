@@ -3,9 +3,11 @@
 
     python tracking/test.py vit_dist vit_48_h32_noKD --dataset_name synthetic:16x50 --threads 0 --num_gpus 1
     python tracking/test.py vit_dist vit_48_h32_noKD --dataset_name synthetic:512x100 --batch 256      # lock-step batches
+    python tracking/test.py vit_dist vit_48_h32_noKD --dataset_name folder:/videos --batch 64 --continuous   # any frame sizes
 
 Same positional arguments and options as the reference, plus ``--batch B`` (> 0 selects the MI355X-native lock-step
-batched runner) and ``--synthetic_weights`` (no trained checkpoint exists in the reference tree).  Result files:
+batched runner; with ``--continuous`` the continuous-batching runner, which keeps B slots busy across frame sizes and
+lengths) and ``--synthetic_weights`` (no trained checkpoint exists in the reference tree).  Result files:
 ``<save_dir>/test/tracking_results/<tracker>/<param>[_<runid>]/<seq>.txt`` and ``<seq>_time.txt``."""
 import argparse
 import os
@@ -16,9 +18,9 @@ sys.path.insert(0, ROOT)
 
 
 def run_tracker(tracker_name, tracker_param, run_id=None, dataset_name="synthetic", sequence=None, debug=0, threads=0,
-                num_gpus=8, batch=0, synthetic_weights=False, frames_per_launch=1, shards=1):
+                num_gpus=8, batch=0, synthetic_weights=False, frames_per_launch=1, shards=1, continuous=False):
     from vittracker_amd.evaluation import Tracker, get_dataset
-    from vittracker_amd.evaluation.running import run_dataset, run_dataset_batched
+    from vittracker_amd.evaluation.running import run_dataset, run_dataset_batched, run_dataset_continuous
     dataset = get_dataset(dataset_name)
     if sequence is not None:
         dataset = type(dataset)([dataset[sequence]])
@@ -36,7 +38,15 @@ def run_tracker(tracker_name, tracker_param, run_id=None, dataset_name="syntheti
         if world > 1:
             import torch
             torch.cuda.set_device(int(os.environ.get("LOCAL_RANK", "0")))
-        run_dataset_batched(dataset, tracker, batch=batch, rank=rank, world=world, frames_per_launch=frames_per_launch, shards=shards)
+        if continuous:
+            if shards > 1 or frames_per_launch > 1 or world > 1:
+                raise SystemExit("--continuous runs one BatchedVitTracker on one GPU: --shards, --frames_per_launch and multi-GPU runs "
+                                 "are not supported with it")
+            run_dataset_continuous(dataset, tracker, batch=batch)
+        else:
+            run_dataset_batched(dataset, tracker, batch=batch, rank=rank, world=world, frames_per_launch=frames_per_launch, shards=shards)
+    elif continuous:
+        raise SystemExit("--continuous needs --batch B")
     else:
         run_dataset(dataset, [tracker], debug, threads, num_gpus=num_gpus)
 
@@ -46,7 +56,7 @@ def main():
     p.add_argument("tracker_name", type=str, help="Name of tracking method.")
     p.add_argument("tracker_param", type=str, help="Name of config file.")
     p.add_argument("--runid", type=int, default=None, help="The run id.")
-    p.add_argument("--dataset_name", type=str, default="synthetic", help="synthetic[:NxT] or folder:<path>")
+    p.add_argument("--dataset_name", type=str, default="synthetic", help="synthetic[:NxT], synthetic_mixed[:NxT] or folder:<path>")
     p.add_argument("--sequence", type=str, default=None, help="Sequence number or name.")
     p.add_argument("--debug", type=int, default=0, help="Debug level.")
     p.add_argument("--threads", type=int, default=0, help="Number of worker processes (0 = sequential).")
@@ -56,6 +66,8 @@ def main():
                    help="with --batch: step a group's sequences as this many independent sub-groups on their own HIP streams (ShardedBatchedTracker)")
     p.add_argument("--frames_per_launch", type=int, default=1,
                    help="with --batch: frames read ahead and tracked per graph launch (BatchedVitTracker.track_chunk)")
+    p.add_argument("--continuous", action="store_true",
+                   help="with --batch: continuous batching -- B slots across every frame size; a finished sequence's slot takes the next one")
     p.add_argument("--synthetic_weights", action="store_true", help="run on the seeded synthetic weights")
     a = p.parse_args()
     try:
@@ -63,7 +75,7 @@ def main():
     except (TypeError, ValueError):
         seq = a.sequence
     run_tracker(a.tracker_name, a.tracker_param, a.runid, a.dataset_name, seq, a.debug, a.threads, a.num_gpus, a.batch,
-                a.synthetic_weights, a.frames_per_launch, a.shards)
+                a.synthetic_weights, a.frames_per_launch, a.shards, a.continuous)
 
 
 if __name__ == "__main__":

@@ -18,7 +18,7 @@ import numpy as np
 from .config import geometry
 from .host_ops import hann2d
 from .model import build_ostrack_dist
-from .native import VtError
+from .native import FrameTable, VtError, pack_offsets
 
 
 def check_params_geometry(params, nat):
@@ -75,6 +75,124 @@ class BatchedVitTracker:
         self._slot = 0
         self.hw = None
         self.frame_id = 0
+        # frames of different sizes (vt_track_step_frames): a pinned host arena and its device twin, [descriptor table | frames]
+        self._arena = None           # (capacity, pinned host uint8 tensor, device uint8 tensor, event of the last arena copy)
+        self._dev_table = None       # FrameTable of caller-owned device frames
+        self._frames_graphs = {}     # device table address -> (graph, device record, pinned host record, table)
+
+    # ---- frames of different sizes ------------------------------------------------------------------------------------
+    @staticmethod
+    def _is_mixed(frames):
+        """A list / tuple of frames whose sizes differ: the frame-table path.  Same-size input keeps the dense path untouched."""
+        if isinstance(frames, np.ndarray) or not isinstance(frames, (list, tuple)) or len(frames) < 2:
+            return False
+        s0 = tuple(frames[0].shape)
+        return any(tuple(f.shape) != s0 for f in frames[1:])
+
+    def _frame_table(self, frames):
+        """The device vt_frame table of B frames of any sizes.  Caller-owned CUDA tensors go in by pointer (only the table is copied);
+        host frames are packed into a pinned arena at 256-byte offsets behind the table and reach the device arena with ONE copy.  The
+        arena grows by doubling; each capacity has its own table address, hence its own captured step."""
+        import torch
+        if len(frames) != self.B:
+            raise ValueError(f"expected {self.B} frames, got {len(frames)}")
+        if all(isinstance(f, torch.Tensor) and f.is_cuda for f in frames):
+            if self._dev_table is None:
+                self._dev_table = FrameTable(self.B, "cuda")
+            for i, f in enumerate(frames):
+                self._dev_table.set_tensor(i, f)
+            return self._dev_table.upload()
+        arrs = []
+        for f in frames:
+            a = f.cpu().numpy() if isinstance(f, torch.Tensor) else np.asarray(f)
+            if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != 3:
+                raise ValueError("every frame must be an (H, W, 3) uint8 array")
+            arrs.append(a)
+        tb = self.B * FrameTable.ITEM
+        offs, end = pack_offsets([a.shape[:2] for a in arrs], start=tb)
+        if self._arena is None or self._arena[0] < end:
+            cap = max(end, 2 * self._arena[0] if self._arena is not None else end)
+            torch.cuda.current_stream().synchronize()       # nothing may still read the old arena
+            if self._arena is not None:
+                self._frames_graphs.pop(self._arena[2].data_ptr(), None)
+            self._arena = (cap, torch.empty(cap, dtype=torch.uint8).pin_memory(), torch.empty(cap, dtype=torch.uint8, device="cuda"), None)
+            self._arena_np = self._arena[1].numpy()
+        cap, host, dev, ev = self._arena
+        if ev is not None:
+            ev.synchronize()                                  # the previous copy out of the pinned arena has been read
+        tab = self._arena_np[:tb].view(FrameTable.DTYPE)
+        base = dev.data_ptr()
+        for i, (a, o) in enumerate(zip(arrs, offs)):
+            H, W = a.shape[:2]
+            pitch = FrameTable.check(base + o, H, W, 0, nbytes=cap - o)
+            tab[i] = (base + o, H, W, pitch)
+            self._arena_np[o:o + H * W * 3].reshape(H, W, 3)[...] = a
+        dev[:end].copy_(host[:end], non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record()
+        self._arena = (cap, host, dev, ev)
+        return dev[:tb]
+
+    def _frames_graph(self, tab):
+        """The whole step on a frame table (vt_track_step_frames -> record), captured once per table address: the table's contents
+        change between replays, its address does not."""
+        import torch
+        hit = self._frames_graphs.get(tab.data_ptr())
+        if hit is not None:
+            return hit
+        rec = torch.empty(self.B, 5, dtype=torch.float64, device="cuda")
+        host = torch.empty(self.B, 5, dtype=torch.float64).pin_memory()
+        g = torch.cuda.CUDAGraph()
+        side = torch.cuda.Stream()
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.graph(g, stream=side):
+            self.nat.track_step_frames(tab, self.states, self.params.search_factor, self.mean, self.std, self.x, self.rf, self.out,
+                                       record=rec, margin=10, stream=torch.cuda.current_stream())
+        torch.cuda.current_stream().wait_stream(side)
+        self._frames_graphs[tab.data_ptr()] = (g, rec, host, tab)
+        return self._frames_graphs[tab.data_ptr()]
+
+    def _track_mixed(self, frames, sync):
+        if self.graph is None:
+            raise VtError("track before initialize")
+        g, rec, host, _ = self._frames_graph(self._frame_table(frames))
+        g.replay()
+        self.frame_id += 1
+        if sync:
+            r = self._records(rec, host)
+            return {"target_bbox": r[:, :4], "confidence": r[:, 4].float()}
+        return {"target_bbox": self.states, "confidence": self.out.conf, "record": rec}
+
+    def reinitialize(self, slots, frames, boxes):
+        """Restart the sequences of `slots` on new frames and boxes (Vit_dist.initialize, lib/test/tracker/vit_dist.py:52-65) while
+        the other slots go on: their templates are cropped from their own frames (any sizes; host arrays or CUDA tensors), their states
+        set, and the template cache rewritten for those slots only (vt_set_template_slots).  No other slot's state or cache changes
+        and no graph is recaptured."""
+        import torch
+        slots = [int(v) for v in slots]
+        n = len(slots)
+        if n == 0:
+            return
+        if self.graph is None:
+            raise VtError("reinitialize before initialize")
+        if len(set(slots)) != n or min(slots) < 0 or max(slots) >= self.B:
+            raise ValueError(f"slots must be distinct indices in [0, {self.B})")
+        if len(frames) != n:
+            raise ValueError(f"expected {n} frames for {n} slots, got {len(frames)}")
+        boxes = np.asarray(boxes, dtype=np.float64).reshape(n, 4)
+        for f in (self.params.template_factor, self.params.search_factor):
+            if not np.all(np.ceil(np.sqrt(boxes[:, 2] * boxes[:, 3]) * f) >= 1):
+                raise Exception("Too small bounding box.")   # processing_utils.py:33-34
+        dev = [f if isinstance(f, torch.Tensor) and f.is_cuda else torch.from_numpy(np.ascontiguousarray(f)).cuda() for f in frames]
+        tab = FrameTable.of(dev)
+        st = torch.as_tensor(boxes).cuda()
+        z = torch.empty(n, 3, self.params.template_size, self.params.template_size, device="cuda")
+        rf = torch.empty(n, dtype=torch.float64, device="cuda")
+        self.nat.crop_frames(tab, st, self.params.template_factor, self.params.template_size, self.mean, self.std, out=z, resize_factor=rf)
+        idx = torch.as_tensor(slots, device="cuda")
+        self.states.index_copy_(0, idx, st)
+        self.z.index_copy_(0, idx, z)
+        self.nat.set_template_slots(z, slots)
 
     def _upload(self, frames):
         """Host frames are copied straight from the caller's array into one of two device frame buffers with ONE blocking copy
@@ -133,9 +251,11 @@ class BatchedVitTracker:
         self._slot_done[k].record()
 
     def initialize(self, frames, init_boxes):
-        """frames: (B,H,W,3) uint8 (numpy, list of arrays or CUDA tensor); init_boxes: (B,4) [x,y,w,h]."""
+        """frames: (B,H,W,3) uint8 (numpy, list of arrays or CUDA tensor) -- or a list of B frames of different sizes;
+        init_boxes: (B,4) [x,y,w,h]."""
         import torch
-        fr = self._upload(frames)
+        mixed = self._is_mixed(frames)
+        fr = self._frame_table(frames) if mixed else self._upload(frames)
         boxes = np.asarray(init_boxes, dtype=np.float64)
         if boxes.shape != (self.B, 4):
             raise ValueError(f"init_boxes must be (B={self.B}, 4) [x, y, w, h]")
@@ -144,9 +264,13 @@ class BatchedVitTracker:
             if not np.all(side >= 1):         # also catches NaN / negative sizes
                 raise Exception("Too small bounding box.")   # processing_utils.py:33-34
         self.states.copy_(torch.as_tensor(boxes))
-        self.nat.crop(fr, self.states, self.params.template_factor, self.params.template_size, self.mean, self.std,
-                      out=self.z, resize_factor=self.rf)
-        self._mark_slot()
+        if mixed:
+            self.nat.crop_frames(fr, self.states, self.params.template_factor, self.params.template_size, self.mean, self.std,
+                                 out=self.z, resize_factor=self.rf)
+        else:
+            self.nat.crop(fr, self.states, self.params.template_factor, self.params.template_size, self.mean, self.std,
+                          out=self.z, resize_factor=self.rf)
+            self._mark_slot()
         # The template never changes after this (lib/test/tracker/vit_dist.py:57-60): its patch embedding and block 0's
         # LayerNorm-1 + qkv rows are computed once here (vt_set_template, bit-identical to recomputing them every frame);
         # graphs captured with z = None read that cache, so they stay valid across re-initialisation.
@@ -163,6 +287,7 @@ class BatchedVitTracker:
         self._held = bool(on) or None
         self.nat.set_open_loop(bool(on))
         self._chunk_graphs.clear()      # the flag is an argument of the captured kernels
+        self._frames_graphs.clear()
         self._fast = [None, None]
 
     def track_record(self, frames):
@@ -196,6 +321,8 @@ class BatchedVitTracker:
         as CPU tensors when sync=True, else the device tensors (valid until the next call)."""
         if self.graph is None:
             raise VtError("track before initialize")
+        if self._is_mixed(frames):      # B frames of different sizes: one step on a frame table
+            return self._track_mixed(frames, sync)
         fr = self._upload(frames)
         H, W = self.hw
         self.frame_id += 1
@@ -262,6 +389,15 @@ class BatchedVitTracker:
         import torch
         if self.graph is None:
             raise VtError("track_chunk before initialize")
+        if isinstance(frames, (list, tuple)) and any(self._is_mixed(f) for f in frames):
+            # n steps of B frames of different sizes: n replays of the frame-table step, records gathered on the device, one sync
+            recs = torch.empty(len(frames), self.B, 5, dtype=torch.float64, device="cuda")
+            for j, f in enumerate(frames):
+                recs[j].copy_(self._track_mixed(f, sync=False)["record"])
+            if sync:
+                r = self._records(recs, torch.empty(recs.shape, dtype=torch.float64).pin_memory())
+                return {"target_bbox": r[:, :, :4], "confidence": r[:, :, 4].float()}
+            return {"target_bbox": recs[:, :, :4], "confidence": recs[:, :, 4]}
         if isinstance(frames, torch.Tensor) and frames.is_cuda:
             buf = frames
             if buf.dtype != torch.uint8 or buf.dim() != 5 or buf.shape[1] != self.B or buf.shape[4] != 3 or not buf.is_contiguous():
@@ -349,6 +485,10 @@ class ShardedBatchedTracker:
         self._each(lambda t, sl: t.initialize(frames[sl], boxes[sl]))
         self._join()
         self.frame_id = 0
+
+    def reinitialize(self, slots, frames, boxes):
+        raise VtError("continuous batching (reinitialize, frames of different sizes) is implemented for BatchedVitTracker only, "
+                      "not for ShardedBatchedTracker")
 
     def track(self, frames, sync: bool = True):
         """One frame for every sequence: frames (B,H,W,3) uint8, host or device.  sync=True: {'target_bbox': (B,4) float64,

@@ -108,6 +108,7 @@ struct vt_model {
     int blocks_tile = -1;            // 1 / 0 force the tile-parallel form of the blocks / forbid it, -1 (default): by batch size
     int open_loop = 0;               // vt_set_open_loop: vt_track_step leaves states_dev untouched (the step's box is in `record`)
     DevBuf zcache;                   // block-0 q / k / v^T images of the template tiles (vt_set_template)
+    DevBuf zstage;                   // vt_set_template_slots: the new slots' cache rows, staged before they are copied into place (allocated on first use)
     DevBuf vlscr;                    // G256 frame-form block kernel (A3): the low pieces of V^T, [B][depth][3][L / 32][64] x 16 B (vt_blocks.h VP2L)
     int tmpl_frames = 0;             // frames whose template rows (tokens + zcache) are cached
     int tmpl_form_batch = 0;         // the form batch vt_set_template ran under (the cache holds THAT form's operands)
@@ -924,9 +925,24 @@ constexpr int CROP_MAX_DEVICES = 64;
 int g_crop_bytes[CROP_MAX_DEVICES];        // 0: not tested yet, 1: fast form, 2: byte-load form
 std::mutex g_crop_mutex;
 
+// The kernel of each crop form: the dense one, or its frame-table twin (vt_track.h: the same body on TableFrames)
+template <bool TB, bool BYTES, bool U8> constexpr auto crop_k() {
+    if constexpr (TB) return &vtt::crop_frames_kernel<BYTES, U8>; else return &vtt::crop_kernel<BYTES, U8>;
+}
+template <bool TB, int G, bool U8> constexpr auto crop_fast_k() {
+    if constexpr (TB) return &vtt::crop_fast_frames_kernel<G, U8>; else return &vtt::crop_fast_kernel<G, U8>;
+}
+template <bool TB, bool U8, int LG, int IPT, bool AL> constexpr auto crop_band_k() {
+    if constexpr (TB) return &vtt::crop_band_kernel<U8, LG, IPT, AL, vtt::TableFrames>; else return &vtt::crop_band_kernel<U8, LG, IPT, AL>;
+}
+
 // u8out: `crops` is a uint8 (B, T, T, 3) patch buffer (sample_target's output; mean3 / std3 unused) instead of the fp32 (B, 3, T, T) crop
-void launch_crop(bool bytes, const unsigned char* frames, int H, int W, const double* states, double factor, int T, const float* mean3,
-                 const float* std3, int B, hipStream_t st, float* crops, double* rf, bool u8out = false) {
+// TB (a std::bool_constant): `frames` is a (B,) vt_frame table (vt_crop_frames; H / W unused) and every form below runs its frame-table
+// twin, chosen by the same rules as the dense form
+template <class TBc>
+void launch_crop_forms(TBc, bool bytes, const unsigned char* frames, int H, int W, const double* states, double factor, int T,
+                       const float* mean3, const float* std3, int B, hipStream_t st, float* crops, double* rf, bool u8out) {
+    constexpr bool TB = TBc::value;
     static const int fast = [] { const char* v = std::getenv("VT_CROP_FAST"); return v && *v ? std::atoi(v) : 1; }();     // groups per workgroup (1, 2, 4); 0: crop_kernel
     static const float none3[3] = {0.f, 1.f, 1.f};
     if (u8out) mean3 = std3 = none3;
@@ -953,8 +969,8 @@ void launch_crop(bool bytes, const unsigned char* frames, int H, int W, const do
         auto pick = [&](auto u8c, auto lgc) {
             constexpr bool U = decltype(u8c)::value;
             constexpr int LG = decltype(lgc)::value;
-            if (aligned) ipt == 4 ? go(&vtt::crop_band_kernel<U, LG, 4, true>, 4) : go(&vtt::crop_band_kernel<U, LG, 2, true>, 2);
-            else ipt == 4 ? go(&vtt::crop_band_kernel<U, LG, 4, false>, 4) : go(&vtt::crop_band_kernel<U, LG, 2, false>, 2);
+            if (aligned) ipt == 4 ? go(crop_band_k<TB, U, LG, 4, true>(), 4) : go(crop_band_k<TB, U, LG, 2, true>(), 2);
+            else ipt == 4 ? go(crop_band_k<TB, U, LG, 4, false>(), 4) : go(crop_band_k<TB, U, LG, 2, false>(), 2);
         };
         auto by_size = [&](auto u8c) {
             if (T == 64) pick(u8c, std::integral_constant<int, 4>{});
@@ -968,13 +984,13 @@ void launch_crop(bool bytes, const unsigned char* frames, int H, int W, const do
     if (!bytes && fast > 0 && (T & 3) == 0 && T <= vtt::CROP_FAST_MAX_T) {
         const int ngroups = (T * (T / 4) + 255) / 256;
         if (u8out) {
-            hipLaunchKernelGGL((vtt::crop_fast_kernel<1, true>), dim3(ngroups, B), dim3(256), 0, st, frames, H, W, states, factor, T, 0.f, 0.f, 0.f, 1.f,
+            hipLaunchKernelGGL((crop_fast_k<TB, 1, true>()), dim3(ngroups, B), dim3(256), 0, st, frames, H, W, states, factor, T, 0.f, 0.f, 0.f, 1.f,
                                1.f, 1.f, crops, rf);
             return;
         }
         auto go = [&](auto g) {
             constexpr int G = decltype(g)::value;
-            hipLaunchKernelGGL((vtt::crop_fast_kernel<G, false>), dim3((ngroups + G - 1) / G, B), dim3(256), 0, st, frames, H, W, states, factor, T, mean3[0],
+            hipLaunchKernelGGL((crop_fast_k<TB, G, false>()), dim3((ngroups + G - 1) / G, B), dim3(256), 0, st, frames, H, W, states, factor, T, mean3[0],
                                mean3[1], mean3[2], std3[0], std3[1], std3[2], crops, rf);
         };
         if (fast >= 4 && ngroups >= 4) go(std::integral_constant<int, 4>{});
@@ -985,17 +1001,23 @@ void launch_crop(bool bytes, const unsigned char* frames, int H, int W, const do
     dim3 grid((T * ((T + 3) / 4) + 255) / 256, B);
     if (u8out) {
         if (bytes)
-            hipLaunchKernelGGL((vtt::crop_kernel<true, true>), grid, dim3(256), 0, st, frames, H, W, states, factor, T, 0.f, 0.f, 0.f, 1.f, 1.f, 1.f, crops, rf);
+            hipLaunchKernelGGL((crop_k<TB, true, true>()), grid, dim3(256), 0, st, frames, H, W, states, factor, T, 0.f, 0.f, 0.f, 1.f, 1.f, 1.f, crops, rf);
         else
-            hipLaunchKernelGGL((vtt::crop_kernel<false, true>), grid, dim3(256), 0, st, frames, H, W, states, factor, T, 0.f, 0.f, 0.f, 1.f, 1.f, 1.f, crops, rf);
+            hipLaunchKernelGGL((crop_k<TB, false, true>()), grid, dim3(256), 0, st, frames, H, W, states, factor, T, 0.f, 0.f, 0.f, 1.f, 1.f, 1.f, crops, rf);
         return;
     }
     if (bytes)
-        hipLaunchKernelGGL(vtt::crop_kernel<true>, grid, dim3(256), 0, st, frames, H, W, states, factor, T, mean3[0], mean3[1], mean3[2],
+        hipLaunchKernelGGL((crop_k<TB, true, false>()), grid, dim3(256), 0, st, frames, H, W, states, factor, T, mean3[0], mean3[1], mean3[2],
                            std3[0], std3[1], std3[2], crops, rf);
     else
-        hipLaunchKernelGGL(vtt::crop_kernel<false>, grid, dim3(256), 0, st, frames, H, W, states, factor, T, mean3[0], mean3[1], mean3[2],
+        hipLaunchKernelGGL((crop_k<TB, false, false>()), grid, dim3(256), 0, st, frames, H, W, states, factor, T, mean3[0], mean3[1], mean3[2],
                            std3[0], std3[1], std3[2], crops, rf);
+}
+
+void launch_crop(bool bytes, const unsigned char* frames, int H, int W, const double* states, double factor, int T, const float* mean3,
+                 const float* std3, int B, hipStream_t st, float* crops, double* rf, bool u8out = false, bool table = false) {
+    if (table) launch_crop_forms(std::true_type{}, bytes, frames, H, W, states, factor, T, mean3, std3, B, st, crops, rf, u8out);
+    else launch_crop_forms(std::false_type{}, bytes, frames, H, W, states, factor, T, mean3, std3, B, st, crops, rf, u8out);
 }
 
 // device buffers of the self test, released on every path
@@ -1467,7 +1489,7 @@ void vt_destroy(vt_model* m) {
     m->stem_w3b.release();
     m->stem_w4b.release();
     m->act_x.release(); m->act_z.release();
-    DevBuf* all[] = {&m->pos_z, &m->pos_x, &m->blocks, &m->blocks3, &m->head, &m->head3, &m->window, &m->tokens, &m->feat, &m->zcache, &m->vlscr, &m->tokens_c,
+    DevBuf* all[] = {&m->pos_z, &m->pos_x, &m->blocks, &m->blocks3, &m->head, &m->head3, &m->window, &m->tokens, &m->feat, &m->zcache, &m->zstage, &m->vlscr, &m->tokens_c,
                      &m->tile_q, &m->tile_k, &m->tile_v, &m->tile_x, &m->head_m1,
                      &m->score, &m->size, &m->offset, &m->pred, &m->hann, &m->conf};
     for (DevBuf* d : all) d->release();
@@ -1769,6 +1791,49 @@ int vt_set_template(vt_model* m, const float* z_dev, int32_t B, void* stream) {
     return VT_OK;
 }
 
+int vt_set_template_slots(vt_model* m, const float* z_dev, const int32_t* slots, int32_t n, void* stream) {
+    if (!m) return fail(VT_ERR_ARG, "null model");
+    if (m->vb) return fail(VT_ERR_ARG, "the template cache is implemented for the vit_48 path only");
+    if (m->tmpl_frames < 1) return fail(VT_ERR_STATE, "vt_set_template_slots needs a template cache: call vt_set_template first");
+    if (m->tmpl_form_batch != m->form_batch)
+        return fail(VT_ERR_STATE, "the template cache was written under another form batch: call vt_set_template again after vt_set_form_batch");
+    if (!z_dev || !slots || n < 1 || n > m->tmpl_frames) return fail(VT_ERR_ARG, "vt_set_template_slots: null pointer or n outside [1, cached frames]");
+    std::vector<char> seen((size_t)m->tmpl_frames, 0);
+    for (int i = 0; i < n; ++i) {
+        if (slots[i] < 0 || slots[i] >= m->tmpl_frames)
+            return fail(VT_ERR_ARG, "vt_set_template_slots: slot " + std::to_string(slots[i]) + " outside [0, " + std::to_string(m->tmpl_frames) + ")");
+        if (seen[(size_t)slots[i]]++) return fail(VT_ERR_ARG, "vt_set_template_slots: slot " + std::to_string(slots[i]) + " named twice");
+    }
+    int rc = check_ready(m, n);
+    if (rc) return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (!m->generic && !m->zstage.p && (rc = m->zstage.alloc(m->zcache.n))) return rc;
+    // Stage: stem(z) + block 0's cache rows of the n templates as frames 0..n-1 of the uncached token matrix and of zstage, under the
+    // forms vt_set_template picked for the whole cache (by max(form batch, cached frames), not by n).  Every stage is per frame under a
+    // given form, so frame i's rows are what the cache holds for that template at any slot.
+    struct Restore {      // the form batch and the cache's address, back on every path
+        vt_model* m;
+        int fb;
+        float* zc;
+        ~Restore() { m->form_batch = fb; m->zcache.p = zc; }
+    } restore{m, m->form_batch, m->zcache.p};
+    m->form_batch = std::max(m->tmpl_form_batch, m->tmpl_frames);
+    if (!m->generic) m->zcache.p = m->zstage.p;
+    if ((rc = run_stem(m, z_dev, nullptr, n, st, m->tokens.p, 0, 2))) return rc;
+    if ((rc = run_blocks(m, m->tokens.p, n, 1, st, m->feat.p, nullptr, 1))) return rc;
+    m->form_batch = restore.fb;
+    m->zcache.p = restore.zc;
+    // ... then into place: each slot's template token rows (rows [0, len_z) of its frame) and its cache rows
+    const size_t C = (size_t)m->cfg.channels, trow = (size_t)m->L * C, tz = (size_t)m->len_z * C;
+    const size_t zf = m->generic ? 0 : m->zcache.n / (size_t)m->cfg.max_batch;
+    for (int i = 0; i < n; ++i) {
+        const size_t s = (size_t)slots[i];
+        HIP_TRY(hipMemcpyAsync(m->tokens_c.p + s * trow, m->tokens.p + (size_t)i * trow, tz * sizeof(float), hipMemcpyDeviceToDevice, st));
+        if (zf) HIP_TRY(hipMemcpyAsync(m->zcache.p + s * zf, m->zstage.p + (size_t)i * zf, zf * sizeof(float), hipMemcpyDeviceToDevice, st));
+    }
+    return VT_OK;
+}
+
 int vt_cal_bbox(vt_model* m, const float* score_dev, const float* size_dev, const float* offset_dev, int32_t B,
                 void* stream, float* bbox_dev, float* max_score_dev) {
     if (!m || !score_dev || !size_dev || !offset_dev || !bbox_dev || B < 1) return fail(VT_ERR_ARG, "bad argument");
@@ -1798,6 +1863,30 @@ int vt_crop_u8(vt_model* m, const uint8_t* frames_dev, int32_t H, int32_t W, con
     if (int rcs = crop_selftest(&crop_bytes)) return rcs;
     launch_crop(crop_bytes, frames_dev, H, W, states_dev, factor, out_size, nullptr, nullptr, B, static_cast<hipStream_t>(stream),
                 reinterpret_cast<float*>(patch_dev), resize_factor_dev, true);
+    HIP_TRY(hipGetLastError());
+    return VT_OK;
+}
+
+int vt_crop_frames(vt_model* m, const vt_frame* frames_dev, const double* states_dev, double factor, int32_t out_size,
+                   const float* mean3, const float* std3, int32_t B, void* stream, float* crops_dev, double* resize_factor_dev) {
+    if (!m || !frames_dev || !states_dev || !crops_dev || !resize_factor_dev || !mean3 || !std3) return fail(VT_ERR_ARG, "null argument");
+    if (B < 1 || out_size < 1 || !(factor > 0.0)) return fail(VT_ERR_ARG, "bad crop arguments");
+    bool crop_bytes = false;
+    if (int rcs = crop_selftest(&crop_bytes)) return rcs;
+    launch_crop(crop_bytes, reinterpret_cast<const unsigned char*>(frames_dev), 0, 0, states_dev, factor, out_size, mean3, std3, B,
+                static_cast<hipStream_t>(stream), crops_dev, resize_factor_dev, false, true);
+    HIP_TRY(hipGetLastError());
+    return VT_OK;
+}
+
+int vt_crop_u8_frames(vt_model* m, const vt_frame* frames_dev, const double* states_dev, double factor, int32_t out_size, int32_t B,
+                      void* stream, uint8_t* patch_dev, double* resize_factor_dev) {
+    if (!m || !frames_dev || !states_dev || !patch_dev || !resize_factor_dev) return fail(VT_ERR_ARG, "null argument");
+    if (B < 1 || out_size < 1 || !(factor > 0.0)) return fail(VT_ERR_ARG, "bad crop arguments");
+    bool crop_bytes = false;
+    if (int rcs = crop_selftest(&crop_bytes)) return rcs;
+    launch_crop(crop_bytes, reinterpret_cast<const unsigned char*>(frames_dev), 0, 0, states_dev, factor, out_size, nullptr, nullptr, B,
+                static_cast<hipStream_t>(stream), reinterpret_cast<float*>(patch_dev), resize_factor_dev, true, true);
     HIP_TRY(hipGetLastError());
     return VT_OK;
 }
@@ -1890,9 +1979,10 @@ int vt_update_state_record(vt_model* m, const float* hann_boxes_dev, const float
     return VT_OK;
 }
 
-int vt_track_step(vt_model* m, const uint8_t* frames, int32_t H, int32_t W, double* states_dev, double factor, const float* mean3,
-                  const float* std3, int32_t B, void* stream, float* crops_dev, double* resize_factor_dev, const vt_outputs* out,
-                  int32_t margin, double* record) {
+// vt_track_step (table == nullptr: frames (B,H,W,3)) and vt_track_step_frames (a (B,) vt_frame table)
+static int track_step(vt_model* m, const uint8_t* frames, int32_t H, int32_t W, const vt_frame* table, double* states_dev, double factor,
+                      const float* mean3, const float* std3, int32_t B, void* stream, float* crops_dev, double* resize_factor_dev,
+                      const vt_outputs* out, int32_t margin, double* record) {
     int rc = check_ready(m, B);
     if (rc) return rc;
     if (m->vb) return fail(VT_ERR_ARG, "vt_track_step is implemented for the vit_48 path only");
@@ -1906,13 +1996,31 @@ int vt_track_step(vt_model* m, const uint8_t* frames, int32_t H, int32_t W, doub
     // whenever the stem form of this batch reads patches and (mean3, std3) is the normalisation folded into its layer 1; else as the
     // fp32 crop of vt_crop.  Either way crops_dev is the workspace: the patch occupies its first B * S * S * 3 bytes.
     const bool u8 = m->track_u8 != 0 && stem_takes_u8(m, B) && same_norm(m, mean3, std3);
-    if (u8) {
+    if (table) {
+        if (u8) {
+            if ((rc = vt_crop_u8_frames(m, table, states_dev, factor, m->cfg.search_size, B, stream, reinterpret_cast<uint8_t*>(crops_dev), resize_factor_dev))) return rc;
+        } else if ((rc = vt_crop_frames(m, table, states_dev, factor, m->cfg.search_size, mean3, std3, B, stream, crops_dev, resize_factor_dev))) return rc;
+    } else if (u8) {
         if ((rc = vt_crop_u8(m, frames, H, W, states_dev, factor, m->cfg.search_size, B, stream, reinterpret_cast<uint8_t*>(crops_dev), resize_factor_dev))) return rc;
     } else if ((rc = vt_crop(m, frames, H, W, states_dev, factor, m->cfg.search_size, mean3, std3, B, stream, crops_dev, resize_factor_dev))) return rc;
     if ((rc = run_stem(m, nullptr, crops_dev, B, st, m->tokens_c.p, 0, 1, u8))) return rc;
     if ((rc = run_blocks(m, m->tokens_c.p, B, -1, st, m->feat.p, nullptr, 2))) return rc;
-    const TrackTail tail{resize_factor_dev, states_dev, record, m->cfg.search_size, H, W, margin, m->open_loop};
+    TrackTail tail{resize_factor_dev, states_dev, record, m->cfg.search_size, H, W, margin, m->open_loop};
+    tail.frames = table;      // the tail clips each sequence against its own frame
     return run_head(m, m->feat.p, B, st, out, 0, &tail);
+}
+
+int vt_track_step(vt_model* m, const uint8_t* frames, int32_t H, int32_t W, double* states_dev, double factor, const float* mean3,
+                  const float* std3, int32_t B, void* stream, float* crops_dev, double* resize_factor_dev, const vt_outputs* out,
+                  int32_t margin, double* record) {
+    return track_step(m, frames, H, W, nullptr, states_dev, factor, mean3, std3, B, stream, crops_dev, resize_factor_dev, out, margin, record);
+}
+
+int vt_track_step_frames(vt_model* m, const vt_frame* frames_dev, double* states_dev, double factor, const float* mean3,
+                         const float* std3, int32_t B, void* stream, float* crops_dev, double* resize_factor_dev, const vt_outputs* out,
+                         int32_t margin, double* record) {
+    if (!frames_dev) return fail(VT_ERR_ARG, "null argument");
+    return track_step(m, nullptr, 0, 0, frames_dev, states_dev, factor, mean3, std3, B, stream, crops_dev, resize_factor_dev, out, margin, record);
 }
 
 // One slice [f0, f0 + nb) of a batch through the whole step, on stream st.

@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "../../include/vittrack.h"      // vt_frame
+
 typedef float f4 __attribute__((ext_vector_type(4)));
 typedef float f2 __attribute__((ext_vector_type(2)));
 
@@ -195,6 +197,7 @@ struct TrackTail {
     double* record;                // optional (B,5) [x,y,w,h,confidence]: device or device-mapped pinned host memory
     int search_size, H, W, margin;
     int keep;                      // open loop (vt_set_open_loop): the new box goes to `record` only, `states` stay as they are
+    const vt_frame* frames = nullptr;      // vt_track_step_frames: sequence b is clipped against frames[b].H / W instead of H / W
 };
 
 __device__ __forceinline__ void update_state_one(int b, const float (&hann_box)[4], float conf, const TrackTail& t) {
@@ -210,12 +213,13 @@ __device__ __forceinline__ void update_state_one(int b, const float (&hann_box)[
     const double cx_real = p[0] + (cx_prev - half_side), cy_real = p[1] + (cy_prev - half_side);
     double bx1 = cx_real - 0.5 * p[2], by1 = cy_real - 0.5 * p[3];
     const double w = p[2], h = p[3];
-    // clip_box(box, H, W, margin) (lib/utils/box_ops.py:97-106)
+    // clip_box(box, H, W, margin) (lib/utils/box_ops.py:97-106), against this sequence's own frame when there is a frame table
+    const int H = t.frames != nullptr ? t.frames[b].H : t.H, W = t.frames != nullptr ? t.frames[b].W : t.W;
     double bx2 = bx1 + w, by2 = by1 + h;
-    bx1 = fmin(fmax(0.0, bx1), (double)(t.W - t.margin));
-    bx2 = fmin(fmax((double)t.margin, bx2), (double)t.W);
-    by1 = fmin(fmax(0.0, by1), (double)(t.H - t.margin));
-    by2 = fmin(fmax((double)t.margin, by2), (double)t.H);
+    bx1 = fmin(fmax(0.0, bx1), (double)(W - t.margin));
+    bx2 = fmin(fmax((double)t.margin, bx2), (double)W);
+    by1 = fmin(fmax(0.0, by1), (double)(H - t.margin));
+    by2 = fmin(fmax((double)t.margin, by2), (double)H);
     const double nw = fmax((double)t.margin, bx2 - bx1), nh = fmax((double)t.margin, by2 - by1);
     if (!t.keep) {
         t.states[4 * b + 0] = bx1;

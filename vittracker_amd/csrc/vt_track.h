@@ -34,6 +34,46 @@ __device__ __forceinline__ void lin_coeff(int d, int src, double scale, int& s0,
     s1 = s + 1 < src ? s + 1 : src - 1;
 }
 
+// ---- frame sources: where sequence b's frame lies.  A template parameter of the crop bodies below; each kernel form has a dense
+// instantiation (today's (B,H,W,3) buffer with one H, W) and a frame-table twin (vt_crop_frames: one vt_frame per sequence).
+struct FrameView {
+    const unsigned char* base;     // the frame's first byte
+    int H, W;
+    unsigned pitch;                // bytes between rows
+    unsigned nrec;                 // bytes readable from `base` (the buffer descriptor's bound: loads beyond it return zero, nothing is fetched)
+    bool tail;                     // the frame's end may be the end of its allocation: crop_band_kernel guards the rows that reach it
+    bool ok;                       // false: an unusable descriptor, poisoned like a too-small box
+};
+struct DenseFrames {      // frames (B,H,W,3): frame b at b H W 3; every frame's bound is the end of the batch, only the last one's is its own end
+    static constexpr bool DENSE = true;
+    __device__ __forceinline__ static FrameView view(const unsigned char* frames, int H, int W, int b, unsigned nb) {
+        const size_t frame_bytes = (size_t)H * W * 3, rest = (size_t)(nb - b) * frame_bytes;      // bytes from this frame to the end of the batch
+        return FrameView{frames + (size_t)b * frame_bytes, H, W, (unsigned)(W * 3), rest > 0xfffffff0ull ? 0xfffffff0u : (unsigned)rest,
+                         b == (int)nb - 1, true};
+    }
+    // the frame's size alone (H, W, pitch, ok): what crop_band_kernel needs before its tables are built; the addresses come later, where
+    // the dense form has always computed them (the dense instantiation keeps its registers)
+    __device__ __forceinline__ static FrameView shape(const unsigned char*, int H, int W, int, unsigned) {
+        return FrameView{nullptr, H, W, (unsigned)(W * 3), 0u, false, true};
+    }
+};
+struct TableFrames {      // `frames` is a (B,) vt_frame table; H, W are unused
+    static constexpr bool DENSE = false;
+    __device__ __forceinline__ static FrameView view(const unsigned char* frames, int, int, int b, unsigned) {
+        // one descriptor per workgroup at a workgroup-uniform address of a read-only argument: scalar LOADS into SGPRs, nothing else
+        const vt_frame* const d = reinterpret_cast<const vt_frame*>(frames) + b;
+        const unsigned char* const data = d->data;
+        const int H = d->H, W = d->W;
+        const long long pitch = d->pitch == 0 ? 3ll * W : d->pitch;
+        // [data, data + pitch (H - 1) + 3 W) is the frame; it must be addressable by a 32-bit buffer offset
+        const bool shape = H >= 1 && W >= 1 && W <= 0x10000000 && pitch >= 3ll * W && pitch <= 0xfffffff0ll;
+        const unsigned long long ext = shape ? (unsigned long long)pitch * (unsigned long long)(H - 1) + 3ull * (unsigned long long)W : ~0ull;
+        const bool ok = shape && data != nullptr && (reinterpret_cast<unsigned long long>(data) & 3ull) == 0 && ext <= 0xfffffff0ull;
+        return FrameView{data, ok ? H : 1, ok ? W : 1, ok ? (unsigned)pitch : 3u, ok ? (unsigned)ext : 0u, true, ok};
+    }
+    __device__ __forceinline__ static FrameView shape(const unsigned char* frames, int H, int W, int b, unsigned nb) { return view(frames, H, W, b, nb); }
+};
+
 // grid (ceil(T * ceil(T/4) / 256), B); frames (B,H,W,3) uint8; states (B,4) double [x,y,w,h]; out (B,3,T,T) float.
 // One thread = four consecutive output pixels of a row (all three channels): the vertical coefficients are computed once,
 // and a channel's four values leave as ONE 16-byte store when T is a multiple of 4 (the crop sizes the tracker uses are:
@@ -42,12 +82,14 @@ __device__ __forceinline__ void lin_coeff(int d, int src, double scale, int& s0,
 // device's unaligned-access mode; vt_create's self test (vittrack.hip: crop_selftest) selects it when the fast form's result differs.
 // U8OUT (round 6): `out` is the uint8 (B, T, T, 3) patch itself -- sample_target's return value, before Preprocessor.process -- which
 // the stems' uint8 forms consume (vt_stem.h: L1In); no normalisation table, a thread's 12 values leave as one 12-byte store.
-template <bool BYTES = false, bool U8OUT = false>
-__global__ __launch_bounds__(256) void crop_kernel(const unsigned char* __restrict__ frames, int H, int W,
-                                                   const double* __restrict__ states, double factor, int T,
-                                                   float m0, float m1, float m2, float s0, float s1, float s2,
-                                                   float* __restrict__ out, double* __restrict__ resize_factor) {
+// Src: the frame source (DenseFrames: crop_kernel; TableFrames: crop_frames_kernel).
+template <class Src, bool BYTES, bool U8OUT>
+__device__ __forceinline__ void crop_body(const unsigned char* __restrict__ frames, int H, int W,
+                                          const double* __restrict__ states, double factor, int T,
+                                          float m0, float m1, float m2, float s0, float s1, float s2,
+                                          float* __restrict__ out, double* __restrict__ resize_factor) {
     const int b = blockIdx.y;
+    const FrameView fv = Src::view(frames, H, W, b, gridDim.y);
     // Preprocessor.process maps a uint8 value to (v / 255 - mean) / std: 256 x 3 possible results.  They are computed ONCE per
     // workgroup with the reference's arithmetic (three separately rounded fp32 ops, below) into an LDS table -- per output value
     // one LDS read instead of a convert, a multiply, a subtract and an IEEE division sequence (~14 VALU instructions of the ~74 a
@@ -74,7 +116,7 @@ __global__ __launch_bounds__(256) void crop_kernel(const unsigned char* __restri
     const int crop_sz = (int)ceil(sqrt(bw * bh) * factor);
     const int T4 = (T + 3) >> 2;                      // pixel groups per row
     const int idx = blockIdx.x * 256 + threadIdx.x;
-    if (!(crop_sz >= 1)) {
+    if (!(crop_sz >= 1) || !fv.ok) {
         // The reference raises 'Too small bounding box.' here (processing_utils.py:33-34).  A kernel cannot
         // raise: the crop and its resize factor are poisoned with NaN, so every box derived from them is NaN and
         // the caller sees it (BatchedVitTracker checks user-supplied boxes on the host before they get here; boxes
@@ -95,8 +137,8 @@ __global__ __launch_bounds__(256) void crop_kernel(const unsigned char* __restri
     const int x2 = x1 + crop_sz, y2 = y1 + crop_sz;
     // valid source range of the padded crop (the reference's pad formula keeps max(x2 - W + 1, 0)
     // columns on the right, i.e. drops the last image column when the crop reaches the border)
-    const int vx0 = x1 < 0 ? 0 : x1, vx1 = x2 - (x2 - W + 1 > 0 ? x2 - W + 1 : 0);
-    const int vy0 = y1 < 0 ? 0 : y1, vy1 = y2 - (y2 - H + 1 > 0 ? y2 - H + 1 : 0);
+    const int vx0 = x1 < 0 ? 0 : x1, vx1 = x2 - (x2 - fv.W + 1 > 0 ? x2 - fv.W + 1 : 0);
+    const int vy0 = y1 < 0 ? 0 : y1, vy1 = y2 - (y2 - fv.H + 1 > 0 ? y2 - fv.H + 1 : 0);
     if (idx == 0) resize_factor[b] = (double)T / (double)crop_sz;
     if (idx >= T * T4) return;
     const int oy = idx / T4, ox0 = (idx - oy * T4) * 4;
@@ -108,12 +150,11 @@ __global__ __launch_bounds__(256) void crop_kernel(const unsigned char* __restri
     // loads, which were the kernel's cost (3072 vector-memory instructions per 128 x 128 crop: 33 us at batch 256, a quarter of the
     // tracker step).  Buffer loads at byte-unaligned offsets (tools/src/probe_unaligned.hip: the hardware returns the right bytes;
     // a load that crosses the end of the buffer returns zeros, so the frame's last pixels are read 8 bytes back and shifted).
-    const size_t frame_bytes = (size_t)H * W * 3, rest = (size_t)(gridDim.y - b) * frame_bytes;      // bytes from this frame to the end of the batch
-    const unsigned nrec = rest > 0xfffffff0ull ? 0xfffffff0u : (unsigned)rest;
-    const auto rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned char*>(frames + (size_t)b * frame_bytes), 0, (int)nrec, 0x00020000);
+    const unsigned nrec = fv.nrec;      // dense: bytes from this frame to the end of the batch; table: the frame's own extent
+    const auto rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned char*>(fv.base), 0, (int)nrec, 0x00020000);
     const int yy0 = y1 + sy0, yy1 = y1 + sy1;
     const bool vr0 = yy0 >= vy0 && yy0 < vy1, vr1 = yy1 >= vy0 && yy1 < vy1;
-    const unsigned rowo0 = (unsigned)(vr0 ? yy0 : 0) * (unsigned)(W * 3), rowo1 = (unsigned)(vr1 ? yy1 : 0) * (unsigned)(W * 3);
+    const unsigned rowo0 = (unsigned)(vr0 ? yy0 : 0) * fv.pitch, rowo1 = (unsigned)(vr1 ? yy1 : 0) * fv.pitch;
     typedef unsigned u2v __attribute__((ext_vector_type(2)));
     auto load8 = [&](unsigned off) -> unsigned long long {      // bytes off .. off + 7 of the frame (the last bytes of the batch: shifted in)
         if constexpr (BYTES) {
@@ -186,6 +227,21 @@ __global__ __launch_bounds__(256) void crop_kernel(const unsigned char* __restri
         }
     }
 }
+template <bool BYTES = false, bool U8OUT = false>
+__global__ __launch_bounds__(256) void crop_kernel(const unsigned char* __restrict__ frames, int H, int W,
+                                                   const double* __restrict__ states, double factor, int T,
+                                                   float m0, float m1, float m2, float s0, float s1, float s2,
+                                                   float* __restrict__ out, double* __restrict__ resize_factor) {
+    crop_body<DenseFrames, BYTES, U8OUT>(frames, H, W, states, factor, T, m0, m1, m2, s0, s1, s2, out, resize_factor);
+}
+// the frame-table twin (vt_crop_frames): `frames` is a (B,) vt_frame table, H / W unused
+template <bool BYTES = false, bool U8OUT = false>
+__global__ __launch_bounds__(256) void crop_frames_kernel(const unsigned char* __restrict__ frames, int H, int W,
+                                                          const double* __restrict__ states, double factor, int T,
+                                                          float m0, float m1, float m2, float s0, float s1, float s2,
+                                                          float* __restrict__ out, double* __restrict__ resize_factor) {
+    crop_body<TableFrames, BYTES, U8OUT>(frames, H, W, states, factor, T, m0, m1, m2, s0, s1, s2, out, resize_factor);
+}
 
 // The crop as the tracker's step runs it (T a multiple of 4, T <= CROP_FAST_MAX_T): same arithmetic, same results bit for bit as
 // crop_kernel (which stays: any T, the byte-load form, the reference of the device self test).  What differs:
@@ -223,12 +279,13 @@ __device__ __forceinline__ void put_byte_shr2(unsigned& dst, unsigned v, unsigne
         default: asm("v_lshrrev_b32_sdwa %0, %1, %2 dst_sel:BYTE_3 dst_unused:UNUSED_PRESERVE src0_sel:DWORD src1_sel:DWORD" : "+v"(dst) : "v"(two), "v"(v)); break;
     }
 }
-template <int G, bool U8OUT = false>
-__global__ __launch_bounds__(256) void crop_fast_kernel(const unsigned char* __restrict__ frames, int H, int W,
-                                                        const double* __restrict__ states, double factor, int T,
-                                                        float m0, float m1, float m2, float s0, float s1, float s2,
-                                                        float* __restrict__ out, double* __restrict__ resize_factor) {
+template <class Src, int G, bool U8OUT>
+__device__ __forceinline__ void crop_fast_body(const unsigned char* __restrict__ frames, int H, int W,
+                                               const double* __restrict__ states, double factor, int T,
+                                               float m0, float m1, float m2, float s0, float s1, float s2,
+                                               float* __restrict__ out, double* __restrict__ resize_factor) {
     const int b = blockIdx.y, tid = threadIdx.x;
+    const FrameView fv = Src::view(frames, H, W, b, gridDim.y);
     __shared__ float norm_lut[U8OUT ? 1 : 3 * 256];
     __shared__ __attribute__((aligned(16))) unsigned xtab[CROP_FAST_MAX_T * 4];      // per output column: window byte offset, weights, right column's shift, -
     unsigned char* const out8 = reinterpret_cast<unsigned char*>(out) + (size_t)b * T * T * 3;      // U8OUT: this frame's (T, T, 3) patch
@@ -248,7 +305,7 @@ __global__ __launch_bounds__(256) void crop_fast_kernel(const unsigned char* __r
     const int crop_sz = (int)ceil(sqrt(bw * bh) * factor);
     const int T4 = T >> 2, nitems = T * T4;
     const int item0 = blockIdx.x * G * 256;
-    if (!(crop_sz >= 1)) {                  // 'Too small bounding box.': NaN poison, as crop_kernel
+    if (!(crop_sz >= 1) || !fv.ok) {        // 'Too small bounding box.' (or an unusable frame descriptor): NaN poison, as crop_kernel
         if (blockIdx.x == 0 && tid == 0) resize_factor[b] = __builtin_nan("");
         for (int g = 0; g < G; ++g) {
             const int idx = item0 + g * 256 + tid;
@@ -264,8 +321,8 @@ __global__ __launch_bounds__(256) void crop_fast_kernel(const unsigned char* __r
     const int x1 = (int)rint(bx + 0.5 * bw - crop_sz * 0.5);
     const int y1 = (int)rint(by + 0.5 * bh - crop_sz * 0.5);
     const int x2 = x1 + crop_sz, y2 = y1 + crop_sz;
-    const int vx0 = x1 < 0 ? 0 : x1, vx1 = x2 - (x2 - W + 1 > 0 ? x2 - W + 1 : 0);
-    const int vy0 = y1 < 0 ? 0 : y1, vy1 = y2 - (y2 - H + 1 > 0 ? y2 - H + 1 : 0);
+    const int vx0 = x1 < 0 ? 0 : x1, vx1 = x2 - (x2 - fv.W + 1 > 0 ? x2 - fv.W + 1 : 0);
+    const int vy0 = y1 < 0 ? 0 : y1, vy1 = y2 - (y2 - fv.H + 1 > 0 ? y2 - fv.H + 1 : 0);
     if (blockIdx.x == 0 && tid == 0) resize_factor[b] = (double)T / (double)crop_sz;
     const double scale = (double)crop_sz / (double)T;
     typedef unsigned u4v __attribute__((ext_vector_type(4)));
@@ -279,9 +336,8 @@ __global__ __launch_bounds__(256) void crop_fast_kernel(const unsigned char* __r
                                                       (unsigned)(vc1 ? 24 * (xx1 - xb) : 0), 0u};
     }
     __syncthreads();
-    const size_t frame_bytes = (size_t)H * W * 3, rest = (size_t)(gridDim.y - b) * frame_bytes;
-    const unsigned nrec = rest > 0xfffffff0ull ? 0xfffffff0u : (unsigned)rest;
-    const auto rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned char*>(frames + ((VT_CROPF_DBG & 4) ? 0 : (size_t)b * frame_bytes)), 0, (int)nrec, 0x00020000);
+    const unsigned nrec = fv.nrec;
+    const auto rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned char*>(((VT_CROPF_DBG & 4) && Src::DENSE) ? frames : fv.base), 0, (int)nrec, 0x00020000);
     typedef unsigned u2v __attribute__((ext_vector_type(2)));
     typedef unsigned short us2 __attribute__((ext_vector_type(2)));
     struct Item {
@@ -300,11 +356,11 @@ __global__ __launch_bounds__(256) void crop_fast_kernel(const unsigned char* __r
         lin_coeff(it.oy, crop_sz, scale, sy0, sy1, by0, by1);
         const int yy0 = y1 + sy0, yy1 = y1 + sy1;
         const bool vr0 = yy0 >= vy0 && yy0 < vy1, vr1 = yy1 >= vy0 && yy1 < vy1;
-        const unsigned rowo0 = (unsigned)(vr0 ? yy0 : 0) * (unsigned)(W * 3), rowo1 = (unsigned)(vr1 ? yy1 : 0) * (unsigned)(W * 3);
+        const unsigned rowo0 = (unsigned)(vr0 ? yy0 : 0) * fv.pitch, rowo1 = (unsigned)(vr1 ? yy1 : 0) * fv.pitch;
         it.byw0 = vr0 ? (unsigned)by0 << 12 : 0u;      // a padded row weighs nothing
         it.byw1 = vr1 ? (unsigned)by1 << 12 : 0u;
         // can a window of this item cross the end of the buffer?  (3 (W - 1) is the largest column offset)
-        const unsigned far = (rowo0 > rowo1 ? rowo0 : rowo1) + 3u * (unsigned)(W - 1) + 8u;
+        const unsigned far = (rowo0 > rowo1 ? rowo0 : rowo1) + 3u * (unsigned)(fv.W - 1) + 8u;
         const bool slow = __builtin_amdgcn_ballot_w64(far > nrec) != 0;
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
@@ -375,6 +431,20 @@ __global__ __launch_bounds__(256) void crop_fast_kernel(const unsigned char* __r
         finish(buf[g & 1]);
     }
 }
+template <int G, bool U8OUT = false>
+__global__ __launch_bounds__(256) void crop_fast_kernel(const unsigned char* __restrict__ frames, int H, int W,
+                                                        const double* __restrict__ states, double factor, int T,
+                                                        float m0, float m1, float m2, float s0, float s1, float s2,
+                                                        float* __restrict__ out, double* __restrict__ resize_factor) {
+    crop_fast_body<DenseFrames, G, U8OUT>(frames, H, W, states, factor, T, m0, m1, m2, s0, s1, s2, out, resize_factor);
+}
+template <int G, bool U8OUT = false>      // the frame-table twin
+__global__ __launch_bounds__(256) void crop_fast_frames_kernel(const unsigned char* __restrict__ frames, int H, int W,
+                                                               const double* __restrict__ states, double factor, int T,
+                                                               float m0, float m1, float m2, float s0, float s1, float s2,
+                                                               float* __restrict__ out, double* __restrict__ resize_factor) {
+    crop_fast_body<TableFrames, G, U8OUT>(frames, H, W, states, factor, T, m0, m1, m2, s0, s1, s2, out, resize_factor);
+}
 
 // crop_band_kernel (round 6) -- the crop at the tracker's sizes (T = 64 / 128 / 256: T / 4 = 2^LGT4 column groups), same arithmetic and
 // results bit for bit as crop_fast_kernel / crop_kernel.  Measured on timing builds of crop_fast_kernel (tools/crop_ab.py, T = 128, 256
@@ -392,14 +462,21 @@ __global__ __launch_bounds__(256) void crop_fast_kernel(const unsigned char* __r
 //     up to 16 bytes (tools/src/probe_gather.hip), and 512 of them per CU and round is what the kernel waits for.  So a window is fetched
 //     as the 12 ALIGNED bytes that contain it (the two pixels' 6 bytes start at byte 0..3 of them) and shifted into place with two
 //     v_alignbit; the batch's last frame keeps the byte-aligned form (its shifted-back windows).
-template <bool U8OUT, int LGT4, int IPT, bool ALIGNED>
+// Frame source: no trailing argument = DenseFrames (the kernel's name and code as before), crop_band_kernel<..., TableFrames> = the frame-
+// table twin.  (Not a body function behind two kernels as crop_kernel / crop_fast_kernel: called through one, this kernel's register
+// allocation moved -- 60 -> 64 VGPRs for crop_band_kernel<false, 6, 2, false> -- while as the kernel itself it compiles as before.)
+template <class... Tab> struct FrameSource { using type = DenseFrames; };
+template <class S> struct FrameSource<S> { using type = S; };
+template <bool U8OUT, int LGT4, int IPT, bool ALIGNED, class... Tab>
 __global__ __launch_bounds__(256) void crop_band_kernel(const unsigned char* __restrict__ frames, int H, int W,
                                                         const double* __restrict__ states, double factor,
                                                         float m0, float m1, float m2, float s0, float s1, float s2,
                                                         float* __restrict__ out, double* __restrict__ resize_factor) {
+    using Src = typename FrameSource<Tab...>::type;
     constexpr int T4 = 1 << LGT4, T = 4 * T4, RPG = 256 >> LGT4, NROWS = IPT * RPG;      // rows per group of 256 items, rows per band
     static_assert(T <= 256 && (T * T4) % (IPT * 256) == 0, "a band is whole rows and the frame whole bands");
     const int b = blockIdx.y, tid = threadIdx.x;
+    const FrameView fs = Src::shape(frames, H, W, b, gridDim.y);      // size and validity now, addresses below
     // VT_CROPF_DBG & 16 (timing build, uint8 form): s_memtime at the phase boundaries of every workgroup, written over the first 48 bytes of its band
     unsigned long long stamp_[7] = {0, 0, 0, 0, 0, 0, 0};
     auto stamp = [&](int i) {
@@ -429,7 +506,7 @@ __global__ __launch_bounds__(256) void crop_band_kernel(const unsigned char* __r
     const int crop_sz = (int)ceil(sqrt(bw * bh) * factor);
     const int row0 = blockIdx.x * NROWS;                 // first output row of this band
     const int cg = tid & (T4 - 1), rl = tid >> LGT4;     // this thread's column group and its row inside a group of 256 items
-    if (!(crop_sz >= 1)) {                  // 'Too small bounding box.': NaN poison, as crop_kernel
+    if (!(crop_sz >= 1) || !fs.ok) {        // 'Too small bounding box.' (or an unusable frame descriptor): NaN poison, as crop_kernel
         if (blockIdx.x == 0 && tid == 0) resize_factor[b] = __builtin_nan("");
 #pragma unroll
         for (int j = 0; j < IPT; ++j) {
@@ -443,8 +520,8 @@ __global__ __launch_bounds__(256) void crop_band_kernel(const unsigned char* __r
     const int x1 = (int)rint(bx + 0.5 * bw - crop_sz * 0.5);
     const int y1 = (int)rint(by + 0.5 * bh - crop_sz * 0.5);
     const int x2 = x1 + crop_sz, y2 = y1 + crop_sz;
-    const int vx0 = x1 < 0 ? 0 : x1, vx1 = x2 - (x2 - W + 1 > 0 ? x2 - W + 1 : 0);
-    const int vy0 = y1 < 0 ? 0 : y1, vy1 = y2 - (y2 - H + 1 > 0 ? y2 - H + 1 : 0);
+    const int vx0 = x1 < 0 ? 0 : x1, vx1 = x2 - (x2 - fs.W + 1 > 0 ? x2 - fs.W + 1 : 0);
+    const int vy0 = y1 < 0 ? 0 : y1, vy1 = y2 - (y2 - fs.H + 1 > 0 ? y2 - fs.H + 1 : 0);
     if (blockIdx.x == 0 && tid == 0) resize_factor[b] = (double)T / (double)crop_sz;
     const double scale = (double)crop_sz / (double)T;
     if ((VT_CROPF_DBG & 16) != 0) { asm volatile("" ::"v"(x1), "v"(y1), "v"(scale)); stamp(1); }
@@ -463,14 +540,14 @@ __global__ __launch_bounds__(256) void crop_band_kernel(const unsigned char* __r
         lin_coeff(row0 + r, crop_sz, scale, sy0, sy1, by0, by1);
         const int yy0 = y1 + sy0, yy1 = y1 + sy1;
         const bool vr0 = yy0 >= vy0 && yy0 < vy1, vr1 = yy1 >= vy0 && yy1 < vy1;
-        *reinterpret_cast<u4v*>(ytab + 4 * r) = u4v{(unsigned)(vr0 ? yy0 : 0) * (unsigned)(W * 3), (unsigned)(vr1 ? yy1 : 0) * (unsigned)(W * 3),
+        *reinterpret_cast<u4v*>(ytab + 4 * r) = u4v{(unsigned)(vr0 ? yy0 : 0) * fs.pitch, (unsigned)(vr1 ? yy1 : 0) * fs.pitch,
                                                      vr0 ? (unsigned)by0 << 12 : 0u, vr1 ? (unsigned)by1 << 12 : 0u};      // a padded row weighs nothing
     }
     __syncthreads();
     stamp(2);
-    const size_t frame_bytes = (size_t)H * W * 3, rest = (size_t)(gridDim.y - b) * frame_bytes;
-    const unsigned nrec = rest > 0xfffffff0ull ? 0xfffffff0u : (unsigned)rest;
-    const unsigned char* const fb = frames + (size_t)b * frame_bytes;
+    const FrameView fv = Src::view(frames, H, W, b, gridDim.y);
+    const unsigned nrec = fv.nrec;
+    const unsigned char* const fb = fv.base;
     const auto rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned char*>(fb), 0, (int)nrec, 0x00020000);
     // ALIGNED: the same bytes through a descriptor whose base is the frame's address rounded DOWN to a dword; offsets carry the remainder
     const unsigned mis = (unsigned)(reinterpret_cast<unsigned long long>(fb) & 3ull);
@@ -487,12 +564,17 @@ __global__ __launch_bounds__(256) void crop_band_kernel(const unsigned char* __r
     // ... and there only in a band that reads the frame's last source row (its windows end at most 11 + 3 bytes past their first byte: inside
     // the next row): every other band of the last frame takes the aligned form too -- the shifted form waits for each pair of windows before it
     // requests the next (the shift is part of the request), a chain of 4 IPT memory round trips that the whole launch waited for
-    bool last = b == (int)gridDim.y - 1;
+    // FRAME TABLE: every frame's end may be the end of its allocation, so every frame takes this guard, on its own H, W and pitch.  Why the
+    // aligned form reads inside [data, data + pitch (H - 1) + 3 W) when the guard lets it run (data 4-byte aligned: mis = 0): a window's
+    // first byte is at o = row offset + 3 xb <= pitch ymax + 3 (W - 1) with ymax <= H - 2; its 12-byte aligned load starts at o & ~3 >= 0
+    // and ends before o + 12 <= pitch (H - 2) + 3 W + 9 <= pitch (H - 1) + 3 W, as pitch >= 3 W >= 16 > 9.  Rows outside the valid range
+    // read row 0.  And whatever the arithmetic, the buffer descriptor's bound (nrec = that extent) keeps every load inside the frame.
+    bool last = fv.tail;      // dense: b == gridDim.y - 1
     if (ALIGNED && last) {
         int sl0, sl1, al0, al1;
         lin_coeff(row0 + NROWS - 1, crop_sz, scale, sl0, sl1, al0, al1);
         const int ymax = y1 + sl1 < vy1 - 1 ? y1 + sl1 : vy1 - 1;       // rows beyond the valid range read row 0
-        if (ymax <= H - 2 && W * 3 >= 16) last = false;
+        if (ymax <= fs.H - 2 && fs.W * 3 >= 16) last = false;
     }
     unsigned two = 2u;
     asm volatile("" : "+v"(two));      // put_byte_shr2's shift operand has to live in a vector register

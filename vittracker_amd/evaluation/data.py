@@ -95,6 +95,37 @@ def synthetic_dataset(n_sequences: int = 8, n_frames: int = 20, H: int = 240, W:
                         for s in range(n_sequences))
 
 
+#: frame sizes of synthetic_mixed: (H, W).  301 x 3 = 903 bytes per row is no multiple of 4; 5 px is narrower than any crop window; 72 x 100 is
+#: smaller than the search crop at both geometries
+MIXED_SIZES = ((240, 320), (201, 301), (120, 160), (72, 100), (40, 5))
+
+
+def mixed_sequence(name: str, n_frames: int, H: int, W: int, seed: int = 0, dataset: str = "synthetic_mixed"):
+    """A target drifting over a random background on a frame of any size (down to a few pixels); ground truth known exactly."""
+    rs = np.random.RandomState(seed)
+    bg = rs.randint(0, 256, (H, W, 3)).astype(np.uint8)
+    tw, th = max(2, min(30 + rs.randint(0, 30), W // 3)), max(2, min(24 + rs.randint(0, 24), H // 3))
+    patch = rs.randint(0, 256, (th, tw, 3)).astype(np.uint8)
+    x0, y0 = rs.randint(0, W - tw + 1), rs.randint(0, H - th + 1)
+    vx, vy = rs.uniform(-1.5, 1.5), rs.uniform(-1.0, 1.0)
+    frames, gt = [], []
+    for t in range(n_frames):
+        x = int(min(max(round(x0 + vx * t), 0), W - tw))
+        y = int(min(max(round(y0 + vy * t), 0), H - th))
+        f = bg.copy()
+        f[y:y + th, x:x + tw] = patch
+        frames.append(f)
+        gt.append([x, y, tw, th])
+    return Sequence(name, frames, dataset, np.array(gt, dtype=np.float64))
+
+
+def synthetic_mixed_dataset(n_sequences: int = 10, n_frames: int = 6):
+    """Deterministic benchmark of mixed frame sizes and lengths: sequence s has frame size MIXED_SIZES[s % 5] and
+    n_frames + ((2654435761 s mod 2^32) >> 7 mod (n_frames + 1)) frames, i.e. lengths from n_frames to 2 n_frames."""
+    return SequenceList(mixed_sequence(f"mixed_{s:04d}", n_frames + (((2654435761 * s) & 0xffffffff) >> 7) % (n_frames + 1), *MIXED_SIZES[s % len(MIXED_SIZES)], seed=500 + s)
+                        for s in range(n_sequences))
+
+
 def folder_dataset(root: str, dataset: str = "folder"):
     """<root>/<seq>/(img/)*.{jpg,jpeg,png,bmp,npy} sorted by name + <root>/<seq>/groundtruth*.txt with one
     `x,y,w,h` (comma / tab / space separated) row per frame, at least the first."""
@@ -114,11 +145,17 @@ def folder_dataset(root: str, dataset: str = "folder"):
 
 
 def get_dataset(*names):
-    """``get_dataset('synthetic')``, ``get_dataset('synthetic:16x50')`` (16 sequences x 50 frames),
+    """``get_dataset('synthetic')``, ``get_dataset('synthetic:16x50')`` (16 sequences x 50 frames), ``get_dataset('synthetic_mixed:512x20')``
+    (512 sequences of five frame sizes, 20 to 40 frames),
     ``get_dataset('folder:/path')`` -- the registry role of lib/test/evaluation/datasets.py:43-48."""
     out = SequenceList()
     for n in names:
-        if n.startswith("synthetic"):
+        if n.startswith("synthetic_mixed"):
+            m = re.fullmatch(r"synthetic_mixed(?::(\d+)x(\d+))?", n)
+            if not m:
+                raise ValueError(f"bad dataset spec {n!r} (want synthetic_mixed or synthetic_mixed:<sequences>x<frames>)")
+            out = out + (synthetic_mixed_dataset(int(m.group(1)), int(m.group(2))) if m.group(1) else synthetic_mixed_dataset())
+        elif n.startswith("synthetic"):
             m = re.fullmatch(r"synthetic(?::(\d+)x(\d+))?", n)
             if not m:
                 raise ValueError(f"bad synthetic dataset spec {n!r} (want synthetic or synthetic:<sequences>x<frames>)")
@@ -126,6 +163,6 @@ def get_dataset(*names):
         elif n.startswith("folder:"):
             out = out + folder_dataset(n[len("folder:"):])
         else:
-            raise ValueError(f"unknown dataset {n!r}: this build ships 'synthetic[:NxT]' and 'folder:<path>' "
+            raise ValueError(f"unknown dataset {n!r}: this build ships 'synthetic[:NxT]', 'synthetic_mixed[:NxT]' and 'folder:<path>' "
                              f"(the reference's benchmark parsers are out of scope)")
     return out

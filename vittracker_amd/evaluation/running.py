@@ -153,3 +153,102 @@ def _run_group(seqs, tracker, params, make_batched, pipelines, frames_per_launch
         print("Tracker: {} {} {} ,  Sequence: {}  FPS: {}".format(tracker.name, tracker.parameter_name, tracker.run_id, s.name,
                                                                  len(out[s.name]["time"]) / sum(out[s.name]["time"])))
     return out
+
+
+# ----------------------------------------------------------------------------------- continuous batching
+def run_dataset_continuous(dataset, tracker, batch, rank=0, world=1, params=None, make_batched=None):
+    """B slots kept live across every frame size and length (continuous batching): each slot steps its own sequence on its own frame
+    (BatchedVitTracker on a frame table), and when a sequence ends its files are written and the next pending sequence is initialised
+    into that slot before the next step (BatchedVitTracker.reinitialize: that slot's template, state and cache only).  Once the queue is
+    empty, idle slots re-step their last frame and their outputs are dropped.  Sequence s belongs to rank s % world; too-small init
+    boxes are screened out per sequence as in run_dataset_batched.  Per-frame time written = step wall time / live sequences; an
+    initialisation's time = its call's wall time / sequences it initialised.  Returns {seq.name: output dict} for this rank's sequences.
+    make_batched(params, B) -> an object with initialize(frames, boxes), track(frames) and reinitialize(slots, frames, boxes)."""
+    from ..parallel import shard_sequences
+    mine = [dataset[i] for i in shard_sequences(len(dataset), rank, world)]
+    todo = [s for s in mine if not results_exist(tracker.results_dir, s)]
+    params = params or tracker.get_parameters()
+    params.debug = 0
+    if make_batched is None:
+        from ..batched import BatchedVitTracker
+        make_batched = BatchedVitTracker
+    import math
+    from collections import deque
+    pending = deque()
+    for s in todo:      # the screen of run_dataset_batched
+        try:
+            x, y, w, h = [float(v) for v in s.init_info()["init_bbox"]]
+            for f in (params.template_factor, params.search_factor):
+                if not math.ceil(math.sqrt(w * h) * f) >= 1:
+                    raise Exception("Too small bounding box.")
+            pending.append(s)
+        except Exception as e:  # noqa: BLE001
+            print("Tracker: {} {} {} ,  Sequence: {}".format(tracker.name, tracker.parameter_name, tracker.run_id, s.name))
+            print(e)
+    if not pending:
+        return {}
+    B = int(batch)
+    bt = make_batched(params, B)
+    if not hasattr(bt, "reinitialize"):
+        raise TypeError("run_dataset_continuous needs a batched tracker with reinitialize() (BatchedVitTracker)")
+    outputs = {}
+    slot_seq = [None] * B        # the sequence a slot is running (None: idle)
+    slot_t = [0] * B             # its next frame index
+    last = [None] * B            # the frame the slot stepped last (idle slots re-step it)
+
+    def start(s):
+        return {"target_bbox": [list(s.init_info()["init_bbox"])], "time": []}
+
+    def finish(b):
+        s = slot_seq[b]
+        save_tracker_output(s, tracker.results_dir, outputs[s.name])
+        print("Tracker: {} {} {} ,  Sequence: {}  FPS: {}".format(tracker.name, tracker.parameter_name, tracker.run_id, s.name,
+                                                                 len(outputs[s.name]["time"]) / sum(outputs[s.name]["time"])))
+        slot_seq[b] = None
+
+    first = [pending.popleft() for _ in range(min(B, len(pending)))]
+    frames = [read_image(s.frames[0]) for s in first]
+    boxes = [s.init_info()["init_bbox"] for s in first]
+    frames += [frames[0]] * (B - len(first))        # slots without a sequence from the start: any valid frame and box, outputs dropped
+    boxes += [boxes[0]] * (B - len(first))
+    t0 = time.time()
+    bt.initialize(frames, boxes)
+    dt = (time.time() - t0) / len(first)
+    for b, s in enumerate(first):
+        slot_seq[b], slot_t[b] = s, 1
+        outputs[s.name] = start(s)
+        outputs[s.name]["time"].append(dt)
+    last = list(frames)
+    while True:
+        # sequences of one frame are done at their initialisation; free slots take the next pending sequences
+        while True:
+            for b in range(B):
+                if slot_seq[b] is not None and slot_t[b] >= len(slot_seq[b]):
+                    finish(b)
+            free = [b for b in range(B) if slot_seq[b] is None]
+            if not free or not pending:
+                break
+            refill = [(b, pending.popleft()) for b in free[:len(pending)]]
+            fr = [read_image(s.frames[0]) for _, s in refill]
+            t0 = time.time()
+            bt.reinitialize([b for b, _ in refill], fr, [s.init_info()["init_bbox"] for _, s in refill])
+            dt = (time.time() - t0) / len(refill)
+            for (b, s), f in zip(refill, fr):
+                slot_seq[b], slot_t[b], last[b] = s, 1, f
+                outputs[s.name] = start(s)
+                outputs[s.name]["time"].append(dt)
+        live = [b for b in range(B) if slot_seq[b] is not None]
+        if not live:
+            break
+        for b in live:
+            last[b] = read_image(slot_seq[b].frames[slot_t[b]])
+        t0 = time.time()
+        res = bt.track(list(last))
+        boxes = np.asarray(res["target_bbox"])
+        wall = time.time() - t0
+        for b in live:
+            s = slot_seq[b]
+            outputs[s.name]["target_bbox"].append(boxes[b].tolist())
+            outputs[s.name]["time"].append(wall / len(live))
+            slot_t[b] += 1
+    return outputs

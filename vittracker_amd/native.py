@@ -26,6 +26,7 @@ SYMBOLS = [
     "vt_graph_launch", "vt_graph_destroy", "vt_query", "vt_selftest_mfma", "vt_probe_clock", "vt_debug_stamps", "vt_crop", "vt_update_state",
     "vt_set_template", "vt_graph_capture_steps", "vt_update_state_record", "vt_track_step", "vt_set_form_batch",
     "vt_crop_u8", "vt_set_normalization", "vt_forward_u8", "vt_stem_u8", "vt_patch_u8_supported", "vt_crop_form", "vt_set_open_loop",
+    "vt_crop_frames", "vt_crop_u8_frames", "vt_track_step_frames", "vt_set_template_slots",
 ]
 
 
@@ -103,6 +104,10 @@ def lib(precision: str = "f32"):
     L.vt_patch_u8_supported.argtypes = [vp, i32]
     L.vt_crop_form.argtypes = []
     L.vt_set_open_loop.argtypes = [vp, i32]
+    L.vt_crop_frames.argtypes = [vp, vp, vp, C.c_double, i32, C.POINTER(C.c_float), C.POINTER(C.c_float), i32, vp, vp, vp]
+    L.vt_crop_u8_frames.argtypes = [vp, vp, vp, C.c_double, i32, i32, vp, vp, vp]
+    L.vt_track_step_frames.argtypes = [vp, vp, vp, C.c_double, C.POINTER(C.c_float), C.POINTER(C.c_float), i32, vp, vp, vp, vp, i32, vp]
+    L.vt_set_template_slots.argtypes = [vp, vp, C.POINTER(i32), i32, vp]
     if precision == "f32":
         _lib = L
     else:
@@ -130,6 +135,125 @@ def _stream(stream):
     import torch
     s = stream if stream is not None else torch.cuda.current_stream()
     return C.c_void_p(s.cuda_stream)
+
+
+#: struct vt_frame (include/vittrack.h): {const uint8_t* data; int32_t H, W; int64_t pitch;}, 24 bytes
+FRAME_DTYPE = np.dtype([("data", "<u8"), ("H", "<i4"), ("W", "<i4"), ("pitch", "<i8")])
+assert FRAME_DTYPE.itemsize == 24
+#: frames packed into one arena start at multiples of this many bytes (vt_frame wants 4; 256 keeps every frame on its own cache lines)
+ARENA_ALIGN = 256
+
+
+def pack_offsets(shapes, start: int = 0, align: int = ARENA_ALIGN):
+    """Byte offsets of HWC uint8 frames of the given (H, W) shapes packed one after the other from `start`, each at a multiple of
+    `align`, rows at pitch 3 W.  Returns (offsets, end)."""
+    offs, o = [], int(start)
+    for H, W in shapes:
+        o = -(-o // align) * align
+        offs.append(o)
+        o += int(H) * int(W) * 3
+    return offs, o
+
+
+class FrameTable:
+    """The (B,) vt_frame descriptor table of vt_crop_frames / vt_track_step_frames (include/vittrack.h): one frame per sequence,
+    each with its own address, H, W and row pitch.  `host` is the numpy view of the descriptors; `dev`, when the table was made for
+    a device, is the (B * 24,) uint8 device tensor the kernels read (upload() copies host -> dev).  Every entry is checked on the
+    host before anything runs: HWC uint8 rows of 3 W contiguous bytes, pitch >= 3 W, a 4-byte-aligned address, and (buffers) the
+    frame inside its buffer."""
+
+    DTYPE = FRAME_DTYPE
+    ITEM = FRAME_DTYPE.itemsize
+
+    def __init__(self, B: int, device=None):
+        import torch
+        self.B = int(B)
+        pin = device is not None and torch.cuda.is_available()
+        self._host_t = torch.zeros(self.B * FRAME_DTYPE.itemsize, dtype=torch.uint8, pin_memory=pin)
+        self.host = self._host_t.numpy().view(FRAME_DTYPE)
+        self.dev = None if device is None else torch.zeros(self.B * FRAME_DTYPE.itemsize, dtype=torch.uint8, device=device)
+        self.keep = [None] * self.B          # tensors the descriptors point into (kept alive with the table)
+        self._copied = None                  # event of the last upload from the pinned host copy: set() waits for it
+
+    @staticmethod
+    def check(ptr: int, H: int, W: int, pitch: int = 0, nbytes: int | None = None):
+        """Validate one descriptor; returns the pitch actually used (0 -> 3 W).  nbytes: bytes available from ptr (a buffer)."""
+        H, W, pitch = int(H), int(W), int(pitch)
+        if H < 1 or W < 1:
+            raise VtError(f"frame of {H}x{W} pixels: H and W must be >= 1")
+        pitch = pitch or 3 * W
+        if pitch < 3 * W:
+            raise VtError(f"row pitch {pitch} is shorter than a row (3 W = {3 * W} bytes)")
+        if not ptr or int(ptr) % 4:
+            raise VtError(f"frame address {int(ptr or 0):#x} is not 4-byte aligned (vt_frame.data must be)")
+        need = pitch * (H - 1) + 3 * W
+        if need > 0xfffffff0:
+            raise VtError(f"a frame of {need} bytes is beyond the 32-bit offsets of the crop kernels")
+        if nbytes is not None and need > int(nbytes):
+            raise VtError(f"a {H}x{W} frame at pitch {pitch} needs {need} bytes, its buffer has {int(nbytes)}")
+        return pitch
+
+    def set(self, i: int, ptr: int, H: int, W: int, pitch: int = 0, nbytes: int | None = None, keep=None):
+        pitch = self.check(ptr, H, W, pitch, nbytes)
+        if self._copied is not None:         # the queued upload has not necessarily read the host copy yet
+            self._copied.synchronize()
+            self._copied = None
+        self.host[i] = (int(ptr), int(H), int(W), pitch)
+        self.keep[i] = keep
+
+    def set_tensor(self, i: int, frame, device_only: bool = True):
+        """Entry i from an (H, W, 3) uint8 tensor on the GPU or in pinned host memory: its rows may be strided (a crop of a larger
+        image), its pixels may not."""
+        import torch
+        if not (isinstance(frame, torch.Tensor) and frame.dtype == torch.uint8 and frame.dim() == 3 and frame.shape[2] == 3):
+            raise VtError("a frame must be an (H, W, 3) uint8 tensor")
+        if device_only and not (frame.is_cuda or frame.is_pinned()):
+            raise VtError("a frame must be on the GPU or in pinned host memory (the kernels read it in place)")
+        H, W = int(frame.shape[0]), int(frame.shape[1])
+        if frame.stride(2) != 1 or (W > 1 and frame.stride(1) != 3) or (H > 1 and frame.stride(0) < 3 * W):
+            raise VtError(f"frame strides {tuple(frame.stride())}: pixels must be 3 contiguous bytes, rows at least 3 W apart")
+        self.set(i, frame.data_ptr(), H, W, frame.stride(0) if H > 1 else 3 * W, keep=frame)
+
+    @classmethod
+    def of(cls, frames, device="cuda", stream=None):
+        """A table of a list of (H, W, 3) uint8 tensors (GPU or pinned), uploaded."""
+        t = cls(len(frames), device)
+        for i, f in enumerate(frames):
+            t.set_tensor(i, f)
+        t.upload(stream)
+        return t
+
+    def upload(self, stream=None):
+        import torch
+        if self.dev is None:
+            raise VtError("this FrameTable has no device copy")
+        with torch.cuda.stream(stream) if stream is not None else _nullctx():
+            self.dev.copy_(self._host_t, non_blocking=self._host_t.is_pinned())
+            if self._host_t.is_pinned():
+                self._copied = torch.cuda.Event()
+                self._copied.record()
+        return self.dev
+
+    def shapes(self):
+        return [(int(h), int(w)) for h, w in zip(self.host["H"], self.host["W"])]
+
+
+class _nullctx:
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        return False
+
+
+def _table_ptr(table, B):
+    """Device address of a (B,) vt_frame table: a FrameTable (its device copy) or a uint8 CUDA tensor of B * 24 bytes."""
+    import torch
+    t = table.dev if isinstance(table, FrameTable) else table
+    if not (isinstance(t, torch.Tensor) and (t.is_cuda or t.is_pinned()) and t.numel() * t.element_size() >= B * FRAME_DTYPE.itemsize
+            and t.is_contiguous()):
+        raise VtError(f"frame table must be a FrameTable with a device copy or a contiguous tensor of {B} x 24 bytes on the GPU")
+    return C.c_void_p(t.data_ptr())
 
 
 def crop_form() -> int:
@@ -437,6 +561,70 @@ class Model:
         _check(self._L.vt_crop_u8(self._h, C.c_void_p(frames.data_ptr()), H, W, C.c_void_p(states.data_ptr()), float(factor), out_size, B,
                                 _stream(stream), C.c_void_p(out.data_ptr()), C.c_void_p(resize_factor.data_ptr())), "vt_crop_u8", self._L)
         return out, resize_factor
+
+    # ---- frame tables: one frame of its own size per sequence (vt_crop_frames & co.)
+    def _table_args(self, states, out_shape, out_dtype, out, resize_factor):
+        import torch
+        if not (states.is_cuda and states.dtype == torch.float64 and states.is_contiguous() and states.dim() == 2 and states.shape[1] == 4):
+            raise VtError("states must be a contiguous (B,4) float64 tensor on the GPU")
+        B = int(states.shape[0])
+        if out is None:
+            out = torch.empty((B,) + out_shape, dtype=out_dtype, device=states.device)
+        elif tuple(out.shape) != (B,) + out_shape or out.dtype != out_dtype or not out.is_cuda or not out.is_contiguous():
+            raise VtError(f"crop output must be a contiguous {(B,) + out_shape} {out_dtype} tensor on the GPU")
+        if resize_factor is None:
+            resize_factor = torch.empty(B, dtype=torch.float64, device=states.device)
+        elif tuple(resize_factor.shape) != (B,) or resize_factor.dtype != torch.float64 or not resize_factor.is_cuda:
+            raise VtError(f"resize_factor must be a ({B},) float64 tensor on the GPU")
+        return B, out, resize_factor
+
+    def crop_frames(self, table, states, factor, out_size, mean, std, out=None, resize_factor=None, stream=None):
+        """crop() with a frame table (FrameTable / vt_crop_frames): sequence b is cropped from its own frame."""
+        import torch
+        B, out, resize_factor = self._table_args(states, (3, out_size, out_size), torch.float32, out, resize_factor)
+        m3 = (C.c_float * 3)(*[float(v) for v in mean])
+        s3 = (C.c_float * 3)(*[float(v) for v in std])
+        _check(self._L.vt_crop_frames(self._h, _table_ptr(table, B), C.c_void_p(states.data_ptr()), float(factor), out_size, m3, s3, B,
+                                    _stream(stream), _ptr(out), C.c_void_p(resize_factor.data_ptr())), "vt_crop_frames", self._L)
+        return out, resize_factor
+
+    def crop_u8_frames(self, table, states, factor, out_size, out=None, resize_factor=None, stream=None):
+        """crop_u8() with a frame table (vt_crop_u8_frames)."""
+        import torch
+        B, out, resize_factor = self._table_args(states, (out_size, out_size, 3), torch.uint8, out, resize_factor)
+        _check(self._L.vt_crop_u8_frames(self._h, _table_ptr(table, B), C.c_void_p(states.data_ptr()), float(factor), out_size, B,
+                                       _stream(stream), C.c_void_p(out.data_ptr()), C.c_void_p(resize_factor.data_ptr())),
+               "vt_crop_u8_frames", self._L)
+        return out, resize_factor
+
+    def track_step_frames(self, table, states, factor, mean, std, x, resize_factor, out: Outputs, record=None, margin=10, stream=None):
+        """track_step() with a frame table (vt_track_step_frames): each sequence is cropped from, and clipped to, its own frame."""
+        import torch
+        B = self._check_x_only(x)
+        if (tuple(states.shape) != (B, 4) or states.dtype != torch.float64 or not states.is_cuda or not states.is_contiguous()
+                or tuple(resize_factor.shape) != (B,) or resize_factor.dtype != torch.float64 or not resize_factor.is_cuda):
+            raise VtError(f"track_step_frames wants states ({B},4) and resize_factor ({B},) float64 on the GPU")
+        if record is not None and (tuple(record.shape) != (B, 5) or record.dtype != torch.float64 or not record.is_contiguous()
+                                   or not (record.is_cuda or record.is_pinned())):
+            raise VtError(f"record must be a contiguous ({B},5) float64 tensor on the GPU or in pinned host memory")
+        self._check_out(out, B)
+        st = out.struct()
+        m3 = (C.c_float * 3)(*[float(v) for v in mean])
+        s3 = (C.c_float * 3)(*[float(v) for v in std])
+        _check(self._L.vt_track_step_frames(self._h, _table_ptr(table, B), C.c_void_p(states.data_ptr()), float(factor), m3, s3, B,
+                                          _stream(stream), _ptr(x), C.c_void_p(resize_factor.data_ptr()), C.byref(st), margin,
+                                          C.c_void_p(record.data_ptr()) if record is not None else None), "vt_track_step_frames", self._L)
+        return out
+
+    def set_template_slots(self, z, slots, stream=None):
+        """Rewrite the template cache of the given slots only (vt_set_template_slots): z (n,3,Tz,Tz) fp32 on the GPU, slots n
+        distinct indices below the cached batch.  Not capturable."""
+        slots = [int(v) for v in slots]
+        n = len(slots)
+        if z is None or tuple(z.shape) != (n, 3, self.template_size, self.template_size):
+            raise VtError(f"expected z ({n},3,{self.template_size},{self.template_size}) for {n} slots")
+        arr = (C.c_int32 * max(n, 1))(*slots)
+        _check(self._L.vt_set_template_slots(self._h, _ptr(z), arr, n, _stream(stream)), "vt_set_template_slots", self._L)
 
     def set_normalization(self, mean, std):
         """Preprocessor's mean / std for the uint8 entry points (folded into the stem's first layer; default: ImageNet)."""
