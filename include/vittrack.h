@@ -238,6 +238,50 @@ int vt_crop_u8_frames(vt_model* m, const vt_frame* frames_dev, const double* sta
 int vt_track_step_frames(vt_model* m, const vt_frame* frames_dev, double* states_dev, double factor, const float* mean3,
                          const float* std3, int32_t B, void* stream, float* crops_dev, double* resize_factor_dev, const vt_outputs* out,
                          int32_t margin, double* record);
+/* --- frames in the pixel formats decoders and capture pipelines hand out: one vt_image descriptor per sequence ---------------
+ * Each descriptor denotes one H x W 8-bit RGB image rgb(d); vt_crop_images, vt_crop_u8_images and vt_track_step_images give, bit for
+ * bit, what their *_frames twins give on a tight vt_frame holding rgb(d).  Only the fetch of a source pixel differs: every bilinear
+ * tap pixel is converted to RGB first, then the crop's arithmetic runs unchanged.
+ *   format     planes                                          rgb(d) at pixel (x, y)
+ *   RGB        plane0: H rows of 3 W bytes                     bytes 0, 1, 2 of the pixel (as vt_frame)
+ *   BGR        plane0: H rows of 3 W bytes                     bytes 2, 1, 0 (cv.cvtColor(f, cv.COLOR_BGR2RGB))
+ *   RGBA       plane0: H rows of 4 W bytes                     bytes 0, 1, 2; the 4th byte is never used
+ *   BGRA       plane0: H rows of 4 W bytes                     bytes 2, 1, 0; the 4th byte is never used
+ *   NV12/NV21  plane0: H rows of W luma bytes; plane1: H/2     BT.601 limited range, each 2 x 2 block sharing one chroma pair (no
+ *              rows of W/2 byte pairs, (U,V) for NV12 and      chroma interpolation), in the fixed-point arithmetic of OpenCV's
+ *              (V,U) for NV21; H and W even                    cv.cvtColor(f, cv.COLOR_YUV2RGB_NV12 / _NV21), int32, >> arithmetic:
+ *       Y = luma[y][x];  U, V = chroma pair at row y >> 1, pair x >> 1;  yy = max(Y - 16, 0) * 1220542
+ *       R = clamp((yy + 1673527 (V - 128)                  + (1 << 19)) >> 20, 0, 255)
+ *       G = clamp((yy -  852492 (V - 128) - 409993 (U - 128) + (1 << 19)) >> 20, 0, 255)
+ *       B = clamp((yy + 2116026 (U - 128)                  + (1 << 19)) >> 20, 0, 255)
+ *     (1.164, 1.596, 0.813, 0.391 and 2.018 times 2^20, written down from OpenCV's ITUR_BT_601_* constants; a GPU test compares them
+ *     with cv2.cvtColor where cv2 is installed.)  BT.709, full range and I420 are not supported.
+ *   pitch0 / pitch1: bytes between rows of plane0 / plane1, >= the row's bytes (0 = the row's bytes).  A plane is [plane, plane +
+ *   pitch (rows - 1) + row bytes); nothing outside it is read.  plane1 / pitch1 are unused by the one-plane formats.
+ * Planes: device memory or device-mapped pinned host memory.  The table (B,) lives there too and is read when the kernels run: a
+ * graph captured on it stays valid when its contents -- pointers, sizes, formats -- change between replays.  A table may mix formats.
+ * A descriptor is unusable -- treated as a too-small box: NaN resize factor, zero (uint8) or NaN (fp32) patch, nothing read through
+ * it, the other sequences unaffected -- when its format is unknown or `reserved` is not 0, a plane it needs is null or not 4-byte
+ * aligned, a pitch is below the row's bytes, H or W is < 1 (or odd for NV12 / NV21), or a plane does not fit a 32-bit offset. */
+enum { VT_PIX_RGB = 0, VT_PIX_BGR = 1, VT_PIX_RGBA = 2, VT_PIX_BGRA = 3, VT_PIX_NV12 = 4, VT_PIX_NV21 = 5 };
+typedef struct vt_image {
+    const uint8_t* plane0;
+    const uint8_t* plane1;
+    int64_t pitch0, pitch1;
+    int32_t H, W, format, reserved;
+} vt_image;
+
+/* vt_crop_frames on a (B,) vt_image table. */
+int vt_crop_images(vt_model* m, const vt_image* images_dev, const double* states_dev, double factor, int32_t out_size,
+                   const float* mean3, const float* std3, int32_t B, void* stream, float* crops_dev, double* resize_factor_dev);
+/* vt_crop_u8_frames on a (B,) vt_image table. */
+int vt_crop_u8_images(vt_model* m, const vt_image* images_dev, const double* states_dev, double factor, int32_t out_size, int32_t B,
+                      void* stream, uint8_t* patch_dev, double* resize_factor_dev);
+/* vt_track_step_frames on a (B,) vt_image table: the same routes, models and open loop; the tail clips each sequence against
+ * images_dev[b].H / W. */
+int vt_track_step_images(vt_model* m, const vt_image* images_dev, double* states_dev, double factor, const float* mean3,
+                         const float* std3, int32_t B, void* stream, float* crops_dev, double* resize_factor_dev, const vt_outputs* out,
+                         int32_t margin, double* record);
 /* Restart single sequences (Vit_dist.initialize, lib/test/tracker/vit_dist.py:52-65, for slots whose sequence ended while the
  * others go on): rewrite the template cache rows of slots[0..n) from z_dev (n,3,Tz,Tz), under the form batch the cache was written
  * with -- afterwards a slot's rows are exactly what vt_set_template would have written for that template at that slot, bit for bit.

@@ -1,0 +1,251 @@
+#!/usr/bin/env python3
+"""Pixel formats on the device: what reading NV12 / NV21, BGR and RGBA / BGRA directly costs against RGB.
+
+    python tools/frame_formats.py [--batch 256] [--rounds 5] [--reps 20] [--distinct 32]
+
+Fixed seeds, 1920 x 1080 frames (`--distinct` different frames, cycled over the sequences) with 30-120 px boxes:
+  crop_us[T][form]        B = 256: the uint8 table crop per launch, T = 128 and 256: "rgb_frames" is vt_crop_u8_frames on the RGB
+                          frames, every other form vt_crop_u8_images on that format
+  step_us[G][form]        B = 256: the G128 / G256 tracker step in open loop (vt_set_open_loop): vt_track_step_frames on RGB against
+                          vt_track_step_images on NV12
+  small_batch_us          B = 1 (the plugin's per-frame step and small template crops, which take crop_image_kernel: single-byte
+                          tap fetches): the T = 128 uint8 crop and the G128 step, frame route on RGB against the image route
+  convert_step_us[G]      B = 256: the caller's alternative without this route: the whole NV12 frames converted to RGB with unfused
+                          int32 torch ops (one kernel per op), then vt_track_step_frames
+Method: every form is a captured graph (`--reps` launches for a crop, one step for a step; outputs preallocated, no host work
+inside); the forms are timed in `--rounds` interleaved rounds (the order rotates every round), each a host-timed region of replays
+with one synchronisation, and the best round of each form is reported.  The shader clock is probed (vt_probe_clock, a dense MFMA
+loop) before and after.  Prints one JSON line."""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
+sys.path.insert(0, ROOT)
+MEAN, STD = [0.485, 0.456, 0.406], [0.229, 0.224, 0.225]
+H, W = 1080, 1920
+FORMATS = ("rgb", "bgr", "rgba", "bgra", "nv12", "nv21")
+
+
+def _model(geom, B):
+    from vittracker_amd import native, synth
+    m = native.Model(geom // 2, geom, max_batch=B)
+    m.load_state_dict(synth.synth_state_dict(0, len_z=(geom // 32) ** 2, len_x=(geom // 16) ** 2))
+    return m
+
+
+def _capture(fn):
+    """fn(stream) captured into a graph (after one eager warm-up call)."""
+    import torch
+    fn(torch.cuda.current_stream())
+    torch.cuda.synchronize()
+    g = torch.cuda.CUDAGraph()
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.graph(g, stream=side):
+        fn(torch.cuda.current_stream())
+    torch.cuda.current_stream().wait_stream(side)
+    torch.cuda.synchronize()
+    return g
+
+
+def _interleaved(graphs, per_replay, rounds, replays):
+    """{name: best us per unit} over `rounds` interleaved rounds of `replays` replays each; `per_replay` units per replay."""
+    import torch
+    best = {}
+    names = list(graphs)
+    for g in graphs.values():           # warm-up
+        g.replay()
+    torch.cuda.synchronize()
+    for r in range(rounds):
+        order = names[r % len(names):] + names[:r % len(names)]
+        for name in order:
+            g = graphs[name]
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(replays):
+                g.replay()
+            torch.cuda.synchronize()
+            us = (time.perf_counter() - t0) / (replays * per_replay) * 1e6
+            best[name] = min(best.get(name, 1e30), us)
+    return {k: round(v, 2) for k, v in best.items()}
+
+
+def _planes(fmt, n, g):
+    """n frames in `fmt`, as device tensors (random bytes: the content does not change the cost)."""
+    import torch
+    mk = lambda *s: torch.randint(0, 256, s, dtype=torch.uint8, device="cuda", generator=g)      # noqa: E731
+    if fmt in ("rgb", "bgr"):
+        return [(mk(H, W, 3),) for _ in range(n)]
+    if fmt in ("rgba", "bgra"):
+        return [(mk(H, W, 4),) for _ in range(n)]
+    return [(mk(H, W), mk(H // 2, W // 2, 2)) for _ in range(n)]
+
+
+def _nv12_to_rgb(y, uv):
+    """The whole frames (n, H, W) / (n, H/2, W/2, 2) -> (n, H, W, 3) uint8 with unfused int32 torch ops: BT.601 limited range,
+    OpenCV's fixed point."""
+    import torch
+    Y = (y.to(torch.int32) - 16).clamp_min_(0) * 1220542
+    c = uv.to(torch.int32) - 128
+    c = c.repeat_interleave(2, dim=1).repeat_interleave(2, dim=2)
+    u, v = c[..., 0], c[..., 1]
+    r = (Y + 1673527 * v + (1 << 19)) >> 20
+    gg = (Y - 852492 * v - 409993 * u + (1 << 19)) >> 20
+    b = (Y + 2116026 * u + (1 << 19)) >> 20
+    return torch.stack([r, gg, b], dim=-1).clamp_(0, 255).to(torch.uint8)
+
+
+def _tables(frames, B, n):
+    from vittracker_amd.native import FrameTable, Image, ImageTable
+    tabs = {}
+    for f in FORMATS:
+        t = ImageTable(B, "cuda")
+        for b in range(B):
+            t.set_image(b, getattr(Image, f)(*frames[f][b % n]))
+        t.upload()
+        tabs[f] = t
+    ftab = FrameTable(B, "cuda")
+    for b in range(B):
+        ftab.set_tensor(b, frames["rgb"][b % n][0])
+    ftab.upload()
+    return tabs, ftab
+
+
+def _step_graphs(m, S, B, states, forms):
+    """{name: captured open-loop step} for forms {name: (native method, table)}."""
+    import torch
+    from vittracker_amd.native import Outputs
+    m.set_open_loop(True)         # held boxes: every form crops the same windows every step
+    m.set_template(torch.zeros(B, 3, S // 2, S // 2, device="cuda"))
+    x = torch.empty(B, 3, S, S, device="cuda")
+    rf = torch.empty(B, dtype=torch.float64, device="cuda")
+    out = Outputs(B, S // 16, "cuda")
+    rec = torch.empty(B, 5, dtype=torch.float64, device="cuda")
+    graphs = {name: _capture(lambda cs, f=f, t=t: f(t, states, 4.0, MEAN, STD, x, rf, out, record=rec, stream=cs))
+              for name, (f, t) in forms.items()}
+    return graphs, (x, rf, out, rec)
+
+
+def main():
+    import torch
+    from vittracker_amd import native
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--batch", type=int, default=256)
+    ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--replays", type=int, default=10)
+    ap.add_argument("--distinct", type=int, default=32)
+    a = ap.parse_args()
+    torch.cuda.set_device(0)
+    B, n = a.batch, a.distinct
+    clock0 = native.probe_clock(20000, 1)[0]
+    g = torch.Generator(device="cuda")
+    g.manual_seed(0)
+    rs = np.random.RandomState(0)
+    states = torch.tensor([[rs.uniform(120, W - 240), rs.uniform(120, H - 240), rs.uniform(30, 120), rs.uniform(30, 120)] for _ in range(B)],
+                          dtype=torch.float64).cuda()
+    frames = {f: _planes(f, n, g) for f in FORMATS}
+    tabs, ftab = _tables(frames, B, n)
+    res = {"B": B, "frame": [H, W], "distinct_frames": n, "rounds": a.rounds, "crop_us": {}, "step_us": {}, "small_batch_us": {},
+           "convert_step_us": {}}
+    # (1) crops, B sequences
+    m = _model(128, B)
+    for T in (128, 256):
+        outs = {}
+
+        def crop_form(name, t):
+            o = torch.empty(B, T, T, 3, dtype=torch.uint8, device="cuda")
+            rf = torch.empty(B, dtype=torch.float64, device="cuda")
+            outs[name] = (o, rf)
+            call = m.crop_u8_frames if name == "rgb_frames" else m.crop_u8_images
+
+            def fn(cs):
+                for _ in range(a.reps):
+                    call(t, states, 4.0, T, out=o, resize_factor=rf, stream=cs)
+            return _capture(fn)
+        graphs = {"rgb_frames": crop_form("rgb_frames", ftab)}
+        graphs.update({f: crop_form(f, tabs[f]) for f in FORMATS})
+        row = _interleaved(graphs, a.reps, a.rounds, a.replays)
+        row["ratio_vs_rgb_frames"] = {f: round(row[f] / row["rgb_frames"], 3) for f in FORMATS}
+        res["crop_us"][str(T)] = row
+    del m
+    # (2) the tracker step, B sequences, NV12 against RGB, in interleaved rounds
+    for S in (128, 256):
+        m = _model(S, B)
+        graphs, keep = _step_graphs(m, S, B, states, {"rgb_frames": (m.track_step_frames, ftab), "nv12": (m.track_step_images, tabs["nv12"])})
+        row = _interleaved(graphs, 1, a.rounds, a.replays * 5)
+        row["nv12_rate_vs_rgb"] = round(row["rgb_frames"] / row["nv12"], 3)
+        res["step_us"][f"G{S}"] = row
+        del m, graphs, keep
+    # (3) small batches: B = 1, the plugin's form (crop_image_kernel against crop_fast_kernel)
+    st1 = states[:1].contiguous()
+    t1 = {f: _one_table(frames, f) for f in ("rgb", "bgr", "nv12")}
+    f1 = native.FrameTable(1, "cuda")
+    f1.set_tensor(0, frames["rgb"][0][0])
+    f1.upload()
+    m = _model(128, 1)
+    o1 = torch.empty(1, 128, 128, 3, dtype=torch.uint8, device="cuda")
+    r1 = torch.empty(1, dtype=torch.float64, device="cuda")
+
+    def crop1(call, t):
+        def fn(cs):
+            for _ in range(a.reps):
+                call(t, st1, 4.0, 128, out=o1, resize_factor=r1, stream=cs)
+        return _capture(fn)
+    graphs = {"crop_rgb_frames": crop1(m.crop_u8_frames, f1)}
+    graphs.update({f"crop_{f}": crop1(m.crop_u8_images, t) for f, t in t1.items()})
+    row = _interleaved(graphs, a.reps, a.rounds, a.replays)
+    graphs, keep = _step_graphs(m, 128, 1, st1, {"step_rgb_frames": (m.track_step_frames, f1), "step_bgr": (m.track_step_images, t1["bgr"]),
+                                                   "step_nv12": (m.track_step_images, t1["nv12"])})
+    row.update(_interleaved(graphs, 1, a.rounds, a.replays * 5))
+    res["small_batch_us"] = {"B": 1, "T": 128, "geom": "G128", **row}
+    del m, graphs, keep
+    # (4) the alternative: whole frames converted with torch ops, then the frame-table step
+    idx = torch.arange(B, device="cuda") % n
+    ys = torch.stack([p[0] for p in frames["nv12"]])[idx]
+    uvs = torch.stack([p[1] for p in frames["nv12"]])[idx]
+    rgb_all = torch.empty(B, H, W, 3, dtype=torch.uint8, device="cuda")
+    ctab = native.FrameTable(B, "cuda")
+    for b in range(B):
+        ctab.set_tensor(b, rgb_all[b])
+    ctab.upload()
+    for S in (128, 256):
+        m = _model(S, B)
+        graphs, (x, rf, out, rec) = _step_graphs(m, S, B, states, {"nv12": (m.track_step_images, tabs["nv12"])})
+
+        def convert_then_step():
+            rgb_all.copy_(_nv12_to_rgb(ys, uvs))
+            m.track_step_frames(ctab, states, 4.0, MEAN, STD, x, rf, out, record=rec)
+        best = 1e30
+        for _ in range(3):
+            convert_then_step()
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(5):
+                convert_then_step()
+            torch.cuda.synchronize()
+            best = min(best, (time.perf_counter() - t0) / 5 * 1e6)
+        nv = _interleaved(graphs, 1, a.rounds, a.replays * 5)["nv12"]
+        res["convert_step_us"][f"G{S}"] = {"torch_int32_convert_then_step": round(best, 2), "nv12_step": nv, "speedup": round(best / nv, 2)}
+        del m, graphs
+    clock1 = native.probe_clock(20000, 1)[0]
+    res["clock_mhz"] = [round(clock0), round(clock1)]
+    print(json.dumps(res))
+
+
+def _one_table(frames, fmt):
+    """A one-entry image table on frame 0 of `fmt`."""
+    from vittracker_amd.native import Image, ImageTable
+    t = ImageTable(1, "cuda")
+    t.set_image(0, getattr(Image, fmt)(*frames[fmt][0]))
+    t.upload()
+    return t
+
+
+if __name__ == "__main__":
+    main()

@@ -18,7 +18,7 @@ import numpy as np
 from .config import geometry
 from .host_ops import hann2d
 from .model import build_ostrack_dist
-from .native import FrameTable, VtError, pack_offsets
+from .native import FrameTable, Image, ImageTable, VtError, pack_image_offsets, pack_offsets
 
 
 def check_params_geometry(params, nat):
@@ -79,6 +79,9 @@ class BatchedVitTracker:
         self._arena = None           # (capacity, pinned host uint8 tensor, device uint8 tensor, event of the last arena copy)
         self._dev_table = None       # FrameTable of caller-owned device frames
         self._frames_graphs = {}     # device table address -> (graph, device record, pinned host record, table)
+        # frames in other pixel formats (vt_track_step_images): a pinned arena and its device twin, [vt_image table | host planes]
+        self._img_arena = None       # (capacity, pinned host uint8 tensor, device uint8 tensor, event of the last arena copy)
+        self._images_graphs = {}     # device table address -> (graph, device record, pinned host record, table)
 
     # ---- frames of different sizes ------------------------------------------------------------------------------------
     @staticmethod
@@ -133,11 +136,72 @@ class BatchedVitTracker:
         self._arena = (cap, host, dev, ev)
         return dev[:tb]
 
-    def _frames_graph(self, tab):
-        """The whole step on a frame table (vt_track_step_frames -> record), captured once per table address: the table's contents
-        change between replays, its address does not."""
+    # ---- frames in other pixel formats (NV12 / NV21, BGR, RGBA / BGRA) ---------------------------------------------------------
+    @staticmethod
+    def _has_image(frames):
+        """A list / tuple of frames of which at least one is an Image: the image-table path.  Lists without one take today's routes."""
+        return isinstance(frames, (list, tuple)) and any(isinstance(f, Image) for f in frames)
+
+    @staticmethod
+    def _as_image(f):
+        """An Image as it is; an RGB frame (host array or CUDA tensor) as Image.rgb."""
         import torch
-        hit = self._frames_graphs.get(tab.data_ptr())
+        if isinstance(f, Image):
+            return f
+        if isinstance(f, torch.Tensor) and not f.is_cuda:
+            f = f.numpy()
+        return Image.rgb(f)
+
+    def _image_table(self, frames):
+        """The device vt_image table of B frames of any formats and sizes.  Device images go in by pointer; the planes of host images
+        are packed into a pinned arena at 256-byte offsets behind the table and reach the device arena, table included, with ONE
+        copy.  The arena grows by doubling; each capacity has its own table address, hence its own captured step."""
+        import torch
+        if len(frames) != self.B:
+            raise ValueError(f"expected {self.B} frames, got {len(frames)}")
+        ims = [self._as_image(f) for f in frames]
+        tb = self.B * ImageTable.ITEM
+        host_ims = [im for im in ims if not im.is_cuda]
+        offs, end = pack_image_offsets(host_ims, start=tb)
+        if self._img_arena is None or self._img_arena[0] < end:
+            cap = max(end, 2 * self._img_arena[0] if self._img_arena is not None else end)
+            torch.cuda.current_stream().synchronize()       # nothing may still read the old arena
+            if self._img_arena is not None:
+                self._images_graphs.pop(self._img_arena[2].data_ptr(), None)
+            self._img_arena = (cap, torch.empty(cap, dtype=torch.uint8).pin_memory(), torch.empty(cap, dtype=torch.uint8, device="cuda"), None)
+            self._img_np = self._img_arena[1].numpy()
+        cap, host, dev, ev = self._img_arena
+        if ev is not None:
+            ev.synchronize()                                  # the previous copy out of the pinned arena has been read
+        tab = self._img_np[:tb].view(ImageTable.DTYPE)
+        base = dev.data_ptr()
+        self._img_keep = [im for im in ims if im.is_cuda]     # device planes the step reads in place
+        it = iter(offs)
+        for i, im in enumerate(ims):
+            if im.is_cuda:
+                d = im.descriptor()
+            else:
+                po = next(it)
+                rows = im.plane_rows()
+                for a, o, (n, rb) in zip(im.planes, po, rows):
+                    self._img_np[o:o + n * rb].reshape(n, rb)[...] = np.asarray(a).reshape(n, rb)
+                d = im.descriptor([base + o for o in po], [rb for _, rb in rows])
+                ImageTable.check(d[6], d[0], d[1], d[4], d[5], d[2], d[3], 0, nbytes0=cap - po[0],
+                                 nbytes1=cap - po[1] if len(po) > 1 else None)
+            if im.is_cuda:
+                ImageTable.check(d[6], d[0], d[1], d[4], d[5], d[2], d[3])
+            tab[i] = d
+        dev[:end].copy_(host[:end], non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record()
+        self._img_arena = (cap, host, dev, ev)
+        return dev[:tb]
+
+    def _table_graph(self, graphs, step, tab):
+        """The whole step on a descriptor table (`step`: nat.track_step_frames or nat.track_step_images -> record), captured once per
+        table address in `graphs`: the table's contents change between replays, its address does not."""
+        import torch
+        hit = graphs.get(tab.data_ptr())
         if hit is not None:
             return hit
         rec = torch.empty(self.B, 5, dtype=torch.float64, device="cuda")
@@ -146,22 +210,31 @@ class BatchedVitTracker:
         side = torch.cuda.Stream()
         side.wait_stream(torch.cuda.current_stream())
         with torch.cuda.graph(g, stream=side):
-            self.nat.track_step_frames(tab, self.states, self.params.search_factor, self.mean, self.std, self.x, self.rf, self.out,
-                                       record=rec, margin=10, stream=torch.cuda.current_stream())
+            step(tab, self.states, self.params.search_factor, self.mean, self.std, self.x, self.rf, self.out,
+                 record=rec, margin=10, stream=torch.cuda.current_stream())
         torch.cuda.current_stream().wait_stream(side)
-        self._frames_graphs[tab.data_ptr()] = (g, rec, host, tab)
-        return self._frames_graphs[tab.data_ptr()]
+        graphs[tab.data_ptr()] = (g, rec, host, tab)
+        return graphs[tab.data_ptr()]
 
-    def _track_mixed(self, frames, sync):
-        if self.graph is None:
-            raise VtError("track before initialize")
-        g, rec, host, _ = self._frames_graph(self._frame_table(frames))
+    def _track_table(self, graphs, step, tab, sync):
+        """One replay of the step on a descriptor table (frame table or image table)."""
+        g, rec, host, _ = self._table_graph(graphs, step, tab)
         g.replay()
         self.frame_id += 1
         if sync:
             r = self._records(rec, host)
             return {"target_bbox": r[:, :4], "confidence": r[:, 4].float()}
         return {"target_bbox": self.states, "confidence": self.out.conf, "record": rec}
+
+    def _track_images(self, frames, sync):
+        if self.graph is None:
+            raise VtError("track before initialize")
+        return self._track_table(self._images_graphs, self.nat.track_step_images, self._image_table(frames), sync)
+
+    def _track_mixed(self, frames, sync):
+        if self.graph is None:
+            raise VtError("track before initialize")
+        return self._track_table(self._frames_graphs, self.nat.track_step_frames, self._frame_table(frames), sync)
 
     def reinitialize(self, slots, frames, boxes):
         """Restart the sequences of `slots` on new frames and boxes (Vit_dist.initialize, lib/test/tracker/vit_dist.py:52-65) while
@@ -183,12 +256,22 @@ class BatchedVitTracker:
         for f in (self.params.template_factor, self.params.search_factor):
             if not np.all(np.ceil(np.sqrt(boxes[:, 2] * boxes[:, 3]) * f) >= 1):
                 raise Exception("Too small bounding box.")   # processing_utils.py:33-34
-        dev = [f if isinstance(f, torch.Tensor) and f.is_cuda else torch.from_numpy(np.ascontiguousarray(f)).cuda() for f in frames]
-        tab = FrameTable.of(dev)
         st = torch.as_tensor(boxes).cuda()
         z = torch.empty(n, 3, self.params.template_size, self.params.template_size, device="cuda")
         rf = torch.empty(n, dtype=torch.float64, device="cuda")
-        self.nat.crop_frames(tab, st, self.params.template_factor, self.params.template_size, self.mean, self.std, out=z, resize_factor=rf)
+        if self._has_image(frames):       # Images (any format): their planes on the device, one vt_image table
+            ims = []
+            for f in map(self._as_image, frames):
+                if not f.is_cuda:
+                    f = Image(f.format, [torch.from_numpy(np.ascontiguousarray(a)).cuda() for a in f.planes], f.H, f.W,
+                              [rb for _, rb in f.plane_rows()])
+                ims.append(f)
+            tab = ImageTable.of(ims)
+            self.nat.crop_images(tab, st, self.params.template_factor, self.params.template_size, self.mean, self.std, out=z, resize_factor=rf)
+        else:
+            dev = [f if isinstance(f, torch.Tensor) and f.is_cuda else torch.from_numpy(np.ascontiguousarray(f)).cuda() for f in frames]
+            tab = FrameTable.of(dev)
+            self.nat.crop_frames(tab, st, self.params.template_factor, self.params.template_size, self.mean, self.std, out=z, resize_factor=rf)
         idx = torch.as_tensor(slots, device="cuda")
         self.states.index_copy_(0, idx, st)
         self.z.index_copy_(0, idx, z)
@@ -251,11 +334,13 @@ class BatchedVitTracker:
         self._slot_done[k].record()
 
     def initialize(self, frames, init_boxes):
-        """frames: (B,H,W,3) uint8 (numpy, list of arrays or CUDA tensor) -- or a list of B frames of different sizes;
+        """frames: (B,H,W,3) uint8 (numpy, list of arrays or CUDA tensor) -- or a list of B frames of different sizes, any of which
+        may be a native.Image (NV12 / NV21, BGR, RGBA / BGRA, RGB);
         init_boxes: (B,4) [x,y,w,h]."""
         import torch
-        mixed = self._is_mixed(frames)
-        fr = self._frame_table(frames) if mixed else self._upload(frames)
+        images = self._has_image(frames)
+        mixed = not images and self._is_mixed(frames)
+        fr = self._image_table(frames) if images else (self._frame_table(frames) if mixed else self._upload(frames))
         boxes = np.asarray(init_boxes, dtype=np.float64)
         if boxes.shape != (self.B, 4):
             raise ValueError(f"init_boxes must be (B={self.B}, 4) [x, y, w, h]")
@@ -264,7 +349,10 @@ class BatchedVitTracker:
             if not np.all(side >= 1):         # also catches NaN / negative sizes
                 raise Exception("Too small bounding box.")   # processing_utils.py:33-34
         self.states.copy_(torch.as_tensor(boxes))
-        if mixed:
+        if images:
+            self.nat.crop_images(fr, self.states, self.params.template_factor, self.params.template_size, self.mean, self.std,
+                                 out=self.z, resize_factor=self.rf)
+        elif mixed:
             self.nat.crop_frames(fr, self.states, self.params.template_factor, self.params.template_size, self.mean, self.std,
                                  out=self.z, resize_factor=self.rf)
         else:
@@ -288,6 +376,7 @@ class BatchedVitTracker:
         self.nat.set_open_loop(bool(on))
         self._chunk_graphs.clear()      # the flag is an argument of the captured kernels
         self._frames_graphs.clear()
+        self._images_graphs.clear()
         self._fast = [None, None]
 
     def track_record(self, frames):
@@ -321,6 +410,8 @@ class BatchedVitTracker:
         as CPU tensors when sync=True, else the device tensors (valid until the next call)."""
         if self.graph is None:
             raise VtError("track before initialize")
+        if self._has_image(frames):     # frames in other pixel formats: one step on an image table
+            return self._track_images(frames, sync)
         if self._is_mixed(frames):      # B frames of different sizes: one step on a frame table
             return self._track_mixed(frames, sync)
         fr = self._upload(frames)

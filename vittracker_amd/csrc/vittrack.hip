@@ -108,6 +108,7 @@ struct vt_model {
     int blocks_tile = -1;            // 1 / 0 force the tile-parallel form of the blocks / forbid it, -1 (default): by batch size
     int open_loop = 0;               // vt_set_open_loop: vt_track_step leaves states_dev untouched (the step's box is in `record`)
     DevBuf zcache;                   // block-0 q / k / v^T images of the template tiles (vt_set_template)
+    DevBuf imsizes;                  // vt_track_step_images: (max_batch,) vt_frame sizes of the step's descriptors, written by its crop for the tail
     DevBuf zstage;                   // vt_set_template_slots: the new slots' cache rows, staged before they are copied into place (allocated on first use)
     DevBuf vlscr;                    // G256 frame-form block kernel (A3): the low pieces of V^T, [B][depth][3][L / 32][64] x 16 B (vt_blocks.h VP2L)
     int tmpl_frames = 0;             // frames whose template rows (tokens + zcache) are cached
@@ -1020,6 +1021,48 @@ void launch_crop(bool bytes, const unsigned char* frames, int H, int W, const do
     else launch_crop_forms(std::false_type{}, bytes, frames, H, W, states, factor, T, mean3, std3, B, st, crops, rf, u8out);
 }
 
+// The crop on a (B,) vt_image table (vt_crop_images & co.): crop_band_image_kernel where launch_crop_forms takes crop_band_kernel (the
+// tracker's sizes, bands filling the chip; the same VT_CROP_BAND settings), crop_image_kernel otherwise.  Neither form depends on the
+// device's unaligned-access mode (dword-aligned windows, or single bytes), so crop_selftest's choice does not apply.  sizes: null, or
+// a (B,) vt_frame table that receives each descriptor's H and W (the tracker tail's clip).
+void launch_crop_images(const vt_image* images, vt_frame* sizes, const double* states, double factor, int T, const float* mean3,
+                        const float* std3, int B, hipStream_t st, float* crops, double* rf, bool u8out) {
+    static const float none3[3] = {0.f, 1.f, 1.f};
+    if (u8out) mean3 = std3 = none3;
+    static const int band = [] { const char* v = std::getenv("VT_CROP_BAND"); return v && *v ? std::atoi(v) : 4; }();
+    static const bool band_set = [] { const char* v = std::getenv("VT_CROP_BAND"); return v && *v; }();
+    const long items = (long)B * T * (T / 4);
+    const bool bands_fill = band < 0 || items >= 2L * 256 * 256;
+    if (band != 0 && bands_fill && (T == 64 || T == 128 || T == 256)) {
+        int ipt = ((band >= 4 || band <= -4) && !(band > 0 && items < 4L * 256 * 256)) ? 4 : 2;
+        if (!u8out && !band_set) ipt = 2;
+        auto go = [&](auto kernel, int ipt_) {
+            hipLaunchKernelGGL(kernel, dim3(T * (T / 4) / (256 * ipt_), B), dim3(256), 0, st, images, sizes, states, factor, mean3[0], mean3[1],
+                               mean3[2], std3[0], std3[1], std3[2], crops, rf);
+        };
+        auto pick = [&](auto u8c, auto lgc) {
+            constexpr bool U = decltype(u8c)::value;
+            constexpr int LG = decltype(lgc)::value;
+            ipt == 4 ? go(&vtt::crop_band_image_kernel<U, LG, 4>, 4) : go(&vtt::crop_band_image_kernel<U, LG, 2>, 2);
+        };
+        auto by_size = [&](auto u8c) {
+            if (T == 64) pick(u8c, std::integral_constant<int, 4>{});
+            else if (T == 128) pick(u8c, std::integral_constant<int, 5>{});
+            else pick(u8c, std::integral_constant<int, 6>{});
+        };
+        if (u8out) by_size(std::true_type{});
+        else by_size(std::false_type{});
+        return;
+    }
+    const dim3 grid((T * ((T + 3) / 4) + 255) / 256, B);
+    if (u8out)
+        hipLaunchKernelGGL(vtt::crop_image_kernel<true>, grid, dim3(256), 0, st, images, sizes, states, factor, T, 0.f, 0.f, 0.f, 1.f, 1.f, 1.f,
+                           crops, rf);
+    else
+        hipLaunchKernelGGL(vtt::crop_image_kernel<false>, grid, dim3(256), 0, st, images, sizes, states, factor, T, mean3[0], mean3[1], mean3[2],
+                           std3[0], std3[1], std3[2], crops, rf);
+}
+
 // device buffers of the self test, released on every path
 struct CropProbe {
     unsigned char *dfr = nullptr, *hfr = nullptr;
@@ -1336,6 +1379,7 @@ int vt_create(const vt_config* cfg, vt_model** out) {
     A(m->pred, B * 4);
     A(m->hann, B * 4);
     A(m->conf, B);
+    A(m->imsizes, B * sizeof(vt_frame) / sizeof(float));
     if (!rc && hipMemset(m->tokens_c.p, 0, m->tokens_c.n * sizeof(float)) != hipSuccess) rc = fail(VT_ERR_HIP, "hipMemset(tokens) failed");
     m->skip_stem_a = env_int("VT_SKIP_STEM_A", 0);
     m->skip_stem_b = env_int("VT_SKIP_STEM_B", 0);
@@ -1489,7 +1533,7 @@ void vt_destroy(vt_model* m) {
     m->stem_w3b.release();
     m->stem_w4b.release();
     m->act_x.release(); m->act_z.release();
-    DevBuf* all[] = {&m->pos_z, &m->pos_x, &m->blocks, &m->blocks3, &m->head, &m->head3, &m->window, &m->tokens, &m->feat, &m->zcache, &m->zstage, &m->vlscr, &m->tokens_c,
+    DevBuf* all[] = {&m->pos_z, &m->pos_x, &m->blocks, &m->blocks3, &m->head, &m->head3, &m->window, &m->tokens, &m->feat, &m->zcache, &m->zstage, &m->imsizes, &m->vlscr, &m->tokens_c,
                      &m->tile_q, &m->tile_k, &m->tile_v, &m->tile_x, &m->head_m1,
                      &m->score, &m->size, &m->offset, &m->pred, &m->hann, &m->conf};
     for (DevBuf* d : all) d->release();
@@ -1891,6 +1935,26 @@ int vt_crop_u8_frames(vt_model* m, const vt_frame* frames_dev, const double* sta
     return VT_OK;
 }
 
+int vt_crop_images(vt_model* m, const vt_image* images_dev, const double* states_dev, double factor, int32_t out_size,
+                   const float* mean3, const float* std3, int32_t B, void* stream, float* crops_dev, double* resize_factor_dev) {
+    if (!m || !images_dev || !states_dev || !crops_dev || !resize_factor_dev || !mean3 || !std3) return fail(VT_ERR_ARG, "null argument");
+    if (B < 1 || out_size < 1 || !(factor > 0.0)) return fail(VT_ERR_ARG, "bad crop arguments");
+    launch_crop_images(images_dev, nullptr, states_dev, factor, out_size, mean3, std3, B, static_cast<hipStream_t>(stream), crops_dev,
+                       resize_factor_dev, false);
+    HIP_TRY(hipGetLastError());
+    return VT_OK;
+}
+
+int vt_crop_u8_images(vt_model* m, const vt_image* images_dev, const double* states_dev, double factor, int32_t out_size, int32_t B,
+                      void* stream, uint8_t* patch_dev, double* resize_factor_dev) {
+    if (!m || !images_dev || !states_dev || !patch_dev || !resize_factor_dev) return fail(VT_ERR_ARG, "null argument");
+    if (B < 1 || out_size < 1 || !(factor > 0.0)) return fail(VT_ERR_ARG, "bad crop arguments");
+    launch_crop_images(images_dev, nullptr, states_dev, factor, out_size, nullptr, nullptr, B, static_cast<hipStream_t>(stream),
+                       reinterpret_cast<float*>(patch_dev), resize_factor_dev, true);
+    HIP_TRY(hipGetLastError());
+    return VT_OK;
+}
+
 int vt_set_normalization(vt_model* m, const float* mean3, const float* std3) {
     if (!m || !mean3 || !std3) return fail(VT_ERR_ARG, "null argument");
     if (m->vb) return fail(VT_ERR_ARG, "uint8 patches are implemented for the vit_48 path only");
@@ -1980,9 +2044,10 @@ int vt_update_state_record(vt_model* m, const float* hann_boxes_dev, const float
 }
 
 // vt_track_step (table == nullptr: frames (B,H,W,3)) and vt_track_step_frames (a (B,) vt_frame table)
+// ... and vt_track_step_images (images: a (B,) vt_image table; its crop writes the descriptors' sizes into m->imsizes for the tail)
 static int track_step(vt_model* m, const uint8_t* frames, int32_t H, int32_t W, const vt_frame* table, double* states_dev, double factor,
                       const float* mean3, const float* std3, int32_t B, void* stream, float* crops_dev, double* resize_factor_dev,
-                      const vt_outputs* out, int32_t margin, double* record) {
+                      const vt_outputs* out, int32_t margin, double* record, const vt_image* images = nullptr) {
     int rc = check_ready(m, B);
     if (rc) return rc;
     if (m->vb) return fail(VT_ERR_ARG, "vt_track_step is implemented for the vit_48 path only");
@@ -1996,7 +2061,12 @@ static int track_step(vt_model* m, const uint8_t* frames, int32_t H, int32_t W, 
     // whenever the stem form of this batch reads patches and (mean3, std3) is the normalisation folded into its layer 1; else as the
     // fp32 crop of vt_crop.  Either way crops_dev is the workspace: the patch occupies its first B * S * S * 3 bytes.
     const bool u8 = m->track_u8 != 0 && stem_takes_u8(m, B) && same_norm(m, mean3, std3);
-    if (table) {
+    if (images) {
+        table = reinterpret_cast<const vt_frame*>(m->imsizes.p);
+        launch_crop_images(images, reinterpret_cast<vt_frame*>(m->imsizes.p), states_dev, factor, m->cfg.search_size, mean3, std3, B, st,
+                           crops_dev, resize_factor_dev, u8);
+        HIP_TRY(hipGetLastError());
+    } else if (table) {
         if (u8) {
             if ((rc = vt_crop_u8_frames(m, table, states_dev, factor, m->cfg.search_size, B, stream, reinterpret_cast<uint8_t*>(crops_dev), resize_factor_dev))) return rc;
         } else if ((rc = vt_crop_frames(m, table, states_dev, factor, m->cfg.search_size, mean3, std3, B, stream, crops_dev, resize_factor_dev))) return rc;
@@ -2021,6 +2091,14 @@ int vt_track_step_frames(vt_model* m, const vt_frame* frames_dev, double* states
                          int32_t margin, double* record) {
     if (!frames_dev) return fail(VT_ERR_ARG, "null argument");
     return track_step(m, nullptr, 0, 0, frames_dev, states_dev, factor, mean3, std3, B, stream, crops_dev, resize_factor_dev, out, margin, record);
+}
+
+int vt_track_step_images(vt_model* m, const vt_image* images_dev, double* states_dev, double factor, const float* mean3,
+                         const float* std3, int32_t B, void* stream, float* crops_dev, double* resize_factor_dev, const vt_outputs* out,
+                         int32_t margin, double* record) {
+    if (!images_dev) return fail(VT_ERR_ARG, "null argument");
+    return track_step(m, nullptr, 0, 0, nullptr, states_dev, factor, mean3, std3, B, stream, crops_dev, resize_factor_dev, out, margin, record,
+                      images_dev);
 }
 
 // One slice [f0, f0 + nb) of a batch through the whole step, on stream st.

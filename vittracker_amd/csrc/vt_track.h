@@ -691,6 +691,430 @@ __global__ __launch_bounds__(256) void crop_band_kernel(const unsigned char* __r
     }
 }
 
+// ---- pixel formats (vt_crop_images & co.): a (B,) vt_image table, one descriptor per sequence (include/vittrack.h).  Each descriptor
+// denotes an RGB image rgb(d); the kernels below crop it with exactly the arithmetic of the kernels above -- only the fetch of a tap
+// pixel differs: it is converted to an RGB dword (R | G << 8 | B << 16) first.  New kernels, not new frame sources of the bodies above:
+// those bodies fetch a 3-byte pixel pair as one window, and the existing instantiations stay as they compile today.
+struct ImageView {
+    const unsigned char* p0;       // plane 0: the packed pixels, or NV12 / NV21 luma
+    const unsigned char* p1;       // plane 1: NV12 / NV21 chroma pairs
+    unsigned pitch0, pitch1;       // bytes between rows
+    unsigned nrec0, nrec1;         // each plane's extent, the bound of its buffer descriptor (loads beyond it return zero, fetch nothing)
+    int H, W, fmt;
+    bool ok;                       // false: an unusable descriptor, poisoned like a too-small box
+};
+__device__ __forceinline__ ImageView image_view(const vt_image* images, int b) {
+    // one descriptor per workgroup at a workgroup-uniform address: scalar loads
+    const vt_image* const d = images + b;
+    const unsigned char* const p0 = d->plane0;
+    const unsigned char* const p1 = d->plane1;
+    const int H = d->H, W = d->W, fmt = d->format;
+    const bool nv = fmt == VT_PIX_NV12 || fmt == VT_PIX_NV21;
+    const long long bpp = (fmt == VT_PIX_RGBA || fmt == VT_PIX_BGRA) ? 4 : (nv ? 1 : 3);
+    bool ok = fmt >= VT_PIX_RGB && fmt <= VT_PIX_NV21 && d->reserved == 0 && H >= 1 && W >= 1 && H <= 0x10000000 && W <= 0x10000000 &&
+              (!nv || ((H | W) & 1) == 0);
+    const long long row0 = bpp * W, pitch0 = d->pitch0 == 0 ? row0 : d->pitch0;
+    ok = ok && pitch0 >= row0 && pitch0 <= 0xfffffff0ll && p0 != nullptr && (reinterpret_cast<unsigned long long>(p0) & 3ull) == 0;
+    const unsigned long long ext0 = ok ? (unsigned long long)pitch0 * (unsigned long long)(H - 1) + (unsigned long long)row0 : 0ull;
+    ok = ok && ext0 <= 0xfffffff0ull;
+    long long pitch1 = 0;
+    unsigned long long ext1 = 0;
+    if (nv) {      // chroma: H / 2 rows of W bytes
+        pitch1 = d->pitch1 == 0 ? (long long)W : d->pitch1;
+        ok = ok && pitch1 >= W && pitch1 <= 0xfffffff0ll && p1 != nullptr && (reinterpret_cast<unsigned long long>(p1) & 3ull) == 0;
+        ext1 = ok ? (unsigned long long)pitch1 * (unsigned long long)(H / 2 - 1) + (unsigned long long)W : 0ull;
+        ok = ok && ext1 <= 0xfffffff0ull;
+    }
+    return ImageView{p0, p1, ok ? (unsigned)pitch0 : 0u, ok ? (unsigned)pitch1 : 0u, ok ? (unsigned)ext0 : 0u, ok ? (unsigned)ext1 : 0u,
+                     ok ? H : 1, ok ? W : 1, fmt, ok};
+}
+// BT.601 limited range in OpenCV's fixed point (include/vittrack.h).  The chroma terms of a pair, rounding constant included ...
+struct ChromaTerms { int r, g, b; };
+__device__ __forceinline__ ChromaTerms chroma_terms(unsigned u8, unsigned v8) {
+    const int u = (int)u8 - 128, v = (int)v8 - 128;
+    return ChromaTerms{1673527 * v + (1 << 19), -852492 * v - 409993 * u + (1 << 19), 2116026 * u + (1 << 19)};
+}
+// ... and one pixel: R | G << 8 | B << 16
+__device__ __forceinline__ unsigned yuv_rgb(unsigned y8, const ChromaTerms& c) {
+    const int yy = (int)(y8 > 16u ? y8 - 16u : 0u) * 1220542;
+    auto ch = [](int s) { s >>= 20; return (unsigned)(s < 0 ? 0 : (s > 255 ? 255 : s)); };
+    return ch(yy + c.r) | (ch(yy + c.g) << 8) | (ch(yy + c.b) << 16);
+}
+// The tracker's tail clips against each sequence's own frame size (TrackTail::frames): the crop of vt_track_step_images writes the
+// sizes of its descriptors into a vt_frame-shaped table as it reads them (sizes may be null: vt_crop_images)
+__device__ __forceinline__ void image_sizes_out(vt_frame* sizes, const vt_image* images, int b) {
+    if (sizes != nullptr) sizes[b] = vt_frame{nullptr, images[b].H, images[b].W, 0};
+}
+
+// crop_image_kernel: crop_kernel on a vt_image table -- any T, fp32 crop or (U8OUT) uint8 patch; vt_crop_images at the sizes the band
+// kernel does not take, and the template crop of BatchedVitTracker.initialize.  One thread = four consecutive output pixels of a row,
+// as crop_kernel; every tap pixel is fetched as single bytes (buffer bounds: a byte beyond its plane reads as zero and is not fetched)
+// and converted to RGB, then crop_kernel's arithmetic, clamp included.
+template <bool U8OUT = false>
+__global__ __launch_bounds__(256) void crop_image_kernel(const vt_image* __restrict__ images, vt_frame* __restrict__ sizes,
+                                                         const double* __restrict__ states, double factor, int T,
+                                                         float m0, float m1, float m2, float s0, float s1, float s2,
+                                                         float* __restrict__ out, double* __restrict__ resize_factor) {
+    const int b = blockIdx.y;
+    const ImageView iv = image_view(images, b);
+    __shared__ float norm_lut[U8OUT ? 1 : 3 * 256];
+    if constexpr (!U8OUT) {
+        const float meanv[3] = {m0, m1, m2}, stdq[3] = {s0, s1, s2};
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {       // Preprocessor.process on the 256 possible values: see crop_kernel
+            float scaled = (float)(int)threadIdx.x * (1.0f / 255.0f);
+            asm volatile("" : "+v"(scaled));
+            float centred = scaled - meanv[c];
+            asm volatile("" : "+v"(centred));
+            norm_lut[c * 256 + threadIdx.x] = centred / stdq[c];
+        }
+        __syncthreads();
+    }
+    unsigned char* const out8 = reinterpret_cast<unsigned char*>(out) + (size_t)b * T * T * 3;
+    const double bx = states[4 * b + 0], by = states[4 * b + 1], bw = states[4 * b + 2], bh = states[4 * b + 3];
+    const int crop_sz = (int)ceil(sqrt(bw * bh) * factor);
+    const int T4 = (T + 3) >> 2;
+    const int idx = blockIdx.x * 256 + threadIdx.x;
+    if (idx == 0) image_sizes_out(sizes, images, b);
+    if (!(crop_sz >= 1) || !iv.ok) {        // 'Too small bounding box.' (or an unusable descriptor): poison, as crop_kernel
+        if (idx == 0) resize_factor[b] = __builtin_nan("");
+        if (idx < T * T4) {
+            const int oy = idx / T4, ox0 = (idx - oy * T4) * 4;
+            for (int c = 0; c < 3; ++c)
+                for (int k = 0; k < 4 && ox0 + k < T; ++k) {
+                    if constexpr (U8OUT) out8[((size_t)oy * T + ox0 + k) * 3 + c] = 0;
+                    else out[(((size_t)b * 3 + c) * T + oy) * T + ox0 + k] = __builtin_nanf("");
+                }
+        }
+        return;
+    }
+    const int x1 = (int)rint(bx + 0.5 * bw - crop_sz * 0.5);
+    const int y1 = (int)rint(by + 0.5 * bh - crop_sz * 0.5);
+    const int x2 = x1 + crop_sz, y2 = y1 + crop_sz;
+    const int vx0 = x1 < 0 ? 0 : x1, vx1 = x2 - (x2 - iv.W + 1 > 0 ? x2 - iv.W + 1 : 0);
+    const int vy0 = y1 < 0 ? 0 : y1, vy1 = y2 - (y2 - iv.H + 1 > 0 ? y2 - iv.H + 1 : 0);
+    if (idx == 0) resize_factor[b] = (double)T / (double)crop_sz;
+    if (idx >= T * T4) return;
+    const int oy = idx / T4, ox0 = (idx - oy * T4) * 4;
+    const double scale = (double)crop_sz / (double)T;
+    int sy0, sy1, by0, by1;
+    lin_coeff(oy, crop_sz, scale, sy0, sy1, by0, by1);
+    const auto rs0 = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned char*>(iv.p0), 0, (int)iv.nrec0, 0x00020000);
+    const auto rs1 = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned char*>(iv.p1 != nullptr ? iv.p1 : iv.p0), 0, (int)iv.nrec1, 0x00020000);
+    auto byte0 = [&](unsigned o) { return (unsigned)__builtin_amdgcn_raw_buffer_load_b8(rs0, (int)o, 0, 0) & 0xffu; };
+    auto byte1 = [&](unsigned o) { return (unsigned)__builtin_amdgcn_raw_buffer_load_b8(rs1, (int)o, 0, 0) & 0xffu; };
+    const int fmt = iv.fmt;
+    const bool swap = fmt == VT_PIX_BGR || fmt == VT_PIX_BGRA;
+    auto pixel = [&](int x, int y) -> unsigned {      // rgb(d) at (x, y), inside the image
+        if (fmt == VT_PIX_NV12 || fmt == VT_PIX_NV21) {
+            const unsigned co = (unsigned)(y >> 1) * iv.pitch1 + 2u * (unsigned)(x >> 1);
+            const unsigned c0 = byte1(co), c1 = byte1(co + 1u);
+            return yuv_rgb(byte0((unsigned)y * iv.pitch0 + (unsigned)x), fmt == VT_PIX_NV12 ? chroma_terms(c0, c1) : chroma_terms(c1, c0));
+        }
+        const unsigned o = (unsigned)y * iv.pitch0 + (unsigned)x * ((fmt == VT_PIX_RGBA || fmt == VT_PIX_BGRA) ? 4u : 3u);
+        const unsigned a = byte0(o), g = byte0(o + 1u), c = byte0(o + 2u);
+        return swap ? (c | (g << 8) | (a << 16)) : (a | (g << 8) | (c << 16));
+    };
+    const int yy0 = y1 + sy0, yy1 = y1 + sy1;
+    const bool vr0 = yy0 >= vy0 && yy0 < vy1, vr1 = yy1 >= vy0 && yy1 < vy1;
+    float res[3][4];
+    unsigned pk[3] = {0u, 0u, 0u};
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int ox = ox0 + k < T ? ox0 + k : T - 1;
+        int sx0, sx1, ax0, ax1;
+        lin_coeff(ox, crop_sz, scale, sx0, sx1, ax0, ax1);
+        const int xx0 = x1 + sx0, xx1 = x1 + sx1;
+        const bool vc0 = xx0 >= vx0 && xx0 < vx1, vc1 = xx1 >= vx0 && xx1 < vx1;
+        // pixel (cy, cx) of the zero-padded crop: rgb(d) inside the valid range, 0 outside (all channels)
+        const unsigned l0 = vr0 && vc0 ? pixel(xx0, yy0) : 0u, l1 = vr1 && vc0 ? pixel(xx0, yy1) : 0u;
+        const unsigned r0w = vr0 && vc1 ? pixel(xx1, yy0) : 0u, r1w = vr1 && vc1 ? pixel(xx1, yy1) : 0u;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {       // crop_kernel's arithmetic
+            const int p00 = (int)((l0 >> (8 * c)) & 0xffu), p01 = (int)((r0w >> (8 * c)) & 0xffu);
+            const int p10 = (int)((l1 >> (8 * c)) & 0xffu), p11 = (int)((r1w >> (8 * c)) & 0xffu);
+            const int r0 = __mul24(p00, ax0) + __mul24(p01, ax1);
+            const int r1 = __mul24(p10, ax0) + __mul24(p11, ax1);
+            int v = ((__mul24(by0, r0 >> 4) >> 16) + (__mul24(by1, r1 >> 4) >> 16) + 2) >> 2;
+            v = v < 0 ? 0 : (v > 255 ? 255 : v);
+            if constexpr (U8OUT) pk[(3 * k + c) >> 2] |= (unsigned)v << (8 * ((3 * k + c) & 3));
+            else res[c][k] = norm_lut[c * 256 + v];
+        }
+    }
+    if constexpr (U8OUT) {
+        unsigned char* o = out8 + ((size_t)oy * T + ox0) * 3;
+        if ((T & 3) == 0) {
+            typedef unsigned u3a __attribute__((ext_vector_type(3), aligned(4)));
+            *reinterpret_cast<u3a*>(o) = u3a{pk[0], pk[1], pk[2]};
+        } else {
+            for (int i = 0; i < 12 && ox0 + i / 3 < T; ++i) o[i] = (unsigned char)(pk[i >> 2] >> (8 * (i & 3)));
+        }
+        return;
+    }
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        float* o = out + (((size_t)b * 3 + c) * T + oy) * T + ox0;
+        if ((T & 3) == 0) {
+            st4(o, f4{res[c][0], res[c][1], res[c][2], res[c][3]});
+        } else {
+            for (int k = 0; k < 4 && ox0 + k < T; ++k) o[k] = res[c][k];
+        }
+    }
+}
+
+// crop_band_image_kernel: crop_band_kernel on a vt_image table (T = 64 / 128 / 256, the tracker's per-step crop), same bands, tables,
+// arithmetic and results.  The format is uniform in a workgroup (one workgroup crops one sequence), so each format family is its own
+// instantiation of the body inside one kernel, picked by a uniform branch; a table may still mix formats.
+//   - packed (RGB / BGR: 3 bytes, RGBA / BGRA: 4 bytes a pixel): a window of two pixels is fetched as the 12 ALIGNED bytes that contain
+//     it and funnel-shifted into place, as crop_band_kernel's aligned form.  The order of the channels is the byte select of the
+//     v_perm_b32 that already picks a channel out of the window: BGR costs nothing.
+//   - NV12 / NV21: a tap pair reads its two luma bytes as the aligned 8 bytes that hold them, and its one or two chroma pairs as the
+//     aligned 8 bytes that hold them; each tap is converted to RGB in int32, then the same 11-bit bilinear code.
+//   - bounds: the crop never reads the last row or column of a frame (its valid range stops one short: see crop_kernel), so the packed
+//     windows and the luma windows stay inside their plane (pitch >= 8); a chroma window of the LAST chroma row can overhang its plane
+//     by up to 6 bytes: a band that reads that row (or a plane narrower than 8 bytes) takes the GUARD form, where a window that would
+//     cross its plane's end is read as single bytes.  The buffer descriptors bound every load to its plane's extent regardless.
+template <bool U8OUT, int LGT4, int IPT>
+__global__ __launch_bounds__(256) void crop_band_image_kernel(const vt_image* __restrict__ images, vt_frame* __restrict__ sizes,
+                                                              const double* __restrict__ states, double factor,
+                                                              float m0, float m1, float m2, float s0, float s1, float s2,
+                                                              float* __restrict__ out, double* __restrict__ resize_factor) {
+    constexpr int T4 = 1 << LGT4, T = 4 * T4, RPG = 256 >> LGT4, NROWS = IPT * RPG;
+    static_assert(T <= 256 && (T * T4) % (IPT * 256) == 0, "a band is whole rows and the frame whole bands");
+    const int b = blockIdx.y, tid = threadIdx.x;
+    const ImageView iv = image_view(images, b);
+    __shared__ float norm_lut[U8OUT ? 1 : 3 * 256];
+    __shared__ __attribute__((aligned(16))) unsigned xtab[T * 4];          // per output column: plane-0 byte offset of the window, packed weights, steps, chroma offset
+    __shared__ __attribute__((aligned(16))) unsigned ytab[NROWS * 4];      // per output row: plane-0 offsets of its two source rows, their weights << 12
+    __shared__ __attribute__((aligned(8))) unsigned ctab[NROWS * 2];       // per output row: chroma-row offsets of its two source rows (NV12 / NV21)
+    unsigned char* const out8 = reinterpret_cast<unsigned char*>(out) + (size_t)b * T * T * 3;
+    typedef unsigned u3a __attribute__((ext_vector_type(3), aligned(4)));
+    typedef unsigned u4v __attribute__((ext_vector_type(4)));
+    typedef unsigned u3v __attribute__((ext_vector_type(3)));
+    typedef unsigned u2v __attribute__((ext_vector_type(2)));
+    typedef unsigned short us2 __attribute__((ext_vector_type(2)));
+    if constexpr (!U8OUT) {
+        const float meanv[3] = {m0, m1, m2}, stdq[3] = {s0, s1, s2};
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            float scaled = (float)tid * (1.0f / 255.0f);
+            asm volatile("" : "+v"(scaled));
+            float centred = scaled - meanv[c];
+            asm volatile("" : "+v"(centred));
+            norm_lut[c * 256 + tid] = centred / stdq[c];
+        }
+    }
+    const double bx = states[4 * b + 0], by = states[4 * b + 1], bw = states[4 * b + 2], bh = states[4 * b + 3];
+    const int crop_sz = (int)ceil(sqrt(bw * bh) * factor);
+    const int row0 = blockIdx.x * NROWS;
+    const int cg = tid & (T4 - 1), rl = tid >> LGT4;
+    if (blockIdx.x == 0 && tid == 0) image_sizes_out(sizes, images, b);
+    if (!(crop_sz >= 1) || !iv.ok) {        // 'Too small bounding box.' (or an unusable descriptor): poison, as crop_kernel
+        if (blockIdx.x == 0 && tid == 0) resize_factor[b] = __builtin_nan("");
+#pragma unroll
+        for (int j = 0; j < IPT; ++j) {
+            const int oy = row0 + j * RPG + rl;
+            if constexpr (U8OUT) *reinterpret_cast<u3a*>(out8 + ((size_t)oy * T + 4 * cg) * 3) = u3a{0u, 0u, 0u};
+            else
+                for (int c = 0; c < 3; ++c) st4(out + (((size_t)b * 3 + c) * T + oy) * T + 4 * cg, splat4(__builtin_nanf("")));
+        }
+        return;
+    }
+    const int fmt = iv.fmt;
+    const bool nv = fmt == VT_PIX_NV12 || fmt == VT_PIX_NV21, four = fmt == VT_PIX_RGBA || fmt == VT_PIX_BGRA;
+    const unsigned bpp = nv ? 1u : (four ? 4u : 3u);
+    const int x1 = (int)rint(bx + 0.5 * bw - crop_sz * 0.5);
+    const int y1 = (int)rint(by + 0.5 * bh - crop_sz * 0.5);
+    const int x2 = x1 + crop_sz, y2 = y1 + crop_sz;
+    const int vx0 = x1 < 0 ? 0 : x1, vx1 = x2 - (x2 - iv.W + 1 > 0 ? x2 - iv.W + 1 : 0);
+    const int vy0 = y1 < 0 ? 0 : y1, vy1 = y2 - (y2 - iv.H + 1 > 0 ? y2 - iv.H + 1 : 0);
+    if (blockIdx.x == 0 && tid == 0) resize_factor[b] = (double)T / (double)crop_sz;
+    const double scale = (double)crop_sz / (double)T;
+    if (tid < T) {                          // column entries: zero padding lives in the weights, as crop_band_kernel
+        int sx0, sx1, ax0, ax1;
+        lin_coeff(tid, crop_sz, scale, sx0, sx1, ax0, ax1);
+        const int xx0 = x1 + sx0, xx1 = x1 + sx1;
+        const bool vc0 = xx0 >= vx0 && xx0 < vx1, vc1 = xx1 >= vx0 && xx1 < vx1;
+        const int xb = vc0 ? xx0 : (vc1 ? xx1 : 0);
+        // steps: bit 0 = the right tap is the next pixel, bit 1 = its chroma pair is the next pair
+        const unsigned step = vc1 && xx1 != xb ? 1u : 0u, cstep = vc1 && (xx1 >> 1) != (xb >> 1) ? 2u : 0u;
+        *reinterpret_cast<u4v*>(xtab + 4 * tid) = u4v{bpp * (unsigned)xb, (unsigned)(vc0 ? ax0 : 0) | ((unsigned)(vc1 ? ax1 : 0) << 16),
+                                                       step | cstep, 2u * (unsigned)(xb >> 1)};
+    }
+    if (tid >= 256 - NROWS) {               // row entries of the band
+        const int r = tid - (256 - NROWS);
+        int sy0, sy1, by0, by1;
+        lin_coeff(row0 + r, crop_sz, scale, sy0, sy1, by0, by1);
+        const int yy0 = y1 + sy0, yy1 = y1 + sy1;
+        const bool vr0 = yy0 >= vy0 && yy0 < vy1, vr1 = yy1 >= vy0 && yy1 < vy1;
+        const unsigned ya = (unsigned)(vr0 ? yy0 : 0), yb = (unsigned)(vr1 ? yy1 : 0);      // rows outside the valid range read row 0
+        *reinterpret_cast<u4v*>(ytab + 4 * r) = u4v{ya * iv.pitch0, yb * iv.pitch0, vr0 ? (unsigned)by0 << 12 : 0u, vr1 ? (unsigned)by1 << 12 : 0u};
+        *reinterpret_cast<u2v*>(ctab + 2 * r) = u2v{(ya >> 1) * iv.pitch1, (yb >> 1) * iv.pitch1};
+    }
+    __syncthreads();
+    const auto rs0 = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned char*>(iv.p0), 0, (int)iv.nrec0, 0x00020000);
+    const auto rs1 = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned char*>(nv ? iv.p1 : iv.p0), 0, (int)iv.nrec1, 0x00020000);
+    unsigned xo[4], wp[4], st[4], xc[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const u4v e = *reinterpret_cast<const u4v*>(xtab + 4 * (4 * cg + k));
+        xo[k] = e.x; wp[k] = e.y; st[k] = e.z; xc[k] = e.w;
+    }
+    // the byte of each channel in an RGB-ordered (or, swapped, BGR-ordered) pixel dword: v_perm_b32 selectors
+    // [left pixel's channel, 0, right pixel's channel, 0], uniform
+    const bool swap = fmt == VT_PIX_BGR || fmt == VT_PIX_BGRA;
+    unsigned sel[3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) sel[c] = 0x0c040c00u + 0x00010001u * (unsigned)(swap ? 2 - c : c);
+    const unsigned ush = fmt == VT_PIX_NV21 ? 8u : 0u;      // bit offset of U in a chroma pair (V at the other byte)
+    unsigned two = 2u;
+    asm volatile("" : "+v"(two));
+    const bool col_live = (wp[0] | wp[1] | wp[2] | wp[3]) != 0u;
+    // the output of one item from its four tap-pair dwords per row (l = left tap, r = right tap: R | G << 8 | B << 16)
+    auto finish = [&](int j, const unsigned (&l0)[4], const unsigned (&r0w)[4], const unsigned (&l1)[4], const unsigned (&r1w)[4],
+                      unsigned byw0, unsigned byw1) {
+        const int oy = row0 + j * RPG + rl;
+        float res[3][4];
+        unsigned pk[3] = {0u, 0u, 0u};
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const us2 wv = __builtin_bit_cast(us2, wp[k]);
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {       // crop_band_kernel's arithmetic
+                const unsigned r0 = __builtin_amdgcn_udot2(__builtin_bit_cast(us2, __builtin_amdgcn_perm(r0w[k], l0[k], sel[c])), wv, 0u, false);
+                const unsigned r1 = __builtin_amdgcn_udot2(__builtin_bit_cast(us2, __builtin_amdgcn_perm(r1w[k], l1[k], sel[c])), wv, 0u, false);
+                const unsigned t0 = mulhi24(byw0, r0 & ~15u), t1 = mulhi24(byw1, r1 & ~15u);
+                if constexpr (U8OUT) {
+                    put_byte_shr2(pk[(3 * k + c) >> 2], t0 + t1 + 2u, two, (3 * k + c) & 3);
+                } else {
+                    const unsigned v4 = (t0 + t1 + 2u) & ~3u;
+                    res[c][k] = *reinterpret_cast<const float*>(reinterpret_cast<const char*>(norm_lut) + c * 1024 + v4);
+                }
+            }
+        }
+        if constexpr (U8OUT) {
+            *reinterpret_cast<u3a*>(out8 + ((size_t)oy * T + 4 * cg) * 3) = u3a{pk[0], pk[1], pk[2]};
+        } else {
+#pragma unroll
+            for (int c = 0; c < 3; ++c) st4(out + (((size_t)b * 3 + c) * T + oy) * T + 4 * cg, f4{res[c][0], res[c][1], res[c][2], res[c][3]});
+        }
+    };
+    constexpr int HS = IPT < 2 ? IPT : 2;      // two items at a time, as crop_band_kernel
+    // packed formats: BPP 3 or 4
+    auto packed = [&](auto bpp_c) {
+        constexpr unsigned BPP = decltype(bpp_c)::value;
+        u3v ra0[IPT][4], ra1[IPT][4];
+        unsigned ro0[IPT], ro1[IPT], byw0[IPT], byw1[IPT];
+        auto issue = [&](int j) {
+            const u4v e = *reinterpret_cast<const u4v*>(ytab + 4 * (j * RPG + rl));
+            ro0[j] = e.x; ro1[j] = e.y; byw0[j] = e.z; byw1[j] = e.w;
+            const bool live = ((e.z | e.w) != 0u) && col_live;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                if (!live) { ra0[j][k] = u3v{0u, 0u, 0u}; ra1[j][k] = u3v{0u, 0u, 0u}; continue; }
+                ra0[j][k] = __builtin_amdgcn_raw_buffer_load_b96(rs0, (int)((e.x + xo[k]) & ~3u), 0, 0);
+                ra1[j][k] = __builtin_amdgcn_raw_buffer_load_b96(rs0, (int)((e.y + xo[k]) & ~3u), 0, 0);
+            }
+        };
+        auto math = [&](int j) {
+            unsigned l0[4], r0w[4], l1[4], r1w[4];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const unsigned b0 = (ro0[j] + xo[k]) << 3, b1 = (ro1[j] + xo[k]) << 3;      // v_alignbit reads bits [4:0]: 8 x (offset & 3)
+                const u2v w0{__builtin_amdgcn_alignbit(ra0[j][k].y, ra0[j][k].x, b0), __builtin_amdgcn_alignbit(ra0[j][k].z, ra0[j][k].y, b0)};
+                const u2v w1{__builtin_amdgcn_alignbit(ra1[j][k].y, ra1[j][k].x, b1), __builtin_amdgcn_alignbit(ra1[j][k].z, ra1[j][k].y, b1)};
+                l0[k] = w0.x; l1[k] = w1.x;
+                if constexpr (BPP == 3) {
+                    r0w[k] = (st[k] & 1u) ? __builtin_amdgcn_alignbit(w0.y, w0.x, 24u) : w0.x;
+                    r1w[k] = (st[k] & 1u) ? __builtin_amdgcn_alignbit(w1.y, w1.x, 24u) : w1.x;
+                } else {
+                    r0w[k] = (st[k] & 1u) ? w0.y : w0.x;
+                    r1w[k] = (st[k] & 1u) ? w1.y : w1.x;
+                }
+            }
+            finish(j, l0, r0w, l1, r1w, byw0[j], byw1[j]);
+        };
+#pragma unroll
+        for (int h = 0; h < IPT; h += HS) {
+#pragma unroll
+            for (int j = 0; j < HS; ++j) issue(h + j);
+#pragma unroll
+            for (int j = 0; j < HS; ++j) math(h + j);
+            __builtin_amdgcn_sched_barrier(0);
+        }
+    };
+    // NV12 / NV21; GUARD: windows that would cross their plane's end are read as single bytes
+    auto yuv = [&](auto guard_c) {
+        constexpr bool GUARD = decltype(guard_c)::value;
+        u2v ya0[IPT][4], ya1[IPT][4], ca0[IPT][4], ca1[IPT][4];
+        unsigned ro0[IPT], ro1[IPT], co0[IPT], co1[IPT], byw0[IPT], byw1[IPT];
+        auto load8 = [&](const auto& rs, unsigned o, unsigned nrec) -> u2v {      // the 8 bytes from the dword that holds byte o
+            const unsigned a = o & ~3u;
+            if (!GUARD || a + 8u <= nrec) return __builtin_amdgcn_raw_buffer_load_b64(rs, (int)a, 0, 0);
+            unsigned lo = 0u, hi = 0u;
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                lo |= ((unsigned)__builtin_amdgcn_raw_buffer_load_b8(rs, (int)(a + i), 0, 0) & 0xffu) << (8 * i);
+                hi |= ((unsigned)__builtin_amdgcn_raw_buffer_load_b8(rs, (int)(a + 4 + i), 0, 0) & 0xffu) << (8 * i);
+            }
+            return u2v{lo, hi};
+        };
+        auto issue = [&](int j) {
+            const u4v e = *reinterpret_cast<const u4v*>(ytab + 4 * (j * RPG + rl));
+            const u2v cr = *reinterpret_cast<const u2v*>(ctab + 2 * (j * RPG + rl));
+            ro0[j] = e.x; ro1[j] = e.y; byw0[j] = e.z; byw1[j] = e.w; co0[j] = cr.x; co1[j] = cr.y;
+            const bool live = ((e.z | e.w) != 0u) && col_live;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                if (!live) {      // (one assignment each: chained, they kept the arrays in scratch)
+                    ya0[j][k] = u2v{0u, 0u}; ya1[j][k] = u2v{0u, 0u}; ca0[j][k] = u2v{0u, 0u}; ca1[j][k] = u2v{0u, 0u};
+                    continue;
+                }
+                ya0[j][k] = load8(rs0, e.x + xo[k], iv.nrec0);
+                ya1[j][k] = load8(rs0, e.y + xo[k], iv.nrec0);
+                ca0[j][k] = load8(rs1, cr.x + xc[k], iv.nrec1);
+                ca1[j][k] = load8(rs1, cr.y + xc[k], iv.nrec1);
+            }
+        };
+        auto taps = [&](const u2v& yw, const u2v& cw, unsigned yo, unsigned co, unsigned s, unsigned& l, unsigned& r) {
+            const unsigned y = __builtin_amdgcn_alignbit(yw.y, yw.x, yo << 3);      // luma of the left tap at byte 0, the next pixel's at byte 1
+            const unsigned c = __builtin_amdgcn_alignbit(cw.y, cw.x, co << 3);      // the left tap's chroma pair at bytes 0-1, the next pair at 2-3
+            const unsigned cl = c & 0xffffu, cr = (s & 2u) ? c >> 16 : cl;
+            l = yuv_rgb(y & 0xffu, chroma_terms((cl >> ush) & 0xffu, (cl >> (8u - ush)) & 0xffu));
+            r = yuv_rgb((s & 1u) ? (y >> 8) & 0xffu : y & 0xffu, chroma_terms((cr >> ush) & 0xffu, (cr >> (8u - ush)) & 0xffu));
+        };
+        auto math = [&](int j) {
+            unsigned l0[4], r0w[4], l1[4], r1w[4];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                taps(ya0[j][k], ca0[j][k], ro0[j] + xo[k], co0[j] + xc[k], st[k], l0[k], r0w[k]);
+                taps(ya1[j][k], ca1[j][k], ro1[j] + xo[k], co1[j] + xc[k], st[k], l1[k], r1w[k]);
+            }
+            finish(j, l0, r0w, l1, r1w, byw0[j], byw1[j]);
+        };
+#pragma unroll
+        for (int h = 0; h < IPT; h += HS) {
+#pragma unroll
+            for (int j = 0; j < HS; ++j) issue(h + j);
+#pragma unroll
+            for (int j = 0; j < HS; ++j) math(h + j);
+            __builtin_amdgcn_sched_barrier(0);
+        }
+    };
+    if (nv) {
+        // the guard: a band whose valid source rows reach row H - 2 reads the last chroma row; planes narrower than 8 bytes
+        int sl0, sl1, al0, al1;
+        lin_coeff(row0 + NROWS - 1, crop_sz, scale, sl0, sl1, al0, al1);
+        const int ymax = y1 + sl1 < vy1 - 1 ? y1 + sl1 : vy1 - 1;
+        if (ymax >= iv.H - 2 || iv.pitch0 < 8u || iv.pitch1 < 8u) yuv(std::true_type{});
+        else yuv(std::false_type{});
+    } else if (four) {
+        packed(std::integral_constant<unsigned, 4>{});
+    } else {
+        packed(std::integral_constant<unsigned, 3>{});
+    }
+}
+
 // One thread per sequence.  hann_boxes (B,4) float [cx,cy,w,h] in [0,1]; states (B,4) double in/out.
 // `record` (optional, (B,5) double, device memory or device-mapped pinned host memory): [x, y, w, h, confidence] of the new state --
 // what track() returns; written here, the step needs no copy kernel and no device -> host copy after it.

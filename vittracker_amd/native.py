@@ -27,6 +27,7 @@ SYMBOLS = [
     "vt_set_template", "vt_graph_capture_steps", "vt_update_state_record", "vt_track_step", "vt_set_form_batch",
     "vt_crop_u8", "vt_set_normalization", "vt_forward_u8", "vt_stem_u8", "vt_patch_u8_supported", "vt_crop_form", "vt_set_open_loop",
     "vt_crop_frames", "vt_crop_u8_frames", "vt_track_step_frames", "vt_set_template_slots",
+    "vt_crop_images", "vt_crop_u8_images", "vt_track_step_images",
 ]
 
 
@@ -108,6 +109,9 @@ def lib(precision: str = "f32"):
     L.vt_crop_u8_frames.argtypes = [vp, vp, vp, C.c_double, i32, i32, vp, vp, vp]
     L.vt_track_step_frames.argtypes = [vp, vp, vp, C.c_double, C.POINTER(C.c_float), C.POINTER(C.c_float), i32, vp, vp, vp, vp, i32, vp]
     L.vt_set_template_slots.argtypes = [vp, vp, C.POINTER(i32), i32, vp]
+    L.vt_crop_images.argtypes = [vp, vp, vp, C.c_double, i32, C.POINTER(C.c_float), C.POINTER(C.c_float), i32, vp, vp, vp]
+    L.vt_crop_u8_images.argtypes = [vp, vp, vp, C.c_double, i32, i32, vp, vp, vp]
+    L.vt_track_step_images.argtypes = [vp, vp, vp, C.c_double, C.POINTER(C.c_float), C.POINTER(C.c_float), i32, vp, vp, vp, vp, i32, vp]
     if precision == "f32":
         _lib = L
     else:
@@ -236,6 +240,243 @@ class FrameTable:
 
     def shapes(self):
         return [(int(h), int(w)) for h, w in zip(self.host["H"], self.host["W"])]
+
+
+# ---- pixel formats (vt_crop_images & co.) -----------------------------------------------------------------------------------
+#: vt_image.format (include/vittrack.h)
+PIX_RGB, PIX_BGR, PIX_RGBA, PIX_BGRA, PIX_NV12, PIX_NV21 = range(6)
+PIX_NAMES = ("rgb", "bgr", "rgba", "bgra", "nv12", "nv21")
+#: struct vt_image (include/vittrack.h): {const uint8_t *plane0, *plane1; int64_t pitch0, pitch1; int32_t H, W, format, reserved;}
+IMAGE_DTYPE = np.dtype([("plane0", "<u8"), ("plane1", "<u8"), ("pitch0", "<i8"), ("pitch1", "<i8"), ("H", "<i4"), ("W", "<i4"),
+                        ("format", "<i4"), ("reserved", "<i4")])
+assert IMAGE_DTYPE.itemsize == 48
+
+
+def _is_nv(fmt: int) -> bool:
+    return fmt in (PIX_NV12, PIX_NV21)
+
+
+def _row_bytes(fmt: int, W: int):
+    """Bytes of one row of plane 0 and of plane 1 (0: no plane 1)."""
+    if _is_nv(fmt):
+        return W, W
+    return (4 if fmt in (PIX_RGBA, PIX_BGRA) else 3) * W, 0
+
+
+class Image:
+    """One frame in a pixel format the tracker reads directly (vt_image, include/vittrack.h): RGB, BGR, RGBA, BGRA, NV12 or NV21.
+    Planes are numpy arrays (host: BatchedVitTracker packs them into its pinned arena) or uint8 tensors on the GPU (read in place).
+    Rows may be strided (a pitch wider than the row), pixels may not.  Build one with the constructors: Image.rgb(a), .bgr(a),
+    .rgba(a), .bgra(a) for (H, W, 3 | 4) arrays, .nv12(y, uv) / .nv21(y, vu) for an (H, W) luma plane and an (H/2, W/2, 2) chroma
+    plane (H, W even)."""
+
+    __slots__ = ("format", "planes", "H", "W", "pitches")
+
+    def __init__(self, fmt: int, planes, H: int, W: int, pitches):
+        self.format, self.planes, self.H, self.W, self.pitches = int(fmt), tuple(planes), int(H), int(W), tuple(int(p) for p in pitches)
+
+    @staticmethod
+    def _strides(a):
+        """(shape, byte strides, on the GPU) of a uint8 numpy array or tensor; anything else raises."""
+        import torch
+        if isinstance(a, torch.Tensor):
+            if a.dtype != torch.uint8:
+                raise VtError(f"image planes must be uint8, got {a.dtype}")
+            if not (a.is_cuda or a.device.type == "cpu"):
+                raise VtError(f"image planes must be numpy arrays or GPU tensors, got a tensor on {a.device}")
+            return tuple(a.shape), tuple(int(v) for v in a.stride()), a.is_cuda
+        if isinstance(a, np.ndarray):
+            if a.dtype != np.uint8:
+                raise VtError(f"image planes must be uint8, got {a.dtype}")
+            return a.shape, a.strides, False
+        raise VtError(f"image planes must be numpy arrays or GPU tensors, got {type(a).__name__}")
+
+    @classmethod
+    def _packed(cls, fmt, a, C_):
+        shape, st, _ = cls._strides(a)
+        if len(shape) != 3 or shape[2] != C_ or shape[0] < 1 or shape[1] < 1:
+            raise VtError(f"a {PIX_NAMES[fmt].upper()} image must be (H, W, {C_}), got {tuple(shape)}")
+        H, W = int(shape[0]), int(shape[1])
+        if st[2] != 1 or (W > 1 and st[1] != C_) or (H > 1 and st[0] < C_ * W):
+            raise VtError(f"{PIX_NAMES[fmt].upper()} strides {tuple(st)}: pixels must be {C_} contiguous bytes, rows at least {C_} W apart")
+        return cls(fmt, (a,), H, W, (st[0] if H > 1 else C_ * W,))
+
+    @classmethod
+    def rgb(cls, a):
+        return cls._packed(PIX_RGB, a, 3)
+
+    @classmethod
+    def bgr(cls, a):
+        """A BGR frame as OpenCV hands it out (cv.imread, cv.VideoCapture)."""
+        return cls._packed(PIX_BGR, a, 3)
+
+    @classmethod
+    def rgba(cls, a):
+        return cls._packed(PIX_RGBA, a, 4)
+
+    @classmethod
+    def bgra(cls, a):
+        return cls._packed(PIX_BGRA, a, 4)
+
+    @classmethod
+    def _yuv(cls, fmt, y, c):
+        sy, ty, gy = cls._strides(y)
+        sc, tc, gc = cls._strides(c)
+        name = PIX_NAMES[fmt].upper()
+        if len(sy) != 2 or sy[0] < 2 or sy[1] < 2 or sy[0] % 2 or sy[1] % 2:
+            raise VtError(f"an {name} luma plane must be (H, W) with H and W even, got {tuple(sy)}")
+        H, W = int(sy[0]), int(sy[1])
+        if tuple(sc) != (H // 2, W // 2, 2):
+            raise VtError(f"an {name} chroma plane must be (H/2, W/2, 2) = {(H // 2, W // 2, 2)}, got {tuple(sc)}")
+        if gy != gc:
+            raise VtError(f"the two planes of an {name} image must both be on the GPU or both on the host")
+        if ty[1] != 1 or ty[0] < W:
+            raise VtError(f"{name} luma strides {tuple(ty)}: pixels must be contiguous bytes, rows at least W apart")
+        if tc[2] != 1 or (W > 2 and tc[1] != 2) or (H > 2 and tc[0] < W):
+            raise VtError(f"{name} chroma strides {tuple(tc)}: pairs must be contiguous bytes, rows at least W apart")
+        return cls(fmt, (y, c), H, W, (ty[0], tc[0] if H > 2 else W))
+
+    @classmethod
+    def nv12(cls, y, uv):
+        """A decoder's NV12 surface: luma (H, W) and interleaved (U, V) pairs (H/2, W/2, 2)."""
+        return cls._yuv(PIX_NV12, y, uv)
+
+    @classmethod
+    def nv21(cls, y, vu):
+        """NV21: as NV12 with (V, U) pairs."""
+        return cls._yuv(PIX_NV21, y, vu)
+
+    @property
+    def is_cuda(self) -> bool:
+        import torch
+        return isinstance(self.planes[0], torch.Tensor) and self.planes[0].is_cuda
+
+    @property
+    def shape(self):
+        """(H, W, 3): the shape of the RGB image it denotes."""
+        return (self.H, self.W, 3)
+
+    def plane_rows(self):
+        """Per plane: (rows, row bytes)."""
+        r0, r1 = _row_bytes(self.format, self.W)
+        return [(self.H, r0)] + ([(self.H // 2, r1)] if r1 else [])
+
+    def descriptor(self, ptrs=None, pitches=None):
+        """The vt_image tuple of this image: at its planes' own addresses (device images), or at `ptrs` with `pitches`."""
+        if ptrs is None:
+            ptrs = [int(p.data_ptr()) for p in self.planes]
+            pitches = self.pitches
+        return (int(ptrs[0]), int(ptrs[1]) if len(ptrs) > 1 else 0, int(pitches[0]), int(pitches[1]) if len(pitches) > 1 else 0,
+                self.H, self.W, self.format, 0)
+
+
+def pack_image_offsets(images, start: int = 0, align: int = ARENA_ALIGN):
+    """Byte offsets of the planes of host Images packed one after the other from `start` at tight pitches, every plane at a
+    multiple of `align`.  Returns ([per image: [plane offsets]], end)."""
+    out, o = [], int(start)
+    for im in images:
+        offs = []
+        for rows, rb in im.plane_rows():
+            o = -(-o // align) * align
+            offs.append(o)
+            o += rows * rb
+        out.append(offs)
+    return out, o
+
+
+class ImageTable:
+    """The (B,) vt_image descriptor table of vt_crop_images / vt_track_step_images (include/vittrack.h), the twin of FrameTable:
+    `host` is the numpy view, `dev` (when made for a device) the (B * 48,) uint8 device tensor the kernels read."""
+
+    DTYPE = IMAGE_DTYPE
+    ITEM = IMAGE_DTYPE.itemsize
+
+    def __init__(self, B: int, device=None):
+        import torch
+        self.B = int(B)
+        pin = device is not None and torch.cuda.is_available()
+        self._host_t = torch.zeros(self.B * self.ITEM, dtype=torch.uint8, pin_memory=pin)
+        self.host = self._host_t.numpy().view(IMAGE_DTYPE)
+        self.dev = None if device is None else torch.zeros(self.B * self.ITEM, dtype=torch.uint8, device=device)
+        self.keep = [None] * self.B
+        self._copied = None
+
+    @staticmethod
+    def check(fmt: int, ptr0: int, ptr1: int, H: int, W: int, pitch0: int = 0, pitch1: int = 0, reserved: int = 0,
+              nbytes0: int | None = None, nbytes1: int | None = None):
+        """The device's rules for an unusable descriptor, on the host: raises VtError where the kernels would poison the sequence.
+        Returns the pitches actually used (0 -> the row's bytes).  nbytes0 / nbytes1: bytes available from each plane (buffers)."""
+        fmt, H, W, pitch0, pitch1 = int(fmt), int(H), int(W), int(pitch0), int(pitch1)
+        if fmt not in range(6):
+            raise VtError(f"unknown pixel format {fmt}")
+        if int(reserved) != 0:
+            raise VtError("vt_image.reserved must be 0")
+        if H < 1 or W < 1 or H > 0x10000000 or W > 0x10000000:
+            raise VtError(f"image of {H}x{W} pixels: H and W must be >= 1")
+        if _is_nv(fmt) and (H % 2 or W % 2):
+            raise VtError(f"an {PIX_NAMES[fmt].upper()} image must have even H and W, got {H}x{W}")
+        r0, r1 = _row_bytes(fmt, W)
+        planes = [(ptr0, pitch0, H, r0, nbytes0)] + ([(ptr1, pitch1, H // 2, r1, nbytes1)] if r1 else [])
+        used = []
+        for k, (ptr, pitch, rows, rb, nb) in enumerate(planes):
+            pitch = pitch or rb
+            if pitch < rb:
+                raise VtError(f"plane {k}: row pitch {pitch} is shorter than a row ({rb} bytes)")
+            if not ptr or int(ptr) % 4:
+                raise VtError(f"plane {k}: address {int(ptr or 0):#x} is null or not 4-byte aligned")
+            need = pitch * (rows - 1) + rb
+            if pitch > 0xfffffff0 or need > 0xfffffff0:
+                raise VtError(f"plane {k}: {need} bytes are beyond the 32-bit offsets of the crop kernels")
+            if nb is not None and need > int(nb):
+                raise VtError(f"plane {k}: needs {need} bytes, its buffer has {int(nb)}")
+            used.append(pitch)
+        return used[0], (used[1] if len(used) > 1 else int(pitch1))
+
+    def set(self, i: int, desc, keep=None, check: bool = True):
+        """Entry i from a vt_image tuple (plane0, plane1, pitch0, pitch1, H, W, format, reserved); check=False writes it as it is."""
+        p0, p1, q0, q1, H, W, fmt, res = (int(v) for v in desc)
+        if check:
+            q0, q1 = self.check(fmt, p0, p1, H, W, q0, q1, res)
+        if self._copied is not None:
+            self._copied.synchronize()
+            self._copied = None
+        self.host[i] = (p0, p1, q0, q1, H, W, fmt, res)
+        self.keep[i] = keep
+
+    def set_image(self, i: int, image: Image):
+        """Entry i from an Image whose planes are on the GPU (read in place)."""
+        if not isinstance(image, Image) or not image.is_cuda:
+            raise VtError("ImageTable.set_image wants an Image whose planes are on the GPU")
+        self.set(i, image.descriptor(), keep=image)
+
+    @classmethod
+    def of(cls, images, device="cuda", stream=None):
+        t = cls(len(images), device)
+        for i, im in enumerate(images):
+            t.set_image(i, im)
+        t.upload(stream)
+        return t
+
+    def upload(self, stream=None):
+        import torch
+        if self.dev is None:
+            raise VtError("this ImageTable has no device copy")
+        with torch.cuda.stream(stream) if stream is not None else _nullctx():
+            self.dev.copy_(self._host_t, non_blocking=self._host_t.is_pinned())
+            if self._host_t.is_pinned():
+                self._copied = torch.cuda.Event()
+                self._copied.record()
+        return self.dev
+
+
+def _image_table_ptr(table, B):
+    """Device address of a (B,) vt_image table: an ImageTable (its device copy) or a uint8 CUDA tensor of B * 48 bytes."""
+    import torch
+    t = table.dev if isinstance(table, ImageTable) else table
+    if not (isinstance(t, torch.Tensor) and (t.is_cuda or t.is_pinned()) and t.numel() * t.element_size() >= B * IMAGE_DTYPE.itemsize
+            and t.is_contiguous()):
+        raise VtError(f"image table must be an ImageTable with a device copy or a contiguous tensor of {B} x 48 bytes on the GPU")
+    return C.c_void_p(t.data_ptr())
 
 
 class _nullctx:
@@ -614,6 +855,45 @@ class Model:
         _check(self._L.vt_track_step_frames(self._h, _table_ptr(table, B), C.c_void_p(states.data_ptr()), float(factor), m3, s3, B,
                                           _stream(stream), _ptr(x), C.c_void_p(resize_factor.data_ptr()), C.byref(st), margin,
                                           C.c_void_p(record.data_ptr()) if record is not None else None), "vt_track_step_frames", self._L)
+        return out
+
+    # ---- pixel formats: one vt_image per sequence (vt_crop_images & co.)
+    def crop_images(self, table, states, factor, out_size, mean, std, out=None, resize_factor=None, stream=None):
+        """crop_frames() on an image table (ImageTable / vt_crop_images): sequence b is cropped from rgb(images[b])."""
+        import torch
+        B, out, resize_factor = self._table_args(states, (3, out_size, out_size), torch.float32, out, resize_factor)
+        m3 = (C.c_float * 3)(*[float(v) for v in mean])
+        s3 = (C.c_float * 3)(*[float(v) for v in std])
+        _check(self._L.vt_crop_images(self._h, _image_table_ptr(table, B), C.c_void_p(states.data_ptr()), float(factor), out_size, m3, s3, B,
+                                    _stream(stream), _ptr(out), C.c_void_p(resize_factor.data_ptr())), "vt_crop_images", self._L)
+        return out, resize_factor
+
+    def crop_u8_images(self, table, states, factor, out_size, out=None, resize_factor=None, stream=None):
+        """crop_u8_frames() on an image table (vt_crop_u8_images)."""
+        import torch
+        B, out, resize_factor = self._table_args(states, (out_size, out_size, 3), torch.uint8, out, resize_factor)
+        _check(self._L.vt_crop_u8_images(self._h, _image_table_ptr(table, B), C.c_void_p(states.data_ptr()), float(factor), out_size, B,
+                                       _stream(stream), C.c_void_p(out.data_ptr()), C.c_void_p(resize_factor.data_ptr())),
+               "vt_crop_u8_images", self._L)
+        return out, resize_factor
+
+    def track_step_images(self, table, states, factor, mean, std, x, resize_factor, out: Outputs, record=None, margin=10, stream=None):
+        """track_step_frames() on an image table (vt_track_step_images)."""
+        import torch
+        B = self._check_x_only(x)
+        if (tuple(states.shape) != (B, 4) or states.dtype != torch.float64 or not states.is_cuda or not states.is_contiguous()
+                or tuple(resize_factor.shape) != (B,) or resize_factor.dtype != torch.float64 or not resize_factor.is_cuda):
+            raise VtError(f"track_step_images wants states ({B},4) and resize_factor ({B},) float64 on the GPU")
+        if record is not None and (tuple(record.shape) != (B, 5) or record.dtype != torch.float64 or not record.is_contiguous()
+                                   or not (record.is_cuda or record.is_pinned())):
+            raise VtError(f"record must be a contiguous ({B},5) float64 tensor on the GPU or in pinned host memory")
+        self._check_out(out, B)
+        st = out.struct()
+        m3 = (C.c_float * 3)(*[float(v) for v in mean])
+        s3 = (C.c_float * 3)(*[float(v) for v in std])
+        _check(self._L.vt_track_step_images(self._h, _image_table_ptr(table, B), C.c_void_p(states.data_ptr()), float(factor), m3, s3, B,
+                                          _stream(stream), _ptr(x), C.c_void_p(resize_factor.data_ptr()), C.byref(st), margin,
+                                          C.c_void_p(record.data_ptr()) if record is not None else None), "vt_track_step_images", self._L)
         return out
 
     def set_template_slots(self, z, slots, stream=None):

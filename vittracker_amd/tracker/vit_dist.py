@@ -24,6 +24,7 @@ import numpy as np
 from ..host_ops import Preprocessor, clip_box, hann2d, sample_target
 from ..batched import check_params_geometry
 from ..model import build_ostrack_dist
+from ..native import Image, VtError
 
 
 class BaseTracker:
@@ -102,8 +103,11 @@ class Vit_dist(BaseTracker):
         self._rec_host = torch.empty(5).pin_memory()
 
     def initialize(self, image, info: dict):
+        """image: an (H, W, 3) RGB array, or a native.Image (NV12 / NV21, BGR, RGBA / BGRA) that the device crop reads directly."""
+        if isinstance(image, Image) and self._bt is None:
+            raise VtError("an Image frame needs the device pipeline (params.host_crop is set)")
         if self._bt is not None:
-            self._bt.initialize(image[None], [list(info["init_bbox"])])
+            self._bt.initialize([image] if isinstance(image, Image) else image[None], [list(info["init_bbox"])])
             self.box_mask_z = None
             self.state = info["init_bbox"]
             self.frame_id = 0
@@ -124,10 +128,12 @@ class Vit_dist(BaseTracker):
 
     def track(self, image, info: dict = None):
         import torch
+        if isinstance(image, Image) and self._bt is None:
+            raise VtError("an Image frame needs the device pipeline (params.host_crop is set)")
         H, W, _ = image.shape
         self.frame_id += 1
         if self._bt is not None:
-            rec = self._bt.track_record(image[None])[0].tolist()      # [x, y, w, h, confidence] of this frame, on the host
+            rec = self._bt.track_record([image] if isinstance(image, Image) else image[None])[0].tolist()      # [x, y, w, h, confidence] of this frame, on the host
             self.state = rec[:4]
             if self.save_all_boxes:
                 # rare mode: two more small copies for the un-clipped box (the windowed decode and this frame's resize factor)
