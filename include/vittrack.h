@@ -121,7 +121,10 @@ int vt_forward(vt_model* m, const float* z_dev, const float* x_dev, int32_t B, v
  * LayerNorm-1 + qkv of those rows are per-token functions of it (vit_dist.py:78-89), hence frame-invariant.  This
  * computes them once for B sequences and keeps them in the model; later vt_forward / vt_graph_capture calls with
  * z_dev == NULL skip that work.  Deeper layers are NOT cached: from block 0's attention on, template tokens depend on
- * the current search tokens. */
+ * the current search tokens.
+ * ViT-Base: what is cached is the templates' bf16 patch-GEMM operand rows (the fp32 -> bf16 gather of z); every step that reads the
+ * cache -- and every vt_forward_u8 with a template of its own -- embeds template rows and search rows with two GEMMs on dense operands,
+ * so cache on == cache off bit for bit, eager and captured (captured steps of >= 64 frames keep their two chains with z_dev == NULL). */
 int vt_set_template(vt_model* m, const float* z_dev, int32_t B, void* stream);
 
 /* --- the three stages of vt_forward, individually (parity tests, profiling) ----------------- */
@@ -159,18 +162,24 @@ int vt_crop_u8(vt_model* m, const uint8_t* frames_dev, int32_t H, int32_t W, con
 /* Preprocessor.__init__'s mean / std (lib/test/tracker/data_utils.py:8-9) for the uint8 entry points below (default: the ImageNet
  * values the reference hard-codes).  Preprocessor.process is affine per channel and the stem's first conv is linear, so the
  * normalisation is folded into that layer's weights in fp64 (here and at vt_load_weights); the conv's zero padding becomes the
- * byte value that normalises to zero.  Synchronises the device; not capturable; VT_ERR_STATE once graphs have been captured. */
+ * byte value that normalises to zero.  Synchronises the device; not capturable; VT_ERR_STATE once graphs have been captured.
+ * ViT-Base: folded into a second bf16 image of the patch-embedding weights that meets the CENTRED bytes p - 128:
+ * W' = W / (255 std_c), b' = b - sum W mean_c / std_c + 128 sum W' from the unrounded fp64 W' (uncentred, the rounding of W' multiplies
+ * the patch's common mode and the tokens leave their 3.2e-3 bound; VB_U8_CENTER=0 restores that form to show it). */
 int vt_set_normalization(vt_model* m, const float* mean3, const float* std3);
 /* Preprocessor.process + OstrackDist.forward on a uint8 search patch (lib/test/tracker/data_utils.py:11-17 +
  * lib/models/vit_dist/vit_dist.py:77-100): x_patch_dev (B,S,S,3) uint8 as vt_crop_u8 writes it; z_dev (B,3,Tz,Tz) fp32 as in
  * vt_forward, or NULL after vt_set_template.  Results agree with vt_forward on the normalised fp32 crop to fp32 rounding (the
  * reference rounds three times per input value, the folded layer once; tests: maps within 1e-5), not bit for bit.
- * vit_48 path (every stem form of the tuned geometries; the shape-generic kernels normalise per tap with the reference's own three
- * rounded operations and are bit-identical to vt_forward); VT_ERR_STATE under the diagnostic switches (vt_patch_u8_supported). */
+ * vit_48 path: every stem form of the tuned geometries; the shape-generic kernels normalise per tap with the reference's own three
+ * rounded operations and are bit-identical to vt_forward; VT_ERR_STATE under the diagnostic switches (vt_patch_u8_supported).
+ * ViT-Base: every batch size; the patch is gathered straight into the bf16 GEMM operand (exact) and the search rows agree with the
+ * fp32 route to bf16 rounding of the weights (tokens within 3.2e-3 of the reference, relative to the centred rows); x_patch_dev must be
+ * 16-byte aligned there (VT_ERR_ARG otherwise). */
 int vt_forward_u8(vt_model* m, const float* z_dev, const uint8_t* x_patch_dev, int32_t B, void* stream, const vt_outputs* out);
 /* The search rows of vt_stem from a uint8 patch: tokens_dev (B,L,C), rows [len_z, L) written, template rows untouched. */
 int vt_stem_u8(vt_model* m, const uint8_t* x_patch_dev, int32_t B, void* stream, float* tokens_dev);
-/* 1 when a batch of B runs a stem form that reads uint8 patches (every vit_48 form outside the diagnostic builds), else 0 (ViT-Base). */
+/* 1 when a batch of B runs a stem form that reads uint8 patches (every vit_48 form outside the diagnostic builds; ViT-Base: always), else 0. */
 int vt_patch_u8_supported(const vt_model* m, int32_t B);
 /* Which crop kernel form the current device runs (decided once per device by a self test against a byte-load twin):
  * 1 = the 8-byte unaligned-window form, 2 = the byte-load form, negative = the self test could not run. */
@@ -193,7 +202,10 @@ int vt_update_state_record(vt_model* m, const float* hann_boxes_dev, const float
 /* The whole per-frame step of Vit_dist.track() (lib/test/tracker/vit_dist.py:87-148) in ONE call: the crop of the search region
  * (search_size of the model's config; crops_dev = a (B,3,S,S) float workspace of the caller) -> the network on the cached
  * template (vt_set_template first) -> vt_update_state_record; with the small-batch head form the decode kernel runs the tail
- * itself (one launch less per step).  record may be NULL.  vit_48 path only.
+ * itself (one launch less per step).  record may be NULL.
+ * ViT-Base: the same contract (crops_dev 16-byte aligned); from 64 frames up the network and each half's tail run as two chains over
+ * frame slices, forked off `stream` after the crop and joined back with events (legal under stream capture and in eager mode;
+ * VT_GRAPH_CHAINS as for vt_graph_capture), bit-identical to one chain.
  * Round 6: the crop reaches the stem as sample_target's uint8 patch -- the step is vt_crop_u8 -> vt_forward_u8(z = NULL) ->
  * vt_update_state_record, bit for bit, and crops_dev holds the (B,S,S,3) uint8 patch in its first bytes -- whenever
  * (mean3, std3) equal the model's normalisation (vt_set_normalization) and vt_patch_u8_supported(m, B); otherwise (and with

@@ -17,7 +17,7 @@ import numpy as np
 
 from .config import geometry
 from .host_ops import hann2d
-from .model import build_ostrack_dist
+from .factory import build_network
 from .native import FrameTable, Image, ImageTable, VtError, pack_image_offsets, pack_offsets
 
 
@@ -43,7 +43,7 @@ class BatchedVitTracker:
         self.cfg = params.cfg
         self.B = batch
         g = geometry(self.cfg)
-        self.net = build_ostrack_dist(self.cfg, max_batch=batch)
+        self.net = build_network(self.cfg, max_batch=batch)      # vit_48 or ViT-Base OSTrack, by the cfg
         ckpt = getattr(params, "checkpoint", None)
         import os
         if ckpt and os.path.isfile(ckpt):

@@ -30,6 +30,18 @@ void destroy(VbModel* m);
 int load_weights(VbModel* m, const TensorMap& tm, std::string* err);
 // patch_embed(z), patch_embed(x), += pos_embed, cat((z, x))  -> the model's f32 residual stream; tokens_out (optional): a copy
 int stem(VbModel* m, const float* z, const float* x, int B, hipStream_t st, float* tokens_out, std::string* err, const Slice* sl = nullptr);
+// The tracker's stem: template rows and search rows embedded by two GEMMs on dense operands (vb_gemm.h EPI_PATCH_ROWS), so that the template's
+// operand can be cached and the search rows can come from a uint8 patch under their own (normalisation-folded) weights.
+//   zsrc  Z_GIVEN: z is the fp32 template crop;  Z_CACHED: the operand rows set_template left (z unused);  Z_NONE: search rows only
+//   x / xu8 (exactly one): fp32 (B,3,256,256) crop, or the uint8 (B,256,256,3) patch of vt_crop_u8* (16-byte aligned)
+//   x_tokens_out (optional): the search rows are copied into rows [64, 320) of this (B,320,768) matrix
+enum ZSrc { Z_GIVEN = 0, Z_CACHED = 1, Z_NONE = 2 };
+int stem_rows(VbModel* m, ZSrc zsrc, const float* z, const float* x, const unsigned char* xu8, int B, hipStream_t st, float* x_tokens_out,
+              std::string* err, const Slice* sl = nullptr);
+// the template cache: the bf16 patch-GEMM operand rows of n templates, into slots[i] (slots == nullptr: slots 0..n-1)
+int set_template(VbModel* m, const float* z, int n, const int32_t* slots, hipStream_t st, std::string* err);
+// Preprocessor.process folded into the uint8 form of the patch-embedding weights (fp64; vitb.hip fold_patch_u8).  Synchronous.
+int set_normalization(VbModel* m, const float* mean3, const float* std3, std::string* err);
 // blocks[0..nblocks) on the residual stream (tokens_in: optional replacement, copied in first), then the final norm:
 // the search rows go to the head's input map (and to feat_out as f32 (B,Lx,C), optional); resid_out optional copy
 int blocks(VbModel* m, const float* tokens_in, int B, int nblocks, hipStream_t st, float* feat_out, float* resid_out, std::string* err,

@@ -86,6 +86,8 @@ enum Epi {
     EPI_GELU = 3,    // out[m][n] = bf16(gelu(acc + bias[n]))
     EPI_CONV = 4,    // out[map row of m][n] = bf16(relu(acc + bias[n]))                 (head towers, BN folded)
     EPI_VT = 5,      // vt[frame][n][token] = bf16(acc + bias[n]): the v projection, stored transposed (operands swapped)
+    EPI_PATCH_ROWS = 6,   // EPI_PATCH on a dense operand of ONE token kind (template rows or search rows only): operand row m is token
+                          // row_o0 + m % 2^row_shift of frame m >> row_shift and lands on row frame * L + token of resid / xb / stats
 };
 
 struct Args {
@@ -123,6 +125,7 @@ struct Args {
     int dbg;              // timing experiments only (VB_DBG, wrong results by design; 0 in production):
                           // 1 = every tile loads the X panel of tile row 0, 2 = ... the W panel of tile column 0,
                           // 4 = no MFMAs, 8 = no epilogue, 16 = no W staging, 32 = no X staging (wide tile)
+    int row_shift, row_o0;      // EPI_PATCH_ROWS: log2(operand rows per frame), first token of the kind (0: template, Lz: search)
 };
 
 // The epilogue staging area is written and read back through differently typed pointers by the same wave: the accesses
@@ -316,7 +319,7 @@ __global__ __launch_bounds__(NWAVES * 64) void gemm_kernel(const Args a) {
         f4 bs[TN];
 #pragma unroll
         for (int i = 0; i < TN; ++i) bs[i] = *reinterpret_cast<const f4a*>(ep + (i * 16 + q4) * 4);
-        if constexpr (EPI == EPI_RESID || EPI == EPI_PATCH) {
+        if constexpr (EPI == EPI_RESID || EPI == EPI_PATCH || EPI == EPI_PATCH_ROWS) {
             lds_fence();
             // f32 residual stream: chunk = 16 rows x 256 B; read-modify-write in whole rows, loads before stores.  Next to it
             // (LayerNorm folded into the next GEMM): the rows' bf16 copy and, per row, this wave's 64-column (sum, centred M2)
@@ -328,12 +331,16 @@ __global__ __launch_bounds__(NWAVES * 64) void gemm_kernel(const Args a) {
             float oc[4];      // the rows' centring constants (Args::cm): ONE set, requested at the top of a row group's iteration and used at its end
                               // (the same few KB for all twelve column tiles of a row: L1 / L2 hits; a ring of AH + 1 sets spilled 40 B)
             const int ch = lane & 15, r0 = lane >> 4;
+            // EPI_PATCH_ROWS: the token of operand row m, and the row of the (frame, token) matrices it is written to
+            auto tok = [&](int m) { return a.row_o0 + (m & ((1 << a.row_shift) - 1)); };
+            auto orow = [&](int m) { return EPI == EPI_PATCH_ROWS ? (m >> a.row_shift) * a.L + tok(m) : m; };
             auto load_c = [&](int j, float (&oc)[4]) {
 #pragma unroll
                 for (int t = 0; t < 4; ++t) {
                     const int m = mw + j * 16 + 4 * t + r0;
                     const int mc = CHECK ? (m < a.M ? m : a.M - 1) : m;
-                    oc[t] = (a.xb && a.cm) ? a.cm[a.cm_mod ? mc % a.cm_mod : mc] : 0.f;
+                    if constexpr (EPI == EPI_PATCH_ROWS) oc[t] = (a.xb && a.cm) ? a.cm[tok(mc)] : 0.f;
+                    else oc[t] = (a.xb && a.cm) ? a.cm[a.cm_mod ? mc % a.cm_mod : mc] : 0.f;
                 }
             };
             auto load_old = [&](int j, f4 (&o)[4]) {
@@ -344,6 +351,7 @@ __global__ __launch_bounds__(NWAVES * 64) void gemm_kernel(const Args a) {
                     if constexpr (EPI == EPI_RESID)
                         o[t] = VB_EPI_NT ? __builtin_nontemporal_load(reinterpret_cast<const f4*>(a.resid + (size_t)mc * a.N + nw + ch * 4))
                                          : ld4(a.resid + (size_t)mc * a.N + nw + ch * 4);
+                    else if constexpr (EPI == EPI_PATCH_ROWS) o[t] = ld4(a.pos + (size_t)tok(mc) * a.N + nw + ch * 4);
                     else o[t] = ld4(a.pos + (size_t)(mc % a.L) * a.N + nw + ch * 4);
                 }
             };
@@ -364,16 +372,17 @@ __global__ __launch_bounds__(NWAVES * 64) void gemm_kernel(const Args a) {
                     const f4 v = *reinterpret_cast<const f4a*>(ep + row * 256 + ((ch ^ row) << 4));
                     const f4 nv = old[t] + v;
                     const bool ok = !CHECK || m < a.M;
+                    const int mo = orow(m);
                     if (ok) {
-                        if (VB_EPI_NT) st4_nt(a.resid + (size_t)m * a.N + nw + ch * 4, nv);
-                        else st4(a.resid + (size_t)m * a.N + nw + ch * 4, nv);
+                        if (VB_EPI_NT) st4_nt(a.resid + (size_t)mo * a.N + nw + ch * 4, nv);
+                        else st4(a.resid + (size_t)mo * a.N + nw + ch * 4, nv);
                     }
                     if (a.xb) {
-                        if (ok) *reinterpret_cast<bf16x4*>(a.xb + (size_t)m * a.N + nw + ch * 4) = to_bf16x4(nv - splat4(oc[t]));
+                        if (ok) *reinterpret_cast<bf16x4*>(a.xb + (size_t)mo * a.N + nw + ch * 4) = to_bf16x4(nv - splat4(oc[t]));
                         const float s = row16_sum(hsum4(nv));
                         const f4 d = nv - splat4(s * (1.0f / 64.0f));
                         const float m2 = row16_sum(hsum4(d * d));
-                        if (ok && ch == 0) a.stats[(size_t)(tn * WN + wn) * a.ldstats + m] = f2{s, m2};
+                        if (ok && ch == 0) a.stats[(size_t)(tn * WN + wn) * a.ldstats + mo] = f2{s, m2};
                     }
                 }
                 lds_fence();

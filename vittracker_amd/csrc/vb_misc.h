@@ -35,6 +35,45 @@ __global__ __launch_bounds__(256) void patchify_kernel(const float* __restrict__
     }
 }
 
+// The search rows of the same operand from the uint8 HWC patch (B, T, T, 3) that vt_crop_u8* writes (sample_target's output), DENSE:
+// P[m = frame * (T / 16)^2 + token][k = c * 256 + r * 16 + s] = bf16(byte - centre).  Preprocessor.process's / 255, - mean, / std live in
+// the weights this operand meets (vitb.hip fold_patch_u8); centre = 128 takes the bytes' common mode out of what those rounded weights
+// multiply.  |byte - centre| has at most 8 significant bits: its bf16 is exact, the conversion is the float's upper half.
+// One thread = pixel row r of one token: 48 contiguous bytes in (offset a multiple of 48: three aligned 16-byte loads), one 32-byte run out
+// per channel.  r is the fastest lane index, so the 16 lanes of a token write each channel's 16 runs as ONE contiguous 512 bytes.
+__global__ __launch_bounds__(256) void patchify_u8_kernel(const unsigned char* __restrict__ xp, bf16* __restrict__ P, int B, int T, float centre) {
+    typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+    const int g = T / 16, Lx = g * g;
+    const size_t total = (size_t)B * Lx * 16;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
+        const int r = (int)(i & 15);
+        const size_t m = i >> 4;
+        const int t = (int)(m % Lx), py = t / g, px = t - py * g;
+        const size_t f = m / Lx;
+        const u32x4* src = reinterpret_cast<const u32x4*>(xp + ((f * T + py * 16 + r) * T + px * 16) * 3);
+        unsigned w[12];
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+            const u32x4 v = __builtin_nontemporal_load(src + j);
+            w[4 * j] = v.x; w[4 * j + 1] = v.y; w[4 * j + 2] = v.z; w[4 * j + 3] = v.w;
+        }
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            unsigned o[8];
+#pragma unroll
+            for (int s = 0; s < 16; s += 2) {      // byte 3 s + c of the row: channel c of pixel s (v_cvt_f32_ubyteN picks it out of its dword)
+                const int k0 = 3 * s + c, k1 = k0 + 3;
+                const float v0 = (float)((w[k0 >> 2] >> (8 * (k0 & 3))) & 255u) - centre;
+                const float v1 = (float)((w[k1 >> 2] >> (8 * (k1 & 3))) & 255u) - centre;
+                o[s >> 1] = __builtin_amdgcn_perm(__float_as_uint(v1), __float_as_uint(v0), 0x07060302u);      // v_perm: the two upper halves
+            }
+            u32x4* dst = reinterpret_cast<u32x4*>(P + m * 768 + c * 256 + r * 16);
+            dst[0] = u32x4{o[0], o[1], o[2], o[3]};
+            dst[1] = u32x4{o[4], o[5], o[6], o[7]};
+        }
+    }
+}
+
 // -------------------------------------------------------------------------------------------- LayerNorm
 // nn.LayerNorm(C, eps) over the f32 residual stream (lib/models/ostrack/vit.py:78,82,130; eps 1e-6): biased variance,
 // two passes over registers.  One wave per token row, C = 768 = 64 lanes x 3 float4.

@@ -73,6 +73,13 @@ struct VbModel {
     Buf<float> rstd;
     Buf<float> rmean;        // per-row mean of the residual stream as of the last finalize: the next producer centres its bf16 copy on it
     Buf<float> cpos;         // [L]: mean over channels of (pos-embed row + patch bias): the patch GEMM's centring constant per token
+    // uint8 search patches (vb::stem_rows): Preprocessor.process folded into a second image of the patch weights (fold_patch_u8), the
+    // centring table rebuilt from its bias; host copies of what the fold starts from, for vt_set_normalization after vt_load_weights
+    Buf<bf16> wpatch_u8; Buf<float> bpatch_u8, cpos_u8;
+    std::vector<float> h_wpatch, h_bpatch, h_pos;
+    float norm_mean[3] = {0.485f, 0.456f, 0.406f}, norm_std[3] = {0.229f, 0.224f, 0.225f};
+    float u8_centre = 128.f;        // VB_U8_CENTER=0: the uncentred fold (diagnostic: NOTES R7-1 shows it over the token bound)
+    Buf<bf16> zop;           // template cache: the templates' operand rows [max_batch * LZ][PATCH_K]
     bool center = true;      // VB_LN_CENTER
     Buf<vbg::f2> stats;
 };
@@ -127,13 +134,13 @@ int launch_gemm(const vbg::Args& a, int groups, hipStream_t st, const Err& E, in
     vbg::Args ad = a;
     ad.dbg = dbg;
     {   // experiment hook: VB_RB_<epilogue id>=rows overrides the tile-row block of that GEMM kind
-        static const int rbs[6] = {env_int("VB_RB_0", -1), env_int("VB_RB_1", -1), env_int("VB_RB_2", -1), env_int("VB_RB_3", -1),
-                                   env_int("VB_RB_4", -1), env_int("VB_RB_5", -1)};
+        static const int rbs[7] = {env_int("VB_RB_0", -1), env_int("VB_RB_1", -1), env_int("VB_RB_2", -1), env_int("VB_RB_3", -1),
+                                   env_int("VB_RB_4", -1), env_int("VB_RB_5", -1), env_int("VB_RB_6", -1)};
         if (rbs[EPI] >= 0) ad.rb = rbs[EPI];
     }
     {   // experiment hook: VB_DESYNC_<epilogue id>=<us>[:groups] -- phase groups of workgroups (Args::desync_ticks)
-        static const struct D { int us[6], g[6]; D() {
-            for (int e = 0; e < 6; ++e) {
+        static const struct D { int us[7], g[7]; D() {
+            for (int e = 0; e < 7; ++e) {
                 const std::string n = "VB_DESYNC_" + std::to_string(e);
                 const char* v = std::getenv(n.c_str());
                 us[e] = v ? std::atoi(v) : 0;
@@ -189,9 +196,51 @@ void fold_layernorm(std::vector<float>& w, std::vector<float>& b, const float* g
     }
 }
 
+// Preprocessor.process (lib/test/tracker/data_utils.py:11-17: / 255, - mean, / std) folded into the patch embedding of the uint8 search
+// patch, in double.  The operand is the CENTRED byte p - ctr (vbm::patchify_u8_kernel, ctr = 128):
+//     W'[n][c,r,s] = W[n][c,r,s] / (255 std_c),      b'[n] = b[n] - sum W mean_c / std_c + ctr sum W'
+// with the bias from the UNROUNDED W'.  What the bf16 rounding of W' then multiplies is p - 128 instead of p: uncentred, the rounding
+// errors of a row of W' meet a common mode of ~2 sigma of the patch and the tokens leave the 3.2e-3 the stage is held to (3.3e-3 on
+// noise patches; centred 1.7e-3; the fp32 route 2.3-2.6e-3: NOTES R7-1, tests/test_vitb_track_host.py).  Compensating with the ROUNDED
+// weights instead is algebraically the uncentred form again.  The centring table of the search rows (Args::cm) follows b'.
+int fold_patch_u8(VbModel* m, const Err& E) {
+    std::vector<float> w((size_t)C * PATCH_K), b(C), cpos(L);
+    double k255[3], ms[3], bsum = 0;
+    for (int c = 0; c < 3; ++c) { k255[c] = 1.0 / (255.0 * (double)m->norm_std[c]); ms[c] = (double)m->norm_mean[c] / (double)m->norm_std[c]; }
+    for (int n = 0; n < C; ++n) {
+        const float* row = m->h_wpatch.data() + (size_t)n * PATCH_K;
+        double sm = 0, sw = 0;
+        for (int k = 0; k < PATCH_K; ++k) {
+            const int c = k >> 8;
+            const double wd = (double)row[k] * k255[c];
+            sm += (double)row[k] * ms[c];
+            sw += wd;
+            w[(size_t)n * PATCH_K + k] = (float)wd;
+        }
+        const double bd = (double)m->h_bpatch[n] - sm + (double)m->u8_centre * sw;
+        b[n] = (float)bd;
+        bsum += bd;
+    }
+    for (int t = 0; t < L; ++t) {
+        double s = 0;
+        for (int k = 0; k < C; ++k) s += m->h_pos[(size_t)t * C + k];
+        cpos[t] = (float)((s + bsum) / C);
+    }
+    int rc;
+    if ((rc = upload_bf16(m->wpatch_u8, w, E)) || (rc = upload_f32(m->bpatch_u8, b.data(), b.size(), E))) return rc;
+    return upload_f32(m->cpos_u8, cpos.data(), cpos.size(), E);
+}
+
 }  // namespace
 
 namespace vb {
+
+int set_normalization(VbModel* m, const float* mean3, const float* std3, std::string* err) {
+    const Err E{err};
+    std::memcpy(m->norm_mean, mean3, 12);
+    std::memcpy(m->norm_std, std3, 12);
+    return m->loaded ? fold_patch_u8(m, E) : VT_OK;      // before vt_load_weights: remembered, load_weights folds with it
+}
 
 int create(const vt_config* cfg, VbModel** out, std::string* err) {
     const Err E{err};
@@ -208,13 +257,14 @@ int create(const vt_config* cfg, VbModel** out, std::string* err) {
     m->fold = env_int("VB_LN_FOLD", 1) != 0;
     m->center = env_int("VB_LN_CENTER", 1) != 0;
     m->fused_qkv = env_int("VB_FUSED_QKV", 1) != 0;
+    m->u8_centre = env_int("VB_U8_CENTER", 1) != 0 ? 128.f : 0.f;
     const size_t B = (size_t)cfg->max_batch, M = B * L, P2 = (size_t)(F + 2) * (F + 2);
     hipError_t e = hipSuccess;
     auto A = [&](auto& buf, size_t n) { if (e == hipSuccess) e = buf.alloc(n); };
     A(m->xn, M * C); A(m->resid, M * C); A(m->qk, M * 2 * C); A(m->vt, M * C); A(m->ao, M * C); A(m->hid, M * HID);
     A(m->map0, B * P2 * C); A(m->map1, 3 * B * P2 * HEAD_CH[1]); A(m->map2, 3 * B * P2 * HEAD_CH[2]);
     A(m->map3, 3 * B * P2 * HEAD_CH[3]); A(m->t4, 3 * B * LX * HEAD_CH[4]);
-    A(m->rstd, M); A(m->stats, (size_t)STAT_P * M); A(m->rmean, M);
+    A(m->rstd, M); A(m->stats, (size_t)STAT_P * M); A(m->rmean, M); A(m->zop, B * LZ * PATCH_K);
     // zero borders of the padded maps (kernels only ever write interiors)
     if (e == hipSuccess) e = hipMemset(m->map0.p, 0, m->map0.n * 2);
     if (e == hipSuccess) e = hipMemset(m->map1.p, 0, m->map1.n * 2);
@@ -222,6 +272,7 @@ int create(const vt_config* cfg, VbModel** out, std::string* err) {
     if (e == hipSuccess) e = hipMemset(m->map3.p, 0, m->map3.n * 2);
     using namespace vbg;
     if (e == hipSuccess) e = allow_lds(gemm_kernel<256, 256, 2, 4, A_PLAIN, EPI_PATCH>, lds_bytes<256, 256>());
+    if (e == hipSuccess) e = allow_lds(gemm_kernel<256, 256, 2, 4, A_PLAIN, EPI_PATCH_ROWS>, lds_bytes<256, 256>());
     if (e == hipSuccess) e = allow_lds(gemm_kernel<256, 256, 2, 4, A_PLAIN, EPI_BF16>, lds_bytes<256, 256>());
     if (e == hipSuccess) e = allow_lds(gemm_kernel<256, 256, 2, 4, A_PLAIN, EPI_VT>, lds_bytes<256, 256>());
     if (e == hipSuccess) e = allow_lds(gemm_kernel<256, 256, 2, 4, A_PLAIN, EPI_RESID>, lds_bytes<256, 256>());
@@ -250,6 +301,7 @@ void destroy(VbModel* m) {
     m->xn.release(); m->qk.release(); m->vt.release(); m->ao.release(); m->hid.release(); m->map0.release();
     m->map1.release(); m->map2.release(); m->map3.release(); m->t4.release(); m->resid.release();
     m->rstd.release(); m->stats.release(); m->rmean.release(); m->cpos.release();
+    m->wpatch_u8.release(); m->bpatch_u8.release(); m->cpos_u8.release(); m->zop.release();
     delete m;
 }
 
@@ -264,6 +316,9 @@ int load_weights(VbModel* m, const TensorMap& tm, std::string* err) {
     if ((rc = upload_bf16(m->wpatch, std::vector<float>(p, p + (size_t)C * PATCH_K), E))) return rc;
     if ((rc = need(tm, bb + "patch_embed.proj.bias", C, &p, E))) return rc;
     if ((rc = upload_f32(m->bpatch, p, C, E))) return rc;
+    m->h_bpatch.assign(p, p + C);
+    if ((rc = need(tm, bb + "patch_embed.proj.weight", (int64_t)C * PATCH_K, &p, E))) return rc;
+    m->h_wpatch.assign(p, p + (size_t)C * PATCH_K);
     {
         std::vector<float> pos((size_t)L * C);
         if ((rc = need(tm, bb + "pos_embed_z", (int64_t)LZ * C, &p, E))) return rc;
@@ -284,6 +339,8 @@ int load_weights(VbModel* m, const TensorMap& tm, std::string* err) {
             cpos[t] = (float)((s + bmean) / C);
         }
         if ((rc = upload_f32(m->cpos, cpos.data(), cpos.size(), E))) return rc;
+        m->h_pos = pos;
+        if ((rc = fold_patch_u8(m, E))) return rc;
     }
     const float scale = 1.0f / std::sqrt((float)HD);     // 0.125: a power of two, folding it into W_q / b_q is exact
     for (int i = 0; i < m->depth; ++i) {
@@ -407,6 +464,72 @@ int stem(VbModel* m, const float* z, const float* x, int B, hipStream_t st, floa
     if ((rc = launch_gemm<256, 256, 2, 4, vbg::A_PLAIN, vbg::EPI_PATCH>(a, 1, st, E, cus))) return rc;
     if (m->fold && (rc = run_finalize(m, r0, M, st, E))) return rc;
     if (tokens_out) VB_HIP(hipMemcpyAsync(tokens_out, resid, (size_t)M * C * 4, hipMemcpyDeviceToDevice, st));
+    return VT_OK;
+}
+
+// one token kind's rows of a crop batch as a dense operand: patchify_kernel with no template (Tz = 0) walks (B, 3, T, T) alone
+static int patchify_dense(const float* img, int T, int B, bf16* P, hipStream_t st, const Err& E) {
+    const size_t items = (size_t)B * (T / 16) * (T / 16) * 96;
+    hipLaunchKernelGGL(vbm::patchify_kernel, dim3((unsigned)std::min<size_t>((items + 255) / 256, 16384)), dim3(256), 0, st, nullptr, img, P, B, 0, T);
+    VB_HIP(hipGetLastError());
+    return VT_OK;
+}
+
+int set_template(VbModel* m, const float* z, int n, const int32_t* slots, hipStream_t st, std::string* err) {
+    const Err E{err};
+    int rc = check(m, n, E);
+    if (rc) return rc;
+    const size_t zrow = (size_t)LZ * PATCH_K;
+    if (!slots) return patchify_dense(z, 128, n, m->zop.p, st, E);
+    for (int i = 0; i < n; ++i) {      // a frame's operand rows depend on that frame alone: straight into place
+        if (slots[i] < 0 || slots[i] >= m->maxB) return E.fail(VT_ERR_ARG, "template slot outside the batch");
+        if ((rc = patchify_dense(z + (size_t)i * 3 * 128 * 128, 128, 1, m->zop.p + (size_t)slots[i] * zrow, st, E))) return rc;
+    }
+    return VT_OK;
+}
+
+int stem_rows(VbModel* m, ZSrc zsrc, const float* z, const float* x, const unsigned char* xu8, int B, hipStream_t st, float* x_tokens_out,
+              std::string* err, const Slice* sl) {
+    const Err E{err};
+    int rc = check(m, B, E);
+    if (rc || (rc = check_slice(m, B, sl, E))) return rc;
+    if ((x != nullptr) == (xu8 != nullptr)) return E.fail(VT_ERR_ARG, "stem_rows: one of the fp32 crop and the uint8 patch");
+    if (xu8 && (reinterpret_cast<uintptr_t>(xu8) & 15)) return E.fail(VT_ERR_ARG, "the uint8 patch must be 16-byte aligned on the ViT-Base path");
+    const size_t f0 = sl ? sl->f0 : 0, r0 = f0 * L;
+    const int cus = sl ? sl->cus : 0;
+    bf16* const xn = m->xn.p + r0 * C;
+    float* const resid = m->resid.p + r0 * C;
+    bf16* const xop = (m->fold ? m->ao.p : m->xn.p) + r0 * C;      // B * LX dense rows inside the slice's B * L (as vb::stem's operand)
+    const bf16* zop = m->zop.p + f0 * LZ * PATCH_K;
+    if (zsrc == Z_GIVEN) {      // not through the cache: a call with its own template leaves vt_set_template's rows alone
+        bf16* const ztmp = m->hid.p + r0 * HID;
+        if ((rc = patchify_dense(z, 128, B, ztmp, st, E))) return rc;
+        zop = ztmp;
+    }
+    if (xu8) {
+        const size_t items = (size_t)B * LX * 16;
+        hipLaunchKernelGGL(vbm::patchify_u8_kernel, dim3((unsigned)std::min<size_t>((items + 255) / 256, 16384)), dim3(256), 0, st, xu8, xop, B, 256,
+                           m->u8_centre);
+        VB_HIP(hipGetLastError());
+    } else if ((rc = patchify_dense(x, 256, B, xop, st, E))) return rc;
+    vbg::Args a{};
+    a.resid = resid; a.pos = m->pos.p; a.N = C; a.K = PATCH_K; a.L = L;
+    if (m->fold) { a.xb = xn; a.stats = m->stats.p + r0; a.ldstats = (int)(m->stats.n / STAT_P); }
+    if (zsrc != Z_NONE) {
+        vbg::Args az = a;
+        az.X = zop; az.W = m->wpatch.p; az.bias = m->bpatch.p; az.M = B * LZ; az.row_shift = 6; az.row_o0 = 0;
+        if (m->fold && m->center) az.cm = m->cpos.p;
+        if ((rc = launch_gemm<256, 256, 2, 4, vbg::A_PLAIN, vbg::EPI_PATCH_ROWS>(az, 1, st, E, cus))) return rc;
+    }
+    a.X = xop; a.M = B * LX; a.row_shift = 8; a.row_o0 = LZ;
+    a.W = xu8 ? m->wpatch_u8.p : m->wpatch.p;
+    a.bias = xu8 ? m->bpatch_u8.p : m->bpatch.p;
+    if (m->fold && m->center) a.cm = xu8 ? m->cpos_u8.p : m->cpos.p;
+    if ((rc = launch_gemm<256, 256, 2, 4, vbg::A_PLAIN, vbg::EPI_PATCH_ROWS>(a, 1, st, E, cus))) return rc;
+    if (m->fold && (rc = run_finalize(m, r0, B * L, st, E))) return rc;
+    if (x_tokens_out)
+        VB_HIP(hipMemcpy2DAsync(x_tokens_out + (size_t)LZ * C, (size_t)L * C * 4, resid + (size_t)LZ * C, (size_t)L * C * 4, (size_t)LX * C * 4, B,
+                                hipMemcpyDeviceToDevice, st));
     return VT_OK;
 }
 

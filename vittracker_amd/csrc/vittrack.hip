@@ -504,7 +504,7 @@ int gen_head(vt_model* m, const float* feat, int B, hipStream_t st, float* score
 // (stem_fused, stem_stream, stem_pipe, stem_a); the diagnostic builds and the shape-generic kernels do not.
 bool stem_takes_u8(const vt_model* m, int B) {
     (void)B;
-    if (m->vb) return false;
+    if (m->vb) return true;          // vitb.hip stem_rows: vbm::patchify_u8_kernel + the normalisation-folded patch weights, at every batch
     if (m->generic) return true;       // vt_generic.h: stem_conv_u8_kernel (the reference's own normalisation per tap)
     return m->stem_w1u.p != nullptr && m->skip_stem_a == 0 && m->skip_stem_b == 0 && m->dbg_stamps == nullptr;
 }
@@ -853,7 +853,9 @@ int run_head(vt_model* m, const float* feat, int B, hipStream_t st, const vt_out
 }
 
 // ViT-Base: towers + conv5 in vitb.hip, then the same decode kernel (first-index argmax, raw and Hann-windowed)
-int run_head_vitb(vt_model* m, const float* feat, int B, hipStream_t st, const vt_outputs* o, const vb::Slice* sl = nullptr) {
+// tail: the tracker step's state tail on the decode kernel's lane (the WHOLE batch's: a slice addresses it from its frame f0 here)
+int run_head_vitb(vt_model* m, const float* feat, int B, hipStream_t st, const vt_outputs* o, const vb::Slice* sl = nullptr,
+                  const TrackTail* tail = nullptr) {
     const size_t f0 = sl ? sl->f0 : 0, n = (size_t)m->len_x;       // outputs of the slice starting at frame f0
     float* score = ((o && o->score_map) ? o->score_map : m->score.p) + f0 * n;
     float* size = ((o && o->size_map) ? o->size_map : m->size.p) + f0 * 2 * n;
@@ -864,7 +866,53 @@ int run_head_vitb(vt_model* m, const float* feat, int B, hipStream_t st, const v
     std::string err;
     int rc = vb::head(m->vb, feat, B, st, score, size, offset, &err, sl);
     if (rc) return fail(rc, err);
-    return run_decode(m, st, score, size, offset, m->window.p, B, pred, hann, conf);
+    if (!tail) return run_decode(m, st, score, size, offset, m->window.p, B, pred, hann, conf);
+    TrackTail t = *tail;
+    t.resize_factor += f0;
+    t.states += 4 * f0;
+    if (t.record) t.record += 5 * f0;
+    if (t.frames) t.frames += f0;
+    return run_decode(m, st, score, size, offset, m->window.p, B, pred, hann, conf, &t);
+}
+
+// ViT-Base: stem on the cached template (or z) + blocks + head of the frames [f0, f0 + nb) of a batch of Btot, on stream st
+int vitb_network(vt_model* m, vb::ZSrc zsrc, const float* z, const float* x, const unsigned char* xu8, size_t f0, int nb, int Btot, int cus,
+                 hipStream_t st, const vt_outputs* out, const TrackTail* tail) {
+    const size_t Tz = m->cfg.template_size, Tx = m->cfg.search_size;
+    const vb::Slice sl{f0, Btot, cus};
+    std::string err;
+    int rc;
+    if ((rc = vb::stem_rows(m->vb, zsrc, z ? z + f0 * 3 * Tz * Tz : nullptr, x ? x + f0 * 3 * Tx * Tx : nullptr, xu8 ? xu8 + f0 * 3 * Tx * Tx : nullptr,
+                            nb, st, nullptr, &err, &sl))) return fail(rc, err);
+    if ((rc = vb::blocks(m->vb, nullptr, nb, -1, st, nullptr, nullptr, &err, &sl))) return fail(rc, err);
+    return run_head_vitb(m, nullptr, nb, st, out, &sl, tail);
+}
+
+// The same as ONE chain, or from 64 frames up (VT_GRAPH_CHAINS: create_vitb) as chains over frame slices: forked off `st` onto the side
+// streams and joined back with events, which is legal under stream capture (the tracker step inside a caller's graph) and in eager mode.
+// Frames are independent, so the chains compute what one chain computes, bit for bit.
+int vitb_network_chains(vt_model* m, vb::ZSrc zsrc, const float* z, const float* x, const unsigned char* xu8, int B, hipStream_t st,
+                        const vt_outputs* out, const TrackTail* tail) {
+    int nch = m->graph_chains;
+    if (nch == 0) nch = B >= 64 ? 2 : 1;
+    nch = std::max(1, std::min({nch, 4, B}));
+    if (nch == 1) return vitb_network(m, zsrc, z, x, xu8, 0, B, B, 0, st, out, tail);
+    int ncu = 256;
+    (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, 0);
+    const int cus = m->chain_cus > 0 ? m->chain_cus : (m->graph_chains == 0 ? ncu : ncu / nch);      // as forward_slice
+    int rc = VT_OK;
+    if (hipEventRecord(m->fork_ev, st) != hipSuccess) return fail(VT_ERR_HIP, "hipEventRecord(fork)");
+    for (int c = 1; c < nch && !rc; ++c)
+        if (hipStreamWaitEvent(m->side_stream[c - 1], m->fork_ev, 0) != hipSuccess) rc = fail(VT_ERR_HIP, "hipStreamWaitEvent(fork)");
+    for (int c = 0; c < nch && !rc; ++c) {
+        const size_t f0 = (size_t)B * c / nch, f1 = (size_t)B * (c + 1) / nch;
+        rc = vitb_network(m, zsrc, z, x, xu8, f0, (int)(f1 - f0), B, cus, c == 0 ? st : m->side_stream[c - 1], out, tail);
+    }
+    for (int c = 1; c < nch; ++c) {   // always join, even after an error, so that a capture can end
+        (void)hipEventRecord(m->join_ev[c - 1], m->side_stream[c - 1]);
+        (void)hipStreamWaitEvent(st, m->join_ev[c - 1], 0);
+    }
+    return rc;
 }
 
 // Graph chains: a chain may start late (VT_CHAIN_DELAY_US x chain index), so that identical chains do not run in lock step
@@ -1158,6 +1206,8 @@ int create_vitb(const vt_config* cfg, vt_model** out) {
     A(m->pred, B * 4); A(m->hann, B * 4); A(m->conf, B);
     if (!rc) rc = upload(m->window, hann2d(m->F));
     if (!rc && hipStreamCreateWithFlags(&m->cap_stream, hipStreamNonBlocking) != hipSuccess) rc = fail(VT_ERR_HIP, "hipStreamCreate failed");
+    A(m->imsizes, B * sizeof(vt_frame) / sizeof(float));      // vt_track_step_images: the descriptors' sizes for the tail
+    m->track_u8 = env_int("VT_TRACK_U8", 1);
     // graph chains (vt_graph_capture_steps): frame slices of one step as concurrent chains.  Default (round 5; 0 = auto): a captured step
     // of >= 64 frames runs as TWO chains of half the frames whose persistent GEMMs each launch a workgroup per CU -- the chains' kernels
     // then fill each other's last, partly empty tile rounds (3.75 of 4, 7.5 of 8 at B = 256) and ramps: 17.63 -> 16.88 ms per step at
@@ -1798,9 +1848,9 @@ int vt_forward(vt_model* m, const float* z_dev, const float* x_dev, int32_t B, v
     if (!x_dev) return fail(VT_ERR_ARG, "null device pointer");
     hipStream_t st = static_cast<hipStream_t>(stream);
     if (!z_dev) {   // cached template (vt_set_template): stem on the search crop only, block 0 loads the template's q / k / v
-        if (m->vb) return fail(VT_ERR_ARG, "the template cache is implemented for the vit_48 path only");
         if (m->tmpl_frames < B)
             return fail(VT_ERR_STATE, "vt_forward with a null template needs vt_set_template for at least " + std::to_string(B) + " frames first");
+        if (m->vb) return vitb_network(m, vb::Z_CACHED, nullptr, x_dev, nullptr, 0, B, B, 0, st, out, nullptr);
         if (m->tmpl_form_batch != m->form_batch)
             return fail(VT_ERR_STATE, "the template cache was written under another form batch: call vt_set_template again after vt_set_form_batch");
         if ((rc = run_stem(m, nullptr, x_dev, B, st, m->tokens_c.p, 0, 1))) return rc;
@@ -1822,8 +1872,15 @@ int vt_set_template(vt_model* m, const float* z_dev, int32_t B, void* stream) {
     int rc = check_ready(m, B);
     if (rc) return rc;
     if (!z_dev) return fail(VT_ERR_ARG, "null device pointer");
-    if (m->vb) return fail(VT_ERR_ARG, "the template cache is implemented for the vit_48 path only");
     hipStream_t st = static_cast<hipStream_t>(stream);
+    if (m->vb) {      // ViT-Base caches the templates' patch-GEMM operand rows (vitb.hip): cached and uncached steps run the same two GEMMs
+        std::string err;
+        m->tmpl_frames = 0;
+        if ((rc = vb::set_template(m->vb, z_dev, B, nullptr, st, &err))) return fail(rc, err);
+        m->tmpl_frames = B;
+        m->tmpl_form_batch = m->form_batch;
+        return VT_OK;
+    }
     m->tmpl_frames = 0;
     // template token rows (stem(z) + pos_embed_z) stay in the cached step's own token matrix (uncached steps use another) ...
     if ((rc = run_stem(m, z_dev, nullptr, B, st, m->tokens_c.p, 0, 2))) return rc;
@@ -1837,7 +1894,6 @@ int vt_set_template(vt_model* m, const float* z_dev, int32_t B, void* stream) {
 
 int vt_set_template_slots(vt_model* m, const float* z_dev, const int32_t* slots, int32_t n, void* stream) {
     if (!m) return fail(VT_ERR_ARG, "null model");
-    if (m->vb) return fail(VT_ERR_ARG, "the template cache is implemented for the vit_48 path only");
     if (m->tmpl_frames < 1) return fail(VT_ERR_STATE, "vt_set_template_slots needs a template cache: call vt_set_template first");
     if (m->tmpl_form_batch != m->form_batch)
         return fail(VT_ERR_STATE, "the template cache was written under another form batch: call vt_set_template again after vt_set_form_batch");
@@ -1851,6 +1907,11 @@ int vt_set_template_slots(vt_model* m, const float* z_dev, const int32_t* slots,
     int rc = check_ready(m, n);
     if (rc) return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
+    if (m->vb) {
+        std::string err;
+        rc = vb::set_template(m->vb, z_dev, n, slots, st, &err);
+        return rc ? fail(rc, err) : VT_OK;
+    }
     if (!m->generic && !m->zstage.p && (rc = m->zstage.alloc(m->zcache.n))) return rc;
     // Stage: stem(z) + block 0's cache rows of the n templates as frames 0..n-1 of the uncached token matrix and of zstage, under the
     // forms vt_set_template picked for the whole cache (by max(form batch, cached frames), not by n).  Every stage is per frame under a
@@ -1957,17 +2018,27 @@ int vt_crop_u8_images(vt_model* m, const vt_image* images_dev, const double* sta
 
 int vt_set_normalization(vt_model* m, const float* mean3, const float* std3) {
     if (!m || !mean3 || !std3) return fail(VT_ERR_ARG, "null argument");
-    if (m->vb) return fail(VT_ERR_ARG, "uint8 patches are implemented for the vit_48 path only");
     for (int c = 0; c < 3; ++c)
         if (!(std3[c] > 0.f) || !std::isfinite(mean3[c]) || !std::isfinite(std3[c])) return fail(VT_ERR_ARG, "bad mean / std");
     if (m->graphs_captured > 0 && (std::memcmp(mean3, m->norm_mean, 12) != 0 || std::memcmp(std3, m->norm_std, 12) != 0))
         return fail(VT_ERR_STATE, "captured graphs read the folded layer-1 weights: set the normalisation before capturing");
+    if (m->vb && !m->weights_loaded) {
+        std::string err;
+        if (int rc = vb::set_normalization(m->vb, mean3, std3, &err)) return fail(rc, err);
+    }
     if (!m->weights_loaded || m->generic) {      // remembered: vt_load_weights folds with these; the shape-generic stem takes them as kernel arguments (not in captured graphs: see above)
         std::memcpy(m->norm_mean, mean3, 12);
         std::memcpy(m->norm_std, std3, 12);
         return VT_OK;
     }
     HIP_TRY(hipDeviceSynchronize());      // no step may be reading the image that is about to be replaced
+    if (m->vb) {
+        std::string err;
+        if (int rc = vb::set_normalization(m->vb, mean3, std3, &err)) return fail(rc, err);
+        std::memcpy(m->norm_mean, mean3, 12);
+        std::memcpy(m->norm_std, std3, 12);
+        return VT_OK;
+    }
     return fold_w1u(m, mean3, std3);
 }
 
@@ -1997,7 +2068,11 @@ int vt_stem_u8(vt_model* m, const uint8_t* x_patch_dev, int32_t B, void* stream,
     int rc = check_ready(m, B);
     if (rc) return rc;
     if (!x_patch_dev || !tokens_dev) return fail(VT_ERR_ARG, "null device pointer");
-    if (m->vb) return fail(VT_ERR_ARG, "uint8 patches are implemented for the vit_48 path only");
+    if (m->vb) {
+        std::string err;
+        rc = vb::stem_rows(m->vb, vb::Z_NONE, nullptr, nullptr, x_patch_dev, B, static_cast<hipStream_t>(stream), tokens_dev, &err);
+        return rc ? fail(rc, err) : VT_OK;
+    }
     return run_stem(m, nullptr, reinterpret_cast<const float*>(x_patch_dev), B, static_cast<hipStream_t>(stream), tokens_dev, 0, 1, true);
 }
 
@@ -2005,12 +2080,14 @@ int vt_forward_u8(vt_model* m, const float* z_dev, const uint8_t* x_patch_dev, i
     int rc = check_ready(m, B);
     if (rc) return rc;
     if (!x_patch_dev) return fail(VT_ERR_ARG, "null device pointer");
-    if (m->vb) return fail(VT_ERR_ARG, "uint8 patches are implemented for the vit_48 path only");
     hipStream_t st = static_cast<hipStream_t>(stream);
     const float* const xu = reinterpret_cast<const float*>(x_patch_dev);
+    if (m->vb && (reinterpret_cast<uintptr_t>(x_patch_dev) & 15)) return fail(VT_ERR_ARG, "the uint8 patch must be 16-byte aligned on the ViT-Base path");
+    if (m->vb && z_dev) return vitb_network_chains(m, vb::Z_GIVEN, z_dev, nullptr, x_patch_dev, B, st, out, nullptr);      // two chains from 64 frames up, as the tracker step
     if (!z_dev) {     // cached template: the tracker step's network part
         if (m->tmpl_frames < B)
             return fail(VT_ERR_STATE, "vt_forward_u8 with a null template needs vt_set_template for at least " + std::to_string(B) + " frames first");
+        if (m->vb) return vitb_network_chains(m, vb::Z_CACHED, nullptr, nullptr, x_patch_dev, B, st, out, nullptr);
         if (m->tmpl_form_batch != m->form_batch)
             return fail(VT_ERR_STATE, "the template cache was written under another form batch: call vt_set_template again after vt_set_form_batch");
         if ((rc = run_stem(m, nullptr, xu, B, st, m->tokens_c.p, 0, 1, true))) return rc;
@@ -2050,7 +2127,6 @@ static int track_step(vt_model* m, const uint8_t* frames, int32_t H, int32_t W, 
                       const vt_outputs* out, int32_t margin, double* record, const vt_image* images = nullptr) {
     int rc = check_ready(m, B);
     if (rc) return rc;
-    if (m->vb) return fail(VT_ERR_ARG, "vt_track_step is implemented for the vit_48 path only");
     if (m->tmpl_frames < B)
         return fail(VT_ERR_STATE, "vt_track_step needs vt_set_template for at least " + std::to_string(B) + " frames first");
     if (m->tmpl_form_batch != m->form_batch)
@@ -2061,6 +2137,7 @@ static int track_step(vt_model* m, const uint8_t* frames, int32_t H, int32_t W, 
     // whenever the stem form of this batch reads patches and (mean3, std3) is the normalisation folded into its layer 1; else as the
     // fp32 crop of vt_crop.  Either way crops_dev is the workspace: the patch occupies its first B * S * S * 3 bytes.
     const bool u8 = m->track_u8 != 0 && stem_takes_u8(m, B) && same_norm(m, mean3, std3);
+    if (m->vb && u8 && (reinterpret_cast<uintptr_t>(crops_dev) & 15)) return fail(VT_ERR_ARG, "the crop workspace must be 16-byte aligned on the ViT-Base path");
     if (images) {
         table = reinterpret_cast<const vt_frame*>(m->imsizes.p);
         launch_crop_images(images, reinterpret_cast<vt_frame*>(m->imsizes.p), states_dev, factor, m->cfg.search_size, mean3, std3, B, st,
@@ -2073,10 +2150,13 @@ static int track_step(vt_model* m, const uint8_t* frames, int32_t H, int32_t W, 
     } else if (u8) {
         if ((rc = vt_crop_u8(m, frames, H, W, states_dev, factor, m->cfg.search_size, B, stream, reinterpret_cast<uint8_t*>(crops_dev), resize_factor_dev))) return rc;
     } else if ((rc = vt_crop(m, frames, H, W, states_dev, factor, m->cfg.search_size, mean3, std3, B, stream, crops_dev, resize_factor_dev))) return rc;
-    if ((rc = run_stem(m, nullptr, crops_dev, B, st, m->tokens_c.p, 0, 1, u8))) return rc;
-    if ((rc = run_blocks(m, m->tokens_c.p, B, -1, st, m->feat.p, nullptr, 2))) return rc;
     TrackTail tail{resize_factor_dev, states_dev, record, m->cfg.search_size, H, W, margin, m->open_loop};
     tail.frames = table;      // the tail clips each sequence against its own frame
+    if (m->vb)      // crop on `st`, then the network and each slice's tail on the chains (two from 64 frames up), joined back into `st`
+        return vitb_network_chains(m, vb::Z_CACHED, nullptr, u8 ? nullptr : crops_dev, u8 ? reinterpret_cast<const unsigned char*>(crops_dev) : nullptr,
+                                   B, st, out, &tail);
+    if ((rc = run_stem(m, nullptr, crops_dev, B, st, m->tokens_c.p, 0, 1, u8))) return rc;
+    if ((rc = run_blocks(m, m->tokens_c.p, B, -1, st, m->feat.p, nullptr, 2))) return rc;
     return run_head(m, m->feat.p, B, st, out, 0, &tail);
 }
 
@@ -2113,6 +2193,7 @@ static int forward_slice(vt_model* m, const float* z, const float* x, size_t f0,
         int ncu = 256;
         (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, 0);
         const vb::Slice sl{f0, Btot, m->chain_cus > 0 ? m->chain_cus : (m->graph_chains == 0 ? ncu : ncu / nch)};
+        if (!z) return vitb_network(m, vb::Z_CACHED, nullptr, x, nullptr, f0, nb, Btot, sl.cus, st, out, nullptr);
         std::string err;
         int rc;
         if ((rc = vb::stem(m->vb, z + f0 * 3 * Tz * Tz, x + f0 * 3 * Tx * Tx, nb, st, nullptr, &err, &sl))) return fail(rc, err);
@@ -2138,7 +2219,10 @@ int vt_graph_capture_steps(vt_model* m, int32_t nsteps, const float* const* z_de
     // one-workgroup-per-frame kernels (large LDS: no two workgroups share a CU): 107.7 -> 132 us with 2 chains.
     int nch = m->graph_chains;   // vit_48: default 1; ViT-Base: 0 = auto (two chains from 64 frames up, create_vitb)
     if (nch == 0) nch = (m->vb && B >= 64) ? 2 : 1;
-    nch = (nsteps > 1 || !z_dev || !z_dev[0]) ? 1 : std::max(1, std::min({nch, 4, (int)B}));
+    const bool cached = !z_dev || !z_dev[0];
+    nch = (nsteps > 1 || (cached && !m->vb)) ? 1 : std::max(1, std::min({nch, 4, (int)B}));
+    if (cached && nch > 1 && m->tmpl_frames < B)
+        return fail(VT_ERR_STATE, "vt_graph_capture with a null template needs vt_set_template for at least " + std::to_string(B) + " frames first");
     if (m->generic) nch = 1;      // the shape-generic kernels share ONE set of scratch buffers (g_a, g_b, g_x, ...): concurrent chains would race on them
     vt_graph* vg = new vt_graph();
     hipError_t e = hipStreamBeginCapture(m->cap_stream, hipStreamCaptureModeThreadLocal);
@@ -2153,7 +2237,7 @@ int vt_graph_capture_steps(vt_model* m, int32_t nsteps, const float* const* z_de
             if (hipStreamWaitEvent(m->side_stream[c - 1], m->fork_ev, 0) != hipSuccess) rc = fail(VT_ERR_HIP, "hipStreamWaitEvent(fork)");
         for (int c = 0; c < nch && !rc; ++c) {
             const size_t f0 = (size_t)B * c / nch, f1 = (size_t)B * (c + 1) / nch;
-            rc = forward_slice(m, z_dev[0], x_dev[0], f0, (int)(f1 - f0), c == 0 ? m->cap_stream : m->side_stream[c - 1], out, B, nch);
+            rc = forward_slice(m, cached ? nullptr : z_dev[0], x_dev[0], f0, (int)(f1 - f0), c == 0 ? m->cap_stream : m->side_stream[c - 1], out, B, nch);
         }
         for (int c = 1; c < nch; ++c) {   // always join, even after an error, so the capture can end
             (void)hipEventRecord(m->join_ev[c - 1], m->side_stream[c - 1]);

@@ -653,7 +653,9 @@ class Model:
     # ---- whole step
     def set_template(self, z, stream=None):
         """Exact template cache (vt_set_template): afterwards ``forward(None, x)`` / ``capture(None, x)`` skip the
-        template's patch embedding and block 0's LayerNorm-1 + qkv of its rows."""
+        template's patch embedding and block 0's LayerNorm-1 + qkv of its rows.  On a ViT-Base model (channels=768) the cache holds the
+        templates' bf16 patch-GEMM operand rows; forward(None, x), forward_u8(None, patch) and track_step* read it, bit-identical to the
+        same call with z."""
         B, tz = z.shape[0], self.template_size
         if tuple(z.shape) != (B, 3, tz, tz):
             raise VtError(f"expected z (B,3,{tz},{tz}), got {tuple(z.shape)}")
@@ -928,7 +930,8 @@ class Model:
         return B
 
     def forward_u8(self, z, x_patch, out: Outputs | None = None, stream=None) -> Outputs:
-        """Preprocessor.process + forward on the uint8 search patch of crop_u8; z: fp32 template crop or None (cached template)."""
+        """Preprocessor.process + forward on the uint8 search patch of crop_u8; z: fp32 template crop or None (cached template).
+        ViT-Base models take it at every batch size; the patch must be 16-byte aligned there (any torch allocation is)."""
         B = self._check_patch(x_patch)
         if z is None:
             if getattr(self, "_tmpl_B", 0) < B:

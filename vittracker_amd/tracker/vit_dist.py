@@ -23,7 +23,7 @@ import numpy as np
 
 from ..host_ops import Preprocessor, clip_box, hann2d, sample_target
 from ..batched import check_params_geometry
-from ..model import build_ostrack_dist
+from ..factory import build_network
 from ..native import Image, VtError
 
 
@@ -77,7 +77,7 @@ class Vit_dist(BaseTracker):
             self.network = self._bt.net
             self.output_window = hann2d(torch.tensor([self.feat_sz, self.feat_sz]).long(), centered=True).cuda()
             return
-        network = build_ostrack_dist(params.cfg)
+        network = build_network(params.cfg)
         ckpt_path = getattr(params, "checkpoint", None)
         if ckpt_path and os.path.isfile(ckpt_path):
             network.load_state_dict(torch.load(ckpt_path, map_location="cpu")["net"], strict=False)  # :25
