@@ -156,7 +156,10 @@ int vt_crop(vt_model* m, const uint8_t* frames_dev, int32_t H, int32_t W, const 
             double* resize_factor_dev);
 /* sample_target ALONE (lib/train/data/processing_utils.py:12-79): patch_dev (B,T,T,3) uint8 is the array sample_target returns --
  * HWC, before Preprocessor.process -- byte for byte (same geometry and fixed-point resize as vt_crop); resize_factor_dev as vt_crop.
- * A too-small box (processing_utils.py:33-34 raises) writes zeros and a NaN resize factor. */
+ * A too-small box (processing_utils.py:33-34 raises) writes zeros and a NaN resize factor.
+ * Every uint8 patch pointer of this header (patch_dev of vt_crop_u8 / _frames / _images, x_patch_dev of vt_stem_u8 / vt_forward_u8, and
+ * crops_dev of the tracker steps, which holds the patch) must be 4-byte aligned: the kernels move a patch as 12-byte groups of four
+ * pixels.  VT_ERR_ARG otherwise (ViT-Base: 16 bytes, see vt_forward_u8). */
 int vt_crop_u8(vt_model* m, const uint8_t* frames_dev, int32_t H, int32_t W, const double* states_dev, double factor,
                int32_t out_size, int32_t B, void* stream, uint8_t* patch_dev, double* resize_factor_dev);
 /* Preprocessor.__init__'s mean / std (lib/test/tracker/data_utils.py:8-9) for the uint8 entry points below (default: the ImageNet
@@ -312,6 +315,8 @@ int vt_graph_capture(vt_model* m, const float* z_dev, const float* x_dev, int32_
  * step (tools/graph_steps.py). */
 int vt_graph_capture_steps(vt_model* m, int32_t nsteps, const float* const* z_dev, const float* const* x_dev, int32_t B,
                            const vt_outputs* out, vt_graph** g);
+/* A graph replays kernels on its model's weights and workspaces: VT_ERR_STATE once that model has been destroyed (the graph itself can
+ * still be destroyed).  Capturing from, and destroying, one model and its graphs is not thread-safe: serialise those calls. */
 int vt_graph_launch(vt_graph* g, void* stream);
 void vt_graph_destroy(vt_graph* g);
 

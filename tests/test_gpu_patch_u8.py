@@ -356,6 +356,51 @@ def test_track_step_with_another_mean_falls_back_to_the_fp32_crop(monkeypatch):
     m.close()
 
 
+def test_misaligned_patch_pointers_are_refused():
+    """The kernels move a uint8 patch as 12-byte groups through 4-byte-aligned pointers (include/vittrack.h): every entry point that
+    takes or writes a patch returns VT_ERR_ARG (-1) for a pointer that is not 4-byte aligned -- before any launch.  Through the C ABI:
+    a torch tensor's own storage is always aligned, so the pointers are the buffer's address plus 1, 2 and 3."""
+    import ctypes as C
+    import torch
+    from vittracker_amd import native
+    from vittracker_amd.native import FrameTable, Image, ImageTable
+    geom, B, H, W = 128, 2, 48, 64
+    m = _model(geom, B)
+    L, h, st = m._L, m._h, native._stream(None)
+    z = torch.zeros(B, 3, geom // 2, geom // 2, device="cuda")
+    m.set_template(z)
+    frames = torch.zeros(B, H, W, 3, dtype=torch.uint8, device="cuda")
+    ftab, itab = FrameTable.of([frames[b] for b in range(B)]), ImageTable.of([Image.rgb(frames[b]) for b in range(B)])
+    states = torch.tensor([[10.0, 8.0, 20.0, 16.0]] * B, dtype=torch.float64, device="cuda")
+    rf = torch.empty(B, dtype=torch.float64, device="cuda")
+    buf = torch.zeros(B * 3 * geom * geom * 4 + 16, dtype=torch.uint8, device="cuda")      # room for a patch, or an fp32 crop, behind any offset
+    tokens = torch.empty(B, m.L, m.channels, device="cuda")
+    out = native.Outputs(B, geom // 16, "cuda")
+    outs = out.struct()
+    m3, s3 = (C.c_float * 3)(*MEAN), (C.c_float * 3)(*STD)
+    vp = lambda t: C.c_void_p(t.data_ptr())
+    assert buf.data_ptr() % 4 == 0 and m.patch_u8_supported(B)
+    for off in (1, 2, 3):
+        p = C.c_void_p(buf.data_ptr() + off)
+        calls = {
+            "vt_crop_u8": lambda: L.vt_crop_u8(h, vp(frames), H, W, vp(states), 4.0, geom, B, st, p, vp(rf)),
+            "vt_crop_u8_frames": lambda: L.vt_crop_u8_frames(h, native._table_ptr(ftab, B), vp(states), 4.0, geom, B, st, p, vp(rf)),
+            "vt_crop_u8_images": lambda: L.vt_crop_u8_images(h, native._image_table_ptr(itab, B), vp(states), 4.0, geom, B, st, p, vp(rf)),
+            "vt_stem_u8": lambda: L.vt_stem_u8(h, p, B, st, vp(tokens)),
+            "vt_forward_u8": lambda: L.vt_forward_u8(h, None, p, B, st, C.byref(outs)),
+            "vt_forward_u8 (z given)": lambda: L.vt_forward_u8(h, vp(z), p, B, st, C.byref(outs)),
+            "vt_track_step": lambda: L.vt_track_step(h, vp(frames), H, W, vp(states), 4.0, m3, s3, B, st, p, vp(rf), C.byref(outs), 10, None),
+        }
+        for name, call in calls.items():
+            assert call() == -1, (name, off)
+            assert "aligned" in L.vt_last_error().decode(), (name, off)
+    # the same calls on the aligned buffer are accepted
+    assert L.vt_crop_u8(h, vp(frames), H, W, vp(states), 4.0, geom, B, st, vp(buf), vp(rf)) == 0
+    assert L.vt_forward_u8(h, None, vp(buf), B, st, C.byref(outs)) == 0
+    torch.cuda.synchronize()
+    m.close()
+
+
 @pytest.mark.parametrize("geom,B", [(128, 3), (256, 2), (128, 200), (256, 130)])
 def test_open_loop_step_leaves_the_states_and_writes_the_same_record(geom, B):
     """vt_set_open_loop: the step crops around the caller's boxes, the record (box + confidence) is the closed-loop step's bit for bit,

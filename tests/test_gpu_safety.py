@@ -80,6 +80,23 @@ def test_graph_is_invalidated_when_its_model_is_resized_or_closed():
         g2.launch()
 
 
+def test_library_refuses_to_launch_a_graph_whose_model_was_destroyed():
+    """The same through the C ABI, where no Python wrapper stands in front: vt_graph_launch on a graph that outlived its model returns
+    VT_ERR_STATE (-3) instead of replaying kernels over freed workspaces; destroying the orphaned graph stays legal."""
+    import torch
+    from vittracker_amd import native
+    m = _model()
+    g, _ = m.capture(torch.zeros(4, 3, 64, 64, device="cuda"), torch.zeros(4, 3, 128, 128, device="cuda"))
+    L, st = m._L, native._stream(None)
+    assert L.vt_graph_launch(g._h, st) == 0
+    torch.cuda.synchronize()
+    m.close()                                    # vt_destroy: the graph is orphaned
+    assert L.vt_graph_launch(g._h, st) == -3
+    assert "destroyed" in L.vt_last_error().decode()
+    assert L.vt_graph_launch(None, st) == -1
+    del g                                        # vt_graph_destroy of the orphan
+
+
 @pytest.mark.parametrize("geom,depth", [("G128", 1), ("G128", 5), ("G128", 12), ("G256", 7), ("G256", 12)])
 def test_depth_other_than_three(geom, depth):
     """vt_create accepts depth 1..12: the dynamic-LDS limits follow the depth (the LayerNorm vectors and
