@@ -270,15 +270,58 @@ int vt_track_step_frames(vt_model* m, const vt_frame* frames_dev, double* states
  *       G = clamp((yy -  852492 (V - 128) - 409993 (U - 128) + (1 << 19)) >> 20, 0, 255)
  *       B = clamp((yy + 2116026 (U - 128)                  + (1 << 19)) >> 20, 0, 255)
  *     (1.164, 1.596, 0.813, 0.391 and 2.018 times 2^20, written down from OpenCV's ITUR_BT_601_* constants; a GPU test compares them
- *     with cv2.cvtColor where cv2 is installed.)  BT.709, full range and I420 are not supported.
+ *     with cv2.cvtColor where cv2 is installed.)
+ *   I420/YV12  plane0: H rows of W luma bytes; plane1: the first chroma plane (U for I420, V for YV12), H/2 rows of W/2 bytes at
+ *              pitch1 (0 = W/2); the second chroma plane begins pitch1 * H/2 bytes after plane1 -- the contiguous buffer of OpenCV
+ *              (COLOR_YUV2RGB_I420) and av_image_copy_to_buffer.  H and W even; plane1's extent covers both chroma planes
+ *              (pitch1 (H - 1) + W/2 bytes); only plane0 and plane1 need 4-byte alignment.
+ *   YUYV/UYVY  plane0: H rows of 2 W bytes, each 4 bytes Y0 U Y1 V (YUYV = YUY2) or U Y0 V Y1 (UYVY): the pair shares its chroma.  W even.
+ *   P010       NV12 in little-endian 16-bit samples: plane0 H rows of 2 W bytes, plane1 H/2 rows of 2 W bytes ((U, V) pairs).  The
+ *              8-bit sample is the HIGH byte of each word, so a P016 surface is read the same way.  H and W even.
+ *   GRAY8      plane0: H rows of W bytes; rgb = (Y, Y, Y), no conversion.
+ * The format word: bits 0-7 the layout (the VT_PIX_* values; 6 and 7 are never assigned), bits 8-11 the matrix (0 = BT.601, 1 =
+ * BT.709), bits 12-15 the range (0 = limited, 1 = full), bits 16-31 zero -- format = VT_PIX_P010 | VT_PIX_BT709 | VT_PIX_FULL.  Every
+ * value that was legal before the colour fields existed means what it meant (NV12 = BT.601 limited).  Matrix and range belong to the
+ * YUV layouts (NV12 / NV21, I420 / YV12, YUYV / UYVY, P010); on the RGB family and GRAY8 they must be 0.
+ * Colour, every YUV layout: chroma is never interpolated (a 2 x 2 block of 4:2:0, a pair of 4:2:2, shares its U, V); int32, >> arithmetic:
+ *       yy = max(Y - 16, 0) * cy   (limited range)      yy = Y * cy   (full range)
+ *       R = clamp((yy + cvr (V - 128)                   + (1 << 19)) >> 20, 0, 255)
+ *       G = clamp((yy - cvg (V - 128) - cug (U - 128)   + (1 << 19)) >> 20, 0, 255)
+ *       B = clamp((yy + cub (U - 128)                   + (1 << 19)) >> 20, 0, 255)
+ *       matrix, range       cy        cvr       cvg      cug      cub
+ *       601 limited         1220542   1673527   852492   409993   2116026     (OpenCV's literals, as above)
+ *       601 full            1048576   1470104   748826   360853   1858077
+ *       709 limited         1220945   1879825   558796   223607   2215014
+ *       709 full            1048576   1651297   490864   196424   1945738
+ *     The three other rows are round(x 2^20) of the exact rationals: luma scale 255/219 (limited) or 1 (full); chroma scale 255/224
+ *     or 1 on 2(1-Kr), 2(1-Kr)Kr/Kg, 2(1-Kb)Kb/Kg, 2(1-Kb) with Kr / Kb = 0.299 / 0.114 (BT.601) and 0.2126 / 0.0722 (BT.709).
+ *     Checked on the CPU over all 2^24 (Y, U, V): the value before the shift stays below 5.8e8 (inside int32), and before clamping
+ *     each channel differs from the fp64 formula by at most 0.5000 / 0.5002 / 0.5000 (601 full / 709 limited / 709 full; OpenCV's
+ *     601-limited literals: up to 0.69).  tests/test_frame_formats_yuv.py repeats the check.
+ *   Not supported: chroma interpolation and chroma siting, BT.2020 / PQ / HLG, 4:4:4 layouts, big-endian samples.
  *   pitch0 / pitch1: bytes between rows of plane0 / plane1, >= the row's bytes (0 = the row's bytes).  A plane is [plane, plane +
  *   pitch (rows - 1) + row bytes); nothing outside it is read.  plane1 / pitch1 are unused by the one-plane formats.
  * Planes: device memory or device-mapped pinned host memory.  The table (B,) lives there too and is read when the kernels run: a
  * graph captured on it stays valid when its contents -- pointers, sizes, formats -- change between replays.  A table may mix formats.
  * A descriptor is unusable -- treated as a too-small box: NaN resize factor, zero (uint8) or NaN (fp32) patch, nothing read through
- * it, the other sequences unaffected -- when its format is unknown or `reserved` is not 0, a plane it needs is null or not 4-byte
- * aligned, a pitch is below the row's bytes, H or W is < 1 (or odd for NV12 / NV21), or a plane does not fit a 32-bit offset. */
+ * it, the other sequences unaffected -- when its format word is not one described above (an unassigned layout, a matrix or range
+ * beyond 1, a bit in 16-31, matrix or range bits on an RGB layout or GRAY8) or `reserved` is not 0, a plane it needs is null or not
+ * 4-byte aligned, a pitch is below the row's bytes, H or W is < 1, W is odd for a 4:2:2 layout, H or W is odd for a 4:2:0 layout, or a
+ * plane does not fit a 32-bit offset. */
 enum { VT_PIX_RGB = 0, VT_PIX_BGR = 1, VT_PIX_RGBA = 2, VT_PIX_BGRA = 3, VT_PIX_NV12 = 4, VT_PIX_NV21 = 5 };
+/* the layouts added to bits 0-7 (6 and 7 are never assigned) ... */
+#define VT_PIX_I420 8
+#define VT_PIX_YV12 9
+#define VT_PIX_YUYV 10
+#define VT_PIX_UYVY 11
+#define VT_PIX_P010 12
+#define VT_PIX_GRAY8 13
+/* ... and the colour tags of a YUV layout, or-ed into the format word: matrix in bits 8-11, range in bits 12-15 */
+#define VT_PIX_BT601 0x0000
+#define VT_PIX_BT709 0x0100
+#define VT_PIX_LIMITED 0x0000
+#define VT_PIX_FULL 0x1000
+#define VT_PIX_LAYOUT(format) ((format) & 0xff)
 typedef struct vt_image {
     const uint8_t* plane0;
     const uint8_t* plane1;

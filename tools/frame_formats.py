@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
-"""Pixel formats on the device: what reading NV12 / NV21, BGR and RGBA / BGRA directly costs against RGB.
+"""Pixel formats on the device: what reading NV12 / NV21, BGR and RGBA / BGRA directly costs against RGB, and what the
+other layouts and colour rows (P010, I420, YUYV / UYVY, GRAY8; BT.709, full range) cost against NV12 BT.601.
 
-    python tools/frame_formats.py [--batch 256] [--rounds 5] [--reps 20] [--distinct 32]
+    python tools/frame_formats.py [--batch 256] [--rounds 5] [--reps 20] [--distinct 32] [--sections crop,step,small,convert,new,parent]
+                                  [--parent-lib OTHER.so]
 
 Fixed seeds, 1920 x 1080 frames (`--distinct` different frames, cycled over the sequences) with 30-120 px boxes:
   crop_us[T][form]        B = 256: the uint8 table crop per launch, T = 128 and 256: "rgb_frames" is vt_crop_u8_frames on the RGB
@@ -12,6 +14,12 @@ Fixed seeds, 1920 x 1080 frames (`--distinct` different frames, cycled over the 
                           tap fetches): the T = 128 uint8 crop and the G128 step, frame route on RGB against the image route
   convert_step_us[G]      B = 256: the caller's alternative without this route: the whole NV12 frames converted to RGB with unfused
                           int32 torch ops (one kernel per op), then vt_track_step_frames
+  new_crop_us[T][form]    (section "new") B = 256: the uint8 table crop of every added layout / colour row, NV12 BT.601 and the RGB
+                          frame route in the same interleaved rounds; ratio_vs_nv12 and the kernel family each form runs
+  parent_ab               (section "parent", --parent-lib: the parent commit's libvittrack_hip.so) the formats that existed, crops
+                          (T = 128 / 256) and G128 / G256 steps at B = 256, this build and the parent's loaded side by side in ONE
+                          process and timed in the same interleaved rounds: per form the median and the [min, max] over the rounds;
+                          inside_parent_range = this build's median lies inside the parent's own round-to-round range
 Method: every form is a captured graph (`--reps` launches for a crop, one step for a step; outputs preallocated, no host work
 inside); the forms are timed in `--rounds` interleaved rounds (the order rotates every round), each a host-timed region of replays
 with one synchronisation, and the best round of each form is reported.  The shader clock is probed (vt_probe_clock, a dense MFMA
@@ -53,10 +61,11 @@ def _capture(fn):
     return g
 
 
-def _interleaved(graphs, per_replay, rounds, replays):
-    """{name: best us per unit} over `rounds` interleaved rounds of `replays` replays each; `per_replay` units per replay."""
+def _interleaved(graphs, per_replay, rounds, replays, all_rounds=False):
+    """{name: best us per unit} over `rounds` interleaved rounds of `replays` replays each; `per_replay` units per replay.
+    all_rounds: {name: [us of every round]} instead."""
     import torch
-    best = {}
+    best, every = {}, {}
     names = list(graphs)
     for g in graphs.values():           # warm-up
         g.replay()
@@ -72,6 +81,9 @@ def _interleaved(graphs, per_replay, rounds, replays):
             torch.cuda.synchronize()
             us = (time.perf_counter() - t0) / (replays * per_replay) * 1e6
             best[name] = min(best.get(name, 1e30), us)
+            every.setdefault(name, []).append(round(us, 2))
+    if all_rounds:
+        return every
     return {k: round(v, 2) for k, v in best.items()}
 
 
@@ -84,6 +96,132 @@ def _planes(fmt, n, g):
     if fmt in ("rgba", "bgra"):
         return [(mk(H, W, 4),) for _ in range(n)]
     return [(mk(H, W), mk(H // 2, W // 2, 2)) for _ in range(n)]
+
+
+#: the added layouts and colour rows: name -> (constructor, keywords, planes of an H x W frame as uint8 shapes, the band kernel's family)
+NEW_FORMS = {
+    "nv12_709": ("nv12", dict(matrix="bt709"), lambda: ((H, W), (H // 2, W // 2, 2)), "NV aligned windows, coefficients from registers"),
+    "nv12_601_full": ("nv12", dict(range="full"), lambda: ((H, W), (H // 2, W // 2, 2)), "NV aligned windows, coefficients from registers"),
+    "nv21_709_full": ("nv21", dict(matrix="bt709", range="full"), lambda: ((H, W), (H // 2, W // 2, 2)), "NV aligned windows, coefficients from registers"),
+    "p010_709": ("p010", dict(matrix="bt709"), lambda: ((H, 2 * W), (H // 2, W // 2, 4)), "P010 aligned windows (8 + 12 bytes)"),
+    "i420": ("i420_buffer", {}, lambda: ((3 * H // 2, W),), "byte fetch"),
+    "i420_709": ("i420_buffer", dict(matrix="bt709"), lambda: ((3 * H // 2, W),), "byte fetch"),
+    "yuyv": ("yuyv", {}, lambda: ((H, W, 2),), "byte fetch"),
+    "uyvy_709": ("uyvy", dict(matrix="bt709"), lambda: ((H, W, 2),), "byte fetch"),
+    "gray": ("gray", {}, lambda: ((H, W),), "byte fetch (luma only)"),
+}
+
+
+def _new_tables(B, n, g):
+    """{form: ImageTable} of the added forms, `n` distinct random frames each, cycled over B sequences."""
+    import torch
+    from vittracker_amd.native import Image, ImageTable
+    tabs, keep = {}, []
+    for name, (ctor, kw, shapes, _) in NEW_FORMS.items():
+        frames = [tuple(torch.randint(0, 256, s, dtype=torch.uint8, device="cuda", generator=g) for s in shapes()) for _ in range(n)]
+        keep.append(frames)
+        t = ImageTable(B, "cuda")
+        for b in range(B):
+            t.set_image(b, getattr(Image, ctor)(*frames[b % n], **kw))
+        t.upload()
+        tabs[name] = t
+    return tabs, keep
+
+
+def _second_native(lib_path):
+    """vittracker_amd.native once more, as a module of its own bound to another build of the library: both in one process."""
+    import importlib.util
+    from vittracker_amd import native
+    spec = importlib.util.spec_from_file_location("vittracker_amd.native_other", native.__file__)
+    mod = importlib.util.module_from_spec(spec)
+    sys.modules[spec.name] = mod
+    spec.loader.exec_module(mod)
+    mod.LIB_PATH = os.path.abspath(lib_path)
+    return mod
+
+
+def _stats(rounds):
+    v = sorted(rounds)
+    return {"median": v[len(v) // 2], "min": v[0], "max": v[-1]}
+
+
+def _parent_ab(a, B, n, g, states):
+    """The formats that existed, this build against the parent's library, in the same interleaved rounds."""
+    import torch
+    from vittracker_amd import native, synth
+    other = _second_native(a.parent_lib)
+    forms = ("rgb", "bgr", "rgba", "nv12")
+    frames = {f: _planes(f, n, g) for f in forms}
+    res = {"crop_us": {}, "step_us": {}}
+
+    def tables(nat):
+        tabs = {}
+        for f in forms:
+            t = nat.ImageTable(B, "cuda")
+            for b in range(B):
+                t.set_image(b, getattr(nat.Image, f)(*frames[f][b % n]))
+            t.upload()
+            tabs[f] = t
+        ft = nat.FrameTable(B, "cuda")
+        for b in range(B):
+            ft.set_tensor(b, frames["rgb"][b % n][0])
+        ft.upload()
+        return tabs, ft
+
+    def model(nat, geom):
+        m = nat.Model(geom // 2, geom, max_batch=B)
+        m.load_state_dict(synth.synth_state_dict(0, len_z=(geom // 32) ** 2, len_x=(geom // 16) ** 2))
+        return m
+    sides = {"this": (native,) + tables(native), "parent": (other,) + tables(other)}
+    identical = True
+    mods = {k: model(v[0], 128) for k, v in sides.items()}
+    for T in (128, 256):
+        graphs, outs = {}, {}
+        for side, (nat, tabs, ft) in sides.items():
+            m = mods[side]
+            for name, t in [("rgb_frames", ft)] + list(tabs.items()):
+                o = torch.empty(B, T, T, 3, dtype=torch.uint8, device="cuda")
+                rf = torch.empty(B, dtype=torch.float64, device="cuda")
+                outs[(side, name)] = (o, rf)
+                call = m.crop_u8_frames if name == "rgb_frames" else m.crop_u8_images
+
+                def fn(cs, call=call, t=t, o=o, rf=rf):
+                    for _ in range(a.reps):
+                        call(t, states, 4.0, T, out=o, resize_factor=rf, stream=cs)
+                graphs[f"{side}:{name}"] = _capture(fn)
+        rounds = _interleaved(graphs, a.reps, a.rounds, a.replays, all_rounds=True)
+        row = {}
+        for name in ["rgb_frames"] + list(forms):
+            identical = identical and torch.equal(outs[("this", name)][0], outs[("parent", name)][0]) and \
+                torch.equal(outs[("this", name)][1], outs[("parent", name)][1])
+            me, pa = _stats(rounds[f"this:{name}"]), _stats(rounds[f"parent:{name}"])
+            row[name] = {"this": me, "parent": pa, "inside_parent_range": pa["min"] <= me["median"] <= pa["max"]}
+        res["crop_us"][str(T)] = row
+    del mods
+    for S in (128, 256):
+        graphs, keep = {}, []
+        for side, (nat, tabs, ft) in sides.items():
+            m = model(nat, S)
+            m.set_open_loop(True)
+            m.set_template(torch.zeros(B, 3, S // 2, S // 2, device="cuda"))
+            x = torch.empty(B, 3, S, S, device="cuda")
+            rf = torch.empty(B, dtype=torch.float64, device="cuda")
+            out = nat.Outputs(B, S // 16, "cuda")
+            rec = torch.empty(B, 5, dtype=torch.float64, device="cuda")
+            keep.append((m, x, rf, out, rec))
+            for name, (f, t) in {"rgb_frames": (m.track_step_frames, ft), "nv12": (m.track_step_images, tabs["nv12"])}.items():
+                graphs[f"{side}:{name}"] = _capture(lambda cs, f=f, t=t, x=x, rf=rf, out=out, rec=rec:
+                                                    f(t, states, 4.0, MEAN, STD, x, rf, out, record=rec, stream=cs))
+        rounds = _interleaved(graphs, 1, a.rounds, a.replays * 5, all_rounds=True)
+        row = {}
+        for name in ("rgb_frames", "nv12"):
+            me, pa = _stats(rounds[f"this:{name}"]), _stats(rounds[f"parent:{name}"])
+            row[name] = {"this": me, "parent": pa, "inside_parent_range": pa["min"] <= me["median"] <= pa["max"]}
+        identical = identical and torch.equal(keep[0][4], keep[1][4])
+        res["step_us"][f"G{S}"] = row
+        del graphs, keep
+    res["outputs_bit_identical"] = bool(identical)
+    return res
 
 
 def _nv12_to_rgb(y, uv):
@@ -140,7 +278,10 @@ def main():
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--replays", type=int, default=10)
     ap.add_argument("--distinct", type=int, default=32)
+    ap.add_argument("--sections", default="crop,step,small,convert", help="of crop, step, small, convert, new, parent")
+    ap.add_argument("--parent-lib", default=None, help="the parent commit's libvittrack_hip.so (section parent)")
     a = ap.parse_args()
+    sections = set(a.sections.split(","))
     torch.cuda.set_device(0)
     B, n = a.batch, a.distinct
     clock0 = native.probe_clock(20000, 1)[0]
@@ -149,10 +290,48 @@ def main():
     rs = np.random.RandomState(0)
     states = torch.tensor([[rs.uniform(120, W - 240), rs.uniform(120, H - 240), rs.uniform(30, 120), rs.uniform(30, 120)] for _ in range(B)],
                           dtype=torch.float64).cuda()
-    frames = {f: _planes(f, n, g) for f in FORMATS}
-    tabs, ftab = _tables(frames, B, n)
     res = {"B": B, "frame": [H, W], "distinct_frames": n, "rounds": a.rounds, "crop_us": {}, "step_us": {}, "small_batch_us": {},
            "convert_step_us": {}}
+    if "parent" in sections:
+        if not a.parent_lib:
+            raise SystemExit("section parent needs --parent-lib")
+        res["parent_ab"] = _parent_ab(a, B, n, g, states)
+    frames = {f: _planes(f, n, g) for f in (FORMATS if sections & {"crop", "step", "small", "convert"} else ("rgb", "nv12"))}
+    if "new" in sections:
+        # (0) the added layouts and colour rows against NV12 BT.601 and the RGB frame route
+        from vittracker_amd.native import FrameTable, Image, ImageTable
+        ntabs, nkeep = _new_tables(B, n, g)
+        nv = ImageTable(B, "cuda")
+        ft = FrameTable(B, "cuda")
+        for b in range(B):
+            nv.set_image(b, Image.nv12(*frames["nv12"][b % n]))
+            ft.set_tensor(b, frames["rgb"][b % n][0])
+        nv.upload(), ft.upload()
+        m = _model(128, B)
+        res["new_crop_us"] = {"family": {k: v[3] for k, v in NEW_FORMS.items()}}
+        for T in (128, 256):
+            outs, graphs = [], {}
+            for name, t in [("rgb_frames", ft), ("nv12", nv)] + list(ntabs.items()):
+                o = torch.empty(B, T, T, 3, dtype=torch.uint8, device="cuda")
+                rf = torch.empty(B, dtype=torch.float64, device="cuda")
+                outs.append((o, rf))
+                call = m.crop_u8_frames if name == "rgb_frames" else m.crop_u8_images
+
+                def fn(cs, call=call, t=t, o=o, rf=rf):
+                    for _ in range(a.reps):
+                        call(t, states, 4.0, T, out=o, resize_factor=rf, stream=cs)
+                graphs[name] = _capture(fn)
+            rounds = _interleaved(graphs, a.reps, a.rounds, a.replays, all_rounds=True)
+            row = {k: _stats(v) for k, v in rounds.items()}
+            row["ratio_vs_nv12"] = {k: round(min(v) / min(rounds["nv12"]), 3) for k, v in rounds.items()}
+            res["new_crop_us"][str(T)] = row
+        del m, graphs, ntabs, nkeep
+    if not sections & {"crop", "step", "small", "convert"}:
+        clock1 = native.probe_clock(20000, 1)[0]
+        res["clock_mhz"] = [round(clock0), round(clock1)]
+        print(json.dumps(res))
+        return
+    tabs, ftab = _tables(frames, B, n)
     # (1) crops, B sequences
     m = _model(128, B)
     for T in (128, 256):

@@ -13,7 +13,18 @@ CSRC = os.path.join(ROOT, "vittracker_amd", "csrc")
 FLAGS = ["-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-Wall", "-Wno-unused-function", "-mllvm", "-align-all-functions=14"]
 
 
+_TABLES = {}
+
+
 def table(src, extra=()):
+    """Rows of one translation unit; compiled once per process (the resource gates of tests/ share it)."""
+    key = (src, tuple(extra))
+    if key not in _TABLES:
+        _TABLES[key] = _compile(src, extra)
+    return [dict(r) for r in _TABLES[key]]
+
+
+def _compile(src, extra=()):
     err = subprocess.run(["hipcc"] + FLAGS + list(extra) + ["-Rpass-analysis=kernel-resource-usage", "-c", "-o", "/dev/null", src],
                          cwd=CSRC, capture_output=True, text=True).stderr
     rows, cur = [], None

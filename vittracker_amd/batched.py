@@ -183,7 +183,7 @@ class BatchedVitTracker:
             else:
                 po = next(it)
                 rows = im.plane_rows()
-                for a, o, (n, rb) in zip(im.planes, po, rows):
+                for a, o, (n, rb) in zip(im.host_planes(), po, rows):
                     self._img_np[o:o + n * rb].reshape(n, rb)[...] = np.asarray(a).reshape(n, rb)
                 d = im.descriptor([base + o for o in po], [rb for _, rb in rows])
                 ImageTable.check(d[6], d[0], d[1], d[4], d[5], d[2], d[3], 0, nbytes0=cap - po[0],
@@ -263,7 +263,7 @@ class BatchedVitTracker:
             ims = []
             for f in map(self._as_image, frames):
                 if not f.is_cuda:
-                    f = Image(f.format, [torch.from_numpy(np.ascontiguousarray(a)).cuda() for a in f.planes], f.H, f.W,
+                    f = Image(f.format, [torch.from_numpy(np.ascontiguousarray(a)).cuda() for a in f.host_planes()], f.H, f.W,
                               [rb for _, rb in f.plane_rows()])
                 ims.append(f)
             tab = ImageTable.of(ims)
@@ -335,7 +335,7 @@ class BatchedVitTracker:
 
     def initialize(self, frames, init_boxes):
         """frames: (B,H,W,3) uint8 (numpy, list of arrays or CUDA tensor) -- or a list of B frames of different sizes, any of which
-        may be a native.Image (NV12 / NV21, BGR, RGBA / BGRA, RGB);
+        may be a native.Image (any layout of include/vittrack.h: NV12 / NV21, P010, I420, YUYV, GRAY8, BGR, RGBA / BGRA, RGB);
         init_boxes: (B,4) [x,y,w,h]."""
         import torch
         images = self._has_image(frames)

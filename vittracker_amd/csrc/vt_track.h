@@ -696,6 +696,52 @@ __global__ __launch_bounds__(256) void crop_band_kernel(const unsigned char* __r
 // pixel differs: it is converted to an RGB dword (R | G << 8 | B << 16) first.  New kernels, not new frame sources of the bodies above:
 // those bodies fetch a 3-byte pixel pair as one window, and the existing instantiations stay as they compile today.
 struct ImageView {
+    const unsigned char* p0;       // plane 0: the packed pixels, or the luma plane
+    const unsigned char* p1;       // plane 1: NV12 / NV21 / P010 chroma pairs, or the first chroma plane of I420 / YV12
+    unsigned pitch0, pitch1;       // bytes between rows
+    unsigned nrec0, nrec1;         // each plane's extent, the bound of its buffer descriptor (loads beyond it return zero, fetch nothing)
+    unsigned p2;                   // I420 / YV12: byte offset of the second chroma plane from p1 (pitch1 H / 2); inside nrec1
+    int H, W, fmt, col;            // fmt: the layout (bits 0-7 of vt_image.format); col: matrix | range << 1 (0 = BT.601 limited)
+    bool ok;                       // false: an unusable descriptor, poisoned like a too-small box
+};
+__device__ __forceinline__ ImageView image_view(const vt_image* images, int b) {
+    // one descriptor per workgroup at a workgroup-uniform address: scalar loads
+    const vt_image* const d = images + b;
+    const unsigned char* const p0 = d->plane0;
+    const unsigned char* const p1 = d->plane1;
+    const int H = d->H, W = d->W;
+    const unsigned word = (unsigned)d->format;
+    const int fmt = (int)(word & 0xffu), mat = (int)((word >> 8) & 0xfu), rng = (int)((word >> 12) & 0xfu);
+    const bool nv = fmt == VT_PIX_NV12 || fmt == VT_PIX_NV21, p010 = fmt == VT_PIX_P010;
+    const bool pl = fmt == VT_PIX_I420 || fmt == VT_PIX_YV12, pk2 = fmt == VT_PIX_YUYV || fmt == VT_PIX_UYVY;
+    const bool sub420 = nv || p010 || pl, yuv = sub420 || pk2;
+    const long long bpp = (fmt == VT_PIX_RGBA || fmt == VT_PIX_BGRA) ? 4 : ((p010 || pk2) ? 2 : ((nv || pl || fmt == VT_PIX_GRAY8) ? 1 : 3));
+    bool ok = ((fmt >= VT_PIX_RGB && fmt <= VT_PIX_NV21) || (fmt >= VT_PIX_I420 && fmt <= VT_PIX_GRAY8)) && (word >> 16) == 0u && mat <= 1 &&
+              rng <= 1 && (yuv || (mat | rng) == 0) && d->reserved == 0 && H >= 1 && W >= 1 && H <= 0x10000000 && W <= 0x10000000 &&
+              (!sub420 || ((H | W) & 1) == 0) && (!pk2 || (W & 1) == 0);
+    const long long row0 = bpp * W, pitch0 = d->pitch0 == 0 ? row0 : d->pitch0;
+    ok = ok && pitch0 >= row0 && pitch0 <= 0xfffffff0ll && p0 != nullptr && (reinterpret_cast<unsigned long long>(p0) & 3ull) == 0;
+    const unsigned long long ext0 = ok ? (unsigned long long)pitch0 * (unsigned long long)(H - 1) + (unsigned long long)row0 : 0ull;
+    ok = ok && ext0 <= 0xfffffff0ull;
+    long long pitch1 = 0;
+    unsigned long long ext1 = 0, p2 = 0;
+    if (sub420) {
+        // chroma: H / 2 rows of W bytes (NV12 / NV21) or 2 W bytes (P010); I420 / YV12: two planes of H / 2 rows of W / 2 bytes back
+        // to back at one pitch, i.e. H rows, and the extent covers both
+        const long long row1 = p010 ? 2ll * W : (pl ? W / 2 : (long long)W);
+        const long long rows1 = pl ? H : H / 2;
+        pitch1 = d->pitch1 == 0 ? row1 : d->pitch1;
+        ok = ok && pitch1 >= row1 && pitch1 <= 0xfffffff0ll && p1 != nullptr && (reinterpret_cast<unsigned long long>(p1) & 3ull) == 0;
+        ext1 = ok ? (unsigned long long)pitch1 * (unsigned long long)(rows1 - 1) + (unsigned long long)row1 : 0ull;
+        ok = ok && ext1 <= 0xfffffff0ull;
+        p2 = (ok && pl) ? (unsigned long long)pitch1 * (unsigned long long)(H / 2) : 0ull;
+    }
+    return ImageView{p0, p1, ok ? (unsigned)pitch0 : 0u, ok ? (unsigned)pitch1 : 0u, ok ? (unsigned)ext0 : 0u, ok ? (unsigned)ext1 : 0u,
+                     (unsigned)p2, ok ? H : 1, ok ? W : 1, fmt, ok ? (mat | (rng << 1)) : 0, ok};
+}
+// The six first layouts (RGB ... NV21, no colour bits) as crop_band_image_kernel has always read them: its own view, so that its code
+// does not change with the layouts added to image_view
+struct ImageView6 {
     const unsigned char* p0;       // plane 0: the packed pixels, or NV12 / NV21 luma
     const unsigned char* p1;       // plane 1: NV12 / NV21 chroma pairs
     unsigned pitch0, pitch1;       // bytes between rows
@@ -703,7 +749,7 @@ struct ImageView {
     int H, W, fmt;
     bool ok;                       // false: an unusable descriptor, poisoned like a too-small box
 };
-__device__ __forceinline__ ImageView image_view(const vt_image* images, int b) {
+__device__ __forceinline__ ImageView6 image_view6(const vt_image* images, int b) {
     // one descriptor per workgroup at a workgroup-uniform address: scalar loads
     const vt_image* const d = images + b;
     const unsigned char* const p0 = d->plane0;
@@ -725,10 +771,12 @@ __device__ __forceinline__ ImageView image_view(const vt_image* images, int b) {
         ext1 = ok ? (unsigned long long)pitch1 * (unsigned long long)(H / 2 - 1) + (unsigned long long)W : 0ull;
         ok = ok && ext1 <= 0xfffffff0ull;
     }
-    return ImageView{p0, p1, ok ? (unsigned)pitch0 : 0u, ok ? (unsigned)pitch1 : 0u, ok ? (unsigned)ext0 : 0u, ok ? (unsigned)ext1 : 0u,
+    return ImageView6{p0, p1, ok ? (unsigned)pitch0 : 0u, ok ? (unsigned)pitch1 : 0u, ok ? (unsigned)ext0 : 0u, ok ? (unsigned)ext1 : 0u,
                      ok ? H : 1, ok ? W : 1, fmt, ok};
 }
-// BT.601 limited range in OpenCV's fixed point (include/vittrack.h).  The chroma terms of a pair, rounding constant included ...
+// BT.601 limited range in OpenCV's fixed point (include/vittrack.h): the literals of crop_band_image_kernel's NV12 / NV21 family.  (Every
+// other path -- crop_image_kernel, crop_band_image_ext -- takes the coefficient row of its descriptor from yuv_coef below, whose BT.601
+// limited row is these numbers.)  The chroma terms of a pair, rounding constant included ...
 struct ChromaTerms { int r, g, b; };
 __device__ __forceinline__ ChromaTerms chroma_terms(unsigned u8, unsigned v8) {
     const int u = (int)u8 - 128, v = (int)v8 - 128;
@@ -740,6 +788,43 @@ __device__ __forceinline__ unsigned yuv_rgb(unsigned y8, const ChromaTerms& c) {
     auto ch = [](int s) { s >>= 20; return (unsigned)(s < 0 ? 0 : (s > 255 ? 255 : s)); };
     return ch(yy + c.r) | (ch(yy + c.g) << 8) | (ch(yy + c.b) << 16);
 }
+// The other colour rows (include/vittrack.h): round(x 2^20) of the exact rationals.  Uniform in a workgroup: scalar selects, SGPRs.
+struct YuvCoef { int cy, cvr, cvg, cug, cub; unsigned yoff; };
+__device__ __forceinline__ YuvCoef yuv_coef(int col) {      // col: matrix | range << 1
+    const bool m709 = (col & 1) != 0, full = (col & 2) != 0;
+    return YuvCoef{full ? 1048576 : (m709 ? 1220945 : 1220542),
+                   m709 ? (full ? 1651297 : 1879825) : (full ? 1470104 : 1673527),
+                   m709 ? (full ? 490864 : 558796) : (full ? 748826 : 852492),
+                   m709 ? (full ? 196424 : 223607) : (full ? 360853 : 409993),
+                   m709 ? (full ? 1945738 : 2215014) : (full ? 1858077 : 2116026),
+                   full ? 0u : 16u};
+}
+__device__ __forceinline__ ChromaTerms chroma_terms(unsigned u8, unsigned v8, const YuvCoef& k) {
+    const int u = (int)u8 - 128, v = (int)v8 - 128;
+    return ChromaTerms{k.cvr * v + (1 << 19), -k.cvg * v - k.cug * u + (1 << 19), k.cub * u + (1 << 19)};
+}
+__device__ __forceinline__ unsigned yuv_rgb(unsigned y8, const ChromaTerms& c, const YuvCoef& k) {
+    const int yy = (int)(y8 > k.yoff ? y8 - k.yoff : 0u) * k.cy;
+    auto ch = [](int s) { s >>= 20; return (unsigned)(s < 0 ? 0 : (s > 255 ? 255 : s)); };
+    return ch(yy + c.r) | (ch(yy + c.g) << 8) | (ch(yy + c.b) << 16);
+}
+// Where the three samples of pixel (x, y) of a YUV layout lie, as uniform multipliers: luma at byte y pitch0 + x ymul + yadd of plane 0;
+// U and V at bytes (y >> cys) cpitch + (x >> 1) cmul + uoff / voff of plane 1 (or, c0: of plane 0 -- the packed 4:2:2 layouts).
+// P010: the sample is the high byte of each little-endian 16-bit word, hence the odd offsets.
+struct YuvLayout { unsigned ymul, yadd, cys, cpitch, cmul, uoff, voff; bool c0; };
+__device__ __forceinline__ YuvLayout yuv_layout(const ImageView& iv) {
+    switch (iv.fmt) {
+        case VT_PIX_NV21: return YuvLayout{1u, 0u, 1u, iv.pitch1, 2u, 1u, 0u, false};
+        case VT_PIX_I420: return YuvLayout{1u, 0u, 1u, iv.pitch1, 1u, 0u, iv.p2, false};
+        case VT_PIX_YV12: return YuvLayout{1u, 0u, 1u, iv.pitch1, 1u, iv.p2, 0u, false};
+        case VT_PIX_YUYV: return YuvLayout{2u, 0u, 0u, iv.pitch0, 4u, 1u, 3u, true};
+        case VT_PIX_UYVY: return YuvLayout{2u, 1u, 0u, iv.pitch0, 4u, 0u, 2u, true};
+        case VT_PIX_P010: return YuvLayout{2u, 1u, 1u, iv.pitch1, 4u, 1u, 3u, false};
+        case VT_PIX_GRAY8: return YuvLayout{1u, 0u, 0u, 0u, 0u, 0u, 0u, true};      // luma only
+        default: return YuvLayout{1u, 0u, 1u, iv.pitch1, 2u, 0u, 1u, false};         // NV12
+    }
+}
+__device__ __forceinline__ bool is_yuv_layout(int fmt) { return fmt == VT_PIX_NV12 || fmt == VT_PIX_NV21 || (fmt >= VT_PIX_I420 && fmt <= VT_PIX_P010); }
 // The tracker's tail clips against each sequence's own frame size (TrackTail::frames): the crop of vt_track_step_images writes the
 // sizes of its descriptors into a vt_frame-shaped table as it reads them (sizes may be null: vt_crop_images)
 __device__ __forceinline__ void image_sizes_out(vt_frame* sizes, const vt_image* images, int b) {
@@ -800,17 +885,22 @@ __global__ __launch_bounds__(256) void crop_image_kernel(const vt_image* __restr
     int sy0, sy1, by0, by1;
     lin_coeff(oy, crop_sz, scale, sy0, sy1, by0, by1);
     const auto rs0 = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned char*>(iv.p0), 0, (int)iv.nrec0, 0x00020000);
-    const auto rs1 = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned char*>(iv.p1 != nullptr ? iv.p1 : iv.p0), 0, (int)iv.nrec1, 0x00020000);
     auto byte0 = [&](unsigned o) { return (unsigned)__builtin_amdgcn_raw_buffer_load_b8(rs0, (int)o, 0, 0) & 0xffu; };
-    auto byte1 = [&](unsigned o) { return (unsigned)__builtin_amdgcn_raw_buffer_load_b8(rs1, (int)o, 0, 0) & 0xffu; };
     const int fmt = iv.fmt;
     const bool swap = fmt == VT_PIX_BGR || fmt == VT_PIX_BGRA;
+    const bool yuvf = is_yuv_layout(fmt);
+    const YuvLayout yl = yuv_layout(iv);
+    const YuvCoef kc = yuv_coef(iv.col);
+    const bool c1 = !yl.c0 && iv.p1 != nullptr;      // where the chroma samples are: plane 1, or plane 0 (packed 4:2:2)
+    const auto rsc = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned char*>(c1 ? iv.p1 : iv.p0), 0, (int)(c1 ? iv.nrec1 : iv.nrec0), 0x00020000);
     auto pixel = [&](int x, int y) -> unsigned {      // rgb(d) at (x, y), inside the image
-        if (fmt == VT_PIX_NV12 || fmt == VT_PIX_NV21) {
-            const unsigned co = (unsigned)(y >> 1) * iv.pitch1 + 2u * (unsigned)(x >> 1);
-            const unsigned c0 = byte1(co), c1 = byte1(co + 1u);
-            return yuv_rgb(byte0((unsigned)y * iv.pitch0 + (unsigned)x), fmt == VT_PIX_NV12 ? chroma_terms(c0, c1) : chroma_terms(c1, c0));
+        if (yuvf) {      // every sample a single byte: see yuv_layout
+            const unsigned co = ((unsigned)y >> yl.cys) * yl.cpitch + (unsigned)(x >> 1) * yl.cmul;
+            const unsigned u = (unsigned)__builtin_amdgcn_raw_buffer_load_b8(rsc, (int)(co + yl.uoff), 0, 0) & 0xffu;
+            const unsigned v = (unsigned)__builtin_amdgcn_raw_buffer_load_b8(rsc, (int)(co + yl.voff), 0, 0) & 0xffu;
+            return yuv_rgb(byte0((unsigned)y * iv.pitch0 + (unsigned)x * yl.ymul + yl.yadd), chroma_terms(u, v, kc), kc);
         }
+        if (fmt == VT_PIX_GRAY8) return byte0((unsigned)y * iv.pitch0 + (unsigned)x) * 0x010101u;
         const unsigned o = (unsigned)y * iv.pitch0 + (unsigned)x * ((fmt == VT_PIX_RGBA || fmt == VT_PIX_BGRA) ? 4u : 3u);
         const unsigned a = byte0(o), g = byte0(o + 1u), c = byte0(o + 2u);
         return swap ? (c | (g << 8) | (a << 16)) : (a | (g << 8) | (c << 16));
@@ -862,6 +952,323 @@ __global__ __launch_bounds__(256) void crop_image_kernel(const vt_image* __restr
     }
 }
 
+// crop_band_image_ext: the band crop of every format word beyond the six first layouts -- NV12 / NV21 under BT.709 or full range, P010,
+// I420 / YV12, YUYV / UYVY, GRAY8 -- called by crop_band_image_kernel (below) behind one uniform branch, with the same bands, tables,
+// arithmetic and results.  A body of its own, so that the code of the six first layouts stays what it was.  Families, each behind a
+// uniform branch (the format is uniform in a workgroup):
+//   - NV12 / NV21, the three other colour rows: crop_band_image_kernel's aligned 8-byte luma and chroma windows and its GUARD rule; the
+//     five coefficients and the luma floor come from SGPRs (yuv_coef) instead of literals
+//   - P010: aligned windows of its own (8 bytes of luma, 12 of chroma), one item at a time; derivation at the lambda
+//   - I420 / YV12, YUYV / UYVY, GRAY8: every sample of a tap as a single byte at the offsets yuv_layout gives, one item at a time
+// LDS: the tables below are this body's own, next to the kernel's (a workgroup allocates both sets: 2 x 7.4 KB at most, T = 256 in the
+// fp32 form; four workgroups a CU stay far inside the CU's LDS) -- the kernel's code was to stay as it compiles, its arrays included.
+// (`four` and `swap` below are false for every word that reaches a family here: an RGB layout with colour bits is poisoned first.)
+// xtab / ytab as in crop_band_kernel; ctab holds per output row the chroma-row offsets of its two source rows ((y >> cys) * cpitch of
+// yuv_layout: plane 1 for the 4:2:0 layouts, plane 0 for packed 4:2:2).
+template <bool U8OUT, int LGT4, int IPT>
+__device__ __forceinline__ void crop_band_image_ext(const vt_image* __restrict__ images, vt_frame* __restrict__ sizes,
+                                                              const double* __restrict__ states, double factor,
+                                                              float m0, float m1, float m2, float s0, float s1, float s2,
+                                                              float* __restrict__ out, double* __restrict__ resize_factor) {
+    constexpr int T4 = 1 << LGT4, T = 4 * T4, RPG = 256 >> LGT4, NROWS = IPT * RPG;
+    static_assert(T <= 256 && (T * T4) % (IPT * 256) == 0, "a band is whole rows and the frame whole bands");
+    const int b = blockIdx.y, tid = threadIdx.x;
+    const ImageView iv = image_view(images, b);
+    __shared__ float norm_lut[U8OUT ? 1 : 3 * 256];
+    __shared__ __attribute__((aligned(16))) unsigned xtab[T * 4];          // per output column: plane-0 byte offset of the window, packed weights, steps, chroma offset
+    __shared__ __attribute__((aligned(16))) unsigned ytab[NROWS * 4];      // per output row: plane-0 offsets of its two source rows, their weights << 12
+    __shared__ __attribute__((aligned(8))) unsigned ctab[NROWS * 2];       // per output row: chroma-row offsets of its two source rows (NV12 / NV21)
+    unsigned char* const out8 = reinterpret_cast<unsigned char*>(out) + (size_t)b * T * T * 3;
+    typedef unsigned u3a __attribute__((ext_vector_type(3), aligned(4)));
+    typedef unsigned u4v __attribute__((ext_vector_type(4)));
+    typedef unsigned u3v __attribute__((ext_vector_type(3)));
+    typedef unsigned u2v __attribute__((ext_vector_type(2)));
+    typedef unsigned short us2 __attribute__((ext_vector_type(2)));
+    if constexpr (!U8OUT) {
+        const float meanv[3] = {m0, m1, m2}, stdq[3] = {s0, s1, s2};
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            float scaled = (float)tid * (1.0f / 255.0f);
+            asm volatile("" : "+v"(scaled));
+            float centred = scaled - meanv[c];
+            asm volatile("" : "+v"(centred));
+            norm_lut[c * 256 + tid] = centred / stdq[c];
+        }
+    }
+    const double bx = states[4 * b + 0], by = states[4 * b + 1], bw = states[4 * b + 2], bh = states[4 * b + 3];
+    const int crop_sz = (int)ceil(sqrt(bw * bh) * factor);
+    const int row0 = blockIdx.x * NROWS;
+    const int cg = tid & (T4 - 1), rl = tid >> LGT4;
+    if (blockIdx.x == 0 && tid == 0) image_sizes_out(sizes, images, b);
+    if (!(crop_sz >= 1) || !iv.ok) {        // 'Too small bounding box.' (or an unusable descriptor): poison, as crop_kernel
+        if (blockIdx.x == 0 && tid == 0) resize_factor[b] = __builtin_nan("");
+#pragma unroll
+        for (int j = 0; j < IPT; ++j) {
+            const int oy = row0 + j * RPG + rl;
+            if constexpr (U8OUT) *reinterpret_cast<u3a*>(out8 + ((size_t)oy * T + 4 * cg) * 3) = u3a{0u, 0u, 0u};
+            else
+                for (int c = 0; c < 3; ++c) st4(out + (((size_t)b * 3 + c) * T + oy) * T + 4 * cg, splat4(__builtin_nanf("")));
+        }
+        return;
+    }
+    const int fmt = iv.fmt;
+    const bool nv = fmt == VT_PIX_NV12 || fmt == VT_PIX_NV21, four = fmt == VT_PIX_RGBA || fmt == VT_PIX_BGRA;
+    const bool newf = fmt >= VT_PIX_I420;      // I420 / YV12, YUYV / UYVY, P010, GRAY8: their column and row entries follow yuv_layout
+    const YuvLayout yl = yuv_layout(iv);
+    const YuvCoef kc = yuv_coef(iv.col);
+    const unsigned bpp = (nv || newf) ? yl.ymul : (four ? 4u : 3u);
+    const int x1 = (int)rint(bx + 0.5 * bw - crop_sz * 0.5);
+    const int y1 = (int)rint(by + 0.5 * bh - crop_sz * 0.5);
+    const int x2 = x1 + crop_sz, y2 = y1 + crop_sz;
+    const int vx0 = x1 < 0 ? 0 : x1, vx1 = x2 - (x2 - iv.W + 1 > 0 ? x2 - iv.W + 1 : 0);
+    const int vy0 = y1 < 0 ? 0 : y1, vy1 = y2 - (y2 - iv.H + 1 > 0 ? y2 - iv.H + 1 : 0);
+    if (blockIdx.x == 0 && tid == 0) resize_factor[b] = (double)T / (double)crop_sz;
+    const double scale = (double)crop_sz / (double)T;
+    if (tid < T) {                          // column entries: zero padding lives in the weights, as crop_band_kernel
+        int sx0, sx1, ax0, ax1;
+        lin_coeff(tid, crop_sz, scale, sx0, sx1, ax0, ax1);
+        const int xx0 = x1 + sx0, xx1 = x1 + sx1;
+        const bool vc0 = xx0 >= vx0 && xx0 < vx1, vc1 = xx1 >= vx0 && xx1 < vx1;
+        const int xb = vc0 ? xx0 : (vc1 ? xx1 : 0);
+        // steps: bit 0 = the right tap is the next pixel, bit 1 = its chroma pair is the next pair
+        const unsigned step = vc1 && xx1 != xb ? 1u : 0u, cstep = vc1 && (xx1 >> 1) != (xb >> 1) ? 2u : 0u;
+        *reinterpret_cast<u4v*>(xtab + 4 * tid) = u4v{bpp * (unsigned)xb + (newf ? yl.yadd : 0u), (unsigned)(vc0 ? ax0 : 0) | ((unsigned)(vc1 ? ax1 : 0) << 16),
+                                                       step | cstep, (newf ? yl.cmul : 2u) * (unsigned)(xb >> 1)};
+    }
+    if (tid >= 256 - NROWS) {               // row entries of the band
+        const int r = tid - (256 - NROWS);
+        int sy0, sy1, by0, by1;
+        lin_coeff(row0 + r, crop_sz, scale, sy0, sy1, by0, by1);
+        const int yy0 = y1 + sy0, yy1 = y1 + sy1;
+        const bool vr0 = yy0 >= vy0 && yy0 < vy1, vr1 = yy1 >= vy0 && yy1 < vy1;
+        const unsigned ya = (unsigned)(vr0 ? yy0 : 0), yb = (unsigned)(vr1 ? yy1 : 0);      // rows outside the valid range read row 0
+        *reinterpret_cast<u4v*>(ytab + 4 * r) = u4v{ya * iv.pitch0, yb * iv.pitch0, vr0 ? (unsigned)by0 << 12 : 0u, vr1 ? (unsigned)by1 << 12 : 0u};
+        *reinterpret_cast<u2v*>(ctab + 2 * r) = newf ? u2v{(ya >> yl.cys) * yl.cpitch, (yb >> yl.cys) * yl.cpitch} : u2v{(ya >> 1) * iv.pitch1, (yb >> 1) * iv.pitch1};
+    }
+    __syncthreads();
+    const auto rs0 = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned char*>(iv.p0), 0, (int)iv.nrec0, 0x00020000);
+    const bool c1 = nv || (newf && !yl.c0);      // chroma in plane 1; else (packed 4:2:2) in plane 0
+    const unsigned nrecc = c1 ? iv.nrec1 : (newf ? iv.nrec0 : 0u);
+    const auto rs1 = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned char*>(c1 ? iv.p1 : iv.p0), 0, (int)nrecc, 0x00020000);
+    unsigned xo[4], wp[4], st[4], xc[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const u4v e = *reinterpret_cast<const u4v*>(xtab + 4 * (4 * cg + k));
+        xo[k] = e.x; wp[k] = e.y; st[k] = e.z; xc[k] = e.w;
+    }
+    // the byte of each channel in an RGB-ordered (or, swapped, BGR-ordered) pixel dword: v_perm_b32 selectors
+    // [left pixel's channel, 0, right pixel's channel, 0], uniform
+    const bool swap = fmt == VT_PIX_BGR || fmt == VT_PIX_BGRA;
+    unsigned sel[3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) sel[c] = 0x0c040c00u + 0x00010001u * (unsigned)(swap ? 2 - c : c);
+    const unsigned ush = fmt == VT_PIX_NV21 ? 8u : 0u;      // bit offset of U in a chroma pair (V at the other byte)
+    unsigned two = 2u;
+    asm volatile("" : "+v"(two));
+    const bool col_live = (wp[0] | wp[1] | wp[2] | wp[3]) != 0u;
+    // the output of one item from its four tap-pair dwords per row (l = left tap, r = right tap: R | G << 8 | B << 16)
+    auto finish = [&](int j, const unsigned (&l0)[4], const unsigned (&r0w)[4], const unsigned (&l1)[4], const unsigned (&r1w)[4],
+                      unsigned byw0, unsigned byw1) {
+        const int oy = row0 + j * RPG + rl;
+        float res[3][4];
+        unsigned pk[3] = {0u, 0u, 0u};
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const us2 wv = __builtin_bit_cast(us2, wp[k]);
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {       // crop_band_kernel's arithmetic
+                const unsigned r0 = __builtin_amdgcn_udot2(__builtin_bit_cast(us2, __builtin_amdgcn_perm(r0w[k], l0[k], sel[c])), wv, 0u, false);
+                const unsigned r1 = __builtin_amdgcn_udot2(__builtin_bit_cast(us2, __builtin_amdgcn_perm(r1w[k], l1[k], sel[c])), wv, 0u, false);
+                const unsigned t0 = mulhi24(byw0, r0 & ~15u), t1 = mulhi24(byw1, r1 & ~15u);
+                if constexpr (U8OUT) {
+                    put_byte_shr2(pk[(3 * k + c) >> 2], t0 + t1 + 2u, two, (3 * k + c) & 3);
+                } else {
+                    const unsigned v4 = (t0 + t1 + 2u) & ~3u;
+                    res[c][k] = *reinterpret_cast<const float*>(reinterpret_cast<const char*>(norm_lut) + c * 1024 + v4);
+                }
+            }
+        }
+        if constexpr (U8OUT) {
+            *reinterpret_cast<u3a*>(out8 + ((size_t)oy * T + 4 * cg) * 3) = u3a{pk[0], pk[1], pk[2]};
+        } else {
+#pragma unroll
+            for (int c = 0; c < 3; ++c) st4(out + (((size_t)b * 3 + c) * T + oy) * T + 4 * cg, f4{res[c][0], res[c][1], res[c][2], res[c][3]});
+        }
+    };
+    constexpr int HS = IPT < 2 ? IPT : 2;      // two items at a time, as crop_band_kernel
+    // NV12 / NV21; GUARD: windows that would cross their plane's end are read as single bytes
+    // VC: one of the three other colour rows -- the same windows, the coefficients and the luma floor from kc (SGPRs) instead of literals
+    auto yuv = [&](auto guard_c) {
+        constexpr bool GUARD = decltype(guard_c)::value;
+        u2v ya0[IPT][4], ya1[IPT][4], ca0[IPT][4], ca1[IPT][4];
+        unsigned ro0[IPT], ro1[IPT], co0[IPT], co1[IPT], byw0[IPT], byw1[IPT];
+        auto load8 = [&](const auto& rs, unsigned o, unsigned nrec) -> u2v {      // the 8 bytes from the dword that holds byte o
+            const unsigned a = o & ~3u;
+            if (!GUARD || a + 8u <= nrec) return __builtin_amdgcn_raw_buffer_load_b64(rs, (int)a, 0, 0);
+            unsigned lo = 0u, hi = 0u;
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                lo |= ((unsigned)__builtin_amdgcn_raw_buffer_load_b8(rs, (int)(a + i), 0, 0) & 0xffu) << (8 * i);
+                hi |= ((unsigned)__builtin_amdgcn_raw_buffer_load_b8(rs, (int)(a + 4 + i), 0, 0) & 0xffu) << (8 * i);
+            }
+            return u2v{lo, hi};
+        };
+        auto issue = [&](int j) {
+            const u4v e = *reinterpret_cast<const u4v*>(ytab + 4 * (j * RPG + rl));
+            const u2v cr = *reinterpret_cast<const u2v*>(ctab + 2 * (j * RPG + rl));
+            ro0[j] = e.x; ro1[j] = e.y; byw0[j] = e.z; byw1[j] = e.w; co0[j] = cr.x; co1[j] = cr.y;
+            const bool live = ((e.z | e.w) != 0u) && col_live;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                if (!live) {      // (one assignment each: chained, they kept the arrays in scratch)
+                    ya0[j][k] = u2v{0u, 0u}; ya1[j][k] = u2v{0u, 0u}; ca0[j][k] = u2v{0u, 0u}; ca1[j][k] = u2v{0u, 0u};
+                    continue;
+                }
+                ya0[j][k] = load8(rs0, e.x + xo[k], iv.nrec0);
+                ya1[j][k] = load8(rs0, e.y + xo[k], iv.nrec0);
+                ca0[j][k] = load8(rs1, cr.x + xc[k], iv.nrec1);
+                ca1[j][k] = load8(rs1, cr.y + xc[k], iv.nrec1);
+            }
+        };
+        auto taps = [&](const u2v& yw, const u2v& cw, unsigned yo, unsigned co, unsigned s, unsigned& l, unsigned& r) {
+            const unsigned y = __builtin_amdgcn_alignbit(yw.y, yw.x, yo << 3);      // luma of the left tap at byte 0, the next pixel's at byte 1
+            const unsigned c = __builtin_amdgcn_alignbit(cw.y, cw.x, co << 3);      // the left tap's chroma pair at bytes 0-1, the next pair at 2-3
+            const unsigned cl = c & 0xffffu, cr = (s & 2u) ? c >> 16 : cl;
+            l = yuv_rgb(y & 0xffu, chroma_terms((cl >> ush) & 0xffu, (cl >> (8u - ush)) & 0xffu, kc), kc);
+            r = yuv_rgb((s & 1u) ? (y >> 8) & 0xffu : y & 0xffu, chroma_terms((cr >> ush) & 0xffu, (cr >> (8u - ush)) & 0xffu, kc), kc);
+        };
+        auto math = [&](int j) {
+            unsigned l0[4], r0w[4], l1[4], r1w[4];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                taps(ya0[j][k], ca0[j][k], ro0[j] + xo[k], co0[j] + xc[k], st[k], l0[k], r0w[k]);
+                taps(ya1[j][k], ca1[j][k], ro1[j] + xo[k], co1[j] + xc[k], st[k], l1[k], r1w[k]);
+            }
+            finish(j, l0, r0w, l1, r1w, byw0[j], byw1[j]);
+        };
+#pragma unroll
+        for (int h = 0; h < IPT; h += HS) {
+#pragma unroll
+            for (int j = 0; j < HS; ++j) issue(h + j);
+#pragma unroll
+            for (int j = 0; j < HS; ++j) math(h + j);
+            __builtin_amdgcn_sched_barrier(0);
+        }
+    };
+    // P010 (also P016): NV12 with 16-bit little-endian samples of which the high byte counts.  The column entries point at the high
+    // bytes (yuv_layout: luma at 2 x + 1), so a tap pair's luma is bytes 0 and 2 of a 3-byte window: the aligned 8 bytes that hold its
+    // first byte cover it (first byte at 1 or 3 of them).  Its one or two chroma pairs are 8 bytes (Ulo Uhi Vlo Vhi, twice) at any
+    // alignment (pitch1 may be odd): the 12 aligned bytes that hold them, two funnel shifts, U and V at bytes 1 and 3 of each dword.
+    // One item at a time: the chroma windows are three registers, and two items' windows do not fit the 128 registers of the others.
+    // GUARD, re-derived for these widths (x <= W - 2, y <= H - 2 always: the crop's valid range stops one short):
+    //   luma: the window's first byte is at o <= pitch0 y + 2 (W - 2) + 1; its aligned 8 bytes end before o + 8 <= pitch0 y + 2 W + 5,
+    //     inside the plane [0, pitch0 (H - 1) + 2 W) for y <= H - 2 as pitch0 >= 2 W >= 4 (the chroma condition below covers it anyway)
+    //   chroma: the pairs start at o <= pitch1 (y >> 1) + 2 W - 4; their aligned 12 bytes end before o + 12 <= pitch1 (y >> 1) + 2 W + 8:
+    //     inside [0, pitch1 (H / 2 - 1) + 2 W) when y >> 1 <= H / 2 - 2 and pitch1 >= 8, and up to 8 bytes past it in the LAST chroma row
+    //     (y = H - 2).  So a band whose valid source rows reach H - 2, or a plane narrower than 8 bytes, takes the guarded form.
+    auto p010 = [&](auto guard_c) {
+        constexpr bool GUARD = decltype(guard_c)::value;
+        auto load8 = [&](unsigned o) -> u2v {
+            const unsigned a = o & ~3u;
+            if (!GUARD || a + 8u <= iv.nrec0) return __builtin_amdgcn_raw_buffer_load_b64(rs0, (int)a, 0, 0);
+            unsigned w[2] = {0u, 0u};
+#pragma unroll
+            for (int i = 0; i < 8; ++i) w[i >> 2] |= ((unsigned)__builtin_amdgcn_raw_buffer_load_b8(rs0, (int)(a + i), 0, 0) & 0xffu) << (8 * (i & 3));
+            return u2v{w[0], w[1]};
+        };
+        auto load12 = [&](unsigned o) -> u3v {
+            const unsigned a = o & ~3u;
+            if (!GUARD || a + 12u <= iv.nrec1) return __builtin_amdgcn_raw_buffer_load_b96(rs1, (int)a, 0, 0);
+            unsigned w[3] = {0u, 0u, 0u};
+#pragma unroll
+            for (int i = 0; i < 12; ++i) w[i >> 2] |= ((unsigned)__builtin_amdgcn_raw_buffer_load_b8(rs1, (int)(a + i), 0, 0) & 0xffu) << (8 * (i & 3));
+            return u3v{w[0], w[1], w[2]};
+        };
+        auto taps = [&](const u2v& yw, const u3v& cw, unsigned yo, unsigned co, unsigned s, unsigned& l, unsigned& r) {
+            const unsigned y = __builtin_amdgcn_alignbit(yw.y, yw.x, yo << 3);      // the left tap's luma at byte 0, the next pixel's at byte 2
+            const unsigned cl = __builtin_amdgcn_alignbit(cw.y, cw.x, co << 3);     // the left tap's pair: U at byte 1, V at byte 3
+            const unsigned cr = (s & 2u) ? __builtin_amdgcn_alignbit(cw.z, cw.y, co << 3) : cl;
+            l = yuv_rgb(y & 0xffu, chroma_terms((cl >> 8) & 0xffu, cl >> 24, kc), kc);
+            r = yuv_rgb((s & 1u) ? (y >> 16) & 0xffu : y & 0xffu, chroma_terms((cr >> 8) & 0xffu, cr >> 24, kc), kc);
+        };
+#pragma unroll
+        for (int j = 0; j < IPT; ++j) {
+            const u4v e = *reinterpret_cast<const u4v*>(ytab + 4 * (j * RPG + rl));
+            const u2v cr = *reinterpret_cast<const u2v*>(ctab + 2 * (j * RPG + rl));
+            const bool live = ((e.z | e.w) != 0u) && col_live;
+            u2v ya0[4], ya1[4];
+            u3v ca0[4], ca1[4];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                if (!live) {
+                    ya0[k] = u2v{0u, 0u}; ya1[k] = u2v{0u, 0u}; ca0[k] = u3v{0u, 0u, 0u}; ca1[k] = u3v{0u, 0u, 0u};
+                    continue;
+                }
+                ya0[k] = load8(e.x + xo[k]);
+                ya1[k] = load8(e.y + xo[k]);
+                ca0[k] = load12(cr.x + xc[k]);
+                ca1[k] = load12(cr.y + xc[k]);
+            }
+            unsigned l0[4], r0w[4], l1[4], r1w[4];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                taps(ya0[k], ca0[k], e.x + xo[k], cr.x + xc[k], st[k], l0[k], r0w[k]);
+                taps(ya1[k], ca1[k], e.y + xo[k], cr.y + xc[k], st[k], l1[k], r1w[k]);
+            }
+            finish(j, l0, r0w, l1, r1w, e.z, e.w);
+            __builtin_amdgcn_sched_barrier(0);
+        }
+    };
+    // I420 / YV12, YUYV / UYVY, GRAY8: the band's tables, every sample of a tap fetched as a single byte through the bounded descriptors
+    // (yuv_layout says where: the two chroma planes of I420 are plane 1 at offsets 0 and p2, packed 4:2:2 keeps its chroma in plane 0).
+    // Every offset lies inside its plane by construction (x + step <= W - 1, rows <= H - 2): no guard form.
+    auto bytewise = [&]() {
+        const bool gray = fmt == VT_PIX_GRAY8;
+        const unsigned ystep = yl.ymul, cstepb = yl.cmul;
+        auto lum = [&](unsigned o) { return (unsigned)__builtin_amdgcn_raw_buffer_load_b8(rs0, (int)o, 0, 0) & 0xffu; };
+        auto chr = [&](unsigned o) { return (unsigned)__builtin_amdgcn_raw_buffer_load_b8(rs1, (int)o, 0, 0) & 0xffu; };
+        auto tap = [&](unsigned yo, unsigned co) -> unsigned {
+            if (gray) return lum(yo) * 0x010101u;
+            const unsigned u = chr(co + yl.uoff), v = chr(co + yl.voff);
+            return yuv_rgb(lum(yo), chroma_terms(u, v, kc), kc);
+        };
+#pragma unroll
+        for (int j = 0; j < IPT; ++j) {
+            const u4v e = *reinterpret_cast<const u4v*>(ytab + 4 * (j * RPG + rl));
+            const u2v cr = *reinterpret_cast<const u2v*>(ctab + 2 * (j * RPG + rl));
+            const bool live = ((e.z | e.w) != 0u) && col_live;
+            unsigned l0[4], r0w[4], l1[4], r1w[4];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                if (!live) { l0[k] = 0u; r0w[k] = 0u; l1[k] = 0u; r1w[k] = 0u; continue; }
+                const unsigned ys = (st[k] & 1u) ? ystep : 0u, cs = (st[k] & 2u) ? cstepb : 0u;
+                l0[k] = tap(e.x + xo[k], cr.x + xc[k]);
+                r0w[k] = tap(e.x + xo[k] + ys, cr.x + xc[k] + cs);
+                l1[k] = tap(e.y + xo[k], cr.y + xc[k]);
+                r1w[k] = tap(e.y + xo[k] + ys, cr.y + xc[k] + cs);
+            }
+            finish(j, l0, r0w, l1, r1w, e.z, e.w);
+            __builtin_amdgcn_sched_barrier(0);
+        }
+    };
+    if (nv || fmt == VT_PIX_P010) {
+        // the guard: a band whose valid source rows reach row H - 2 reads the last chroma row; planes narrower than 8 bytes
+        int sl0, sl1, al0, al1;
+        lin_coeff(row0 + NROWS - 1, crop_sz, scale, sl0, sl1, al0, al1);
+        const int ymax = y1 + sl1 < vy1 - 1 ? y1 + sl1 : vy1 - 1;
+        const bool guard = ymax >= iv.H - 2 || iv.pitch0 < 8u || iv.pitch1 < 8u;
+        if (!nv) {
+            if (guard) p010(std::true_type{});
+            else p010(std::false_type{});
+        } else {      // NV12 / NV21 under one of the three other colour rows (BT.601 limited never comes here)
+            if (guard) yuv(std::true_type{});
+            else yuv(std::false_type{});
+        }
+    } else {
+        bytewise();
+    }
+}
+
 // crop_band_image_kernel: crop_band_kernel on a vt_image table (T = 64 / 128 / 256, the tracker's per-step crop), same bands, tables,
 // arithmetic and results.  The format is uniform in a workgroup (one workgroup crops one sequence), so each format family is its own
 // instantiation of the body inside one kernel, picked by a uniform branch; a table may still mix formats.
@@ -882,7 +1289,13 @@ __global__ __launch_bounds__(256) void crop_band_image_kernel(const vt_image* __
     constexpr int T4 = 1 << LGT4, T = 4 * T4, RPG = 256 >> LGT4, NROWS = IPT * RPG;
     static_assert(T <= 256 && (T * T4) % (IPT * 256) == 0, "a band is whole rows and the frame whole bands");
     const int b = blockIdx.y, tid = threadIdx.x;
-    const ImageView iv = image_view(images, b);
+    // a format word beyond the six first layouts -- another layout, or colour bits -- is cropped by crop_band_image_ext (above); the code
+    // below is, to the instruction, what cropped those six before the others existed, and they pay one scalar compare for them
+    if ((unsigned)images[b].format > (unsigned)VT_PIX_NV21) {
+        crop_band_image_ext<U8OUT, LGT4, IPT>(images, sizes, states, factor, m0, m1, m2, s0, s1, s2, out, resize_factor);
+        return;
+    }
+    const ImageView6 iv = image_view6(images, b);
     __shared__ float norm_lut[U8OUT ? 1 : 3 * 256];
     __shared__ __attribute__((aligned(16))) unsigned xtab[T * 4];          // per output column: plane-0 byte offset of the window, packed weights, steps, chroma offset
     __shared__ __attribute__((aligned(16))) unsigned ytab[NROWS * 4];      // per output row: plane-0 offsets of its two source rows, their weights << 12

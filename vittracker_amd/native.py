@@ -252,23 +252,66 @@ IMAGE_DTYPE = np.dtype([("plane0", "<u8"), ("plane1", "<u8"), ("pitch0", "<i8"),
 assert IMAGE_DTYPE.itemsize == 48
 
 
-def _is_nv(fmt: int) -> bool:
-    return fmt in (PIX_NV12, PIX_NV21)
+#: the layouts added to bits 0-7 of vt_image.format (6 and 7 are never assigned) ...
+PIX_I420, PIX_YV12, PIX_YUYV, PIX_UYVY, PIX_P010, PIX_GRAY8 = range(8, 14)
+PIX_LAYOUT_NAMES = dict(enumerate(PIX_NAMES))
+PIX_LAYOUT_NAMES.update({PIX_I420: "i420", PIX_YV12: "yv12", PIX_YUYV: "yuyv", PIX_UYVY: "uyvy", PIX_P010: "p010", PIX_GRAY8: "gray8"})
+#: ... its bits 8-11 (the matrix of a YUV layout) and 12-15 (its range); bits 16-31 must be 0
+PIX_MATRICES = ("bt601", "bt709")
+PIX_RANGES = ("limited", "full")
+_YUV420 = (PIX_NV12, PIX_NV21, PIX_I420, PIX_YV12, PIX_P010)
+_YUV422 = (PIX_YUYV, PIX_UYVY)
+
+
+def pix_format(layout: int, matrix: str = "bt601", range: str = "limited") -> int:      # noqa: A002  (the keyword the constructors take)
+    """The vt_image.format word of a layout and its colour tags."""
+    if matrix not in PIX_MATRICES:
+        raise VtError(f"matrix must be one of {PIX_MATRICES}, got {matrix!r}")
+    if range not in PIX_RANGES:
+        raise VtError(f"range must be one of {PIX_RANGES}, got {range!r}")
+    return int(layout) | (PIX_MATRICES.index(matrix) << 8) | (PIX_RANGES.index(range) << 12)
+
+
+def pix_fields(fmt: int):
+    """(layout, matrix bits, range bits, bits 16-31) of a format word."""
+    fmt = int(fmt) & 0xffffffff
+    return fmt & 0xff, (fmt >> 8) & 0xf, (fmt >> 12) & 0xf, fmt >> 16
+
+
+def pix_name(fmt: int) -> str:
+    return PIX_LAYOUT_NAMES.get(int(fmt) & 0xff, f"format {int(fmt)}").upper()
 
 
 def _row_bytes(fmt: int, W: int):
     """Bytes of one row of plane 0 and of plane 1 (0: no plane 1)."""
-    if _is_nv(fmt):
+    lay = fmt & 0xff
+    if lay in (PIX_NV12, PIX_NV21):
         return W, W
-    return (4 if fmt in (PIX_RGBA, PIX_BGRA) else 3) * W, 0
+    if lay == PIX_P010:
+        return 2 * W, 2 * W
+    if lay in (PIX_I420, PIX_YV12):
+        return W, W // 2
+    if lay in _YUV422:
+        return 2 * W, 0
+    if lay == PIX_GRAY8:
+        return W, 0
+    return (4 if lay in (PIX_RGBA, PIX_BGRA) else 3) * W, 0
+
+
+def _plane1_rows(fmt: int, H: int) -> int:
+    """Rows of plane 1: H / 2, or H for I420 / YV12 (its two chroma planes of H / 2 rows lie back to back at one pitch)."""
+    return H if (fmt & 0xff) in (PIX_I420, PIX_YV12) else H // 2
 
 
 class Image:
-    """One frame in a pixel format the tracker reads directly (vt_image, include/vittrack.h): RGB, BGR, RGBA, BGRA, NV12 or NV21.
+    """One frame in a pixel format the tracker reads directly (vt_image, include/vittrack.h): RGB, BGR, RGBA, BGRA, GRAY8, NV12, NV21,
+    P010 / P016, I420, YV12, YUYV (YUY2) or UYVY.
     Planes are numpy arrays (host: BatchedVitTracker packs them into its pinned arena) or uint8 tensors on the GPU (read in place).
     Rows may be strided (a pitch wider than the row), pixels may not.  Build one with the constructors: Image.rgb(a), .bgr(a),
-    .rgba(a), .bgra(a) for (H, W, 3 | 4) arrays, .nv12(y, uv) / .nv21(y, vu) for an (H, W) luma plane and an (H/2, W/2, 2) chroma
-    plane (H, W even)."""
+    .rgba(a), .bgra(a) for (H, W, 3 | 4) arrays, .gray(a) for (H, W), .nv12(y, uv) / .nv21(y, vu) for an (H, W) luma plane and an
+    (H/2, W/2, 2) chroma plane (H, W even), .p010(y, uv) for the same shapes in 16-bit samples, .i420(y, u, v) / .yv12(y, v, u) /
+    .i420_buffer(buf) for planar 4:2:0, .yuyv(a) / .uyvy(a) for (H, W, 2) packed 4:2:2.  Every YUV constructor takes
+    matrix="bt601" | "bt709" and range="limited" | "full" (default: BT.601 limited)."""
 
     __slots__ = ("format", "planes", "H", "W", "pitches")
 
@@ -294,11 +337,12 @@ class Image:
     @classmethod
     def _packed(cls, fmt, a, C_):
         shape, st, _ = cls._strides(a)
+        name = pix_name(fmt)
         if len(shape) != 3 or shape[2] != C_ or shape[0] < 1 or shape[1] < 1:
-            raise VtError(f"a {PIX_NAMES[fmt].upper()} image must be (H, W, {C_}), got {tuple(shape)}")
+            raise VtError(f"a {name} image must be (H, W, {C_}), got {tuple(shape)}")
         H, W = int(shape[0]), int(shape[1])
         if st[2] != 1 or (W > 1 and st[1] != C_) or (H > 1 and st[0] < C_ * W):
-            raise VtError(f"{PIX_NAMES[fmt].upper()} strides {tuple(st)}: pixels must be {C_} contiguous bytes, rows at least {C_} W apart")
+            raise VtError(f"{name} strides {tuple(st)}: pixels must be {C_} contiguous bytes, rows at least {C_} W apart")
         return cls(fmt, (a,), H, W, (st[0] if H > 1 else C_ * W,))
 
     @classmethod
@@ -319,32 +363,149 @@ class Image:
         return cls._packed(PIX_BGRA, a, 4)
 
     @classmethod
-    def _yuv(cls, fmt, y, c):
+    def gray(cls, a):
+        """An 8-bit grey frame (thermal / IR cameras), (H, W): rgb = (Y, Y, Y), no conversion."""
+        shape, st, _ = cls._strides(a)
+        if len(shape) != 2 or shape[0] < 1 or shape[1] < 1:
+            raise VtError(f"a GRAY8 image must be (H, W), got {tuple(shape)}")
+        H, W = int(shape[0]), int(shape[1])
+        if (W > 1 and st[1] != 1) or (H > 1 and st[0] < W):
+            raise VtError(f"GRAY8 strides {tuple(st)}: pixels must be contiguous bytes, rows at least W apart")
+        return cls(PIX_GRAY8, (a,), H, W, (st[0] if H > 1 else W,))
+
+    @classmethod
+    def _yuv(cls, fmt, y, c, spp=1):
+        """Two-plane 4:2:0: luma (H, W * spp) bytes and chroma pairs (H/2, W/2, 2 * spp) bytes; spp: bytes per sample."""
         sy, ty, gy = cls._strides(y)
         sc, tc, gc = cls._strides(c)
-        name = PIX_NAMES[fmt].upper()
+        name = pix_name(fmt)
+        if len(sy) != 2 or sy[1] % spp:
+            raise VtError(f"an {name} luma plane must be (H, W) with H and W even, got {tuple(sy)}")
+        sy = (sy[0], sy[1] // spp)
+        if sy[0] < 2 or sy[1] < 2 or sy[0] % 2 or sy[1] % 2:
+            raise VtError(f"an {name} luma plane must be (H, W) with H and W even, got {tuple(sy)}")
+        H, W = int(sy[0]), int(sy[1])
+        if tuple(sc) != (H // 2, W // 2, 2 * spp):
+            raise VtError(f"an {name} chroma plane must be (H/2, W/2, 2) = {(H // 2, W // 2, 2)}, got {(sc[0], sc[1], sc[2] // spp) if len(sc) == 3 else tuple(sc)}")
+        if gy != gc:
+            raise VtError(f"the two planes of an {name} image must both be on the GPU or both on the host")
+        if ty[1] != 1 or ty[0] < W * spp:
+            raise VtError(f"{name} luma strides {tuple(ty)}: pixels must be contiguous bytes, rows at least {'2 ' if spp == 2 else ''}W apart")
+        if tc[2] != 1 or (W > 2 and tc[1] != 2 * spp) or (H > 2 and tc[0] < W * spp):
+            raise VtError(f"{name} chroma strides {tuple(tc)}: pairs must be contiguous bytes, rows at least {'2 ' if spp == 2 else ''}W apart")
+        return cls(fmt, (y, c), H, W, (ty[0], tc[0] if H > 2 else W * spp))
+
+    @classmethod
+    def nv12(cls, y, uv, matrix="bt601", range="limited"):      # noqa: A002
+        """A decoder's NV12 surface: luma (H, W) and interleaved (U, V) pairs (H/2, W/2, 2)."""
+        return cls._yuv(pix_format(PIX_NV12, matrix, range), y, uv)
+
+    @classmethod
+    def nv21(cls, y, vu, matrix="bt601", range="limited"):      # noqa: A002
+        """NV21: as NV12 with (V, U) pairs."""
+        return cls._yuv(pix_format(PIX_NV21, matrix, range), y, vu)
+
+    @staticmethod
+    def _bytes16(a, what):
+        """A 16-bit plane as bytes (last axis doubled): uint16 / int16 numpy arrays and tensors, or their uint8 views as they are."""
+        import torch
+        if isinstance(a, np.ndarray):
+            if a.dtype == np.uint8:
+                return a
+            if a.dtype.kind not in "ui" or a.dtype.itemsize != 2 or a.dtype.byteorder == ">":
+                raise VtError(f"P010 {what} must be little-endian 16-bit samples or their uint8 view, got {a.dtype}")
+            if a.ndim == 0 or a.strides[-1] != 2:
+                raise VtError(f"P010 {what} strides {a.strides}: samples must be contiguous")
+            return a.view(np.uint8)      # the last axis doubled; rows keep their stride
+        if isinstance(a, torch.Tensor):
+            if a.dtype == torch.uint8:
+                return a
+            if a.dtype not in (torch.int16, torch.uint16) or (a.dim() and a.shape[-1] > 1 and a.stride(-1) != 1):
+                raise VtError(f"P010 {what} must be contiguous 16-bit samples or their uint8 view, got {a.dtype}")
+            return a.view(torch.uint8)
+        raise VtError(f"image planes must be numpy arrays or GPU tensors, got {type(a).__name__}")
+
+    @classmethod
+    def p010(cls, y, uv, matrix="bt601", range="limited"):      # noqa: A002
+        """A 10-bit decoder's P010 surface (a P016 one is read the same way): NV12's layout in little-endian 16-bit samples -- luma
+        (H, W) and (U, V) pairs (H/2, W/2, 2) as uint16 / int16 arrays or tensors, or their uint8 views (H, 2 W) and (H/2, W/2, 4).
+        The 8-bit sample is the high byte of each word."""
+        yb, cb = cls._bytes16(y, "luma"), cls._bytes16(uv, "chroma")
+        return cls._yuv(pix_format(PIX_P010, matrix, range), yb, cb, spp=2)
+
+    @classmethod
+    def _planar(cls, fmt, y, c1, c2):
+        sy, ty, gy = cls._strides(y)
+        name = pix_name(fmt)
         if len(sy) != 2 or sy[0] < 2 or sy[1] < 2 or sy[0] % 2 or sy[1] % 2:
             raise VtError(f"an {name} luma plane must be (H, W) with H and W even, got {tuple(sy)}")
         H, W = int(sy[0]), int(sy[1])
-        if tuple(sc) != (H // 2, W // 2, 2):
-            raise VtError(f"an {name} chroma plane must be (H/2, W/2, 2) = {(H // 2, W // 2, 2)}, got {tuple(sc)}")
-        if gy != gc:
-            raise VtError(f"the two planes of an {name} image must both be on the GPU or both on the host")
         if ty[1] != 1 or ty[0] < W:
             raise VtError(f"{name} luma strides {tuple(ty)}: pixels must be contiguous bytes, rows at least W apart")
-        if tc[2] != 1 or (W > 2 and tc[1] != 2) or (H > 2 and tc[0] < W):
-            raise VtError(f"{name} chroma strides {tuple(tc)}: pairs must be contiguous bytes, rows at least W apart")
-        return cls(fmt, (y, c), H, W, (ty[0], tc[0] if H > 2 else W))
+        pitch1 = None
+        for c in (c1, c2):
+            sc, tc, gc = cls._strides(c)
+            if tuple(sc) != (H // 2, W // 2):
+                raise VtError(f"an {name} chroma plane must be (H/2, W/2) = {(H // 2, W // 2)}, got {tuple(sc)}")
+            if gc != gy:
+                raise VtError(f"the planes of an {name} image must all be on the GPU or all on the host")
+            if (W > 2 and tc[1] != 1) or (H > 2 and tc[0] < W // 2):
+                raise VtError(f"{name} chroma strides {tuple(tc)}: pixels must be contiguous bytes, rows at least W/2 apart")
+            q = tc[0] if H > 2 else None
+            if pitch1 is not None and q is not None and q != pitch1:
+                raise VtError(f"the two chroma planes of an {name} image must have one row pitch, got {pitch1} and {q}")
+            pitch1 = q if q is not None else pitch1
+        pitch1 = pitch1 if pitch1 is not None else W // 2
+        if gy and int(c2.data_ptr()) != int(c1.data_ptr()) + pitch1 * (H // 2):
+            # the descriptor has one plane-1 pointer: the second chroma plane is found pitch1 * H/2 bytes after the first
+            raise VtError(f"the chroma planes of a device {name} image are not contiguous: the second must begin pitch1 * H/2 = "
+                          f"{pitch1 * (H // 2)} bytes after the first (one buffer, as Image.i420_buffer takes); copy them into one")
+        return cls(fmt, (y, c1, c2), H, W, (ty[0], pitch1))
 
     @classmethod
-    def nv12(cls, y, uv):
-        """A decoder's NV12 surface: luma (H, W) and interleaved (U, V) pairs (H/2, W/2, 2)."""
-        return cls._yuv(PIX_NV12, y, uv)
+    def i420(cls, y, u, v, matrix="bt601", range="limited"):      # noqa: A002
+        """Planar 4:2:0 as software decoders produce it (ffmpeg's yuv420p): luma (H, W), U and V (H/2, W/2) each.  On the GPU the V
+        plane must begin pitch1 * H/2 bytes after the U plane; host planes are packed that way into the arena."""
+        return cls._planar(pix_format(PIX_I420, matrix, range), y, u, v)
 
     @classmethod
-    def nv21(cls, y, vu):
-        """NV21: as NV12 with (V, U) pairs."""
-        return cls._yuv(PIX_NV21, y, vu)
+    def yv12(cls, y, v, u, matrix="bt601", range="limited"):      # noqa: A002
+        """YV12: I420 with the V plane first."""
+        return cls._planar(pix_format(PIX_YV12, matrix, range), y, v, u)
+
+    @classmethod
+    def i420_buffer(cls, buf, matrix="bt601", range="limited"):      # noqa: A002
+        """One contiguous I420 buffer as OpenCV (COLOR_YUV2RGB_I420) and av_image_copy_to_buffer lay it out: a (3H/2, W) array of tight
+        rows -- H rows of luma, then the U plane, then the V plane (H/2 rows of W/2 bytes each)."""
+        shape, st, _ = cls._strides(buf)
+        if len(shape) != 2 or shape[0] < 3 or shape[0] % 3 or shape[1] < 2 or shape[1] % 2:
+            raise VtError(f"an I420 buffer must be (3H/2, W) with H and W even, got {tuple(shape)}")
+        H, W = 2 * int(shape[0]) // 3, int(shape[1])
+        if st[1] != 1 or st[0] != W:
+            raise VtError(f"I420 buffer strides {tuple(st)}: rows must be tight (W bytes apart), the chroma planes follow the luma plane")
+        c = buf[H:].reshape(H, W // 2)      # both chroma planes, H / 2 rows each: a view
+        return cls(pix_format(PIX_I420, matrix, range), (buf[:H], c), H, W, (W, W // 2))
+
+    @classmethod
+    def _packed422(cls, fmt, a):
+        shape, st, _ = cls._strides(a)
+        name = pix_name(fmt)
+        if len(shape) != 3 or shape[2] != 2 or shape[0] < 1 or shape[1] < 2 or shape[1] % 2:
+            raise VtError(f"a {name} image must be (H, W, 2) with W even, got {tuple(shape)}")
+        H, W = int(shape[0]), int(shape[1])
+        if st[2] != 1 or st[1] != 2 or (H > 1 and st[0] < 2 * W):
+            raise VtError(f"{name} strides {tuple(st)}: pixels must be 2 contiguous bytes, rows at least 2 W apart")
+        return cls(fmt, (a,), H, W, (st[0] if H > 1 else 2 * W,))
+
+    @classmethod
+    def yuyv(cls, a, matrix="bt601", range="limited"):      # noqa: A002
+        """Packed 4:2:2 as capture cards and webcams produce it (YUY2): (H, W, 2), each 4 bytes Y0 U Y1 V."""
+        return cls._packed422(pix_format(PIX_YUYV, matrix, range), a)
+
+    @classmethod
+    def uyvy(cls, a, matrix="bt601", range="limited"):      # noqa: A002
+        """UYVY: each 4 bytes U Y0 V Y1."""
+        return cls._packed422(pix_format(PIX_UYVY, matrix, range), a)
 
     @property
     def is_cuda(self) -> bool:
@@ -357,9 +518,16 @@ class Image:
         return (self.H, self.W, 3)
 
     def plane_rows(self):
-        """Per plane: (rows, row bytes)."""
+        """Per plane of the descriptor: (rows, row bytes).  I420 / YV12: plane 1 is both chroma planes back to back, H rows of W / 2."""
         r0, r1 = _row_bytes(self.format, self.W)
-        return [(self.H, r0)] + ([(self.H // 2, r1)] if r1 else [])
+        return [(self.H, r0)] + ([(_plane1_rows(self.format, self.H), r1)] if r1 else [])
+
+    def host_planes(self):
+        """The host planes as plane_rows() counts them: three separate I420 / YV12 planes give luma and the two chroma planes stacked."""
+        pl = [p.numpy() if hasattr(p, "numpy") else np.asarray(p) for p in self.planes]
+        if len(pl) == 3:
+            return [pl[0], np.concatenate([pl[1], pl[2]], axis=0)]
+        return pl
 
     def descriptor(self, ptrs=None, pitches=None):
         """The vt_image tuple of this image: at its planes' own addresses (device images), or at `ptrs` with `pitches`."""
@@ -407,16 +575,23 @@ class ImageTable:
         """The device's rules for an unusable descriptor, on the host: raises VtError where the kernels would poison the sequence.
         Returns the pitches actually used (0 -> the row's bytes).  nbytes0 / nbytes1: bytes available from each plane (buffers)."""
         fmt, H, W, pitch0, pitch1 = int(fmt), int(H), int(W), int(pitch0), int(pitch1)
-        if fmt not in range(6):
+        lay, mat, rng, high = pix_fields(fmt)
+        if lay not in PIX_LAYOUT_NAMES:
             raise VtError(f"unknown pixel format {fmt}")
+        if high or mat >= len(PIX_MATRICES) or rng >= len(PIX_RANGES):
+            raise VtError(f"unknown pixel format {fmt:#x}: matrix {mat}, range {rng}, bits 16-31 {high:#x}")
+        if (mat or rng) and lay not in _YUV420 + _YUV422:
+            raise VtError(f"a {pix_name(fmt)} image takes no matrix or range bits, got format {fmt:#x}")
         if int(reserved) != 0:
             raise VtError("vt_image.reserved must be 0")
         if H < 1 or W < 1 or H > 0x10000000 or W > 0x10000000:
             raise VtError(f"image of {H}x{W} pixels: H and W must be >= 1")
-        if _is_nv(fmt) and (H % 2 or W % 2):
-            raise VtError(f"an {PIX_NAMES[fmt].upper()} image must have even H and W, got {H}x{W}")
+        if lay in _YUV420 and (H % 2 or W % 2):
+            raise VtError(f"an {pix_name(fmt)} image must have even H and W, got {H}x{W}")
+        if lay in _YUV422 and W % 2:
+            raise VtError(f"a {pix_name(fmt)} image must have even W, got {H}x{W}")
         r0, r1 = _row_bytes(fmt, W)
-        planes = [(ptr0, pitch0, H, r0, nbytes0)] + ([(ptr1, pitch1, H // 2, r1, nbytes1)] if r1 else [])
+        planes = [(ptr0, pitch0, H, r0, nbytes0)] + ([(ptr1, pitch1, _plane1_rows(fmt, H), r1, nbytes1)] if r1 else [])
         used = []
         for k, (ptr, pitch, rows, rb, nb) in enumerate(planes):
             pitch = pitch or rb
