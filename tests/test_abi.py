@@ -59,3 +59,17 @@ def test_missing_library_fails_loudly(monkeypatch, tmp_path):
     monkeypatch.setattr(native, "LIB_PATH", str(tmp_path / "nope.so"))
     with pytest.raises(native.VtError, match="no CPU fallback"):
         native.lib()
+
+
+@pytest.mark.parametrize("precision", ["f32", "f16"])
+def test_every_symbol_is_bound_with_its_argument_types(precision):
+    """ctypes passes every argument of a function without argtypes as a C int -- a 64-bit device pointer would be truncated without an
+    error -- so lib() must have declared every symbol of the header, not only the ones somebody remembered."""
+    from vittracker_amd import native
+    if not (os.path.exists(native.LIB_PATH) and os.path.exists(native.LIB_PATH_F16)):
+        import __graft_entry__ as ge
+        ge.build()
+    L = native.lib(precision)
+    assert sorted(native.SYMBOLS) == _declared_symbols()
+    for s in native.SYMBOLS:
+        assert getattr(L, s).argtypes is not None, s

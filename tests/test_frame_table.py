@@ -23,6 +23,31 @@ def test_pack_offsets_are_aligned_and_disjoint():
     assert end == offs[-1] + 72 * 100 * 3
 
 
+def test_one_packer_serves_frames_and_image_planes():
+    """pack_planes against offsets written down from pack_offsets / pack_image_offsets as they were before they shared it: odd widths,
+    a 1 x 1 frame, two-plane images, a start behind a table and an alignment other than the arena's."""
+    from vittracker_amd.native import Image, pack_image_offsets, pack_planes
+    shapes = [(1, 1), (33, 47), (40, 5), (201, 301), (64, 64), (7, 3)]
+    want = {(24 * 6, 256): ([256, 512, 5376, 6144, 187648, 199936], 199999),
+            (0, 256): ([0, 256, 5120, 5888, 187392, 199680], 199743),
+            (100, 4): ([100, 104, 4760, 5360, 186864, 199152], 199215)}
+    for (start, align), (offs, end) in want.items():
+        assert pack_offsets(shapes, start=start, align=align) == (offs, end)
+        assert pack_planes([[H * W * 3] for H, W in shapes], start, align) == ([[o] for o in offs], end)
+    z = lambda *s: np.zeros(s, np.uint8)
+    ims = [Image.nv12(z(36, 54), z(18, 27, 2)), Image.rgb(z(1, 1, 3)), Image.i420(z(6, 4), z(3, 2), z(3, 2)), Image.gray(z(5, 7)),
+           Image.yuyv(z(3, 6, 2)), Image.p010(np.zeros((10, 12), np.uint16), np.zeros((5, 6, 2), np.uint16)), Image.bgra(z(9, 11, 4)),
+           Image.rgb(z(33, 47, 3))]
+    want = {(48 * 8, 256): ([[512, 2560], [3584], [3840, 4096], [4352], [4608], [4864, 5120], [5376], [5888]], 10541),
+            (0, 256): ([[0, 2048], [3072], [3328, 3584], [3840], [4096], [4352, 4608], [4864], [5376]], 10029),
+            (100, 4): ([[100, 2044], [3016], [3020, 3044], [3056], [3092], [3128, 3368], [3488], [3884]], 8537)}
+    sizes = [[rows * rb for rows, rb in im.plane_rows()] for im in ims]
+    assert sizes == [[1944, 972], [3], [24, 12], [35], [36], [240, 120], [396], [4653]]
+    for (start, align), (offs, end) in want.items():
+        assert pack_image_offsets(ims, start=start, align=align) == (offs, end)
+        assert pack_planes(sizes, start, align) == (offs, end)
+
+
 def test_frame_table_checks_every_descriptor():
     t = FrameTable(3)
     t.set(0, 4096, 10, 7)                              # pitch 0 -> 3 W

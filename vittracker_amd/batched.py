@@ -13,6 +13,8 @@ Semantics per sequence are those of ``Vit_dist.initialize / track``
 """
 from __future__ import annotations
 
+from types import SimpleNamespace
+
 import numpy as np
 
 from .config import geometry
@@ -29,6 +31,39 @@ def check_params_geometry(params, nat):
         raise VtError(f"tracker crop sizes (TEST.TEMPLATE_SIZE={params.template_size}, TEST.SEARCH_SIZE="
                       f"{params.search_size}) differ from the model geometry (DATA.TEMPLATE.SIZE={nat.template_size}, "
                       f"DATA.SEARCH.SIZE={nat.search_size})")
+
+
+class _Arena:
+    """A pinned host buffer and its device twin, [descriptor table | frames or planes]: the CPU packs a step's host frames into `np`
+    (the numpy view of `host`) and they reach `dev` with ONE copy.  It grows by doubling; each capacity has its own device address."""
+
+    def __init__(self):
+        self.cap, self.host, self.np, self.dev, self.copied = 0, None, None, None, None
+
+    def reserve(self, end: int):
+        """Make room for `end` bytes and wait until the CPU may write them.  Returns the device address the arena had when it had to
+        grow (the caller drops the graph captured on it), else None."""
+        import torch
+        old = None
+        if self.cap < end:
+            torch.cuda.current_stream().synchronize()       # nothing may still read the old arena
+            old = self.dev.data_ptr() if self.dev is not None else None
+            self.cap = max(end, 2 * self.cap)
+            self.host = torch.empty(self.cap, dtype=torch.uint8).pin_memory()
+            self.np = self.host.numpy()
+            self.dev = torch.empty(self.cap, dtype=torch.uint8, device="cuda")
+            self.copied = None
+        if self.copied is not None:
+            self.copied.synchronize()                         # the previous copy out of the pinned arena has been read
+        return old
+
+    def flush(self, end: int):
+        """Copy [0, end) to the device and record the event the next reserve() waits for.  Returns the device tensor."""
+        import torch
+        self.dev[:end].copy_(self.host[:end], non_blocking=True)
+        self.copied = torch.cuda.Event()
+        self.copied.record()
+        return self.dev
 
 
 class BatchedVitTracker:
@@ -75,13 +110,13 @@ class BatchedVitTracker:
         self._slot = 0
         self.hw = None
         self.frame_id = 0
-        # frames of different sizes (vt_track_step_frames): a pinned host arena and its device twin, [descriptor table | frames]
-        self._arena = None           # (capacity, pinned host uint8 tensor, device uint8 tensor, event of the last arena copy)
+        # the two table routes -- frames of different sizes (vt_track_step_frames) and frames in other pixel formats
+        # (vt_track_step_images) --, each with the arena of its host frames and its graphs: device table address -> (graph, device
+        # record, pinned host record, table)
+        self._routes = {FrameTable: SimpleNamespace(arena=_Arena(), graphs={}, step=self.nat.track_step_frames),
+                        ImageTable: SimpleNamespace(arena=_Arena(), graphs={}, step=self.nat.track_step_images)}
         self._dev_table = None       # FrameTable of caller-owned device frames
-        self._frames_graphs = {}     # device table address -> (graph, device record, pinned host record, table)
-        # frames in other pixel formats (vt_track_step_images): a pinned arena and its device twin, [vt_image table | host planes]
-        self._img_arena = None       # (capacity, pinned host uint8 tensor, device uint8 tensor, event of the last arena copy)
-        self._images_graphs = {}     # device table address -> (graph, device record, pinned host record, table)
+        self._img_keep = []          # device planes the image table of the last step points into
 
     # ---- frames of different sizes ------------------------------------------------------------------------------------
     @staticmethod
@@ -113,28 +148,17 @@ class BatchedVitTracker:
             arrs.append(a)
         tb = self.B * FrameTable.ITEM
         offs, end = pack_offsets([a.shape[:2] for a in arrs], start=tb)
-        if self._arena is None or self._arena[0] < end:
-            cap = max(end, 2 * self._arena[0] if self._arena is not None else end)
-            torch.cuda.current_stream().synchronize()       # nothing may still read the old arena
-            if self._arena is not None:
-                self._frames_graphs.pop(self._arena[2].data_ptr(), None)
-            self._arena = (cap, torch.empty(cap, dtype=torch.uint8).pin_memory(), torch.empty(cap, dtype=torch.uint8, device="cuda"), None)
-            self._arena_np = self._arena[1].numpy()
-        cap, host, dev, ev = self._arena
-        if ev is not None:
-            ev.synchronize()                                  # the previous copy out of the pinned arena has been read
-        tab = self._arena_np[:tb].view(FrameTable.DTYPE)
-        base = dev.data_ptr()
+        r = self._routes[FrameTable]
+        ar = r.arena
+        r.graphs.pop(ar.reserve(end), None)
+        tab = ar.np[:tb].view(FrameTable.DTYPE)
+        base = ar.dev.data_ptr()
         for i, (a, o) in enumerate(zip(arrs, offs)):
             H, W = a.shape[:2]
-            pitch = FrameTable.check(base + o, H, W, 0, nbytes=cap - o)
+            pitch = FrameTable.check(base + o, H, W, 0, nbytes=ar.cap - o)
             tab[i] = (base + o, H, W, pitch)
-            self._arena_np[o:o + H * W * 3].reshape(H, W, 3)[...] = a
-        dev[:end].copy_(host[:end], non_blocking=True)
-        ev = torch.cuda.Event()
-        ev.record()
-        self._arena = (cap, host, dev, ev)
-        return dev[:tb]
+            ar.np[o:o + H * W * 3].reshape(H, W, 3)[...] = a
+        return ar.flush(end)[:tb]
 
     # ---- frames in other pixel formats (NV12 / NV21, BGR, RGBA / BGRA) ---------------------------------------------------------
     @staticmethod
@@ -156,25 +180,17 @@ class BatchedVitTracker:
         """The device vt_image table of B frames of any formats and sizes.  Device images go in by pointer; the planes of host images
         are packed into a pinned arena at 256-byte offsets behind the table and reach the device arena, table included, with ONE
         copy.  The arena grows by doubling; each capacity has its own table address, hence its own captured step."""
-        import torch
         if len(frames) != self.B:
             raise ValueError(f"expected {self.B} frames, got {len(frames)}")
         ims = [self._as_image(f) for f in frames]
         tb = self.B * ImageTable.ITEM
         host_ims = [im for im in ims if not im.is_cuda]
         offs, end = pack_image_offsets(host_ims, start=tb)
-        if self._img_arena is None or self._img_arena[0] < end:
-            cap = max(end, 2 * self._img_arena[0] if self._img_arena is not None else end)
-            torch.cuda.current_stream().synchronize()       # nothing may still read the old arena
-            if self._img_arena is not None:
-                self._images_graphs.pop(self._img_arena[2].data_ptr(), None)
-            self._img_arena = (cap, torch.empty(cap, dtype=torch.uint8).pin_memory(), torch.empty(cap, dtype=torch.uint8, device="cuda"), None)
-            self._img_np = self._img_arena[1].numpy()
-        cap, host, dev, ev = self._img_arena
-        if ev is not None:
-            ev.synchronize()                                  # the previous copy out of the pinned arena has been read
-        tab = self._img_np[:tb].view(ImageTable.DTYPE)
-        base = dev.data_ptr()
+        r = self._routes[ImageTable]
+        ar = r.arena
+        r.graphs.pop(ar.reserve(end), None)
+        tab = ar.np[:tb].view(ImageTable.DTYPE)
+        base = ar.dev.data_ptr()
         self._img_keep = [im for im in ims if im.is_cuda]     # device planes the step reads in place
         it = iter(offs)
         for i, im in enumerate(ims):
@@ -184,57 +200,60 @@ class BatchedVitTracker:
                 po = next(it)
                 rows = im.plane_rows()
                 for a, o, (n, rb) in zip(im.host_planes(), po, rows):
-                    self._img_np[o:o + n * rb].reshape(n, rb)[...] = np.asarray(a).reshape(n, rb)
+                    ar.np[o:o + n * rb].reshape(n, rb)[...] = np.asarray(a).reshape(n, rb)
                 d = im.descriptor([base + o for o in po], [rb for _, rb in rows])
-                ImageTable.check(d[6], d[0], d[1], d[4], d[5], d[2], d[3], 0, nbytes0=cap - po[0],
-                                 nbytes1=cap - po[1] if len(po) > 1 else None)
+                ImageTable.check(d[6], d[0], d[1], d[4], d[5], d[2], d[3], 0, nbytes0=ar.cap - po[0],
+                                 nbytes1=ar.cap - po[1] if len(po) > 1 else None)
             if im.is_cuda:
                 ImageTable.check(d[6], d[0], d[1], d[4], d[5], d[2], d[3])
             tab[i] = d
-        dev[:end].copy_(host[:end], non_blocking=True)
-        ev = torch.cuda.Event()
-        ev.record()
-        self._img_arena = (cap, host, dev, ev)
-        return dev[:tb]
+        return ar.flush(end)[:tb]
 
-    def _table_graph(self, graphs, step, tab):
-        """The whole step on a descriptor table (`step`: nat.track_step_frames or nat.track_step_images -> record), captured once per
-        table address in `graphs`: the table's contents change between replays, its address does not."""
+    def _route(self, frames, restart=False):
+        """Which source `frames` are, and the table or tensor for it: a list with at least one Image takes the image table
+        (ImageTable, device table), any other list of differing sizes the frame table (FrameTable, device table), everything else the
+        dense path (None, the (B,H,W,3) tensor).  restart: the frames of reinitialize(), one per restarted slot -- always a table, made
+        of device copies of their own (the arenas and the dense buffers belong to the running step)."""
         import torch
-        hit = graphs.get(tab.data_ptr())
-        if hit is not None:
-            return hit
-        rec = torch.empty(self.B, 5, dtype=torch.float64, device="cuda")
-        host = torch.empty(self.B, 5, dtype=torch.float64).pin_memory()
-        g = torch.cuda.CUDAGraph()
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.graph(g, stream=side):
-            step(tab, self.states, self.params.search_factor, self.mean, self.std, self.x, self.rf, self.out,
-                 record=rec, margin=10, stream=torch.cuda.current_stream())
-        torch.cuda.current_stream().wait_stream(side)
-        graphs[tab.data_ptr()] = (g, rec, host, tab)
-        return graphs[tab.data_ptr()]
+        if self._has_image(frames):
+            if not restart:
+                return ImageTable, self._image_table(frames)
+            ims = []
+            for f in map(self._as_image, frames):
+                if not f.is_cuda:
+                    f = Image(f.format, [torch.from_numpy(np.ascontiguousarray(a)).cuda() for a in f.host_planes()], f.H, f.W,
+                              [rb for _, rb in f.plane_rows()])
+                ims.append(f)
+            return ImageTable, ImageTable.of(ims)
+        if restart:
+            return FrameTable, FrameTable.of([f if isinstance(f, torch.Tensor) and f.is_cuda else torch.from_numpy(np.ascontiguousarray(f)).cuda()
+                                              for f in frames])
+        if self._is_mixed(frames):
+            return FrameTable, self._frame_table(frames)
+        return None, self._upload(frames)
 
-    def _track_table(self, graphs, step, tab, sync):
-        """One replay of the step on a descriptor table (frame table or image table)."""
-        g, rec, host, _ = self._table_graph(graphs, step, tab)
+    def _track_table(self, route, tab, sync):
+        """One replay of the whole step on a descriptor table (route.step: nat.track_step_frames or nat.track_step_images -> record),
+        captured once per table address in route.graphs: the table's contents change between replays, its address does not."""
+        import torch
+        hit = route.graphs.get(tab.data_ptr())
+        if hit is None:
+            rec = torch.empty(self.B, 5, dtype=torch.float64, device="cuda")
+            host = torch.empty(self.B, 5, dtype=torch.float64).pin_memory()
+            g = torch.cuda.CUDAGraph()
+            side = torch.cuda.Stream()
+            side.wait_stream(torch.cuda.current_stream())
+            with torch.cuda.graph(g, stream=side):
+                route.step(tab, self.states, self.params.search_factor, self.mean, self.std, self.x, self.rf, self.out,
+                           record=rec, margin=10, stream=torch.cuda.current_stream())
+            torch.cuda.current_stream().wait_stream(side)
+            hit = route.graphs[tab.data_ptr()] = (g, rec, host, tab)
+        g, rec, host, _ = hit
         g.replay()
         self.frame_id += 1
         if sync:
-            r = self._records(rec, host)
-            return {"target_bbox": r[:, :4], "confidence": r[:, 4].float()}
+            return self._result(self._records(rec, host))
         return {"target_bbox": self.states, "confidence": self.out.conf, "record": rec}
-
-    def _track_images(self, frames, sync):
-        if self.graph is None:
-            raise VtError("track before initialize")
-        return self._track_table(self._images_graphs, self.nat.track_step_images, self._image_table(frames), sync)
-
-    def _track_mixed(self, frames, sync):
-        if self.graph is None:
-            raise VtError("track before initialize")
-        return self._track_table(self._frames_graphs, self.nat.track_step_frames, self._frame_table(frames), sync)
 
     def reinitialize(self, slots, frames, boxes):
         """Restart the sequences of `slots` on new frames and boxes (Vit_dist.initialize, lib/test/tracker/vit_dist.py:52-65) while
@@ -259,19 +278,8 @@ class BatchedVitTracker:
         st = torch.as_tensor(boxes).cuda()
         z = torch.empty(n, 3, self.params.template_size, self.params.template_size, device="cuda")
         rf = torch.empty(n, dtype=torch.float64, device="cuda")
-        if self._has_image(frames):       # Images (any format): their planes on the device, one vt_image table
-            ims = []
-            for f in map(self._as_image, frames):
-                if not f.is_cuda:
-                    f = Image(f.format, [torch.from_numpy(np.ascontiguousarray(a)).cuda() for a in f.host_planes()], f.H, f.W,
-                              [rb for _, rb in f.plane_rows()])
-                ims.append(f)
-            tab = ImageTable.of(ims)
-            self.nat.crop_images(tab, st, self.params.template_factor, self.params.template_size, self.mean, self.std, out=z, resize_factor=rf)
-        else:
-            dev = [f if isinstance(f, torch.Tensor) and f.is_cuda else torch.from_numpy(np.ascontiguousarray(f)).cuda() for f in frames]
-            tab = FrameTable.of(dev)
-            self.nat.crop_frames(tab, st, self.params.template_factor, self.params.template_size, self.mean, self.std, out=z, resize_factor=rf)
+        kind, tab = self._route(frames, restart=True)
+        self.nat._crop(kind, tab, st, self.params.template_factor, self.params.template_size, (self.mean, self.std), z, rf, None)
         idx = torch.as_tensor(slots, device="cuda")
         self.states.index_copy_(0, idx, st)
         self.z.index_copy_(0, idx, z)
@@ -338,9 +346,7 @@ class BatchedVitTracker:
         may be a native.Image (any layout of include/vittrack.h: NV12 / NV21, P010, I420, YUYV, GRAY8, BGR, RGBA / BGRA, RGB);
         init_boxes: (B,4) [x,y,w,h]."""
         import torch
-        images = self._has_image(frames)
-        mixed = not images and self._is_mixed(frames)
-        fr = self._image_table(frames) if images else (self._frame_table(frames) if mixed else self._upload(frames))
+        kind, fr = self._route(frames)
         boxes = np.asarray(init_boxes, dtype=np.float64)
         if boxes.shape != (self.B, 4):
             raise ValueError(f"init_boxes must be (B={self.B}, 4) [x, y, w, h]")
@@ -349,15 +355,8 @@ class BatchedVitTracker:
             if not np.all(side >= 1):         # also catches NaN / negative sizes
                 raise Exception("Too small bounding box.")   # processing_utils.py:33-34
         self.states.copy_(torch.as_tensor(boxes))
-        if images:
-            self.nat.crop_images(fr, self.states, self.params.template_factor, self.params.template_size, self.mean, self.std,
-                                 out=self.z, resize_factor=self.rf)
-        elif mixed:
-            self.nat.crop_frames(fr, self.states, self.params.template_factor, self.params.template_size, self.mean, self.std,
-                                 out=self.z, resize_factor=self.rf)
-        else:
-            self.nat.crop(fr, self.states, self.params.template_factor, self.params.template_size, self.mean, self.std,
-                          out=self.z, resize_factor=self.rf)
+        self.nat._crop(kind, fr, self.states, self.params.template_factor, self.params.template_size, (self.mean, self.std), self.z, self.rf, None)
+        if kind is None:
             self._mark_slot()
         # The template never changes after this (lib/test/tracker/vit_dist.py:57-60): its patch embedding and block 0's
         # LayerNorm-1 + qkv rows are computed once here (vt_set_template, bit-identical to recomputing them every frame);
@@ -375,8 +374,8 @@ class BatchedVitTracker:
         self._held = bool(on) or None
         self.nat.set_open_loop(bool(on))
         self._chunk_graphs.clear()      # the flag is an argument of the captured kernels
-        self._frames_graphs.clear()
-        self._images_graphs.clear()
+        for route in self._routes.values():
+            route.graphs.clear()
         self._fast = [None, None]
 
     def track_record(self, frames):
@@ -410,11 +409,9 @@ class BatchedVitTracker:
         as CPU tensors when sync=True, else the device tensors (valid until the next call)."""
         if self.graph is None:
             raise VtError("track before initialize")
-        if self._has_image(frames):     # frames in other pixel formats: one step on an image table
-            return self._track_images(frames, sync)
-        if self._is_mixed(frames):      # B frames of different sizes: one step on a frame table
-            return self._track_mixed(frames, sync)
-        fr = self._upload(frames)
+        kind, fr = self._route(frames)
+        if kind is not None:            # frames of different sizes or in other pixel formats: one step on their descriptor table
+            return self._track_table(self._routes[kind], fr, sync)
         H, W = self.hw
         self.frame_id += 1
         if self.frames is not None and any(fr.data_ptr() == f.data_ptr() for f in self.frames):
@@ -428,8 +425,7 @@ class BatchedVitTracker:
                 self._fast[k] = (self._frames_np[k], g, rec.numpy())
                 self._fast_shape = tuple(self._frames_np[k].shape)
             if sync:
-                r = self._records(rec, host)
-                return {"target_bbox": r[0, :, :4], "confidence": r[0, :, 4].float()}
+                return self._result(self._records(rec, host)[0])
             return {"target_bbox": self.states, "confidence": self.out.conf}
         # a caller-owned device tensor (a new address every call would mean a new capture every call): eager launches, as ONE library
         # call (vt_track_step: crop -> network on the cached template with the state update on the head's decoding lane)
@@ -484,11 +480,8 @@ class BatchedVitTracker:
             # n steps of B frames of different sizes: n replays of the frame-table step, records gathered on the device, one sync
             recs = torch.empty(len(frames), self.B, 5, dtype=torch.float64, device="cuda")
             for j, f in enumerate(frames):
-                recs[j].copy_(self._track_mixed(f, sync=False)["record"])
-            if sync:
-                r = self._records(recs, torch.empty(recs.shape, dtype=torch.float64).pin_memory())
-                return {"target_bbox": r[:, :, :4], "confidence": r[:, :, 4].float()}
-            return {"target_bbox": recs[:, :, :4], "confidence": recs[:, :, 4]}
+                recs[j].copy_(self._track_table(self._routes[FrameTable], self._frame_table(f), sync=False)["record"])
+            return self._result(self._records(recs, torch.empty(recs.shape, dtype=torch.float64).pin_memory()) if sync else recs, sync)
         if isinstance(frames, torch.Tensor) and frames.is_cuda:
             buf = frames
             if buf.dtype != torch.uint8 or buf.dim() != 5 or buf.shape[1] != self.B or buf.shape[4] != 3 or not buf.is_contiguous():
@@ -507,10 +500,12 @@ class BatchedVitTracker:
         g, rec, host, _ = self._chunk_graph(buf, to_host=sync)
         g.replay()
         self.frame_id += n
-        if sync:
-            r = self._records(rec, host)
-            return {"target_bbox": r[:, :, :4], "confidence": r[:, :, 4].float()}
-        return {"target_bbox": rec[:, :, :4], "confidence": rec[:, :, 4]}
+        return self._result(self._records(rec, host) if sync else rec, sync)
+
+    @staticmethod
+    def _result(r, host: bool = True):
+        """Records (..., 5) [x, y, w, h, confidence] as the dict track() returns; host records give the confidence in float32."""
+        return {"target_bbox": r[..., :4], "confidence": r[..., 4].float() if host else r[..., 4]}
 
     @staticmethod
     def _records(rec, host):
@@ -571,6 +566,21 @@ class ShardedBatchedTracker:
         for st in self.streams:
             cur.wait_stream(st)
 
+    def _gather(self, res, sync, dim):
+        """The shards' results as one: per-shard lists of device tensors (sync=False), or host tensors concatenated along the batch
+        axis `dim` after one asynchronous copy per shard on its own stream."""
+        import torch
+        if not sync:
+            self._join()
+            return {"target_bbox": [r["target_bbox"] for r in res], "confidence": [r["confidence"] for r in res]}
+        host = []
+        for r, st in zip(res, self.streams):
+            with torch.cuda.stream(st):
+                host.append((r["target_bbox"].to("cpu", non_blocking=True), r["confidence"].to("cpu", non_blocking=True)))
+        for st in self.streams:
+            st.synchronize()
+        return {"target_bbox": torch.cat([h[0] for h in host], dim=dim), "confidence": torch.cat([h[1] for h in host], dim=dim).float()}
+
     def initialize(self, frames, init_boxes):
         boxes = np.asarray(init_boxes, dtype=np.float64)
         self._each(lambda t, sl: t.initialize(frames[sl], boxes[sl]))
@@ -584,19 +594,9 @@ class ShardedBatchedTracker:
     def track(self, frames, sync: bool = True):
         """One frame for every sequence: frames (B,H,W,3) uint8, host or device.  sync=True: {'target_bbox': (B,4) float64,
         'confidence': (B,)} on the host; sync=False: the same keys as LISTS of per-shard device tensors (valid until the next call)."""
-        import torch
         res = self._each(lambda t, sl: t.track(frames[sl], sync=False))
         self.frame_id += 1
-        if not sync:
-            self._join()
-            return {"target_bbox": [r["target_bbox"] for r in res], "confidence": [r["confidence"] for r in res]}
-        host = []
-        for r, st in zip(res, self.streams):
-            with torch.cuda.stream(st):
-                host.append((r["target_bbox"].to("cpu", non_blocking=True), r["confidence"].to("cpu", non_blocking=True)))
-        for st in self.streams:
-            st.synchronize()
-        return {"target_bbox": torch.cat([h[0] for h in host]), "confidence": torch.cat([h[1] for h in host]).float()}
+        return self._gather(res, sync, 0)
 
     def track_chunk(self, frames, sync: bool = True):
         """n frames per launch and shard: frames (n,B,H,W,3) uint8 host data, or a list of per-shard contiguous CUDA tensors
@@ -611,13 +611,4 @@ class ShardedBatchedTracker:
         idx = {id(t): k for k, t in enumerate(self.trackers)}
         res = self._each(lambda t, sl: t.track_chunk(parts[idx[id(t)]], sync=False))
         self.frame_id += int(parts[0].shape[0])
-        if not sync:
-            self._join()
-            return {"target_bbox": [r["target_bbox"] for r in res], "confidence": [r["confidence"] for r in res]}
-        host = []
-        for r, st in zip(res, self.streams):
-            with torch.cuda.stream(st):
-                host.append((r["target_bbox"].to("cpu", non_blocking=True), r["confidence"].to("cpu", non_blocking=True)))
-        for st in self.streams:
-            st.synchronize()
-        return {"target_bbox": torch.cat([h[0] for h in host], dim=1), "confidence": torch.cat([h[1] for h in host], dim=1).float()}
+        return self._gather(res, sync, 1)

@@ -6,6 +6,7 @@ fails, an exception is raised (``VtError``).
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import os
 import weakref
@@ -18,17 +19,6 @@ LIB_PATH = os.environ.get("VITTRACK_LIB") or os.path.join(_HERE, "csrc", "libvit
 #: the same sources built with every vit_48 contraction on f16 MFMA (BASELINE config 5; make -C csrc all)
 LIB_PATH_F16 = os.path.join(_HERE, "csrc", "libvittrack_hip_f16.so")
 PRECISIONS = ("f32", "f16")
-
-#: every symbol include/vittrack.h declares (tests check the library exports all of them)
-SYMBOLS = [
-    "vt_last_error", "vt_version", "vt_create", "vt_destroy", "vt_load_weights", "vt_set_window",
-    "vt_forward", "vt_stem", "vt_blocks", "vt_head", "vt_cal_bbox", "vt_graph_capture",
-    "vt_graph_launch", "vt_graph_destroy", "vt_query", "vt_selftest_mfma", "vt_probe_clock", "vt_debug_stamps", "vt_crop", "vt_update_state",
-    "vt_set_template", "vt_graph_capture_steps", "vt_update_state_record", "vt_track_step", "vt_set_form_batch",
-    "vt_crop_u8", "vt_set_normalization", "vt_forward_u8", "vt_stem_u8", "vt_patch_u8_supported", "vt_crop_form", "vt_set_open_loop",
-    "vt_crop_frames", "vt_crop_u8_frames", "vt_track_step_frames", "vt_set_template_slots",
-    "vt_crop_images", "vt_crop_u8_images", "vt_track_step_images",
-]
 
 
 class VtError(RuntimeError):
@@ -47,6 +37,49 @@ class VtTensor(C.Structure):
 class VtOutputs(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("score_map", "size_map", "offset_map", "pred_boxes", "hann_boxes", "conf")]
 
+
+_vp, _i32, _f3p, _outp = C.c_void_p, C.c_int32, C.POINTER(C.c_float), C.POINTER(VtOutputs)
+#: the C ABI of include/vittrack.h: name -> (restype, argtypes).  lib() applies it to each library, so a symbol cannot be exported
+#: without its argument types (ctypes passes an undeclared argument as a C int: a 64-bit device pointer would be truncated)
+ABI = {
+    "vt_last_error": (C.c_char_p, []),
+    "vt_version": (C.c_char_p, []),
+    "vt_create": (C.c_int, [C.POINTER(VtConfig), C.POINTER(_vp)]),
+    "vt_destroy": (None, [_vp]),
+    "vt_load_weights": (C.c_int, [_vp, C.POINTER(VtTensor), _i32]),
+    "vt_set_window": (C.c_int, [_vp, _vp]),
+    "vt_forward": (C.c_int, [_vp, _vp, _vp, _i32, _vp, _outp]),
+    "vt_stem": (C.c_int, [_vp, _vp, _vp, _i32, _vp, _vp]),
+    "vt_blocks": (C.c_int, [_vp, _vp, _i32, _i32, _vp, _vp, _vp]),
+    "vt_head": (C.c_int, [_vp, _vp, _i32, _vp, _outp]),
+    "vt_cal_bbox": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp]),
+    "vt_graph_capture": (C.c_int, [_vp, _vp, _vp, _i32, _outp, C.POINTER(_vp)]),
+    "vt_graph_capture_steps": (C.c_int, [_vp, _i32, C.POINTER(_vp), C.POINTER(_vp), _i32, _outp, C.POINTER(_vp)]),
+    "vt_graph_launch": (C.c_int, [_vp, _vp]),
+    "vt_graph_destroy": (None, [_vp]),
+    "vt_query": (C.c_int, [_vp] + [C.POINTER(_i32)] * 4),
+    "vt_selftest_mfma": (C.c_int, [_vp]),
+    "vt_probe_clock": (C.c_int, [_i32, _i32] + [C.POINTER(C.c_double)] * 3),
+    "vt_debug_stamps": (C.c_int, [_vp, _i32, _vp]),
+    "vt_update_state": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp]),
+    "vt_update_state_record": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp]),
+    "vt_set_template": (C.c_int, [_vp, _vp, _i32, _vp]),
+    "vt_set_template_slots": (C.c_int, [_vp, _vp, C.POINTER(_i32), _i32, _vp]),
+    "vt_set_form_batch": (C.c_int, [_vp, _i32]),
+    "vt_set_normalization": (C.c_int, [_vp, _f3p, _f3p]),
+    "vt_set_open_loop": (C.c_int, [_vp, _i32]),
+    "vt_forward_u8": (C.c_int, [_vp, _vp, _vp, _i32, _vp, _outp]),
+    "vt_stem_u8": (C.c_int, [_vp, _vp, _i32, _vp, _vp]),
+    "vt_patch_u8_supported": (C.c_int, [_vp, _i32]),
+    "vt_crop_form": (C.c_int, []),
+}
+# the three frame sources of the crops and of the step: a dense (B,H,W,3) batch (frames, H, W), a vt_frame table, a vt_image table
+for _sfx, _src in (("", [_vp, _i32, _i32]), ("_frames", [_vp]), ("_images", [_vp])):
+    ABI["vt_crop" + _sfx] = (C.c_int, [_vp] + _src + [_vp, C.c_double, _i32, _f3p, _f3p, _i32, _vp, _vp, _vp])
+    ABI["vt_crop_u8" + _sfx] = (C.c_int, [_vp] + _src + [_vp, C.c_double, _i32, _i32, _vp, _vp, _vp])
+    ABI["vt_track_step" + _sfx] = (C.c_int, [_vp] + _src + [_vp, C.c_double, _f3p, _f3p, _i32, _vp, _vp, _vp, _vp, _i32, _vp])
+#: every symbol include/vittrack.h declares (tests check the library exports all of them)
+SYMBOLS = list(ABI)
 
 _lib = None          # the fp32 library (kept as a module attribute: __graft_entry__.build() resets it)
 _libs = {}
@@ -70,48 +103,9 @@ def lib(precision: str = "f32"):
     # (seen when a process created a Model before it had ever imported torch).
     import torch  # noqa: F401
     L = C.CDLL(path)
-    vp, i32 = C.c_void_p, C.c_int32
-    L.vt_last_error.restype = C.c_char_p
-    L.vt_version.restype = C.c_char_p
-    L.vt_create.argtypes = [C.POINTER(VtConfig), C.POINTER(vp)]
-    L.vt_destroy.argtypes = [vp]
-    L.vt_destroy.restype = None
-    L.vt_load_weights.argtypes = [vp, C.POINTER(VtTensor), i32]
-    L.vt_set_window.argtypes = [vp, vp]
-    L.vt_forward.argtypes = [vp, vp, vp, i32, vp, C.POINTER(VtOutputs)]
-    L.vt_stem.argtypes = [vp, vp, vp, i32, vp, vp]
-    L.vt_blocks.argtypes = [vp, vp, i32, i32, vp, vp, vp]
-    L.vt_head.argtypes = [vp, vp, i32, vp, C.POINTER(VtOutputs)]
-    L.vt_cal_bbox.argtypes = [vp, vp, vp, vp, i32, vp, vp, vp]
-    L.vt_graph_capture.argtypes = [vp, vp, vp, i32, C.POINTER(VtOutputs), C.POINTER(vp)]
-    L.vt_graph_capture_steps.argtypes = [vp, i32, C.POINTER(vp), C.POINTER(vp), i32, C.POINTER(VtOutputs), C.POINTER(vp)]
-    L.vt_graph_launch.argtypes = [vp, vp]
-    L.vt_graph_destroy.argtypes = [vp]
-    L.vt_graph_destroy.restype = None
-    L.vt_query.argtypes = [vp] + [C.POINTER(i32)] * 4
-    L.vt_selftest_mfma.argtypes = [vp]
-    L.vt_probe_clock.argtypes = [i32, i32] + [C.POINTER(C.c_double)] * 3
-    L.vt_debug_stamps.argtypes = [vp, i32, vp]
-    L.vt_crop.argtypes = [vp, vp, i32, i32, vp, C.c_double, i32, C.POINTER(C.c_float), C.POINTER(C.c_float), i32, vp, vp, vp]
-    L.vt_update_state.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, vp, vp]
-    L.vt_update_state_record.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp]
-    L.vt_set_template.argtypes = [vp, vp, i32, vp]
-    L.vt_set_form_batch.argtypes = [vp, i32]
-    L.vt_track_step.argtypes = [vp, vp, i32, i32, vp, C.c_double, C.POINTER(C.c_float), C.POINTER(C.c_float), i32, vp, vp, vp, vp, i32, vp]
-    L.vt_crop_u8.argtypes = [vp, vp, i32, i32, vp, C.c_double, i32, i32, vp, vp, vp]
-    L.vt_set_normalization.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_float)]
-    L.vt_forward_u8.argtypes = [vp, vp, vp, i32, vp, C.POINTER(VtOutputs)]
-    L.vt_stem_u8.argtypes = [vp, vp, i32, vp, vp]
-    L.vt_patch_u8_supported.argtypes = [vp, i32]
-    L.vt_crop_form.argtypes = []
-    L.vt_set_open_loop.argtypes = [vp, i32]
-    L.vt_crop_frames.argtypes = [vp, vp, vp, C.c_double, i32, C.POINTER(C.c_float), C.POINTER(C.c_float), i32, vp, vp, vp]
-    L.vt_crop_u8_frames.argtypes = [vp, vp, vp, C.c_double, i32, i32, vp, vp, vp]
-    L.vt_track_step_frames.argtypes = [vp, vp, vp, C.c_double, C.POINTER(C.c_float), C.POINTER(C.c_float), i32, vp, vp, vp, vp, i32, vp]
-    L.vt_set_template_slots.argtypes = [vp, vp, C.POINTER(i32), i32, vp]
-    L.vt_crop_images.argtypes = [vp, vp, vp, C.c_double, i32, C.POINTER(C.c_float), C.POINTER(C.c_float), i32, vp, vp, vp]
-    L.vt_crop_u8_images.argtypes = [vp, vp, vp, C.c_double, i32, i32, vp, vp, vp]
-    L.vt_track_step_images.argtypes = [vp, vp, vp, C.c_double, C.POINTER(C.c_float), C.POINTER(C.c_float), i32, vp, vp, vp, vp, i32, vp]
+    for name, (restype, argtypes) in ABI.items():
+        fn = getattr(L, name)
+        fn.restype, fn.argtypes = restype, argtypes
     if precision == "f32":
         _lib = L
     else:
@@ -135,6 +129,11 @@ def _ptr(t):
     return C.c_void_p(t.data_ptr())
 
 
+def _f3(v):
+    """The three floats of a per-channel mean or std, as the C ABI takes them."""
+    return (C.c_float * 3)(*[float(x) for x in v])
+
+
 def _stream(stream):
     import torch
     s = stream if stream is not None else torch.cuda.current_stream()
@@ -148,36 +147,90 @@ assert FRAME_DTYPE.itemsize == 24
 ARENA_ALIGN = 256
 
 
+def pack_planes(sizes, start: int = 0, align: int = ARENA_ALIGN):
+    """Byte offsets of items packed one after the other from `start`, every plane of every item at a multiple of `align`.  sizes: per
+    item the byte counts of its planes.  Returns ([per item: [plane offsets]], end)."""
+    out, o = [], int(start)
+    for planes in sizes:
+        offs = []
+        for n in planes:
+            o = -(-o // align) * align
+            offs.append(o)
+            o += int(n)
+        out.append(offs)
+    return out, o
+
+
 def pack_offsets(shapes, start: int = 0, align: int = ARENA_ALIGN):
     """Byte offsets of HWC uint8 frames of the given (H, W) shapes packed one after the other from `start`, each at a multiple of
     `align`, rows at pitch 3 W.  Returns (offsets, end)."""
-    offs, o = [], int(start)
-    for H, W in shapes:
-        o = -(-o // align) * align
-        offs.append(o)
-        o += int(H) * int(W) * 3
-    return offs, o
+    offs, end = pack_planes([[int(H) * int(W) * 3] for H, W in shapes], start, align)
+    return [o[0] for o in offs], end
 
 
-class FrameTable:
-    """The (B,) vt_frame descriptor table of vt_crop_frames / vt_track_step_frames (include/vittrack.h): one frame per sequence,
-    each with its own address, H, W and row pitch.  `host` is the numpy view of the descriptors; `dev`, when the table was made for
-    a device, is the (B * 24,) uint8 device tensor the kernels read (upload() copies host -> dev).  Every entry is checked on the
-    host before anything runs: HWC uint8 rows of 3 W contiguous bytes, pitch >= 3 W, a 4-byte-aligned address, and (buffers) the
-    frame inside its buffer."""
-
-    DTYPE = FRAME_DTYPE
-    ITEM = FRAME_DTYPE.itemsize
+class _DescriptorTable:
+    """A (B,) table of the descriptors of one frame per sequence (include/vittrack.h).  `host` is the numpy view of the descriptors
+    (pinned when the table was made for a device); `dev` is the (B * ITEM,) uint8 device tensor the kernels read (upload() copies host
+    -> dev); `keep` holds what the descriptors point into.  Subclasses give DTYPE and ITEM, KIND (the suffix of their entry points:
+    vt_crop_<KIND>), WHAT (their name in ptr()'s message), the host-side check of one descriptor, and `_put`, the entry of one frame
+    object."""
 
     def __init__(self, B: int, device=None):
         import torch
         self.B = int(B)
         pin = device is not None and torch.cuda.is_available()
-        self._host_t = torch.zeros(self.B * FRAME_DTYPE.itemsize, dtype=torch.uint8, pin_memory=pin)
-        self.host = self._host_t.numpy().view(FRAME_DTYPE)
-        self.dev = None if device is None else torch.zeros(self.B * FRAME_DTYPE.itemsize, dtype=torch.uint8, device=device)
+        self._host_t = torch.zeros(self.B * self.ITEM, dtype=torch.uint8, pin_memory=pin)
+        self.host = self._host_t.numpy().view(self.DTYPE)
+        self.dev = None if device is None else torch.zeros(self.B * self.ITEM, dtype=torch.uint8, device=device)
         self.keep = [None] * self.B          # tensors the descriptors point into (kept alive with the table)
-        self._copied = None                  # event of the last upload from the pinned host copy: set() waits for it
+        self._copied = None                  # event of the last upload from the pinned host copy: _write() waits for it
+
+    def _write(self, i: int, desc: tuple, keep):
+        if self._copied is not None:         # the queued upload has not necessarily read the host copy yet
+            self._copied.synchronize()
+            self._copied = None
+        self.host[i] = desc
+        self.keep[i] = keep
+
+    @classmethod
+    def of(cls, items, device="cuda", stream=None):
+        """A table of a list of frame objects on the GPU or in pinned memory (what `_put` takes), uploaded."""
+        t = cls(len(items), device)
+        for i, f in enumerate(items):
+            t._put(i, f)
+        t.upload(stream)
+        return t
+
+    def upload(self, stream=None):
+        import torch
+        if self.dev is None:
+            raise VtError(f"this {type(self).__name__} has no device copy")
+        with torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext():
+            self.dev.copy_(self._host_t, non_blocking=self._host_t.is_pinned())
+            if self._host_t.is_pinned():
+                self._copied = torch.cuda.Event()
+                self._copied.record()
+        return self.dev
+
+    @classmethod
+    def ptr(cls, table, B):
+        """Device address of a (B,) table of this class: an instance (its device copy) or a uint8 tensor of B * ITEM bytes."""
+        import torch
+        t = table.dev if isinstance(table, cls) else table
+        if not (isinstance(t, torch.Tensor) and (t.is_cuda or t.is_pinned()) and t.numel() * t.element_size() >= B * cls.ITEM
+                and t.is_contiguous()):
+            raise VtError(f"{cls.WHAT} with a device copy or a contiguous tensor of {B} x {cls.ITEM} bytes on the GPU")
+        return C.c_void_p(t.data_ptr())
+
+
+class FrameTable(_DescriptorTable):
+    """The (B,) vt_frame descriptor table of vt_crop_frames / vt_track_step_frames (include/vittrack.h): one frame per sequence,
+    each with its own address, H, W and row pitch.  Every entry is checked on the host before anything runs: HWC uint8 rows of 3 W
+    contiguous bytes, pitch >= 3 W, a 4-byte-aligned address, and (buffers) the frame inside its buffer."""
+
+    DTYPE = FRAME_DTYPE
+    ITEM = FRAME_DTYPE.itemsize
+    KIND, WHAT = "frames", "frame table must be a FrameTable"
 
     @staticmethod
     def check(ptr: int, H: int, W: int, pitch: int = 0, nbytes: int | None = None):
@@ -199,11 +252,7 @@ class FrameTable:
 
     def set(self, i: int, ptr: int, H: int, W: int, pitch: int = 0, nbytes: int | None = None, keep=None):
         pitch = self.check(ptr, H, W, pitch, nbytes)
-        if self._copied is not None:         # the queued upload has not necessarily read the host copy yet
-            self._copied.synchronize()
-            self._copied = None
-        self.host[i] = (int(ptr), int(H), int(W), pitch)
-        self.keep[i] = keep
+        self._write(i, (int(ptr), int(H), int(W), pitch), keep)
 
     def set_tensor(self, i: int, frame, device_only: bool = True):
         """Entry i from an (H, W, 3) uint8 tensor on the GPU or in pinned host memory: its rows may be strided (a crop of a larger
@@ -218,25 +267,7 @@ class FrameTable:
             raise VtError(f"frame strides {tuple(frame.stride())}: pixels must be 3 contiguous bytes, rows at least 3 W apart")
         self.set(i, frame.data_ptr(), H, W, frame.stride(0) if H > 1 else 3 * W, keep=frame)
 
-    @classmethod
-    def of(cls, frames, device="cuda", stream=None):
-        """A table of a list of (H, W, 3) uint8 tensors (GPU or pinned), uploaded."""
-        t = cls(len(frames), device)
-        for i, f in enumerate(frames):
-            t.set_tensor(i, f)
-        t.upload(stream)
-        return t
-
-    def upload(self, stream=None):
-        import torch
-        if self.dev is None:
-            raise VtError("this FrameTable has no device copy")
-        with torch.cuda.stream(stream) if stream is not None else _nullctx():
-            self.dev.copy_(self._host_t, non_blocking=self._host_t.is_pinned())
-            if self._host_t.is_pinned():
-                self._copied = torch.cuda.Event()
-                self._copied.record()
-        return self.dev
+    _put = set_tensor
 
     def shapes(self):
         return [(int(h), int(w)) for h, w in zip(self.host["H"], self.host["W"])]
@@ -541,33 +572,16 @@ class Image:
 def pack_image_offsets(images, start: int = 0, align: int = ARENA_ALIGN):
     """Byte offsets of the planes of host Images packed one after the other from `start` at tight pitches, every plane at a
     multiple of `align`.  Returns ([per image: [plane offsets]], end)."""
-    out, o = [], int(start)
-    for im in images:
-        offs = []
-        for rows, rb in im.plane_rows():
-            o = -(-o // align) * align
-            offs.append(o)
-            o += rows * rb
-        out.append(offs)
-    return out, o
+    return pack_planes([[rows * rb for rows, rb in im.plane_rows()] for im in images], start, align)
 
 
-class ImageTable:
-    """The (B,) vt_image descriptor table of vt_crop_images / vt_track_step_images (include/vittrack.h), the twin of FrameTable:
-    `host` is the numpy view, `dev` (when made for a device) the (B * 48,) uint8 device tensor the kernels read."""
+class ImageTable(_DescriptorTable):
+    """The (B,) vt_image descriptor table of vt_crop_images / vt_track_step_images (include/vittrack.h): one frame per sequence in
+    its own pixel format, size and plane pitches."""
 
     DTYPE = IMAGE_DTYPE
     ITEM = IMAGE_DTYPE.itemsize
-
-    def __init__(self, B: int, device=None):
-        import torch
-        self.B = int(B)
-        pin = device is not None and torch.cuda.is_available()
-        self._host_t = torch.zeros(self.B * self.ITEM, dtype=torch.uint8, pin_memory=pin)
-        self.host = self._host_t.numpy().view(IMAGE_DTYPE)
-        self.dev = None if device is None else torch.zeros(self.B * self.ITEM, dtype=torch.uint8, device=device)
-        self.keep = [None] * self.B
-        self._copied = None
+    KIND, WHAT = "images", "image table must be an ImageTable"
 
     @staticmethod
     def check(fmt: int, ptr0: int, ptr1: int, H: int, W: int, pitch0: int = 0, pitch1: int = 0, reserved: int = 0,
@@ -612,11 +626,7 @@ class ImageTable:
         p0, p1, q0, q1, H, W, fmt, res = (int(v) for v in desc)
         if check:
             q0, q1 = self.check(fmt, p0, p1, H, W, q0, q1, res)
-        if self._copied is not None:
-            self._copied.synchronize()
-            self._copied = None
-        self.host[i] = (p0, p1, q0, q1, H, W, fmt, res)
-        self.keep[i] = keep
+        self._write(i, (p0, p1, q0, q1, H, W, fmt, res), keep)
 
     def set_image(self, i: int, image: Image):
         """Entry i from an Image whose planes are on the GPU (read in place)."""
@@ -624,52 +634,11 @@ class ImageTable:
             raise VtError("ImageTable.set_image wants an Image whose planes are on the GPU")
         self.set(i, image.descriptor(), keep=image)
 
-    @classmethod
-    def of(cls, images, device="cuda", stream=None):
-        t = cls(len(images), device)
-        for i, im in enumerate(images):
-            t.set_image(i, im)
-        t.upload(stream)
-        return t
-
-    def upload(self, stream=None):
-        import torch
-        if self.dev is None:
-            raise VtError("this ImageTable has no device copy")
-        with torch.cuda.stream(stream) if stream is not None else _nullctx():
-            self.dev.copy_(self._host_t, non_blocking=self._host_t.is_pinned())
-            if self._host_t.is_pinned():
-                self._copied = torch.cuda.Event()
-                self._copied.record()
-        return self.dev
+    _put = set_image
 
 
-def _image_table_ptr(table, B):
-    """Device address of a (B,) vt_image table: an ImageTable (its device copy) or a uint8 CUDA tensor of B * 48 bytes."""
-    import torch
-    t = table.dev if isinstance(table, ImageTable) else table
-    if not (isinstance(t, torch.Tensor) and (t.is_cuda or t.is_pinned()) and t.numel() * t.element_size() >= B * IMAGE_DTYPE.itemsize
-            and t.is_contiguous()):
-        raise VtError(f"image table must be an ImageTable with a device copy or a contiguous tensor of {B} x 48 bytes on the GPU")
-    return C.c_void_p(t.data_ptr())
-
-
-class _nullctx:
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        return False
-
-
-def _table_ptr(table, B):
-    """Device address of a (B,) vt_frame table: a FrameTable (its device copy) or a uint8 CUDA tensor of B * 24 bytes."""
-    import torch
-    t = table.dev if isinstance(table, FrameTable) else table
-    if not (isinstance(t, torch.Tensor) and (t.is_cuda or t.is_pinned()) and t.numel() * t.element_size() >= B * FRAME_DTYPE.itemsize
-            and t.is_contiguous()):
-        raise VtError(f"frame table must be a FrameTable with a device copy or a contiguous tensor of {B} x 24 bytes on the GPU")
-    return C.c_void_p(t.data_ptr())
+# the device-pointer check under its two earlier names (tests/test_gpu_patch_u8.py calls the C ABI with them)
+_table_ptr, _image_table_ptr = FrameTable.ptr, ImageTable.ptr
 
 
 def crop_form() -> int:
@@ -927,60 +896,22 @@ class Model:
         _check(self._L.vt_head(self._h, _ptr(feat), B, _stream(stream), C.byref(st)), "vt_head", self._L)
         return out
 
-    # ---- pre / post steps of track() on the device
-    def crop(self, frames, states, factor, out_size, mean, std, out=None, resize_factor=None, stream=None):
-        """frames (B,H,W,3) uint8 cuda -- or PINNED host memory, which the kernel reads over the bus (a few sequences: no upload) --,
-        states (B,4) float64 cuda -> (crops (B,3,T,T) fp32, resize_factor (B) fp64)."""
+    # ---- pre / post steps of track() on the device, from each of the three frame sources: a dense (B,H,W,3) batch, a frame table
+    # (one frame of its own size per sequence, vt_*_frames), an image table (its own pixel format as well, vt_*_images)
+    def _source(self, kind, src, B):
+        """Entry-point suffix and leading arguments of a frame source for B sequences.  kind None: `src` is a dense (B,H,W,3) uint8
+        tensor; kind FrameTable / ImageTable: a table of that class or a uint8 tensor holding its descriptors."""
+        if kind is not None:
+            return "_" + kind.KIND, (kind.ptr(src, B),)
         import torch
-        if not ((frames.is_cuda or frames.is_pinned()) and frames.dtype == torch.uint8 and frames.is_contiguous() and frames.dim() == 4
-                and frames.shape[3] == 3):
+        if not ((src.is_cuda or src.is_pinned()) and src.dtype == torch.uint8 and src.is_contiguous() and src.dim() == 4
+                and src.shape[3] == 3):
             raise VtError("frames must be a contiguous (B,H,W,3) uint8 tensor on the GPU (or in pinned host memory)")
-        if not (states.is_cuda and states.dtype == torch.float64 and states.is_contiguous()):
-            raise VtError("states must be a contiguous (B,4) float64 tensor on the GPU")
-        B, H, W, _ = frames.shape
-        if tuple(states.shape) != (B, 4):
-            raise VtError(f"states must be ({B},4) for {B} frames, got {tuple(states.shape)}")
-        if out is None:
-            out = torch.empty(B, 3, out_size, out_size, device=states.device)
-        elif tuple(out.shape) != (B, 3, out_size, out_size):
-            raise VtError(f"crop output must be ({B},3,{out_size},{out_size}), got {tuple(out.shape)}")
-        if resize_factor is None:
-            resize_factor = torch.empty(B, dtype=torch.float64, device=states.device)
-        elif tuple(resize_factor.shape) != (B,) or resize_factor.dtype != torch.float64 or not resize_factor.is_cuda:
-            raise VtError(f"resize_factor must be a ({B},) float64 tensor on the GPU")
-        m3 = (C.c_float * 3)(*[float(v) for v in mean])
-        s3 = (C.c_float * 3)(*[float(v) for v in std])
-        _check(self._L.vt_crop(self._h, C.c_void_p(frames.data_ptr()), H, W, C.c_void_p(states.data_ptr()), float(factor),
-                             out_size, m3, s3, B, _stream(stream), _ptr(out), C.c_void_p(resize_factor.data_ptr())),
-               "vt_crop", self._L)
-        return out, resize_factor
+        b, H, W, _ = src.shape
+        if b != B:
+            raise VtError(f"states must be ({b},4) for {b} frames (and so the step's crop workspace), got a batch of {B}")
+        return "", (C.c_void_p(src.data_ptr()), H, W)
 
-    # ---- the uint8 patch path (round 6): sample_target's output goes to the stem as it is
-    def crop_u8(self, frames, states, factor, out_size, out=None, resize_factor=None, stream=None):
-        """sample_target alone: frames (B,H,W,3) uint8 (GPU or pinned), states (B,4) float64 cuda -> (patch (B,T,T,3) uint8 --
-        the array the reference's sample_target returns --, resize_factor (B) fp64)."""
-        import torch
-        if not ((frames.is_cuda or frames.is_pinned()) and frames.dtype == torch.uint8 and frames.is_contiguous() and frames.dim() == 4
-                and frames.shape[3] == 3):
-            raise VtError("frames must be a contiguous (B,H,W,3) uint8 tensor on the GPU (or in pinned host memory)")
-        if not (states.is_cuda and states.dtype == torch.float64 and states.is_contiguous()):
-            raise VtError("states must be a contiguous (B,4) float64 tensor on the GPU")
-        B, H, W, _ = frames.shape
-        if tuple(states.shape) != (B, 4):
-            raise VtError(f"states must be ({B},4) for {B} frames, got {tuple(states.shape)}")
-        if out is None:
-            out = torch.empty(B, out_size, out_size, 3, dtype=torch.uint8, device=states.device)
-        elif tuple(out.shape) != (B, out_size, out_size, 3) or out.dtype != torch.uint8 or not out.is_cuda or not out.is_contiguous():
-            raise VtError(f"patch output must be a contiguous ({B},{out_size},{out_size},3) uint8 tensor on the GPU")
-        if resize_factor is None:
-            resize_factor = torch.empty(B, dtype=torch.float64, device=states.device)
-        elif tuple(resize_factor.shape) != (B,) or resize_factor.dtype != torch.float64 or not resize_factor.is_cuda:
-            raise VtError(f"resize_factor must be a ({B},) float64 tensor on the GPU")
-        _check(self._L.vt_crop_u8(self._h, C.c_void_p(frames.data_ptr()), H, W, C.c_void_p(states.data_ptr()), float(factor), out_size, B,
-                                _stream(stream), C.c_void_p(out.data_ptr()), C.c_void_p(resize_factor.data_ptr())), "vt_crop_u8", self._L)
-        return out, resize_factor
-
-    # ---- frame tables: one frame of its own size per sequence (vt_crop_frames & co.)
     def _table_args(self, states, out_shape, out_dtype, out, resize_factor):
         import torch
         if not (states.is_cuda and states.dtype == torch.float64 and states.is_contiguous() and states.dim() == 2 and states.shape[1] == 4):
@@ -996,82 +927,77 @@ class Model:
             raise VtError(f"resize_factor must be a ({B},) float64 tensor on the GPU")
         return B, out, resize_factor
 
+    def _crop(self, kind, src, states, factor, out_size, norm, out, resize_factor, stream):
+        """vt_crop* (norm = (mean, std): the normalised fp32 crop) or vt_crop_u8* (norm = (): sample_target's uint8 patch) of a source."""
+        import torch
+        shape, dtype = ((3, out_size, out_size), torch.float32) if norm else ((out_size, out_size, 3), torch.uint8)
+        B, out, resize_factor = self._table_args(states, shape, dtype, out, resize_factor)
+        sfx, lead = self._source(kind, src, B)
+        name = ("vt_crop" if norm else "vt_crop_u8") + sfx
+        _check(getattr(self._L, name)(self._h, *lead, C.c_void_p(states.data_ptr()), float(factor), out_size, *map(_f3, norm), B,
+                                      _stream(stream), C.c_void_p(out.data_ptr()), C.c_void_p(resize_factor.data_ptr())), name, self._L)
+        return out, resize_factor
+
+    def crop(self, frames, states, factor, out_size, mean, std, out=None, resize_factor=None, stream=None):
+        """frames (B,H,W,3) uint8 cuda -- or PINNED host memory, which the kernel reads over the bus (a few sequences: no upload) --,
+        states (B,4) float64 cuda -> (crops (B,3,T,T) fp32, resize_factor (B) fp64)."""
+        return self._crop(None, frames, states, factor, out_size, (mean, std), out, resize_factor, stream)
+
+    def crop_u8(self, frames, states, factor, out_size, out=None, resize_factor=None, stream=None):
+        """sample_target alone (the uint8 patch path: its output goes to the stem as it is): frames (B,H,W,3) uint8 (GPU or pinned),
+        states (B,4) float64 cuda -> (patch (B,T,T,3) uint8 -- the array the reference's sample_target returns --, resize_factor (B)
+        fp64)."""
+        return self._crop(None, frames, states, factor, out_size, (), out, resize_factor, stream)
+
     def crop_frames(self, table, states, factor, out_size, mean, std, out=None, resize_factor=None, stream=None):
         """crop() with a frame table (FrameTable / vt_crop_frames): sequence b is cropped from its own frame."""
-        import torch
-        B, out, resize_factor = self._table_args(states, (3, out_size, out_size), torch.float32, out, resize_factor)
-        m3 = (C.c_float * 3)(*[float(v) for v in mean])
-        s3 = (C.c_float * 3)(*[float(v) for v in std])
-        _check(self._L.vt_crop_frames(self._h, _table_ptr(table, B), C.c_void_p(states.data_ptr()), float(factor), out_size, m3, s3, B,
-                                    _stream(stream), _ptr(out), C.c_void_p(resize_factor.data_ptr())), "vt_crop_frames", self._L)
-        return out, resize_factor
+        return self._crop(FrameTable, table, states, factor, out_size, (mean, std), out, resize_factor, stream)
 
     def crop_u8_frames(self, table, states, factor, out_size, out=None, resize_factor=None, stream=None):
         """crop_u8() with a frame table (vt_crop_u8_frames)."""
-        import torch
-        B, out, resize_factor = self._table_args(states, (out_size, out_size, 3), torch.uint8, out, resize_factor)
-        _check(self._L.vt_crop_u8_frames(self._h, _table_ptr(table, B), C.c_void_p(states.data_ptr()), float(factor), out_size, B,
-                                       _stream(stream), C.c_void_p(out.data_ptr()), C.c_void_p(resize_factor.data_ptr())),
-               "vt_crop_u8_frames", self._L)
-        return out, resize_factor
+        return self._crop(FrameTable, table, states, factor, out_size, (), out, resize_factor, stream)
 
-    def track_step_frames(self, table, states, factor, mean, std, x, resize_factor, out: Outputs, record=None, margin=10, stream=None):
-        """track_step() with a frame table (vt_track_step_frames): each sequence is cropped from, and clipped to, its own frame."""
-        import torch
-        B = self._check_x_only(x)
-        if (tuple(states.shape) != (B, 4) or states.dtype != torch.float64 or not states.is_cuda or not states.is_contiguous()
-                or tuple(resize_factor.shape) != (B,) or resize_factor.dtype != torch.float64 or not resize_factor.is_cuda):
-            raise VtError(f"track_step_frames wants states ({B},4) and resize_factor ({B},) float64 on the GPU")
-        if record is not None and (tuple(record.shape) != (B, 5) or record.dtype != torch.float64 or not record.is_contiguous()
-                                   or not (record.is_cuda or record.is_pinned())):
-            raise VtError(f"record must be a contiguous ({B},5) float64 tensor on the GPU or in pinned host memory")
-        self._check_out(out, B)
-        st = out.struct()
-        m3 = (C.c_float * 3)(*[float(v) for v in mean])
-        s3 = (C.c_float * 3)(*[float(v) for v in std])
-        _check(self._L.vt_track_step_frames(self._h, _table_ptr(table, B), C.c_void_p(states.data_ptr()), float(factor), m3, s3, B,
-                                          _stream(stream), _ptr(x), C.c_void_p(resize_factor.data_ptr()), C.byref(st), margin,
-                                          C.c_void_p(record.data_ptr()) if record is not None else None), "vt_track_step_frames", self._L)
-        return out
-
-    # ---- pixel formats: one vt_image per sequence (vt_crop_images & co.)
     def crop_images(self, table, states, factor, out_size, mean, std, out=None, resize_factor=None, stream=None):
         """crop_frames() on an image table (ImageTable / vt_crop_images): sequence b is cropped from rgb(images[b])."""
-        import torch
-        B, out, resize_factor = self._table_args(states, (3, out_size, out_size), torch.float32, out, resize_factor)
-        m3 = (C.c_float * 3)(*[float(v) for v in mean])
-        s3 = (C.c_float * 3)(*[float(v) for v in std])
-        _check(self._L.vt_crop_images(self._h, _image_table_ptr(table, B), C.c_void_p(states.data_ptr()), float(factor), out_size, m3, s3, B,
-                                    _stream(stream), _ptr(out), C.c_void_p(resize_factor.data_ptr())), "vt_crop_images", self._L)
-        return out, resize_factor
+        return self._crop(ImageTable, table, states, factor, out_size, (mean, std), out, resize_factor, stream)
 
     def crop_u8_images(self, table, states, factor, out_size, out=None, resize_factor=None, stream=None):
         """crop_u8_frames() on an image table (vt_crop_u8_images)."""
-        import torch
-        B, out, resize_factor = self._table_args(states, (out_size, out_size, 3), torch.uint8, out, resize_factor)
-        _check(self._L.vt_crop_u8_images(self._h, _image_table_ptr(table, B), C.c_void_p(states.data_ptr()), float(factor), out_size, B,
-                                       _stream(stream), C.c_void_p(out.data_ptr()), C.c_void_p(resize_factor.data_ptr())),
-               "vt_crop_u8_images", self._L)
-        return out, resize_factor
+        return self._crop(ImageTable, table, states, factor, out_size, (), out, resize_factor, stream)
 
-    def track_step_images(self, table, states, factor, mean, std, x, resize_factor, out: Outputs, record=None, margin=10, stream=None):
-        """track_step_frames() on an image table (vt_track_step_images)."""
+    def _step(self, kind, src, states, factor, mean, std, x, resize_factor, out, record, margin, stream):
+        """vt_track_step* on a source: the argument checks of the three public steps and the call."""
         import torch
         B = self._check_x_only(x)
+        sfx, lead = self._source(kind, src, B)
         if (tuple(states.shape) != (B, 4) or states.dtype != torch.float64 or not states.is_cuda or not states.is_contiguous()
                 or tuple(resize_factor.shape) != (B,) or resize_factor.dtype != torch.float64 or not resize_factor.is_cuda):
-            raise VtError(f"track_step_images wants states ({B},4) and resize_factor ({B},) float64 on the GPU")
+            raise VtError(f"track_step{sfx} wants states ({B},4) and resize_factor ({B},) float64 on the GPU")
         if record is not None and (tuple(record.shape) != (B, 5) or record.dtype != torch.float64 or not record.is_contiguous()
                                    or not (record.is_cuda or record.is_pinned())):
             raise VtError(f"record must be a contiguous ({B},5) float64 tensor on the GPU or in pinned host memory")
         self._check_out(out, B)
         st = out.struct()
-        m3 = (C.c_float * 3)(*[float(v) for v in mean])
-        s3 = (C.c_float * 3)(*[float(v) for v in std])
-        _check(self._L.vt_track_step_images(self._h, _image_table_ptr(table, B), C.c_void_p(states.data_ptr()), float(factor), m3, s3, B,
-                                          _stream(stream), _ptr(x), C.c_void_p(resize_factor.data_ptr()), C.byref(st), margin,
-                                          C.c_void_p(record.data_ptr()) if record is not None else None), "vt_track_step_images", self._L)
+        name = "vt_track_step" + sfx
+        _check(getattr(self._L, name)(self._h, *lead, C.c_void_p(states.data_ptr()), float(factor), _f3(mean), _f3(std), B,
+                                      _stream(stream), _ptr(x), C.c_void_p(resize_factor.data_ptr()), C.byref(st), margin,
+                                      C.c_void_p(record.data_ptr()) if record is not None else None), name, self._L)
         return out
+
+    def track_step(self, frames, states, factor, mean, std, x, resize_factor, out: Outputs, record=None, margin=10, stream=None):
+        """crop -> network on the cached template -> map back / clip / state update (-> record) as ONE library call (vt_track_step):
+        the same kernels as crop() + forward(None, x) + update_state_record(), with the tail fused into the decode kernel on the
+        small-batch path.  frames (B,H,W,3) uint8 on the GPU or pinned; x: the (B,3,S,S) crop workspace; states (B,4) / resize_factor
+        (B,) float64 on the GPU; record: optional (B,5) float64, GPU or pinned."""
+        return self._step(None, frames, states, factor, mean, std, x, resize_factor, out, record, margin, stream)
+
+    def track_step_frames(self, table, states, factor, mean, std, x, resize_factor, out: Outputs, record=None, margin=10, stream=None):
+        """track_step() with a frame table (vt_track_step_frames): each sequence is cropped from, and clipped to, its own frame."""
+        return self._step(FrameTable, table, states, factor, mean, std, x, resize_factor, out, record, margin, stream)
+
+    def track_step_images(self, table, states, factor, mean, std, x, resize_factor, out: Outputs, record=None, margin=10, stream=None):
+        """track_step_frames() on an image table (vt_track_step_images)."""
+        return self._step(ImageTable, table, states, factor, mean, std, x, resize_factor, out, record, margin, stream)
 
     def set_template_slots(self, z, slots, stream=None):
         """Rewrite the template cache of the given slots only (vt_set_template_slots): z (n,3,Tz,Tz) fp32 on the GPU, slots n
@@ -1085,9 +1011,7 @@ class Model:
 
     def set_normalization(self, mean, std):
         """Preprocessor's mean / std for the uint8 entry points (folded into the stem's first layer; default: ImageNet)."""
-        m3 = (C.c_float * 3)(*[float(v) for v in mean])
-        s3 = (C.c_float * 3)(*[float(v) for v in std])
-        _check(self._L.vt_set_normalization(self._h, m3, s3), "vt_set_normalization", self._L)
+        _check(self._L.vt_set_normalization(self._h, _f3(mean), _f3(std)), "vt_set_normalization", self._L)
 
     def set_open_loop(self, on: bool = True):
         """vt_set_open_loop: track_step (and graphs captured from now on) leave `states` untouched; the step's box is in `record`."""
@@ -1152,33 +1076,6 @@ class Model:
                                             H, W, margin, B, _stream(stream), C.c_void_p(states.data_ptr()),
                                             C.c_void_p(record.data_ptr())), "vt_update_state_record", self._L)
         return record
-
-    def track_step(self, frames, states, factor, mean, std, x, resize_factor, out: Outputs, record=None, margin=10, stream=None):
-        """crop -> network on the cached template -> map back / clip / state update (-> record) as ONE library call (vt_track_step):
-        the same kernels as crop() + forward(None, x) + update_state_record(), with the tail fused into the decode kernel on the
-        small-batch path.  frames (B,H,W,3) uint8 on the GPU or pinned; x: the (B,3,S,S) crop workspace; states (B,4) / resize_factor
-        (B,) float64 on the GPU; record: optional (B,5) float64, GPU or pinned."""
-        import torch
-        if not ((frames.is_cuda or frames.is_pinned()) and frames.dtype == torch.uint8 and frames.is_contiguous() and frames.dim() == 4
-                and frames.shape[3] == 3):
-            raise VtError("frames must be a contiguous (B,H,W,3) uint8 tensor on the GPU (or in pinned host memory)")
-        B, H, W, _ = frames.shape
-        if self._check_x_only(x) != B:
-            raise VtError(f"crop workspace is for {x.shape[0]} frames, got {B}")
-        if (tuple(states.shape) != (B, 4) or states.dtype != torch.float64 or not states.is_cuda or not states.is_contiguous()
-                or tuple(resize_factor.shape) != (B,) or resize_factor.dtype != torch.float64 or not resize_factor.is_cuda):
-            raise VtError(f"track_step wants states ({B},4) and resize_factor ({B},) float64 on the GPU")
-        if record is not None and (tuple(record.shape) != (B, 5) or record.dtype != torch.float64 or not record.is_contiguous()
-                                   or not (record.is_cuda or record.is_pinned())):
-            raise VtError(f"record must be a contiguous ({B},5) float64 tensor on the GPU or in pinned host memory")
-        self._check_out(out, B)
-        st = out.struct()
-        m3 = (C.c_float * 3)(*[float(v) for v in mean])
-        s3 = (C.c_float * 3)(*[float(v) for v in std])
-        _check(self._L.vt_track_step(self._h, C.c_void_p(frames.data_ptr()), H, W, C.c_void_p(states.data_ptr()), float(factor), m3, s3, B,
-                                   _stream(stream), _ptr(x), C.c_void_p(resize_factor.data_ptr()), C.byref(st), margin,
-                                   C.c_void_p(record.data_ptr()) if record is not None else None), "vt_track_step", self._L)
-        return out
 
     def cal_bbox(self, score, size, offset, stream=None):
         import torch
