@@ -119,6 +119,76 @@ print("FORM-OK")
     assert p.returncode == 0 and "FORM-OK" in p.stdout, p.stdout[-2000:] + p.stderr[-2000:]
 
 
+POISON_CODE = r"""
+import sys, numpy as np, torch
+sys.path.insert(0, %r); sys.path.insert(0, %r)
+import test_gpu_patch_u8 as T, test_gpu_pipeline as P, test_gpu_frame_formats_yuv as Y
+import pixel_oracle, pixel_oracle_yuv as oy
+from vittracker_amd.native import FrameTable, ImageTable
+rs = np.random.RandomState(11)
+B, H, W = 6, 40, 50
+SMALL = [5.0, 5.0, 0.0, 0.0]
+boxes = [[rs.uniform(-5, W - 10), rs.uniform(-5, H - 10), rs.uniform(4, 30), rs.uniform(4, 30)] for _ in range(B)]
+frames = rs.randint(0, 256, (B, H, W, 3)).astype(np.uint8)
+dev = torch.from_numpy(frames).cuda()
+lays = ["rgb", "bgra", "nv12", "nv21", "p010", "i420"]
+planes = [(pixel_oracle if f in Y.OLD else oy).random_planes(rs, f, H, W) for f in lays]
+rgbs = [Y._rgb(f, p, "bt601", "limited") for f, p in zip(lays, planes)]
+m = T._model(128, B)
+want = {}
+
+def check(route, S, got8, gotf, rgb, small, unusable):
+    (patch, rf), (crop, rf2) = [(a.cpu().numpy(), r.cpu().numpy()) for a, r in (got8, gotf)]
+    for b in range(B):
+        if b in small or b in unusable:
+            assert np.isnan(rf[b]) and np.isnan(rf2[b]) and not patch[b].any() and np.isnan(crop[b]).all(), (route, S, b)
+            continue
+        key = (id(rgb), b, S)
+        if key not in want:
+            want[key] = T._host_patch(rgb[b], boxes[b], 2.0, S) + (P._host_crop(rgb[b], boxes[b], 2.0, S)[0],)
+        p, f, c = want[key]
+        assert np.array_equal(patch[b], p) and float(rf[b]) == f and float(rf2[b]) == f and np.array_equal(crop[b], c), (route, S, b)
+
+def states(small):
+    return torch.tensor([SMALL if b in small else boxes[b] for b in range(B)], dtype=torch.float64).cuda()
+
+ftab = FrameTable(B, "cuda")
+for b in range(B):
+    ftab.set_tensor(b, dev[b])
+ftab.host[3] = (0, H, W, 0)                # null data
+ftab.upload()
+itab = ImageTable(B, "cuda")
+for b in range(B):
+    itab.set_image(b, Y._image(lays[b], planes[b], 0))
+d = dict(zip(itab.DTYPE.names, itab.host[2].tolist()))
+d["reserved"] = 1
+itab.set(2, tuple(d[n] for n in itab.DTYPE.names), check=False)
+itab.upload()
+for S in (64, 128, 256, 96):
+    st = states((1, 4))
+    check("dense", S, m.crop_u8(dev, st, 2.0, S), m.crop(dev, st, 2.0, S, T.MEAN, T.STD), frames, (1, 4), ())
+    st = states((1,))
+    check("frames", S, m.crop_u8_frames(ftab, st, 2.0, S), m.crop_frames(ftab, st, 2.0, S, T.MEAN, T.STD), frames, (1,), (3,))
+    st = states((0,))
+    check("images", S, m.crop_u8_images(itab, st, 2.0, S), m.crop_images(itab, st, 2.0, S, T.MEAN, T.STD), rgbs, (0,), (2,))
+print("POISON-OK")
+"""
+
+
+@pytest.mark.parametrize("env", [{}, {"VT_CROP_BYTES": "1"}, {"VT_CROP_FAST": "0"}, {"VT_CROP_BAND": "0"}, {"VT_CROP_BAND": "-4"}, {"VT_CROP_BAND": "-2"},
+                                 {"VT_CROP_BAND": "-4", "VT_CROP_ALIGNED": "0"}])
+def test_poisoned_sequences_under_every_forced_crop_form(env):
+    """A too-small box and an unusable descriptor under the default and every forced crop form (one child each: a process reads the
+    switches once), on the dense, frame-table and image-table routes, T = 64 / 128 / 256 and 96 (the generic kernels), uint8 patch and
+    fp32 crop: the poisoned sequence has a NaN resize factor, an all-zero patch and an all-NaN crop; every other one equals
+    host_ops.sample_target on its frame (its format's oracle RGB frame), resize factor included."""
+    import subprocess
+    import sys
+    p = subprocess.run([sys.executable, "-c", POISON_CODE % (REPO, os.path.join(REPO, "tests"))], env=dict(os.environ, **env),
+                       capture_output=True, text=True, timeout=300)
+    assert p.returncode == 0 and "POISON-OK" in p.stdout, p.stdout[-2000:] + p.stderr[-3000:]
+
+
 def test_crop_u8_too_small_box_poisons_the_resize_factor():
     import torch
     m = _model(128, 2)

@@ -6,9 +6,11 @@
     python tools/compare_builds.py OTHER.so --matrix [--f16 OTHER_F16.so] [--envs a,b] [--configs g128,vitb] [--batches 1,96] [--out FILE]
 
 --matrix: one child process per (library, environment); the current build against OTHER.  Environments: the default, every entry of
-VARIANTS in tests/test_gpu_variants.py, VT_TRACK_U8=0, VT_GRAPH_CHAINS=2 and 3.  Configs: g128, g256, generic (112, 224), f16 (the f16
+VARIANTS in tests/test_gpu_variants.py, VT_TRACK_U8=0, VT_GRAPH_CHAINS=2 and 3, and the crop forms tests/test_gpu_patch_u8.py forces
+(crop_bytes, crop_fast_off, crop_band_off, crop_band4, crop_band2, crop_band4_unaligned).  Configs: g128, g256, generic (112, 224), f16 (the f16
 build at G128, needs --f16), vitb.  Batches 1, 7, 96, 256 (ViT-Base 1, 96).  Entries: forward, forward on the cached template, forward_u8,
-capture + replay, track_step, track_step_frames, track_step_images (NV12) -- four steps each for the tracker entries, so the state
+capture + replay, track_step, track_step_frames, track_step_images (NV12, and I420 under BT.709: the other body of the band image kernel)
+-- four steps each for the tracker entries, so the state
 feeds back.  A child prints sha256 over the bytes of all six outputs (+ states and record) per case, or the library's error code where it
 refuses the case: both libraries must refuse with the same code.  Children run one after the other."""
 import argparse, json, os, subprocess, sys
@@ -81,6 +83,7 @@ def child(configs, batches):
             frames = [torch.from_numpy(rs.randint(0, 256, (B, H, W, 3)).astype(np.uint8)).cuda() for _ in range(4)]
             luma = [torch.from_numpy(rs.randint(0, 256, (B, H, W)).astype(np.uint8)).cuda() for _ in range(4)]
             chroma = [torch.from_numpy(rs.randint(0, 256, (B, H // 2, W // 2, 2)).astype(np.uint8)).cuda() for _ in range(4)]
+            planar = [c.permute(0, 3, 1, 2).contiguous() for c in chroma]      # (B, 2, H/2, W/2): a frame's U and V planes back to back
             box0 = torch.tensor([[rs.uniform(0, 90), rs.uniform(0, 60), rs.uniform(10, 60), rs.uniform(10, 50)] for _ in range(B)],
                                 dtype=torch.float64).cuda()
             tag = f"{cfg}/B{B}/"
@@ -122,7 +125,10 @@ def child(configs, batches):
                     else:
                         tab = ImageTable(B, "cuda")
                         for b in range(B):
-                            tab.set_image(b, Image.nv12(luma[t][b], chroma[t][b]))
+                            if kind == "i420":      # the NV12 frame's U and V as two planes
+                                tab.set_image(b, Image.i420(luma[t][b], planar[t][b, 0], planar[t][b, 1], matrix="bt709"))
+                            else:
+                                tab.set_image(b, Image.nv12(luma[t][b], chroma[t][b]))
                         tab.upload()
                         m.track_step_images(tab, st, 4.0, MEAN, STD, ws, rf, out, record=rec)
                     recs.append(rec)
@@ -130,6 +136,7 @@ def child(configs, batches):
             case(tag + "track_step", lambda: tracked("dense"))
             case(tag + "track_step_frames", lambda: tracked("frames"))
             case(tag + "track_step_images", lambda: tracked("images"))
+            case(tag + "track_step_images_i420", lambda: tracked("i420"))
             m.close()
     print("RESULT " + json.dumps(res))
 
@@ -143,6 +150,9 @@ def environments():
     envs = {"default": {}}
     envs.update(ns["VARIANTS"])
     envs.update({"track_u8_off": {"VT_TRACK_U8": "0"}, "chains2": {"VT_GRAPH_CHAINS": "2"}, "chains3": {"VT_GRAPH_CHAINS": "3"}})
+    envs.update({"crop_bytes": {"VT_CROP_BYTES": "1"}, "crop_fast_off": {"VT_CROP_FAST": "0"}, "crop_band_off": {"VT_CROP_BAND": "0"},
+                 "crop_band4": {"VT_CROP_BAND": "-4"}, "crop_band2": {"VT_CROP_BAND": "-2"},
+                 "crop_band4_unaligned": {"VT_CROP_BAND": "-4", "VT_CROP_ALIGNED": "0"}})
     return envs
 
 

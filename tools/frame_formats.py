@@ -16,7 +16,8 @@ Fixed seeds, 1920 x 1080 frames (`--distinct` different frames, cycled over the 
                           int32 torch ops (one kernel per op), then vt_track_step_frames
   new_crop_us[T][form]    (section "new") B = 256: the uint8 table crop of every added layout / colour row, NV12 BT.601 and the RGB
                           frame route in the same interleaved rounds; ratio_vs_nv12 and the kernel family each form runs
-  parent_ab               (section "parent", --parent-lib: the parent commit's libvittrack_hip.so) the formats that existed, crops
+  parent_ab               (section "parent", --parent-lib: the parent commit's libvittrack_hip.so) the six first layouts' families and
+                          the added ones (NV12 BT.709, P010, I420, YUYV, GRAY8: the second body of the band image kernel), crops
                           (T = 128 / 256) and G128 / G256 steps at B = 256, this build and the parent's loaded side by side in ONE
                           process and timed in the same interleaved rounds: per form the median and the [min, max] over the rounds;
                           inside_parent_range = this build's median lies inside the parent's own round-to-round range
@@ -151,7 +152,10 @@ def _parent_ab(a, B, n, g, states):
     from vittracker_amd import native, synth
     other = _second_native(a.parent_lib)
     forms = ("rgb", "bgr", "rgba", "nv12")
+    new_forms = ("nv12_709", "p010_709", "i420", "yuyv", "gray")      # the rows that reach crop_band_image_ext, one per family and more
     frames = {f: _planes(f, n, g) for f in forms}
+    for f in new_forms:
+        frames[f] = [tuple(torch.randint(0, 256, s, dtype=torch.uint8, device="cuda", generator=g) for s in NEW_FORMS[f][2]()) for _ in range(n)]
     res = {"crop_us": {}, "step_us": {}}
 
     def tables(nat):
@@ -160,6 +164,12 @@ def _parent_ab(a, B, n, g, states):
             t = nat.ImageTable(B, "cuda")
             for b in range(B):
                 t.set_image(b, getattr(nat.Image, f)(*frames[f][b % n]))
+            t.upload()
+            tabs[f] = t
+        for f in new_forms:
+            t = nat.ImageTable(B, "cuda")
+            for b in range(B):
+                t.set_image(b, getattr(nat.Image, NEW_FORMS[f][0])(*frames[f][b % n], **NEW_FORMS[f][1]))
             t.upload()
             tabs[f] = t
         ft = nat.FrameTable(B, "cuda")
@@ -191,7 +201,7 @@ def _parent_ab(a, B, n, g, states):
                 graphs[f"{side}:{name}"] = _capture(fn)
         rounds = _interleaved(graphs, a.reps, a.rounds, a.replays, all_rounds=True)
         row = {}
-        for name in ["rgb_frames"] + list(forms):
+        for name in ["rgb_frames"] + list(forms) + list(new_forms):
             identical = identical and torch.equal(outs[("this", name)][0], outs[("parent", name)][0]) and \
                 torch.equal(outs[("this", name)][1], outs[("parent", name)][1])
             me, pa = _stats(rounds[f"this:{name}"]), _stats(rounds[f"parent:{name}"])

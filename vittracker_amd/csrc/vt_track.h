@@ -74,6 +74,147 @@ struct TableFrames {      // `frames` is a (B,) vt_frame table; H, W are unused
     __device__ __forceinline__ static FrameView shape(const unsigned char* frames, int H, int W, int b, unsigned nb) { return view(frames, H, W, b, nb); }
 };
 
+// ---- what every crop kernel below shares: the prologue of a workgroup (normalisation table, box geometry, poison), the table entries of
+// a column and a row, and a band's guard row.  All forced inline: a kernel is still one function, and the measurements in the kernel
+// comments below are of the kernels as wholes.
+typedef unsigned u2v __attribute__((ext_vector_type(2)));
+typedef unsigned u3v __attribute__((ext_vector_type(3)));
+typedef unsigned u4v __attribute__((ext_vector_type(4)));
+typedef unsigned u3a __attribute__((ext_vector_type(3), aligned(4)));      // a patch item's 12 bytes: 4-byte aligned only
+typedef unsigned short us2 __attribute__((ext_vector_type(2)));
+
+// Preprocessor.process maps a uint8 value to (v / 255 - mean) / std: 256 x 3 possible results.  They are computed ONCE per
+// workgroup (256 threads, one value each) with the reference's arithmetic (three separately rounded fp32 ops, below) into an LDS
+// table -- per output value one LDS read instead of a convert, a multiply, a subtract and an IEEE division sequence (~14 VALU
+// instructions of the ~74 a value cost).  The caller's barrier publishes it.
+__device__ __forceinline__ void fill_norm_lut(float* norm_lut, float m0, float m1, float m2, float s0, float s1, float s2) {
+    const float meanv[3] = {m0, m1, m2}, stdq[3] = {s0, s1, s2};
+    const int tid = threadIdx.x;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        // torch's CUDA `tensor / 255.0` multiplies by the float reciprocal (div_true with a CPU scalar);
+        // Preprocessor.process runs on the GPU, so that is the reference arithmetic
+        // Three separately rounded ops, as three torch kernels: the empty asm keeps hipcc from
+        // contracting the multiply and the subtraction into one fma (the _rn intrinsics do not).
+        float scaled = (float)tid * (1.0f / 255.0f);
+        asm volatile("" : "+v"(scaled));
+        float centred = scaled - meanv[c];
+        asm volatile("" : "+v"(centred));
+        norm_lut[c * 256 + tid] = centred / stdq[c];
+    }
+}
+
+// The square crop of sequence b in frame pixels (the fp64 geometry of sample_target) and what of it lies inside an H x W frame.
+struct CropWindow {
+    int crop_sz;                // side: ceil(sqrt(w h) factor); below 1: 'Too small bounding box.'
+    int x1, y1;                 // origin, Python round(): half to even
+    int vx0, vx1, vy0, vy1;     // valid source range of the padded crop
+    double scale;               // crop_sz / T
+};
+__device__ __forceinline__ int crop_side(const double* states, int b, double factor) {
+    return (int)ceil(sqrt(states[4 * b + 2] * states[4 * b + 3]) * factor);
+}
+__device__ __forceinline__ CropWindow crop_window(const double* states, int b, int crop_sz, int T, int H, int W) {      // crop_sz: crop_side's
+    const double bx = states[4 * b + 0], by = states[4 * b + 1], bw = states[4 * b + 2], bh = states[4 * b + 3];
+    const int x1 = (int)rint(bx + 0.5 * bw - crop_sz * 0.5);
+    const int y1 = (int)rint(by + 0.5 * bh - crop_sz * 0.5);
+    const int x2 = x1 + crop_sz, y2 = y1 + crop_sz;
+    // the reference's pad formula keeps max(x2 - W + 1, 0) columns on the right, i.e. drops the last image column when the crop
+    // reaches the border
+    return CropWindow{crop_sz, x1, y1, x1 < 0 ? 0 : x1, x2 - (x2 - W + 1 > 0 ? x2 - W + 1 : 0), y1 < 0 ? 0 : y1, y2 - (y2 - H + 1 > 0 ? y2 - H + 1 : 0),
+                      (double)crop_sz / (double)T};
+}
+
+// The reference raises 'Too small bounding box.' (processing_utils.py:33-34) where crop_sz < 1.  A kernel cannot raise: the crop and
+// its resize factor are poisoned with NaN, so every box derived from them is NaN and the caller sees it (BatchedVitTracker checks
+// user-supplied boxes on the host before they get here; boxes produced by vt_update_state are at least `margin` wide and never take
+// this branch).  An unusable frame or image descriptor is poisoned the same way.  Patch bytes cannot carry the poison and are zeroed:
+// the NaN resize factor carries it.  poison_item writes the item at (oy, ox0 .. ox0 + 3); RAGGED: T may be no multiple of 4.
+template <bool U8OUT, bool RAGGED>
+__device__ __forceinline__ void poison_item(float* out, unsigned char* out8, int b, int T, int oy, int ox0) {
+    if constexpr (RAGGED) {
+        for (int c = 0; c < 3; ++c)
+            for (int k = 0; k < 4 && ox0 + k < T; ++k) {
+                if constexpr (U8OUT) out8[((size_t)oy * T + ox0 + k) * 3 + c] = 0;
+                else out[(((size_t)b * 3 + c) * T + oy) * T + ox0 + k] = __builtin_nanf("");
+            }
+    } else {
+        if constexpr (U8OUT) *reinterpret_cast<u3a*>(out8 + ((size_t)oy * T + ox0) * 3) = u3a{0u, 0u, 0u};
+        else {
+            float* const o = out + (((size_t)b * 3) * T + oy) * T + ox0;
+            for (int c = 0; c < 3; ++c) st4(o + (size_t)c * T * T, splat4(__builtin_nanf("")));
+        }
+    }
+}
+// ... and a band's IPT items of this thread (column group cg, rows row0 + j RPG + rl), with the sequence's resize factor
+template <bool U8OUT, int T, int IPT, int RPG>
+__device__ __forceinline__ void poison_band(float* out, unsigned char* out8, double* resize_factor, int b, int row0, int rl, int cg) {
+    if (blockIdx.x == 0 && threadIdx.x == 0) resize_factor[b] = __builtin_nan("");
+#pragma unroll
+    for (int j = 0; j < IPT; ++j) poison_item<U8OUT, false>(out, out8, b, T, row0 + j * RPG + rl, 4 * cg);
+}
+
+// Output column ox: its two source columns in the frame, whether each lies inside the valid range (outside: zero padding), their
+// 11-bit weights, and the base pixel xb of the pair's window: the left column when it is inside the frame, else the right one (then
+// the left is padding)
+struct ColumnTap { int xx0, xx1, xb, ax0, ax1; bool vc0, vc1; };
+__device__ __forceinline__ ColumnTap column_tap(int ox, const CropWindow& g) {
+    int sx0, sx1, ax0, ax1;
+    lin_coeff(ox, g.crop_sz, g.scale, sx0, sx1, ax0, ax1);
+    const int xx0 = g.x1 + sx0, xx1 = g.x1 + sx1;
+    const bool vc0 = xx0 >= g.vx0 && xx0 < g.vx1, vc1 = xx1 >= g.vx0 && xx1 < g.vx1;
+    return ColumnTap{xx0, xx1, vc0 ? xx0 : (vc1 ? xx1 : 0), ax0, ax1, vc0, vc1};
+}
+// the xtab entries of the table-driven kernels: zero padding lives in the WEIGHTS (packed for v_dot2: a padded column weighs nothing).
+// RGB frames: window byte offset, weights, the right column's bit offset inside the window (0 or 24), -
+__device__ __forceinline__ u4v frame_column_entry(const ColumnTap& t) {
+    return u4v{3u * (unsigned)t.xb, (unsigned)(t.vc0 ? t.ax0 : 0) | ((unsigned)(t.vc1 ? t.ax1 : 0) << 16), (unsigned)(t.vc1 ? 24 * (t.xx1 - t.xb) : 0), 0u};
+}
+// vt_image layouts: plane-0 byte offset of the left tap (bpp bytes a pixel, yadd: see yuv_layout), weights, steps (bit 0 = the right
+// tap is the next pixel, bit 1 = its chroma pair is the next pair), chroma byte offset (cmul bytes a pair)
+__device__ __forceinline__ u4v image_column_entry(const ColumnTap& t, unsigned bpp, unsigned yadd, unsigned cmul) {
+    const unsigned step = t.vc1 && t.xx1 != t.xb ? 1u : 0u, cstep = t.vc1 && (t.xx1 >> 1) != (t.xb >> 1) ? 2u : 0u;
+    return u4v{bpp * (unsigned)t.xb + yadd, (unsigned)(t.vc0 ? t.ax0 : 0) | ((unsigned)(t.vc1 ? t.ax1 : 0) << 16), step | cstep, cmul * (unsigned)(t.xb >> 1)};
+}
+
+// Output row oy: its two source rows (a row outside the valid range reads row 0), their 11-bit weights and validity
+struct RowTap {
+    unsigned ya, yb;
+    int by0, by1;
+    bool vr0, vr1;
+    __device__ __forceinline__ unsigned w0() const { return vr0 ? (unsigned)by0 << 12 : 0u; }      // << 12 for mulhi24; a padded row weighs nothing
+    __device__ __forceinline__ unsigned w1() const { return vr1 ? (unsigned)by1 << 12 : 0u; }
+};
+__device__ __forceinline__ RowTap row_tap(int oy, const CropWindow& g) {
+    int sy0, sy1, by0, by1;
+    lin_coeff(oy, g.crop_sz, g.scale, sy0, sy1, by0, by1);
+    const int yy0 = g.y1 + sy0, yy1 = g.y1 + sy1;
+    const bool vr0 = yy0 >= g.vy0 && yy0 < g.vy1, vr1 = yy1 >= g.vy0 && yy1 < g.vy1;
+    return RowTap{(unsigned)(vr0 ? yy0 : 0), (unsigned)(vr1 ? yy1 : 0), by0, by1, vr0, vr1};
+}
+// A band's tables, before its barrier.  xtab: the first T threads, one column each (`column`: the entry of a ColumnTap).  ytab, by the
+// LAST NROWS threads (the first T are busy with the columns), per output row of the band: byte offsets of its two source rows in plane
+// 0, their weights << 12.  ctab (may be null), per output row: the chroma-row offsets (y >> cys) cpitch of its two source rows.
+template <int T, int NROWS, class Column>
+__device__ __forceinline__ void fill_band_tables(unsigned* xtab, unsigned* ytab, unsigned* ctab, int row0, const CropWindow& g,
+                                                 unsigned pitch0, unsigned cys, unsigned cpitch, Column&& column) {
+    const int tid = threadIdx.x;
+    if (tid < T) *reinterpret_cast<u4v*>(xtab + 4 * tid) = column(column_tap(tid, g));
+    if (tid >= 256 - NROWS) {
+        const int r = tid - (256 - NROWS);
+        const RowTap t = row_tap(row0 + r, g);
+        *reinterpret_cast<u4v*>(ytab + 4 * r) = u4v{t.ya * pitch0, t.yb * pitch0, t.w0(), t.w1()};
+        if (ctab != nullptr) *reinterpret_cast<u2v*>(ctab + 2 * r) = u2v{(t.ya >> cys) * cpitch, (t.yb >> cys) * cpitch};
+    }
+}
+// the last source row a band's guards have to reckon with: the lower tap of its last output row (rows beyond the valid range read row 0)
+template <int NROWS>
+__device__ __forceinline__ int band_last_source_row(int row0, const CropWindow& g) {
+    int sl0, sl1, al0, al1;
+    lin_coeff(row0 + NROWS - 1, g.crop_sz, g.scale, sl0, sl1, al0, al1);
+    return g.y1 + sl1 < g.vy1 - 1 ? g.y1 + sl1 : g.vy1 - 1;
+}
+
 // grid (ceil(T * ceil(T/4) / 256), B); frames (B,H,W,3) uint8; states (B,4) double [x,y,w,h]; out (B,3,T,T) float.
 // One thread = four consecutive output pixels of a row (all three channels): the vertical coefficients are computed once,
 // and a channel's four values leave as ONE 16-byte store when T is a multiple of 4 (the crop sizes the tracker uses are:
@@ -90,61 +231,27 @@ __device__ __forceinline__ void crop_body(const unsigned char* __restrict__ fram
                                           float* __restrict__ out, double* __restrict__ resize_factor) {
     const int b = blockIdx.y;
     const FrameView fv = Src::view(frames, H, W, b, gridDim.y);
-    // Preprocessor.process maps a uint8 value to (v / 255 - mean) / std: 256 x 3 possible results.  They are computed ONCE per
-    // workgroup with the reference's arithmetic (three separately rounded fp32 ops, below) into an LDS table -- per output value
-    // one LDS read instead of a convert, a multiply, a subtract and an IEEE division sequence (~14 VALU instructions of the ~74 a
-    // value cost).
     __shared__ float norm_lut[U8OUT ? 1 : 3 * 256];
     if constexpr (!U8OUT) {
-        const float meanv[3] = {m0, m1, m2}, stdq[3] = {s0, s1, s2};
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            // torch's CUDA `tensor / 255.0` multiplies by the float reciprocal (div_true with a CPU scalar);
-            // Preprocessor.process runs on the GPU, so that is the reference arithmetic
-            // Three separately rounded ops, as three torch kernels: the empty asm keeps hipcc from
-            // contracting the multiply and the subtraction into one fma (the _rn intrinsics do not).
-            float scaled = (float)(int)threadIdx.x * (1.0f / 255.0f);
-            asm volatile("" : "+v"(scaled));
-            float centred = scaled - meanv[c];
-            asm volatile("" : "+v"(centred));
-            norm_lut[c * 256 + threadIdx.x] = centred / stdq[c];
-        }
+        fill_norm_lut(norm_lut, m0, m1, m2, s0, s1, s2);
         __syncthreads();
     }
     unsigned char* const out8 = reinterpret_cast<unsigned char*>(out) + (size_t)b * T * T * 3;      // U8OUT: this frame's patch
-    const double bx = states[4 * b + 0], by = states[4 * b + 1], bw = states[4 * b + 2], bh = states[4 * b + 3];
-    const int crop_sz = (int)ceil(sqrt(bw * bh) * factor);
+    const int crop_sz = crop_side(states, b, factor);
     const int T4 = (T + 3) >> 2;                      // pixel groups per row
     const int idx = blockIdx.x * 256 + threadIdx.x;
     if (!(crop_sz >= 1) || !fv.ok) {
-        // The reference raises 'Too small bounding box.' here (processing_utils.py:33-34).  A kernel cannot
-        // raise: the crop and its resize factor are poisoned with NaN, so every box derived from them is NaN and
-        // the caller sees it (BatchedVitTracker checks user-supplied boxes on the host before they get here; boxes
-        // produced by vt_update_state are at least `margin` wide and never take this branch).
         if (idx == 0) resize_factor[b] = __builtin_nan("");
-        if (idx < T * T4) {
-            const int oy = idx / T4, ox0 = (idx - oy * T4) * 4;
-            for (int c = 0; c < 3; ++c)
-                for (int k = 0; k < 4 && ox0 + k < T; ++k) {
-                    if constexpr (U8OUT) out8[((size_t)oy * T + ox0 + k) * 3 + c] = 0;      // bytes cannot carry the poison: the NaN resize factor does
-                    else out[(((size_t)b * 3 + c) * T + oy) * T + ox0 + k] = __builtin_nanf("");
-                }
-        }
+        if (idx < T * T4) poison_item<U8OUT, true>(out, out8, b, T, idx / T4, (idx - idx / T4 * T4) * 4);
         return;
     }
-    const int x1 = (int)rint(bx + 0.5 * bw - crop_sz * 0.5);     // Python round(): half to even
-    const int y1 = (int)rint(by + 0.5 * bh - crop_sz * 0.5);
-    const int x2 = x1 + crop_sz, y2 = y1 + crop_sz;
-    // valid source range of the padded crop (the reference's pad formula keeps max(x2 - W + 1, 0)
-    // columns on the right, i.e. drops the last image column when the crop reaches the border)
-    const int vx0 = x1 < 0 ? 0 : x1, vx1 = x2 - (x2 - fv.W + 1 > 0 ? x2 - fv.W + 1 : 0);
-    const int vy0 = y1 < 0 ? 0 : y1, vy1 = y2 - (y2 - fv.H + 1 > 0 ? y2 - fv.H + 1 : 0);
+    const CropWindow g = crop_window(states, b, crop_sz, T, fv.H, fv.W);
     if (idx == 0) resize_factor[b] = (double)T / (double)crop_sz;
     if (idx >= T * T4) return;
     const int oy = idx / T4, ox0 = (idx - oy * T4) * 4;
-    const double scale = (double)crop_sz / (double)T;
+    // a thread's own row and columns, with validity masks (not row_tap / column_tap: through them crop_kernel<false, *> takes 52 / 53 VGPRs for 51 / 52)
     int sy0, sy1, by0, by1;
-    lin_coeff(oy, crop_sz, scale, sy0, sy1, by0, by1);
+    lin_coeff(oy, g.crop_sz, g.scale, sy0, sy1, by0, by1);
     // Source pixels: an RGB pixel is 3 consecutive bytes, and the two columns a bilinear sample reads are neighbours (or the same
     // pixel at the crop's edge), so ONE 8-byte load at byte offset 3 x covers both -- 8 loads per thread instead of 48 single-byte
     // loads, which were the kernel's cost (3072 vector-memory instructions per 128 x 128 crop: 33 us at batch 256, a quarter of the
@@ -152,10 +259,9 @@ __device__ __forceinline__ void crop_body(const unsigned char* __restrict__ fram
     // a load that crosses the end of the buffer returns zeros, so the frame's last pixels are read 8 bytes back and shifted).
     const unsigned nrec = fv.nrec;      // dense: bytes from this frame to the end of the batch; table: the frame's own extent
     const auto rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned char*>(fv.base), 0, (int)nrec, 0x00020000);
-    const int yy0 = y1 + sy0, yy1 = y1 + sy1;
-    const bool vr0 = yy0 >= vy0 && yy0 < vy1, vr1 = yy1 >= vy0 && yy1 < vy1;
+    const int yy0 = g.y1 + sy0, yy1 = g.y1 + sy1;
+    const bool vr0 = yy0 >= g.vy0 && yy0 < g.vy1, vr1 = yy1 >= g.vy0 && yy1 < g.vy1;
     const unsigned rowo0 = (unsigned)(vr0 ? yy0 : 0) * fv.pitch, rowo1 = (unsigned)(vr1 ? yy1 : 0) * fv.pitch;
-    typedef unsigned u2v __attribute__((ext_vector_type(2)));
     auto load8 = [&](unsigned off) -> unsigned long long {      // bytes off .. off + 7 of the frame (the last bytes of the batch: shifted in)
         if constexpr (BYTES) {
             unsigned long long r = 0;
@@ -177,9 +283,9 @@ __device__ __forceinline__ void crop_body(const unsigned char* __restrict__ fram
     for (int k = 0; k < 4; ++k) {       // all eight loads first
         const int ox = ox0 + k < T ? ox0 + k : T - 1;
         int sx0, sx1;
-        lin_coeff(ox, crop_sz, scale, sx0, sx1, ax0a[k], ax1a[k]);
-        const int xx0 = x1 + sx0, xx1 = x1 + sx1;
-        vc0a[k] = xx0 >= vx0 && xx0 < vx1; vc1a[k] = xx1 >= vx0 && xx1 < vx1;
+        lin_coeff(ox, g.crop_sz, g.scale, sx0, sx1, ax0a[k], ax1a[k]);
+        const int xx0 = g.x1 + sx0, xx1 = g.x1 + sx1;
+        vc0a[k] = xx0 >= g.vx0 && xx0 < g.vx1; vc1a[k] = xx1 >= g.vx0 && xx1 < g.vx1;
         // base pixel of the 8-byte window: the left column when it is inside the frame, else the right one (then the left is padding)
         const int xb = vc0a[k] ? xx0 : (vc1a[k] ? xx1 : 0);
         sh1[k] = vc1a[k] ? 24 * (xx1 - xb) : 0;                     // bit offset of the right column's pixel inside the window: 0 or 24
@@ -196,6 +302,7 @@ __device__ __forceinline__ void crop_body(const unsigned char* __restrict__ fram
         const unsigned r0w = vr0 && vc1 ? (unsigned)(q0[k] >> sh1[k]) : 0u, r1w = vr1 && vc1 ? (unsigned)(q1[k] >> sh1[k]) : 0u;
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
+            // item 7b: not merged, see NOTES.md (crop kernels)
             const int p00 = (int)((l0 >> (8 * c)) & 0xffu), p01 = (int)((r0w >> (8 * c)) & 0xffu);
             const int p10 = (int)((l1 >> (8 * c)) & 0xffu), p11 = (int)((r1w >> (8 * c)) & 0xffu);
             // every factor is below 2^24 (8-bit pixels, 12-bit weights, 15-bit row sums): the 24-bit multiplier gives the same integers
@@ -289,76 +396,40 @@ __device__ __forceinline__ void crop_fast_body(const unsigned char* __restrict__
     __shared__ float norm_lut[U8OUT ? 1 : 3 * 256];
     __shared__ __attribute__((aligned(16))) unsigned xtab[CROP_FAST_MAX_T * 4];      // per output column: window byte offset, weights, right column's shift, -
     unsigned char* const out8 = reinterpret_cast<unsigned char*>(out) + (size_t)b * T * T * 3;      // U8OUT: this frame's (T, T, 3) patch
-    typedef unsigned u3a __attribute__((ext_vector_type(3), aligned(4)));
-    if constexpr (!U8OUT) {
-        const float meanv[3] = {m0, m1, m2}, stdq[3] = {s0, s1, s2};
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {       // Preprocessor.process on the 256 possible values: see crop_kernel
-            float scaled = (float)tid * (1.0f / 255.0f);
-            asm volatile("" : "+v"(scaled));
-            float centred = scaled - meanv[c];
-            asm volatile("" : "+v"(centred));
-            norm_lut[c * 256 + tid] = centred / stdq[c];
-        }
-    }
-    const double bx = states[4 * b + 0], by = states[4 * b + 1], bw = states[4 * b + 2], bh = states[4 * b + 3];
-    const int crop_sz = (int)ceil(sqrt(bw * bh) * factor);
+    if constexpr (!U8OUT) fill_norm_lut(norm_lut, m0, m1, m2, s0, s1, s2);
+    const int crop_sz = crop_side(states, b, factor);
     const int T4 = T >> 2, nitems = T * T4;
     const int item0 = blockIdx.x * G * 256;
-    if (!(crop_sz >= 1) || !fv.ok) {        // 'Too small bounding box.' (or an unusable frame descriptor): NaN poison, as crop_kernel
+    if (!(crop_sz >= 1) || !fv.ok) {
         if (blockIdx.x == 0 && tid == 0) resize_factor[b] = __builtin_nan("");
-        for (int g = 0; g < G; ++g) {
-            const int idx = item0 + g * 256 + tid;
-            if (idx < nitems) {
-                const int oy = idx / T4, ox0 = (idx - oy * T4) * 4;
-                if constexpr (U8OUT) *reinterpret_cast<u3a*>(out8 + ((size_t)oy * T + ox0) * 3) = u3a{0u, 0u, 0u};      // the NaN resize factor carries the poison
-                else
-                    for (int c = 0; c < 3; ++c) st4(out + (((size_t)b * 3 + c) * T + oy) * T + ox0, splat4(__builtin_nanf("")));
-            }
+        for (int gi = 0; gi < G; ++gi) {
+            const int idx = item0 + gi * 256 + tid;
+            if (idx < nitems) poison_item<U8OUT, false>(out, out8, b, T, idx / T4, (idx - idx / T4 * T4) * 4);
         }
         return;
     }
-    const int x1 = (int)rint(bx + 0.5 * bw - crop_sz * 0.5);
-    const int y1 = (int)rint(by + 0.5 * bh - crop_sz * 0.5);
-    const int x2 = x1 + crop_sz, y2 = y1 + crop_sz;
-    const int vx0 = x1 < 0 ? 0 : x1, vx1 = x2 - (x2 - fv.W + 1 > 0 ? x2 - fv.W + 1 : 0);
-    const int vy0 = y1 < 0 ? 0 : y1, vy1 = y2 - (y2 - fv.H + 1 > 0 ? y2 - fv.H + 1 : 0);
+    const CropWindow g = crop_window(states, b, crop_sz, T, fv.H, fv.W);
     if (blockIdx.x == 0 && tid == 0) resize_factor[b] = (double)T / (double)crop_sz;
-    const double scale = (double)crop_sz / (double)T;
-    typedef unsigned u4v __attribute__((ext_vector_type(4)));
-    for (int ox = tid; ox < T; ox += 256) {
-        int sx0, sx1, ax0, ax1;
-        lin_coeff(ox, crop_sz, scale, sx0, sx1, ax0, ax1);
-        const int xx0 = x1 + sx0, xx1 = x1 + sx1;
-        const bool vc0 = xx0 >= vx0 && xx0 < vx1, vc1 = xx1 >= vx0 && xx1 < vx1;
-        const int xb = vc0 ? xx0 : (vc1 ? xx1 : 0);         // base pixel of the window: the left column when it is inside the frame
-        *reinterpret_cast<u4v*>(xtab + 4 * ox) = u4v{3u * (unsigned)xb, (unsigned)(vc0 ? ax0 : 0) | ((unsigned)(vc1 ? ax1 : 0) << 16),
-                                                      (unsigned)(vc1 ? 24 * (xx1 - xb) : 0), 0u};
-    }
+    for (int ox = tid; ox < T; ox += 256) *reinterpret_cast<u4v*>(xtab + 4 * ox) = frame_column_entry(column_tap(ox, g));
     __syncthreads();
     const unsigned nrec = fv.nrec;
     const auto rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned char*>(((VT_CROPF_DBG & 4) && Src::DENSE) ? frames : fv.base), 0, (int)nrec, 0x00020000);
-    typedef unsigned u2v __attribute__((ext_vector_type(2)));
-    typedef unsigned short us2 __attribute__((ext_vector_type(2)));
     struct Item {
         unsigned long long q0[4], q1[4];
         unsigned wp[4], sh[4], byw0, byw1;
         int oy, ox0;
         bool live;
     };
-    auto fetch = [&](int g, Item& it) {
-        const int idx = item0 + g * 256 + tid;
+    auto fetch = [&](int gi, Item& it) {
+        const int idx = item0 + gi * 256 + tid;
         it.live = idx < nitems;
         const int idc = it.live ? idx : nitems - 1;
         it.oy = idc / T4;
         it.ox0 = (idc - it.oy * T4) * 4;
-        int sy0, sy1, by0, by1;
-        lin_coeff(it.oy, crop_sz, scale, sy0, sy1, by0, by1);
-        const int yy0 = y1 + sy0, yy1 = y1 + sy1;
-        const bool vr0 = yy0 >= vy0 && yy0 < vy1, vr1 = yy1 >= vy0 && yy1 < vy1;
-        const unsigned rowo0 = (unsigned)(vr0 ? yy0 : 0) * fv.pitch, rowo1 = (unsigned)(vr1 ? yy1 : 0) * fv.pitch;
-        it.byw0 = vr0 ? (unsigned)by0 << 12 : 0u;      // a padded row weighs nothing
-        it.byw1 = vr1 ? (unsigned)by1 << 12 : 0u;
+        const RowTap rt = row_tap(it.oy, g);
+        const unsigned rowo0 = rt.ya * fv.pitch, rowo1 = rt.yb * fv.pitch;
+        it.byw0 = rt.w0();
+        it.byw1 = rt.w1();
         // can a window of this item cross the end of the buffer?  (3 (W - 1) is the largest column offset)
         const unsigned far = (rowo0 > rowo1 ? rowo0 : rowo1) + 3u * (unsigned)(fv.W - 1) + 8u;
         const bool slow = __builtin_amdgcn_ballot_w64(far > nrec) != 0;
@@ -385,6 +456,7 @@ __device__ __forceinline__ void crop_fast_body(const unsigned char* __restrict__
             }
         }
     };
+    // item 7: not merged, see NOTES.md (crop kernels)
     auto finish = [&](const Item& it) {
         float res[3][4];
         unsigned pk[3] = {0u, 0u, 0u};      // U8OUT: the 12 bytes of the item's four pixels, HWC
@@ -426,9 +498,9 @@ __device__ __forceinline__ void crop_fast_body(const unsigned char* __restrict__
     Item buf[2];
     fetch(0, buf[0]);
 #pragma unroll
-    for (int g = 0; g < G; ++g) {
-        if (g + 1 < G) fetch(g + 1, buf[(g + 1) & 1]);
-        finish(buf[g & 1]);
+    for (int gi = 0; gi < G; ++gi) {
+        if (gi + 1 < G) fetch(gi + 1, buf[(gi + 1) & 1]);
+        finish(buf[gi & 1]);
     }
 }
 template <int G, bool U8OUT = false>
@@ -487,14 +559,11 @@ __global__ __launch_bounds__(256) void crop_band_kernel(const unsigned char* __r
     __shared__ __attribute__((aligned(16))) unsigned xtab[T * 4];          // per output column: window byte offset, packed weights, right column's shift, -
     __shared__ __attribute__((aligned(16))) unsigned ytab[NROWS * 4];      // per output row of the band: byte offsets of its two source rows, their weights << 12
     unsigned char* const out8 = reinterpret_cast<unsigned char*>(out) + (size_t)b * T * T * 3;
-    typedef unsigned u3a __attribute__((ext_vector_type(3), aligned(4)));
-    typedef unsigned u4v __attribute__((ext_vector_type(4)));
-    typedef unsigned u2v __attribute__((ext_vector_type(2)));
-    typedef unsigned short us2 __attribute__((ext_vector_type(2)));
+    // not fill_norm_lut: through it crop_band_kernel<false, 6, 2, false> takes 64 VGPRs for 60 (tests/test_resource_usage.py holds it to the committed table)
     if constexpr (!U8OUT) {
         const float meanv[3] = {m0, m1, m2}, stdq[3] = {s0, s1, s2};
 #pragma unroll
-        for (int c = 0; c < 3; ++c) {       // Preprocessor.process on the 256 possible values: see crop_kernel
+        for (int c = 0; c < 3; ++c) {       // Preprocessor.process on the 256 possible values: see fill_norm_lut
             float scaled = (float)tid * (1.0f / 255.0f);
             asm volatile("" : "+v"(scaled));
             float centred = scaled - meanv[c];
@@ -502,47 +571,17 @@ __global__ __launch_bounds__(256) void crop_band_kernel(const unsigned char* __r
             norm_lut[c * 256 + tid] = centred / stdq[c];
         }
     }
-    const double bx = states[4 * b + 0], by = states[4 * b + 1], bw = states[4 * b + 2], bh = states[4 * b + 3];
-    const int crop_sz = (int)ceil(sqrt(bw * bh) * factor);
+    const int crop_sz = crop_side(states, b, factor);
     const int row0 = blockIdx.x * NROWS;                 // first output row of this band
     const int cg = tid & (T4 - 1), rl = tid >> LGT4;     // this thread's column group and its row inside a group of 256 items
-    if (!(crop_sz >= 1) || !fs.ok) {        // 'Too small bounding box.' (or an unusable frame descriptor): NaN poison, as crop_kernel
-        if (blockIdx.x == 0 && tid == 0) resize_factor[b] = __builtin_nan("");
-#pragma unroll
-        for (int j = 0; j < IPT; ++j) {
-            const int oy = row0 + j * RPG + rl;
-            if constexpr (U8OUT) *reinterpret_cast<u3a*>(out8 + ((size_t)oy * T + 4 * cg) * 3) = u3a{0u, 0u, 0u};
-            else
-                for (int c = 0; c < 3; ++c) st4(out + (((size_t)b * 3 + c) * T + oy) * T + 4 * cg, splat4(__builtin_nanf("")));
-        }
+    if (!(crop_sz >= 1) || !fs.ok) {        // see poison_item
+        poison_band<U8OUT, T, IPT, RPG>(out, out8, resize_factor, b, row0, rl, cg);
         return;
     }
-    const int x1 = (int)rint(bx + 0.5 * bw - crop_sz * 0.5);
-    const int y1 = (int)rint(by + 0.5 * bh - crop_sz * 0.5);
-    const int x2 = x1 + crop_sz, y2 = y1 + crop_sz;
-    const int vx0 = x1 < 0 ? 0 : x1, vx1 = x2 - (x2 - fs.W + 1 > 0 ? x2 - fs.W + 1 : 0);
-    const int vy0 = y1 < 0 ? 0 : y1, vy1 = y2 - (y2 - fs.H + 1 > 0 ? y2 - fs.H + 1 : 0);
+    const CropWindow g = crop_window(states, b, crop_sz, T, fs.H, fs.W);
     if (blockIdx.x == 0 && tid == 0) resize_factor[b] = (double)T / (double)crop_sz;
-    const double scale = (double)crop_sz / (double)T;
-    if ((VT_CROPF_DBG & 16) != 0) { asm volatile("" ::"v"(x1), "v"(y1), "v"(scale)); stamp(1); }
-    if (tid < T) {                          // column entries (as crop_fast_kernel)
-        int sx0, sx1, ax0, ax1;
-        lin_coeff(tid, crop_sz, scale, sx0, sx1, ax0, ax1);
-        const int xx0 = x1 + sx0, xx1 = x1 + sx1;
-        const bool vc0 = xx0 >= vx0 && xx0 < vx1, vc1 = xx1 >= vx0 && xx1 < vx1;
-        const int xb = vc0 ? xx0 : (vc1 ? xx1 : 0);
-        *reinterpret_cast<u4v*>(xtab + 4 * tid) = u4v{3u * (unsigned)xb, (unsigned)(vc0 ? ax0 : 0) | ((unsigned)(vc1 ? ax1 : 0) << 16),
-                                                       (unsigned)(vc1 ? 24 * (xx1 - xb) : 0), 0u};
-    }
-    if (tid >= 256 - NROWS) {               // row entries of the band, by the LAST threads (the first T are busy with the columns)
-        const int r = tid - (256 - NROWS);
-        int sy0, sy1, by0, by1;
-        lin_coeff(row0 + r, crop_sz, scale, sy0, sy1, by0, by1);
-        const int yy0 = y1 + sy0, yy1 = y1 + sy1;
-        const bool vr0 = yy0 >= vy0 && yy0 < vy1, vr1 = yy1 >= vy0 && yy1 < vy1;
-        *reinterpret_cast<u4v*>(ytab + 4 * r) = u4v{(unsigned)(vr0 ? yy0 : 0) * fs.pitch, (unsigned)(vr1 ? yy1 : 0) * fs.pitch,
-                                                     vr0 ? (unsigned)by0 << 12 : 0u, vr1 ? (unsigned)by1 << 12 : 0u};      // a padded row weighs nothing
-    }
+    if ((VT_CROPF_DBG & 16) != 0) { asm volatile("" ::"v"(g.x1), "v"(g.y1), "v"(g.scale)); stamp(1); }
+    fill_band_tables<T, NROWS>(xtab, ytab, nullptr, row0, g, fs.pitch, 0u, 0u, frame_column_entry);
     __syncthreads();
     stamp(2);
     const FrameView fv = Src::view(frames, H, W, b, gridDim.y);
@@ -558,7 +597,6 @@ __global__ __launch_bounds__(256) void crop_band_kernel(const unsigned char* __r
         const u4v e = *reinterpret_cast<const u4v*>(xtab + 4 * (4 * cg + k));
         xo[k] = e.x + (ALIGNED ? mis : 0u); wp[k] = e.y; sh[k] = e.z;
     }
-    typedef unsigned u3v __attribute__((ext_vector_type(3)));
     // a window can cross the end of the buffer only in the batch's last frame (its last rows): there every load takes the byte-aligned,
     // shifted-back form.  The two forms are two instantiations of one body (AL: aligned 12-byte loads), so neither holds the other's registers.
     // ... and there only in a band that reads the frame's last source row (its windows end at most 11 + 3 bytes past their first byte: inside
@@ -571,10 +609,7 @@ __global__ __launch_bounds__(256) void crop_band_kernel(const unsigned char* __r
     // read row 0.  And whatever the arithmetic, the buffer descriptor's bound (nrec = that extent) keeps every load inside the frame.
     bool last = fv.tail;      // dense: b == gridDim.y - 1
     if (ALIGNED && last) {
-        int sl0, sl1, al0, al1;
-        lin_coeff(row0 + NROWS - 1, crop_sz, scale, sl0, sl1, al0, al1);
-        const int ymax = y1 + sl1 < vy1 - 1 ? y1 + sl1 : vy1 - 1;       // rows beyond the valid range read row 0
-        if (ymax <= fs.H - 2 && fs.W * 3 >= 16) last = false;
+        if (band_last_source_row<NROWS>(row0, g) <= fs.H - 2 && fs.W * 3 >= 16) last = false;
     }
     unsigned two = 2u;
     asm volatile("" : "+v"(two));      // put_byte_shr2's shift operand has to live in a vector register
@@ -635,6 +670,7 @@ __global__ __launch_bounds__(256) void crop_band_kernel(const unsigned char* __r
                 const unsigned l0 = w0.x, l1 = w1.x;
                 const unsigned r0w = __builtin_amdgcn_alignbit(w0.y, l0, sh[k]);       // the window >> 0 or 24 bits
                 const unsigned r1w = __builtin_amdgcn_alignbit(w1.y, l1, sh[k]);
+                // item 7: not merged, see NOTES.md (crop kernels); as a helper it cost the fp32 forms with four items 92 VGPRs for 89
                 const us2 wv = __builtin_bit_cast(us2, wp[k]);
 #pragma unroll
                 for (int c = 0; c < 3; ++c) {
@@ -659,6 +695,7 @@ __global__ __launch_bounds__(256) void crop_band_kernel(const unsigned char* __r
                 for (int c = 0; c < 3; ++c) st4(out + (((size_t)b * 3 + c) * T + oy) * T + 4 * cg, f4{res[c][0], res[c][1], res[c][2], res[c][3]});
             }
         };
+        // item 8: not merged, see NOTES.md (crop kernels); as a helper it cost the fp32 aligned forms with four items 92 VGPRs for 89
         // two items at a time (the conditional loads are waited for as a whole anyway): half the window registers, so that the kernel
         // stays within 128 registers = four workgroups per CU = ONE round of the 1024 bands of 256 G128 frames
         constexpr int HS = IPT < 2 ? IPT : 2;
@@ -844,46 +881,25 @@ __global__ __launch_bounds__(256) void crop_image_kernel(const vt_image* __restr
     const ImageView iv = image_view(images, b);
     __shared__ float norm_lut[U8OUT ? 1 : 3 * 256];
     if constexpr (!U8OUT) {
-        const float meanv[3] = {m0, m1, m2}, stdq[3] = {s0, s1, s2};
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {       // Preprocessor.process on the 256 possible values: see crop_kernel
-            float scaled = (float)(int)threadIdx.x * (1.0f / 255.0f);
-            asm volatile("" : "+v"(scaled));
-            float centred = scaled - meanv[c];
-            asm volatile("" : "+v"(centred));
-            norm_lut[c * 256 + threadIdx.x] = centred / stdq[c];
-        }
+        fill_norm_lut(norm_lut, m0, m1, m2, s0, s1, s2);
         __syncthreads();
     }
     unsigned char* const out8 = reinterpret_cast<unsigned char*>(out) + (size_t)b * T * T * 3;
-    const double bx = states[4 * b + 0], by = states[4 * b + 1], bw = states[4 * b + 2], bh = states[4 * b + 3];
-    const int crop_sz = (int)ceil(sqrt(bw * bh) * factor);
+    const int crop_sz = crop_side(states, b, factor);
     const int T4 = (T + 3) >> 2;
     const int idx = blockIdx.x * 256 + threadIdx.x;
     if (idx == 0) image_sizes_out(sizes, images, b);
-    if (!(crop_sz >= 1) || !iv.ok) {        // 'Too small bounding box.' (or an unusable descriptor): poison, as crop_kernel
+    if (!(crop_sz >= 1) || !iv.ok) {        // see poison_item
         if (idx == 0) resize_factor[b] = __builtin_nan("");
-        if (idx < T * T4) {
-            const int oy = idx / T4, ox0 = (idx - oy * T4) * 4;
-            for (int c = 0; c < 3; ++c)
-                for (int k = 0; k < 4 && ox0 + k < T; ++k) {
-                    if constexpr (U8OUT) out8[((size_t)oy * T + ox0 + k) * 3 + c] = 0;
-                    else out[(((size_t)b * 3 + c) * T + oy) * T + ox0 + k] = __builtin_nanf("");
-                }
-        }
+        if (idx < T * T4) poison_item<U8OUT, true>(out, out8, b, T, idx / T4, (idx - idx / T4 * T4) * 4);
         return;
     }
-    const int x1 = (int)rint(bx + 0.5 * bw - crop_sz * 0.5);
-    const int y1 = (int)rint(by + 0.5 * bh - crop_sz * 0.5);
-    const int x2 = x1 + crop_sz, y2 = y1 + crop_sz;
-    const int vx0 = x1 < 0 ? 0 : x1, vx1 = x2 - (x2 - iv.W + 1 > 0 ? x2 - iv.W + 1 : 0);
-    const int vy0 = y1 < 0 ? 0 : y1, vy1 = y2 - (y2 - iv.H + 1 > 0 ? y2 - iv.H + 1 : 0);
+    const CropWindow g = crop_window(states, b, crop_sz, T, iv.H, iv.W);
     if (idx == 0) resize_factor[b] = (double)T / (double)crop_sz;
     if (idx >= T * T4) return;
     const int oy = idx / T4, ox0 = (idx - oy * T4) * 4;
-    const double scale = (double)crop_sz / (double)T;
     int sy0, sy1, by0, by1;
-    lin_coeff(oy, crop_sz, scale, sy0, sy1, by0, by1);
+    lin_coeff(oy, g.crop_sz, g.scale, sy0, sy1, by0, by1);
     const auto rs0 = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned char*>(iv.p0), 0, (int)iv.nrec0, 0x00020000);
     auto byte0 = [&](unsigned o) { return (unsigned)__builtin_amdgcn_raw_buffer_load_b8(rs0, (int)o, 0, 0) & 0xffu; };
     const int fmt = iv.fmt;
@@ -902,25 +918,26 @@ __global__ __launch_bounds__(256) void crop_image_kernel(const vt_image* __restr
         }
         if (fmt == VT_PIX_GRAY8) return byte0((unsigned)y * iv.pitch0 + (unsigned)x) * 0x010101u;
         const unsigned o = (unsigned)y * iv.pitch0 + (unsigned)x * ((fmt == VT_PIX_RGBA || fmt == VT_PIX_BGRA) ? 4u : 3u);
-        const unsigned a = byte0(o), g = byte0(o + 1u), c = byte0(o + 2u);
-        return swap ? (c | (g << 8) | (a << 16)) : (a | (g << 8) | (c << 16));
+        const unsigned a = byte0(o), gr = byte0(o + 1u), c = byte0(o + 2u);
+        return swap ? (c | (gr << 8) | (a << 16)) : (a | (gr << 8) | (c << 16));
     };
-    const int yy0 = y1 + sy0, yy1 = y1 + sy1;
-    const bool vr0 = yy0 >= vy0 && yy0 < vy1, vr1 = yy1 >= vy0 && yy1 < vy1;
+    const int yy0 = g.y1 + sy0, yy1 = g.y1 + sy1;
+    const bool vr0 = yy0 >= g.vy0 && yy0 < g.vy1, vr1 = yy1 >= g.vy0 && yy1 < g.vy1;
     float res[3][4];
     unsigned pk[3] = {0u, 0u, 0u};
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
         const int ox = ox0 + k < T ? ox0 + k : T - 1;
         int sx0, sx1, ax0, ax1;
-        lin_coeff(ox, crop_sz, scale, sx0, sx1, ax0, ax1);
-        const int xx0 = x1 + sx0, xx1 = x1 + sx1;
-        const bool vc0 = xx0 >= vx0 && xx0 < vx1, vc1 = xx1 >= vx0 && xx1 < vx1;
+        lin_coeff(ox, g.crop_sz, g.scale, sx0, sx1, ax0, ax1);
+        const int xx0 = g.x1 + sx0, xx1 = g.x1 + sx1;
+        const bool vc0 = xx0 >= g.vx0 && xx0 < g.vx1, vc1 = xx1 >= g.vx0 && xx1 < g.vx1;
         // pixel (cy, cx) of the zero-padded crop: rgb(d) inside the valid range, 0 outside (all channels)
         const unsigned l0 = vr0 && vc0 ? pixel(xx0, yy0) : 0u, l1 = vr1 && vc0 ? pixel(xx0, yy1) : 0u;
         const unsigned r0w = vr0 && vc1 ? pixel(xx1, yy0) : 0u, r1w = vr1 && vc1 ? pixel(xx1, yy1) : 0u;
 #pragma unroll
         for (int c = 0; c < 3; ++c) {       // crop_kernel's arithmetic
+            // item 7b: not merged, see NOTES.md (crop kernels)
             const int p00 = (int)((l0 >> (8 * c)) & 0xffu), p01 = (int)((r0w >> (8 * c)) & 0xffu);
             const int p10 = (int)((l1 >> (8 * c)) & 0xffu), p11 = (int)((r1w >> (8 * c)) & 0xffu);
             const int r0 = __mul24(p00, ax0) + __mul24(p01, ax1);
@@ -934,7 +951,6 @@ __global__ __launch_bounds__(256) void crop_image_kernel(const vt_image* __restr
     if constexpr (U8OUT) {
         unsigned char* o = out8 + ((size_t)oy * T + ox0) * 3;
         if ((T & 3) == 0) {
-            typedef unsigned u3a __attribute__((ext_vector_type(3), aligned(4)));
             *reinterpret_cast<u3a*>(o) = u3a{pk[0], pk[1], pk[2]};
         } else {
             for (int i = 0; i < 12 && ox0 + i / 3 < T; ++i) o[i] = (unsigned char)(pk[i >> 2] >> (8 * (i & 3)));
@@ -974,41 +990,19 @@ __device__ __forceinline__ void crop_band_image_ext(const vt_image* __restrict__
     static_assert(T <= 256 && (T * T4) % (IPT * 256) == 0, "a band is whole rows and the frame whole bands");
     const int b = blockIdx.y, tid = threadIdx.x;
     const ImageView iv = image_view(images, b);
+    // item 11: not merged, see NOTES.md (crop kernels)
     __shared__ float norm_lut[U8OUT ? 1 : 3 * 256];
     __shared__ __attribute__((aligned(16))) unsigned xtab[T * 4];          // per output column: plane-0 byte offset of the window, packed weights, steps, chroma offset
     __shared__ __attribute__((aligned(16))) unsigned ytab[NROWS * 4];      // per output row: plane-0 offsets of its two source rows, their weights << 12
     __shared__ __attribute__((aligned(8))) unsigned ctab[NROWS * 2];       // per output row: chroma-row offsets of its two source rows (NV12 / NV21)
     unsigned char* const out8 = reinterpret_cast<unsigned char*>(out) + (size_t)b * T * T * 3;
-    typedef unsigned u3a __attribute__((ext_vector_type(3), aligned(4)));
-    typedef unsigned u4v __attribute__((ext_vector_type(4)));
-    typedef unsigned u3v __attribute__((ext_vector_type(3)));
-    typedef unsigned u2v __attribute__((ext_vector_type(2)));
-    typedef unsigned short us2 __attribute__((ext_vector_type(2)));
-    if constexpr (!U8OUT) {
-        const float meanv[3] = {m0, m1, m2}, stdq[3] = {s0, s1, s2};
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            float scaled = (float)tid * (1.0f / 255.0f);
-            asm volatile("" : "+v"(scaled));
-            float centred = scaled - meanv[c];
-            asm volatile("" : "+v"(centred));
-            norm_lut[c * 256 + tid] = centred / stdq[c];
-        }
-    }
-    const double bx = states[4 * b + 0], by = states[4 * b + 1], bw = states[4 * b + 2], bh = states[4 * b + 3];
-    const int crop_sz = (int)ceil(sqrt(bw * bh) * factor);
+    if constexpr (!U8OUT) fill_norm_lut(norm_lut, m0, m1, m2, s0, s1, s2);
+    const int crop_sz = crop_side(states, b, factor);
     const int row0 = blockIdx.x * NROWS;
     const int cg = tid & (T4 - 1), rl = tid >> LGT4;
     if (blockIdx.x == 0 && tid == 0) image_sizes_out(sizes, images, b);
-    if (!(crop_sz >= 1) || !iv.ok) {        // 'Too small bounding box.' (or an unusable descriptor): poison, as crop_kernel
-        if (blockIdx.x == 0 && tid == 0) resize_factor[b] = __builtin_nan("");
-#pragma unroll
-        for (int j = 0; j < IPT; ++j) {
-            const int oy = row0 + j * RPG + rl;
-            if constexpr (U8OUT) *reinterpret_cast<u3a*>(out8 + ((size_t)oy * T + 4 * cg) * 3) = u3a{0u, 0u, 0u};
-            else
-                for (int c = 0; c < 3; ++c) st4(out + (((size_t)b * 3 + c) * T + oy) * T + 4 * cg, splat4(__builtin_nanf("")));
-        }
+    if (!(crop_sz >= 1) || !iv.ok) {        // see poison_item
+        poison_band<U8OUT, T, IPT, RPG>(out, out8, resize_factor, b, row0, rl, cg);
         return;
     }
     const int fmt = iv.fmt;
@@ -1017,34 +1011,10 @@ __device__ __forceinline__ void crop_band_image_ext(const vt_image* __restrict__
     const YuvLayout yl = yuv_layout(iv);
     const YuvCoef kc = yuv_coef(iv.col);
     const unsigned bpp = (nv || newf) ? yl.ymul : (four ? 4u : 3u);
-    const int x1 = (int)rint(bx + 0.5 * bw - crop_sz * 0.5);
-    const int y1 = (int)rint(by + 0.5 * bh - crop_sz * 0.5);
-    const int x2 = x1 + crop_sz, y2 = y1 + crop_sz;
-    const int vx0 = x1 < 0 ? 0 : x1, vx1 = x2 - (x2 - iv.W + 1 > 0 ? x2 - iv.W + 1 : 0);
-    const int vy0 = y1 < 0 ? 0 : y1, vy1 = y2 - (y2 - iv.H + 1 > 0 ? y2 - iv.H + 1 : 0);
+    const CropWindow g = crop_window(states, b, crop_sz, T, iv.H, iv.W);
     if (blockIdx.x == 0 && tid == 0) resize_factor[b] = (double)T / (double)crop_sz;
-    const double scale = (double)crop_sz / (double)T;
-    if (tid < T) {                          // column entries: zero padding lives in the weights, as crop_band_kernel
-        int sx0, sx1, ax0, ax1;
-        lin_coeff(tid, crop_sz, scale, sx0, sx1, ax0, ax1);
-        const int xx0 = x1 + sx0, xx1 = x1 + sx1;
-        const bool vc0 = xx0 >= vx0 && xx0 < vx1, vc1 = xx1 >= vx0 && xx1 < vx1;
-        const int xb = vc0 ? xx0 : (vc1 ? xx1 : 0);
-        // steps: bit 0 = the right tap is the next pixel, bit 1 = its chroma pair is the next pair
-        const unsigned step = vc1 && xx1 != xb ? 1u : 0u, cstep = vc1 && (xx1 >> 1) != (xb >> 1) ? 2u : 0u;
-        *reinterpret_cast<u4v*>(xtab + 4 * tid) = u4v{bpp * (unsigned)xb + (newf ? yl.yadd : 0u), (unsigned)(vc0 ? ax0 : 0) | ((unsigned)(vc1 ? ax1 : 0) << 16),
-                                                       step | cstep, (newf ? yl.cmul : 2u) * (unsigned)(xb >> 1)};
-    }
-    if (tid >= 256 - NROWS) {               // row entries of the band
-        const int r = tid - (256 - NROWS);
-        int sy0, sy1, by0, by1;
-        lin_coeff(row0 + r, crop_sz, scale, sy0, sy1, by0, by1);
-        const int yy0 = y1 + sy0, yy1 = y1 + sy1;
-        const bool vr0 = yy0 >= vy0 && yy0 < vy1, vr1 = yy1 >= vy0 && yy1 < vy1;
-        const unsigned ya = (unsigned)(vr0 ? yy0 : 0), yb = (unsigned)(vr1 ? yy1 : 0);      // rows outside the valid range read row 0
-        *reinterpret_cast<u4v*>(ytab + 4 * r) = u4v{ya * iv.pitch0, yb * iv.pitch0, vr0 ? (unsigned)by0 << 12 : 0u, vr1 ? (unsigned)by1 << 12 : 0u};
-        *reinterpret_cast<u2v*>(ctab + 2 * r) = newf ? u2v{(ya >> yl.cys) * yl.cpitch, (yb >> yl.cys) * yl.cpitch} : u2v{(ya >> 1) * iv.pitch1, (yb >> 1) * iv.pitch1};
-    }
+    fill_band_tables<T, NROWS>(xtab, ytab, ctab, row0, g, iv.pitch0, newf ? yl.cys : 1u, newf ? yl.cpitch : iv.pitch1,
+                               [&](const ColumnTap& t) { return image_column_entry(t, bpp, newf ? yl.yadd : 0u, newf ? yl.cmul : 2u); });
     __syncthreads();
     const auto rs0 = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned char*>(iv.p0), 0, (int)iv.nrec0, 0x00020000);
     const bool c1 = nv || (newf && !yl.c0);      // chroma in plane 1; else (packed 4:2:2) in plane 0
@@ -1067,6 +1037,7 @@ __device__ __forceinline__ void crop_band_image_ext(const vt_image* __restrict__
     asm volatile("" : "+v"(two));
     const bool col_live = (wp[0] | wp[1] | wp[2] | wp[3]) != 0u;
     // the output of one item from its four tap-pair dwords per row (l = left tap, r = right tap: R | G << 8 | B << 16)
+    // item 7: not merged, see NOTES.md (crop kernels)
     auto finish = [&](int j, const unsigned (&l0)[4], const unsigned (&r0w)[4], const unsigned (&l1)[4], const unsigned (&r1w)[4],
                       unsigned byw0, unsigned byw1) {
         const int oy = row0 + j * RPG + rl;
@@ -1098,6 +1069,7 @@ __device__ __forceinline__ void crop_band_image_ext(const vt_image* __restrict__
     constexpr int HS = IPT < 2 ? IPT : 2;      // two items at a time, as crop_band_kernel
     // NV12 / NV21; GUARD: windows that would cross their plane's end are read as single bytes
     // VC: one of the three other colour rows -- the same windows, the coefficients and the luma floor from kc (SGPRs) instead of literals
+    // items 9 and 8: not merged, see NOTES.md (crop kernels)
     auto yuv = [&](auto guard_c) {
         constexpr bool GUARD = decltype(guard_c)::value;
         u2v ya0[IPT][4], ya1[IPT][4], ca0[IPT][4], ca1[IPT][4];
@@ -1253,9 +1225,7 @@ __device__ __forceinline__ void crop_band_image_ext(const vt_image* __restrict__
     };
     if (nv || fmt == VT_PIX_P010) {
         // the guard: a band whose valid source rows reach row H - 2 reads the last chroma row; planes narrower than 8 bytes
-        int sl0, sl1, al0, al1;
-        lin_coeff(row0 + NROWS - 1, crop_sz, scale, sl0, sl1, al0, al1);
-        const int ymax = y1 + sl1 < vy1 - 1 ? y1 + sl1 : vy1 - 1;
+        const int ymax = band_last_source_row<NROWS>(row0, g);
         const bool guard = ymax >= iv.H - 2 || iv.pitch0 < 8u || iv.pitch1 < 8u;
         if (!nv) {
             if (guard) p010(std::true_type{});
@@ -1301,69 +1271,22 @@ __global__ __launch_bounds__(256) void crop_band_image_kernel(const vt_image* __
     __shared__ __attribute__((aligned(16))) unsigned ytab[NROWS * 4];      // per output row: plane-0 offsets of its two source rows, their weights << 12
     __shared__ __attribute__((aligned(8))) unsigned ctab[NROWS * 2];       // per output row: chroma-row offsets of its two source rows (NV12 / NV21)
     unsigned char* const out8 = reinterpret_cast<unsigned char*>(out) + (size_t)b * T * T * 3;
-    typedef unsigned u3a __attribute__((ext_vector_type(3), aligned(4)));
-    typedef unsigned u4v __attribute__((ext_vector_type(4)));
-    typedef unsigned u3v __attribute__((ext_vector_type(3)));
-    typedef unsigned u2v __attribute__((ext_vector_type(2)));
-    typedef unsigned short us2 __attribute__((ext_vector_type(2)));
-    if constexpr (!U8OUT) {
-        const float meanv[3] = {m0, m1, m2}, stdq[3] = {s0, s1, s2};
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            float scaled = (float)tid * (1.0f / 255.0f);
-            asm volatile("" : "+v"(scaled));
-            float centred = scaled - meanv[c];
-            asm volatile("" : "+v"(centred));
-            norm_lut[c * 256 + tid] = centred / stdq[c];
-        }
-    }
-    const double bx = states[4 * b + 0], by = states[4 * b + 1], bw = states[4 * b + 2], bh = states[4 * b + 3];
-    const int crop_sz = (int)ceil(sqrt(bw * bh) * factor);
+    if constexpr (!U8OUT) fill_norm_lut(norm_lut, m0, m1, m2, s0, s1, s2);
+    const int crop_sz = crop_side(states, b, factor);
     const int row0 = blockIdx.x * NROWS;
     const int cg = tid & (T4 - 1), rl = tid >> LGT4;
     if (blockIdx.x == 0 && tid == 0) image_sizes_out(sizes, images, b);
-    if (!(crop_sz >= 1) || !iv.ok) {        // 'Too small bounding box.' (or an unusable descriptor): poison, as crop_kernel
-        if (blockIdx.x == 0 && tid == 0) resize_factor[b] = __builtin_nan("");
-#pragma unroll
-        for (int j = 0; j < IPT; ++j) {
-            const int oy = row0 + j * RPG + rl;
-            if constexpr (U8OUT) *reinterpret_cast<u3a*>(out8 + ((size_t)oy * T + 4 * cg) * 3) = u3a{0u, 0u, 0u};
-            else
-                for (int c = 0; c < 3; ++c) st4(out + (((size_t)b * 3 + c) * T + oy) * T + 4 * cg, splat4(__builtin_nanf("")));
-        }
+    if (!(crop_sz >= 1) || !iv.ok) {        // see poison_item
+        poison_band<U8OUT, T, IPT, RPG>(out, out8, resize_factor, b, row0, rl, cg);
         return;
     }
     const int fmt = iv.fmt;
     const bool nv = fmt == VT_PIX_NV12 || fmt == VT_PIX_NV21, four = fmt == VT_PIX_RGBA || fmt == VT_PIX_BGRA;
     const unsigned bpp = nv ? 1u : (four ? 4u : 3u);
-    const int x1 = (int)rint(bx + 0.5 * bw - crop_sz * 0.5);
-    const int y1 = (int)rint(by + 0.5 * bh - crop_sz * 0.5);
-    const int x2 = x1 + crop_sz, y2 = y1 + crop_sz;
-    const int vx0 = x1 < 0 ? 0 : x1, vx1 = x2 - (x2 - iv.W + 1 > 0 ? x2 - iv.W + 1 : 0);
-    const int vy0 = y1 < 0 ? 0 : y1, vy1 = y2 - (y2 - iv.H + 1 > 0 ? y2 - iv.H + 1 : 0);
+    const CropWindow g = crop_window(states, b, crop_sz, T, iv.H, iv.W);
     if (blockIdx.x == 0 && tid == 0) resize_factor[b] = (double)T / (double)crop_sz;
-    const double scale = (double)crop_sz / (double)T;
-    if (tid < T) {                          // column entries: zero padding lives in the weights, as crop_band_kernel
-        int sx0, sx1, ax0, ax1;
-        lin_coeff(tid, crop_sz, scale, sx0, sx1, ax0, ax1);
-        const int xx0 = x1 + sx0, xx1 = x1 + sx1;
-        const bool vc0 = xx0 >= vx0 && xx0 < vx1, vc1 = xx1 >= vx0 && xx1 < vx1;
-        const int xb = vc0 ? xx0 : (vc1 ? xx1 : 0);
-        // steps: bit 0 = the right tap is the next pixel, bit 1 = its chroma pair is the next pair
-        const unsigned step = vc1 && xx1 != xb ? 1u : 0u, cstep = vc1 && (xx1 >> 1) != (xb >> 1) ? 2u : 0u;
-        *reinterpret_cast<u4v*>(xtab + 4 * tid) = u4v{bpp * (unsigned)xb, (unsigned)(vc0 ? ax0 : 0) | ((unsigned)(vc1 ? ax1 : 0) << 16),
-                                                       step | cstep, 2u * (unsigned)(xb >> 1)};
-    }
-    if (tid >= 256 - NROWS) {               // row entries of the band
-        const int r = tid - (256 - NROWS);
-        int sy0, sy1, by0, by1;
-        lin_coeff(row0 + r, crop_sz, scale, sy0, sy1, by0, by1);
-        const int yy0 = y1 + sy0, yy1 = y1 + sy1;
-        const bool vr0 = yy0 >= vy0 && yy0 < vy1, vr1 = yy1 >= vy0 && yy1 < vy1;
-        const unsigned ya = (unsigned)(vr0 ? yy0 : 0), yb = (unsigned)(vr1 ? yy1 : 0);      // rows outside the valid range read row 0
-        *reinterpret_cast<u4v*>(ytab + 4 * r) = u4v{ya * iv.pitch0, yb * iv.pitch0, vr0 ? (unsigned)by0 << 12 : 0u, vr1 ? (unsigned)by1 << 12 : 0u};
-        *reinterpret_cast<u2v*>(ctab + 2 * r) = u2v{(ya >> 1) * iv.pitch1, (yb >> 1) * iv.pitch1};
-    }
+    fill_band_tables<T, NROWS>(xtab, ytab, ctab, row0, g, iv.pitch0, 1u, iv.pitch1,
+                               [&](const ColumnTap& t) { return image_column_entry(t, bpp, 0u, 2u); });
     __syncthreads();
     const auto rs0 = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned char*>(iv.p0), 0, (int)iv.nrec0, 0x00020000);
     const auto rs1 = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned char*>(nv ? iv.p1 : iv.p0), 0, (int)iv.nrec1, 0x00020000);
@@ -1384,6 +1307,7 @@ __global__ __launch_bounds__(256) void crop_band_image_kernel(const vt_image* __
     asm volatile("" : "+v"(two));
     const bool col_live = (wp[0] | wp[1] | wp[2] | wp[3]) != 0u;
     // the output of one item from its four tap-pair dwords per row (l = left tap, r = right tap: R | G << 8 | B << 16)
+    // item 7: not merged, see NOTES.md (crop kernels)
     auto finish = [&](int j, const unsigned (&l0)[4], const unsigned (&r0w)[4], const unsigned (&l1)[4], const unsigned (&r1w)[4],
                       unsigned byw0, unsigned byw1) {
         const int oy = row0 + j * RPG + rl;
@@ -1414,6 +1338,7 @@ __global__ __launch_bounds__(256) void crop_band_image_kernel(const vt_image* __
     };
     constexpr int HS = IPT < 2 ? IPT : 2;      // two items at a time, as crop_band_kernel
     // packed formats: BPP 3 or 4
+    // item 8: not merged, see NOTES.md (crop kernels)
     auto packed = [&](auto bpp_c) {
         constexpr unsigned BPP = decltype(bpp_c)::value;
         u3v ra0[IPT][4], ra1[IPT][4];
@@ -1457,6 +1382,7 @@ __global__ __launch_bounds__(256) void crop_band_image_kernel(const vt_image* __
         }
     };
     // NV12 / NV21; GUARD: windows that would cross their plane's end are read as single bytes
+    // items 9 and 8: not merged, see NOTES.md (crop kernels)
     auto yuv = [&](auto guard_c) {
         constexpr bool GUARD = decltype(guard_c)::value;
         u2v ya0[IPT][4], ya1[IPT][4], ca0[IPT][4], ca1[IPT][4];
@@ -1516,9 +1442,7 @@ __global__ __launch_bounds__(256) void crop_band_image_kernel(const vt_image* __
     };
     if (nv) {
         // the guard: a band whose valid source rows reach row H - 2 reads the last chroma row; planes narrower than 8 bytes
-        int sl0, sl1, al0, al1;
-        lin_coeff(row0 + NROWS - 1, crop_sz, scale, sl0, sl1, al0, al1);
-        const int ymax = y1 + sl1 < vy1 - 1 ? y1 + sl1 : vy1 - 1;
+        const int ymax = band_last_source_row<NROWS>(row0, g);
         if (ymax >= iv.H - 2 || iv.pitch0 < 8u || iv.pitch1 < 8u) yuv(std::true_type{});
         else yuv(std::false_type{});
     } else if (four) {
