@@ -51,7 +51,8 @@ typedef struct vt_graph vt_graph;
  *     plain fp32, one thread per output value, reference-implementation speed, the same outputs (held to the reference's own outputs at
  *     two other width triples: tests/golden/make_golden_cfg.py) and the whole ABI (stages, template cache, graphs, vt_crop / vt_track_step,
  *     uint8 patches).
- *     channels 768, heads 12, head_channels 256, stride 16, (template, search) = (128, 256), depth 12                   -- ViT-Base
+ *     channels 768, heads 12, head_channels 256, stride 16, depth 1..24 (12), (template, search) = (128, 256) or (192, 384) -- ViT-Base:
+ *         OSTrack-256 (64 + 256 = 320 tokens, 16 x 16 maps) and OSTrack-384 (144 + 576 = 720 tokens, 24 x 24 maps)
  * and rejects everything else with VT_ERR_ARG and a message naming these.  The tuned kernels are specialised on their tile
  * counts (token tiles per frame, feature chunks, map sides are template parameters -- that is where their register blocking comes
  * from), so widths and crop sizes are NOT run-time parameters of THOSE kernels. */
@@ -91,8 +92,13 @@ const char* vt_version(void);
 /* build_ostrack_dist(cfg) + .cuda() on the current device (vit_dist.py:159-164;
  * lib/test/tracker/vit_dist.py:24-28).  Supported: see SUPPORTED SHAPES above (the shipped vit_48_h32 on tuned kernels -- fp32, or
  * f16 contractions in libvittrack_hip_f16.so --, any other widths / stride-16 geometry on the shape-generic fp32 kernels), and
- * channels 768, heads 12, head_channels 256, (128,256): the OSTrack-256 ViT-Base
- * (lib/models/ostrack/ostrack.py:164-286 with lib/models/ostrack/vit.py:94-139; bf16 contractions). */
+ * channels 768, heads 12, head_channels 256 at (128,256) or (192,384): the OSTrack-256 / OSTrack-384 ViT-Base
+ * (lib/models/ostrack/ostrack.py:164-286 with lib/models/ostrack/vit.py:94-139; bf16 contractions).  The two geometries run the same
+ * GEMM, LayerNorm and head kernels on run-time token counts and map sides; attention is the 320-token kernels at (128,256) (fused with
+ * the qkv projection unless VB_FUSED_QKV=0) and, at (192,384), always qk GEMM + v GEMM + the key-streaming kernel of vb_attn_stream.h
+ * (VB_FUSED_QKV has no effect there; VB_ATTN_STREAM=1 with VB_FUSED_QKV=0 selects that kernel at (128,256) too).  Crops are 192 px /
+ * 384 px, uint8 patches (B,384,384,3) with 1152-byte rows, the template cache max_batch x 144 operand rows, the Hann window 576 values.
+ * Any other ViT-Base geometry or width: VT_ERR_ARG, "unsupported ViT-Base configuration" naming both. */
 int vt_create(const vt_config* cfg, vt_model** out);
 void vt_destroy(vt_model* m);
 

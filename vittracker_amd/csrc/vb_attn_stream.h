@@ -1,0 +1,221 @@
+// vb_attn_stream.h -- key-streaming multi-head self-attention for token counts that fit neither the LDS nor one softmax row in
+// registers (OSTrack-384: L = 144 + 576 = 720), bf16 MFMA, gfx950.  Same arithmetic as vb_attn.h (v_mfma_f32_16x16x32_bf16, keys on
+// the MFMA rows for S^T = K q^T, P rounded to bf16 and fed to O^T = V^T P^T from S^T's own registers, f32 max / sum / accumulators,
+// exp2 with the log2 e factor), same inputs and output: qk [M][2 C] (q pre-scaled | k) from the EPI_BF16 GEMM, vt [frame][C][L] from
+// the EPI_VT GEMM, out [M][C].
+//
+// Plan.  One workgroup = one (frame, head, query range): 4 waves x NQ = 3 query tiles of 16 = 192 queries, all of a wave's tiles in ONE
+// pass over the keys, so a (frame, head) is split over ceil(L / 192) workgroups (L = 720: 4, the last with 9 of its 12 tile slots in
+// use; L = 320: 2).  Keys are streamed in chunks of KC = 64 (L = 720: 11 whole chunks + one of 32 keys of which 16 exist; L = 320: 5
+// whole chunks) with an online softmax: per query a running max m and a per-lane partial sum l; when a chunk moves the max, l and
+// the O accumulators are rescaled by exp2((m_old - m_new) log2 e).  m starts at -1e30 (finite: no inf - inf), so the first chunk's
+// rescale factor is exactly 0 on accumulators that are exactly 0.
+//
+// LDS: a chunk is 8 KiB of K (4 key tiles x 2 k-steps of 1 KiB st_16x32 sub-tiles, rows permuted as in vb_attn.h so that P's
+// B-operand is S^T's registers) + 8 KiB of V^T (4 d tiles x 2 32-key sub-chunks) = 16 KiB, double-buffered: 32 KiB per workgroup
+// (<= 80 KiB: two workgroups per CU, 8 waves = 2 per SIMD, 256 VGPRs each).  Every piece is one LDS-DMA wave-instruction (vbg::glds16),
+// 4 per wave and chunk.  Per chunk ONE barrier: wait for the own pieces of chunk c, barrier (chunk c has landed for everyone, and
+// everyone is done reading chunk c - 1's buffer), issue chunk c + 1's DMA into that buffer, then run chunk c's 16 NQ MFMAs per wave
+// under it.
+//
+// Registers per wave (NQ = 3): S 3 x 16 + O 3 x 16 + q fragments 3 x 8 + m, l 6 + K / V^T fragment and P operands + addresses:
+// measured 172 VGPRs at L = 720 and 166 at L = 320 of the 256 the two-workgroup occupancy allows, ScratchSize 0
+// (profiles/r6_resource_usage.txt).  Every K / V^T fragment read from LDS feeds NQ = 3 MFMAs.
+//
+// The partial last chunk (L % 32 = 16).  A lane's eight scores of a 32-key sub-chunk are keys 32 c + 8 (lane >> 4) + {0..7}: those
+// >= L are set to -inf BEFORE the chunk maximum, so their P is exp2(-inf) = 0 whatever the K rows read there held, and the V^T
+// fragment's columns for those keys are set to 0 in registers (the same lane arithmetic: V^T's k elements of a lane are the same eight
+// keys), so 0 x V^T is 0 whatever was staged -- a NaN in a neighbour frame cannot reach this one.  What is READ past a frame's last token
+// is therefore never used, it only has to be mapped memory: the next frame's rows / the head of the next feature row (possibly stale,
+// possibly being written by another chain's GEMM at that moment: whole bf16 elements, discarded either way), and past the last frame
+// the 32-row / 32-element tail both workspaces carry (vitb.hip zero-fills them once, at create).
+//
+// Remainder query tiles (45 tiles over 4 x 12 slots): a slot beyond the last tile computes the last tile again and does not store;
+// no wave leaves the chunk loop early, every wave meets every barrier.
+#pragma once
+#include "vb_attn.h"
+
+namespace vbs {
+
+using vbg::bf16;
+using vbg::bf16x4;
+using vbg::bf16x8;
+
+constexpr int KC = 64;                      // keys per chunk
+constexpr int NQ = 3;                       // query tiles per wave
+constexpr int WAVES = 4;
+constexpr int QT_PER_WG = WAVES * NQ;       // 12 tiles = 192 queries per workgroup
+constexpr int CHUNK_BYTES = 2 * KC * 64 * 2;      // K + V^T, HD = 64
+constexpr int LDS_BYTES = 2 * CHUNK_BYTES;        // double-buffered: 32 KiB
+constexpr int PAD_TOKENS = 32;              // rows (qk) / elements (vt) the last chunk may read past the workspace's last frame
+
+template <int L> constexpr int splits() { return (L / 16 + QT_PER_WG - 1) / QT_PER_WG; }
+
+// grid = B * heads * splits<L>(), 256 threads, LDS_BYTES of dynamic LDS
+template <int L>
+__global__ __launch_bounds__(256, 2) void attn_stream_kernel(const bf16* __restrict__ qk, const bf16* __restrict__ vt,
+                                                          bf16* __restrict__ out, int heads) {
+    constexpr int HD = 64, KS = HD / 32, DT = HD / 16;
+    constexpr int NT = L / 16;                         // query tiles
+    constexpr int NSUB = (L + 31) / 32;                // 32-key sub-chunks, the last one partial when L % 32 != 0
+    constexpr int NCH = (NSUB + 1) / 2;                // chunks
+    constexpr int LAST_SUB = NSUB - 2 * (NCH - 1);     // sub-chunks of the last chunk (1 or 2)
+    constexpr bool PARTIAL = L % 32 != 0;
+    constexpr int SPLITS = splits<L>();
+    static_assert(L % 16 == 0 && L % 8 == 0 && NCH >= 2, "token count");
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int fh = blockIdx.x / SPLITS, sp = blockIdx.x - fh * SPLITS;
+    const int f = fh / heads, h = fh - f * heads, C = heads * HD;
+    const bf16* qf = qk + (size_t)f * L * 2 * C + h * HD;          // q rows of this frame / head
+    const bf16* kf = qf + C;
+    const bf16* vf = vt + ((size_t)f * C + h * HD) * L;
+    const int l15 = lane & 15, q = lane >> 4;
+
+    // this wave's query tiles; a slot past the last tile recomputes the last tile and stores nothing
+    int qts[NQ];
+    bf16x8 qfrag[NQ][KS];
+#pragma unroll
+    for (int u = 0; u < NQ; ++u) {
+        qts[u] = sp * QT_PER_WG + w * NQ + u;
+        const int qt = qts[u] < NT ? qts[u] : NT - 1;
+#pragma unroll
+        for (int ks = 0; ks < KS; ++ks)
+            qfrag[u][ks] = *reinterpret_cast<const bf16x8*>(qf + (size_t)(qt * 16 + l15) * 2 * C + ks * 32 + q * 8);
+    }
+
+    // ---- staging: chunk c's K rows (permuted) and V^T columns into buffer `b`, nsub 32-key sub-chunks of it; 2 nsub pieces per wave
+    const int pl = vbg::swz_byte(lane * 16), prow = pl >> 6, pk = (pl & 63) >> 1;
+    auto stage = [&](int c, int b, int nsub) {
+        char* Kimg = smem + b * CHUNK_BYTES;
+        char* Vimg = Kimg + KC * HD * 2;
+        for (int s = w; s < nsub * 2 * KS; s += WAVES) {           // K sub-tile s = key tile t (of this chunk) x k-step
+            const int t = s / KS, ks = s - t * KS;
+            const int key = c * KC + 32 * (t >> 1) + 8 * (prow >> 2) + (prow & 3) + 4 * (t & 1);
+            vbg::glds16(kf + (size_t)key * 2 * C + ks * 32 + pk, Kimg + s * 1024 + lane * 16);
+        }
+        for (int s = w; s < nsub * DT; s += WAVES) {               // V^T sub-tile s = d tile x sub-chunk (sub-chunk fastest)
+            const int dt = s / nsub, sc = s - dt * nsub;
+            vbg::glds16(vf + (size_t)(dt * 16 + prow) * L + c * KC + sc * 32 + pk, Vimg + (dt * 2 + sc) * 1024 + lane * 16);
+        }
+    };
+
+    const int fr = vbg::swz_byte(l15 * 64 + q * 16);
+    constexpr float LOG2E = 1.4426950408889634f;
+    float mrun[NQ], lsum[NQ];
+    f4 O[NQ][DT];
+#pragma unroll
+    for (int u = 0; u < NQ; ++u) {
+        mrun[u] = -1e30f;
+        lsum[u] = 0.f;
+#pragma unroll
+        for (int dt = 0; dt < DT; ++dt) O[u][dt] = splat4(0.f);
+    }
+
+    // ---- one chunk: S^T = K q^T on NS sub-chunks, online softmax, O^T += V^T P^T
+    auto compute = [&](auto ns_tag, auto mask_tag, int c, int b) {
+        constexpr int NS = decltype(ns_tag)::value;
+        constexpr bool MASK = decltype(mask_tag)::value;
+        const char* Kimg = smem + b * CHUNK_BYTES;
+        const char* Vimg = Kimg + KC * HD * 2;
+        f4 S[NQ][2 * NS];
+#pragma unroll
+        for (int t = 0; t < 2 * NS; ++t) {
+#pragma unroll
+            for (int u = 0; u < NQ; ++u) S[u][t] = splat4(0.f);
+#pragma unroll
+            for (int ks = 0; ks < KS; ++ks) {
+                const bf16x8 kf8 = *reinterpret_cast<const bf16x8*>(Kimg + (t * KS + ks) * 1024 + fr);
+#pragma unroll
+                for (int u = 0; u < NQ; ++u) S[u][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf8, qfrag[u][ks], S[u][t], 0, 0, 0);
+            }
+        }
+        if constexpr (MASK) {      // the last sub-chunk: this lane's keys are base + {0..3} (even tile) and base + 4 + {0..3} (odd tile)
+            const int base = c * KC + (NS - 1) * 32 + 8 * q;
+#pragma unroll
+            for (int u = 0; u < NQ; ++u)
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    if (base + j >= L) S[u][2 * NS - 2][j] = -INFINITY;
+                    if (base + 4 + j >= L) S[u][2 * NS - 1][j] = -INFINITY;
+                }
+        }
+#pragma unroll
+        for (int u = 0; u < NQ; ++u) {
+            float m0 = fmaxf(S[u][0].x, S[u][0].y), m1 = fmaxf(S[u][0].z, S[u][0].w);
+#pragma unroll
+            for (int t = 1; t < 2 * NS; ++t) {
+                m0 = fmaxf(fmaxf(m0, S[u][t].x), S[u][t].y);
+                m1 = fmaxf(fmaxf(m1, S[u][t].z), S[u][t].w);
+            }
+            const float mx = fmaxf(mrun[u], quad_max(fmaxf(m0, m1)));      // finite: every chunk holds an existing key
+            const float alpha = __builtin_amdgcn_exp2f((mrun[u] - mx) * LOG2E);
+            mrun[u] = mx;
+            const vbg::f2 l2 = {LOG2E, LOG2E}, nmb = {-mx * LOG2E, -mx * LOG2E};
+            vbg::f2 s0 = {0.f, 0.f}, s1 = {0.f, 0.f};
+#pragma unroll
+            for (int t = 0; t < 2 * NS; ++t) {
+                const vbg::f2 a = __builtin_elementwise_fma(vbg::f2{S[u][t].x, S[u][t].y}, l2, nmb);
+                const vbg::f2 b2 = __builtin_elementwise_fma(vbg::f2{S[u][t].z, S[u][t].w}, l2, nmb);
+                const vbg::f2 pa = {__builtin_amdgcn_exp2f(a.x), __builtin_amdgcn_exp2f(a.y)};
+                const vbg::f2 pb = {__builtin_amdgcn_exp2f(b2.x), __builtin_amdgcn_exp2f(b2.y)};
+                S[u][t] = f4{pa.x, pa.y, pb.x, pb.y};
+                s0 += pa;
+                s1 += pb;
+            }
+            const vbg::f2 st = s0 + s1;
+            lsum[u] = fmaf(lsum[u], alpha, st.x + st.y);      // this lane's keys only: the four lane groups are summed once, at the end
+#pragma unroll
+            for (int dt = 0; dt < DT; ++dt) O[u][dt] = O[u][dt] * splat4(alpha);
+        }
+#pragma unroll
+        for (int sc = 0; sc < NS; ++sc) {
+            bf16x8 p[NQ];
+#pragma unroll
+            for (int u = 0; u < NQ; ++u) {
+                const bf16x4 lo = vbg::to_bf16x4(S[u][2 * sc]), hi = vbg::to_bf16x4(S[u][2 * sc + 1]);
+                p[u] = bf16x8{lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
+            }
+#pragma unroll
+            for (int dt = 0; dt < DT; ++dt) {
+                bf16x8 vf8 = *reinterpret_cast<const bf16x8*>(Vimg + (dt * 2 + sc) * 1024 + fr);
+                if constexpr (MASK) {      // this lane's V^T columns are keys base + {0..7}: those past the frame are not the frame's, so they are 0
+                    if (sc == NS - 1) {
+                        const int base = c * KC + sc * 32 + 8 * q;
+#pragma unroll
+                        for (int j = 0; j < 8; ++j)
+                            if (base + j >= L) vf8[j] = (bf16)0.0f;
+                    }
+                }
+#pragma unroll
+                for (int u = 0; u < NQ; ++u) O[u][dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vf8, p[u], O[u][dt], 0, 0, 0);
+            }
+        }
+    };
+
+    using I1 = std::integral_constant<int, 1>;
+    using I2 = std::integral_constant<int, 2>;
+    stage(0, 0, 2);
+    for (int c = 0; c + 1 < NCH; ++c) {
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // this wave's pieces of chunk c (and, at c = 0, its q fragments)
+        __syncthreads();                                     // chunk c is whole; nobody reads chunk c - 1's buffer any more
+        stage(c + 1, (c + 1) & 1, c + 2 < NCH ? 2 : LAST_SUB);
+        compute(I2{}, std::false_type{}, c, c & 1);
+    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    if constexpr (LAST_SUB == 2) compute(I2{}, std::integral_constant<bool, PARTIAL>{}, NCH - 1, (NCH - 1) & 1);
+    else compute(I1{}, std::integral_constant<bool, PARTIAL>{}, NCH - 1, (NCH - 1) & 1);
+
+#pragma unroll
+    for (int u = 0; u < NQ; ++u) {
+        const float inv = 1.0f / quad_sum(lsum[u]);
+        if (qts[u] < NT) {
+            bf16* o = out + (size_t)(f * L + qts[u] * 16 + l15) * C + h * HD + q * 4;
+#pragma unroll
+            for (int dt = 0; dt < DT; ++dt) *reinterpret_cast<bf16x4*>(o + dt * 16) = vbg::to_bf16x4(O[u][dt] * splat4(inv));
+        }
+    }
+}
+
+}  // namespace vbs

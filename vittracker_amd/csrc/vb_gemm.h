@@ -88,6 +88,9 @@ enum Epi {
     EPI_VT = 5,      // vt[frame][n][token] = bf16(acc + bias[n]): the v projection, stored transposed (operands swapped)
     EPI_PATCH_ROWS = 6,   // EPI_PATCH on a dense operand of ONE token kind (template rows or search rows only): operand row m is token
                           // row_o0 + m % 2^row_shift of frame m >> row_shift and lands on row frame * L + token of resid / xb / stats
+    EPI_PATCH_ROWS_N = 7, // EPI_PATCH_ROWS for a kind whose rows per frame are no power of two (OSTrack-384: 144 / 576): Args::row_shift
+                          // holds the rows per frame themselves, frame = m / rows by a multiply-high with ceil(2^32 / rows), exact
+                          // while M * rows < 2^32 (checked by the host).  Its own instantiation: EPI_PATCH_ROWS keeps its code
 };
 
 struct Args {
@@ -125,7 +128,8 @@ struct Args {
     int dbg;              // timing experiments only (VB_DBG, wrong results by design; 0 in production):
                           // 1 = every tile loads the X panel of tile row 0, 2 = ... the W panel of tile column 0,
                           // 4 = no MFMAs, 8 = no epilogue, 16 = no W staging, 32 = no X staging (wide tile)
-    int row_shift, row_o0;      // EPI_PATCH_ROWS: log2(operand rows per frame), first token of the kind (0: template, Lz: search)
+    int row_shift, row_o0;      // EPI_PATCH_ROWS: log2(operand rows per frame), first token of the kind (0: template, Lz: search);
+                                // EPI_PATCH_ROWS_N: row_shift = the operand rows per frame (not their log2)
 };
 
 // The epilogue staging area is written and read back through differently typed pointers by the same wave: the accesses
@@ -319,7 +323,7 @@ __global__ __launch_bounds__(NWAVES * 64) void gemm_kernel(const Args a) {
         f4 bs[TN];
 #pragma unroll
         for (int i = 0; i < TN; ++i) bs[i] = *reinterpret_cast<const f4a*>(ep + (i * 16 + q4) * 4);
-        if constexpr (EPI == EPI_RESID || EPI == EPI_PATCH || EPI == EPI_PATCH_ROWS) {
+        if constexpr (EPI == EPI_RESID || EPI == EPI_PATCH || EPI == EPI_PATCH_ROWS || EPI == EPI_PATCH_ROWS_N) {
             lds_fence();
             // f32 residual stream: chunk = 16 rows x 256 B; read-modify-write in whole rows, loads before stores.  Next to it
             // (LayerNorm folded into the next GEMM): the rows' bf16 copy and, per row, this wave's 64-column (sum, centred M2)
@@ -332,14 +336,20 @@ __global__ __launch_bounds__(NWAVES * 64) void gemm_kernel(const Args a) {
                               // (the same few KB for all twelve column tiles of a row: L1 / L2 hits; a ring of AH + 1 sets spilled 40 B)
             const int ch = lane & 15, r0 = lane >> 4;
             // EPI_PATCH_ROWS: the token of operand row m, and the row of the (frame, token) matrices it is written to
-            auto tok = [&](int m) { return a.row_o0 + (m & ((1 << a.row_shift) - 1)); };
-            auto orow = [&](int m) { return EPI == EPI_PATCH_ROWS ? (m >> a.row_shift) * a.L + tok(m) : m; };
+            constexpr bool ROWS = EPI == EPI_PATCH_ROWS || EPI == EPI_PATCH_ROWS_N;
+            const unsigned rows_magic = EPI == EPI_PATCH_ROWS_N ? 0xFFFFFFFFu / (unsigned)a.row_shift + 1u : 0u;      // ceil(2^32 / rows)
+            auto frame = [&](int m) { return EPI == EPI_PATCH_ROWS_N ? (int)__umulhi((unsigned)m, rows_magic) : m >> a.row_shift; };
+            auto tok = [&](int m) {
+                if constexpr (EPI == EPI_PATCH_ROWS_N) return a.row_o0 + m - frame(m) * a.row_shift;
+                else return a.row_o0 + (m & ((1 << a.row_shift) - 1));
+            };
+            auto orow = [&](int m) { return ROWS ? frame(m) * a.L + tok(m) : m; };
             auto load_c = [&](int j, float (&oc)[4]) {
 #pragma unroll
                 for (int t = 0; t < 4; ++t) {
                     const int m = mw + j * 16 + 4 * t + r0;
                     const int mc = CHECK ? (m < a.M ? m : a.M - 1) : m;
-                    if constexpr (EPI == EPI_PATCH_ROWS) oc[t] = (a.xb && a.cm) ? a.cm[tok(mc)] : 0.f;
+                    if constexpr (ROWS) oc[t] = (a.xb && a.cm) ? a.cm[tok(mc)] : 0.f;
                     else oc[t] = (a.xb && a.cm) ? a.cm[a.cm_mod ? mc % a.cm_mod : mc] : 0.f;
                 }
             };
@@ -351,7 +361,7 @@ __global__ __launch_bounds__(NWAVES * 64) void gemm_kernel(const Args a) {
                     if constexpr (EPI == EPI_RESID)
                         o[t] = VB_EPI_NT ? __builtin_nontemporal_load(reinterpret_cast<const f4*>(a.resid + (size_t)mc * a.N + nw + ch * 4))
                                          : ld4(a.resid + (size_t)mc * a.N + nw + ch * 4);
-                    else if constexpr (EPI == EPI_PATCH_ROWS) o[t] = ld4(a.pos + (size_t)tok(mc) * a.N + nw + ch * 4);
+                    else if constexpr (ROWS) o[t] = ld4(a.pos + (size_t)tok(mc) * a.N + nw + ch * 4);
                     else o[t] = ld4(a.pos + (size_t)(mc % a.L) * a.N + nw + ch * 4);
                 }
             };

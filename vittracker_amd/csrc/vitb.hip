@@ -1,6 +1,7 @@
 // vitb.hip -- host side of the ViT-Base OSTrack path (BASELINE config 4): weight packing (bf16, BatchNorm folded, conv
 // weights as [cout][tap][cin], attention scale folded into W_q), workspace, launch sequence.  Kernels: vb_gemm.h,
-// vb_attn.h, vb_misc.h.  Reached through the same C ABI as the vit_48 path (vt_create with channels = 768).
+// vb_attn.h, vb_qkvattn.h, vb_attn_stream.h (the 384 geometry's attention), vb_misc.h.  Reached through the same C ABI as the
+// vit_48 path (vt_create with channels = 768).
 #include "vb_api.h"
 
 #include <algorithm>
@@ -10,6 +11,7 @@
 #include <vector>
 
 #include "vb_attn.h"
+#include "vb_attn_stream.h"
 #include "vb_gemm.h"
 #include "vb_misc.h"
 #include "vb_qkvattn.h"
@@ -18,7 +20,10 @@ using vbg::bf16;
 
 namespace {
 
-constexpr int C = 768, HEADS = 12, HD = 64, HID = 3072, L = 320, LZ = 64, LX = 256, F = 16, PATCH_K = 768, HW = 256 /* head width */;
+constexpr int C = 768, HEADS = 12, HD = 64, HID = 3072, PATCH_K = 768, HW = 256 /* head width */;
+// The two geometries (template / search crop -> tokens at stride 16): OSTrack-256 = 128 / 256 -> 64 + 256 = 320, OSTrack-384 = 192 / 384 ->
+// 144 + 576 = 720.  The model carries its own (VbModel::L, LZ, LX, F, TZ, TX); the token counts below are the attention kernels' template arguments.
+constexpr int L256 = 320, L384 = 720;
 constexpr float LN_EPS = 1e-6f;
 constexpr int HEAD_CH[5] = {768, 256, 128, 64, 32};
 
@@ -58,6 +63,10 @@ struct BlockW {
 struct VbModel {
     vt_config cfg{};
     int depth = 12, maxB = 0;
+    int TZ = 128, TX = 256, LZ = 64, LX = 256, L = 320, F = 16;      // crop sides, template / search / all tokens per frame, head map side
+    int zshift = 6, xshift = 8;     // log2(LZ), log2(LX) where they are powers of two (EPI_PATCH_ROWS); -1 otherwise (EPI_PATCH_ROWS_N)
+    bool g384 = false;              // OSTrack-384: always qk GEMM + v GEMM + vbs::attn_stream_kernel (VB_FUSED_QKV has no effect)
+    bool attn_stream = false;       // VB_ATTN_STREAM (with VB_FUSED_QKV=0): the streaming attention kernel at the 256 geometry too
     bool loaded = false;
     // parameters
     Buf<bf16> wpatch; Buf<float> bpatch, pos, ng, nb;
@@ -134,13 +143,13 @@ int launch_gemm(const vbg::Args& a, int groups, hipStream_t st, const Err& E, in
     vbg::Args ad = a;
     ad.dbg = dbg;
     {   // experiment hook: VB_RB_<epilogue id>=rows overrides the tile-row block of that GEMM kind
-        static const int rbs[7] = {env_int("VB_RB_0", -1), env_int("VB_RB_1", -1), env_int("VB_RB_2", -1), env_int("VB_RB_3", -1),
-                                   env_int("VB_RB_4", -1), env_int("VB_RB_5", -1), env_int("VB_RB_6", -1)};
+        static const int rbs[8] = {env_int("VB_RB_0", -1), env_int("VB_RB_1", -1), env_int("VB_RB_2", -1), env_int("VB_RB_3", -1),
+                                   env_int("VB_RB_4", -1), env_int("VB_RB_5", -1), env_int("VB_RB_6", -1), env_int("VB_RB_7", -1)};
         if (rbs[EPI] >= 0) ad.rb = rbs[EPI];
     }
     {   // experiment hook: VB_DESYNC_<epilogue id>=<us>[:groups] -- phase groups of workgroups (Args::desync_ticks)
-        static const struct D { int us[7], g[7]; D() {
-            for (int e = 0; e < 7; ++e) {
+        static const struct D { int us[8], g[8]; D() {
+            for (int e = 0; e < 8; ++e) {
                 const std::string n = "VB_DESYNC_" + std::to_string(e);
                 const char* v = std::getenv(n.c_str());
                 us[e] = v ? std::atoi(v) : 0;
@@ -165,10 +174,10 @@ hipError_t allow_lds(K kernel, int bytes) {
     return hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
 }
 
-int run_layernorm(const float* resid, const float* g, const float* b, int B, hipStream_t st, bf16* xn, bf16* map, float* feat, const Err& E,
-                  bf16* xb = nullptr, float* rstd = nullptr, float* mean = nullptr) {
-    const int M = B * L;
-    hipLaunchKernelGGL((vbm::layernorm_kernel<C>), dim3((M + 3) / 4), dim3(256), 0, st, resid, g, b, LN_EPS, M, L, LZ, F, xn, map, feat, xb,
+int run_layernorm(const VbModel* m, const float* resid, const float* g, const float* b, int B, hipStream_t st, bf16* xn, bf16* map, float* feat,
+                  const Err& E, bf16* xb = nullptr, float* rstd = nullptr, float* mean = nullptr) {
+    const int M = B * m->L;
+    hipLaunchKernelGGL((vbm::layernorm_kernel<C>), dim3((M + 3) / 4), dim3(256), 0, st, resid, g, b, LN_EPS, M, m->L, m->LZ, m->F, xn, map, feat, xb,
                        rstd, mean);
     VB_HIP(hipGetLastError());
     return VT_OK;
@@ -204,6 +213,7 @@ void fold_layernorm(std::vector<float>& w, std::vector<float>& b, const float* g
 // noise patches; centred 1.7e-3; the fp32 route 2.3-2.6e-3: NOTES R7-1, tests/test_vitb_track_host.py).  Compensating with the ROUNDED
 // weights instead is algebraically the uncentred form again.  The centring table of the search rows (Args::cm) follows b'.
 int fold_patch_u8(VbModel* m, const Err& E) {
+    const int L = m->L;
     std::vector<float> w((size_t)C * PATCH_K), b(C), cpos(L);
     double k255[3], ms[3], bsum = 0;
     for (int c = 0; c < 3; ++c) { k255[c] = 1.0 / (255.0 * (double)m->norm_std[c]); ms[c] = (double)m->norm_mean[c] / (double)m->norm_std[c]; }
@@ -244,24 +254,41 @@ int set_normalization(VbModel* m, const float* mean3, const float* std3, std::st
 
 int create(const vt_config* cfg, VbModel** out, std::string* err) {
     const Err E{err};
-    if (cfg->channels != C || cfg->heads != HEADS || cfg->head_channels != HW || cfg->stride != 16 || cfg->template_size != 128 ||
-        cfg->search_size != 256)
+    const bool g256 = cfg->template_size == 128 && cfg->search_size == 256, g384 = cfg->template_size == 192 && cfg->search_size == 384;
+    if (cfg->channels != C || cfg->heads != HEADS || cfg->head_channels != HW || cfg->stride != 16 || !(g256 || g384))
         return E.fail(VT_ERR_ARG, "unsupported ViT-Base configuration: this build implements CHANNELS=768, HEADS=12, "
-                                  "HEAD.NUM_CHANNELS=256, STRIDE=16, template 128 / search 256 (OSTrack-256)");
+                                  "HEAD.NUM_CHANNELS=256, STRIDE=16, template 128 / search 256 (OSTrack-256) or template 192 / search 384 "
+                                  "(OSTrack-384); got channels=" + std::to_string(cfg->channels) + " heads=" + std::to_string(cfg->heads) +
+                                  " head_channels=" + std::to_string(cfg->head_channels) + " stride=" + std::to_string(cfg->stride) +
+                                  " template=" + std::to_string(cfg->template_size) + " search=" + std::to_string(cfg->search_size));
     if (cfg->depth < 1 || cfg->depth > 24 || cfg->max_batch < 1) return E.fail(VT_ERR_ARG, "bad depth / max_batch");
+    // the EPI_PATCH_ROWS_N epilogue finds a row's frame by a multiply-high that is exact while rows * rows-per-frame < 2^32
+    if (g384 && (uint64_t)cfg->max_batch * 576 * 576 >= (1ull << 32)) return E.fail(VT_ERR_ARG, "max_batch too large for the 192 / 384 geometry");
     VbModel* m = new VbModel();
     m->cfg = *cfg;
     m->depth = cfg->depth;
     m->maxB = cfg->max_batch;
     m->blk.resize(m->depth);
+    m->g384 = g384;
+    m->TZ = cfg->template_size; m->TX = cfg->search_size;
+    m->F = m->TX / 16;
+    m->LZ = (m->TZ / 16) * (m->TZ / 16); m->LX = m->F * m->F; m->L = m->LZ + m->LX;
+    const int L = m->L, LZ = m->LZ, LX = m->LX, F = m->F;
+    auto log2_exact = [](int v) { int s = 0; while ((1 << s) < v) ++s; return (1 << s) == v ? s : -1; };
+    m->zshift = log2_exact(LZ); m->xshift = log2_exact(LX);
     m->fold = env_int("VB_LN_FOLD", 1) != 0;
     m->center = env_int("VB_LN_CENTER", 1) != 0;
     m->fused_qkv = env_int("VB_FUSED_QKV", 1) != 0;
     m->u8_centre = env_int("VB_U8_CENTER", 1) != 0 ? 128.f : 0.f;
+    m->attn_stream = env_int("VB_ATTN_STREAM", 0) != 0;
     const size_t B = (size_t)cfg->max_batch, M = B * L, P2 = (size_t)(F + 2) * (F + 2);
     hipError_t e = hipSuccess;
     auto A = [&](auto& buf, size_t n) { if (e == hipSuccess) e = buf.alloc(n); };
-    A(m->xn, M * C); A(m->resid, M * C); A(m->qk, M * 2 * C); A(m->vt, M * C); A(m->ao, M * C); A(m->hid, M * HID);
+    // the streaming attention kernel's last key chunk reads up to PAD_TOKENS rows (qk) / elements (vt) past a frame's last token: the
+    // workspaces carry that tail so the reads stay inside them, and are zero-filled ONCE, here.  Nothing read there is used: the kernel
+    // masks those keys' scores and zeroes their V^T columns in registers (vb_attn_stream.h)
+    constexpr size_t PAD = vbs::PAD_TOKENS;
+    A(m->xn, M * C); A(m->resid, M * C); A(m->qk, (M + PAD) * 2 * C); A(m->vt, M * C + PAD); A(m->ao, M * C); A(m->hid, M * HID);
     A(m->map0, B * P2 * C); A(m->map1, 3 * B * P2 * HEAD_CH[1]); A(m->map2, 3 * B * P2 * HEAD_CH[2]);
     A(m->map3, 3 * B * P2 * HEAD_CH[3]); A(m->t4, 3 * B * LX * HEAD_CH[4]);
     A(m->rstd, M); A(m->stats, (size_t)STAT_P * M); A(m->rmean, M); A(m->zop, B * LZ * PATCH_K);
@@ -270,16 +297,21 @@ int create(const vt_config* cfg, VbModel** out, std::string* err) {
     if (e == hipSuccess) e = hipMemset(m->map1.p, 0, m->map1.n * 2);
     if (e == hipSuccess) e = hipMemset(m->map2.p, 0, m->map2.n * 2);
     if (e == hipSuccess) e = hipMemset(m->map3.p, 0, m->map3.n * 2);
+    if (e == hipSuccess) e = hipMemset(m->qk.p, 0, m->qk.n * 2);
+    if (e == hipSuccess) e = hipMemset(m->vt.p, 0, m->vt.n * 2);
     using namespace vbg;
     if (e == hipSuccess) e = allow_lds(gemm_kernel<256, 256, 2, 4, A_PLAIN, EPI_PATCH>, lds_bytes<256, 256>());
     if (e == hipSuccess) e = allow_lds(gemm_kernel<256, 256, 2, 4, A_PLAIN, EPI_PATCH_ROWS>, lds_bytes<256, 256>());
+    if (e == hipSuccess) e = allow_lds(gemm_kernel<256, 256, 2, 4, A_PLAIN, EPI_PATCH_ROWS_N>, lds_bytes<256, 256>());
     if (e == hipSuccess) e = allow_lds(gemm_kernel<256, 256, 2, 4, A_PLAIN, EPI_BF16>, lds_bytes<256, 256>());
     if (e == hipSuccess) e = allow_lds(gemm_kernel<256, 256, 2, 4, A_PLAIN, EPI_VT>, lds_bytes<256, 256>());
     if (e == hipSuccess) e = allow_lds(gemm_kernel<256, 256, 2, 4, A_PLAIN, EPI_RESID>, lds_bytes<256, 256>());
     if (e == hipSuccess) e = allow_lds(gemm_kernel<256, 256, 2, 4, A_PLAIN, EPI_GELU>, lds_bytes<256, 256>());
     if (e == hipSuccess) e = allow_lds(gemm_kernel<256, 256, 2, 4, A_CONV, EPI_CONV>, lds_bytes<256, 256>());
     if (e == hipSuccess) e = allow_lds(gemm_kernel<256, 64, 8, 1, A_CONV, EPI_CONV>, lds_bytes<256, 64>());
-    if (e == hipSuccess) e = allow_lds(vba::attn_kernel<L, HD>, vba::Geo<L, HD>::LDS_BYTES);
+    if (e == hipSuccess) e = allow_lds(vba::attn_kernel<L256, HD>, vba::Geo<L256, HD>::LDS_BYTES);
+    if (e == hipSuccess) e = allow_lds(vbs::attn_stream_kernel<L256>, vbs::LDS_BYTES);
+    if (e == hipSuccess) e = allow_lds(vbs::attn_stream_kernel<L384>, vbs::LDS_BYTES);
     if (e == hipSuccess) e = allow_lds(vbq::qkv_attn_kernel, vbq::LDS_BYTES);
     if (e != hipSuccess) {
         destroy(m);
@@ -312,6 +344,7 @@ int load_weights(VbModel* m, const TensorMap& tm, std::string* err) {
     int rc;
     const float* p;
     const std::string bb = "backbone.";
+    const int L = m->L, LZ = m->LZ, LX = m->LX;
     if ((rc = need(tm, bb + "patch_embed.proj.weight", (int64_t)C * PATCH_K, &p, E))) return rc;
     if ((rc = upload_bf16(m->wpatch, std::vector<float>(p, p + (size_t)C * PATCH_K), E))) return rc;
     if ((rc = need(tm, bb + "patch_embed.proj.bias", C, &p, E))) return rc;
@@ -446,7 +479,7 @@ int stem(VbModel* m, const float* z, const float* x, int B, hipStream_t st, floa
     const Err E{err};
     int rc = check(m, B, E);
     if (rc || (rc = check_slice(m, B, sl, E))) return rc;
-    const int M = B * L;
+    const int L = m->L, M = B * L;
     const size_t r0 = (sl ? sl->f0 : 0) * L;          // first token row of the slice
     const int cus = sl ? sl->cus : 0;
     bf16* const xn = m->xn.p + r0 * C;
@@ -454,7 +487,7 @@ int stem(VbModel* m, const float* z, const float* x, int B, hipStream_t st, floa
     float* const resid = m->resid.p + r0 * C;
     const size_t items = (size_t)M * 96;
     hipLaunchKernelGGL(vbm::patchify_kernel, dim3((unsigned)std::min<size_t>((items + 255) / 256, 16384)), dim3(256), 0, st, z, x, patches,
-                       B, 128, 256);
+                       B, m->TZ, m->TX);
     VB_HIP(hipGetLastError());
     vbg::Args a{};
     a.X = patches; a.W = m->wpatch.p; a.bias = m->bpatch.p; a.resid = resid; a.pos = m->pos.p;
@@ -479,11 +512,12 @@ int set_template(VbModel* m, const float* z, int n, const int32_t* slots, hipStr
     const Err E{err};
     int rc = check(m, n, E);
     if (rc) return rc;
-    const size_t zrow = (size_t)LZ * PATCH_K;
-    if (!slots) return patchify_dense(z, 128, n, m->zop.p, st, E);
+    const int TZ = m->TZ;
+    const size_t zrow = (size_t)m->LZ * PATCH_K;
+    if (!slots) return patchify_dense(z, TZ, n, m->zop.p, st, E);
     for (int i = 0; i < n; ++i) {      // a frame's operand rows depend on that frame alone: straight into place
         if (slots[i] < 0 || slots[i] >= m->maxB) return E.fail(VT_ERR_ARG, "template slot outside the batch");
-        if ((rc = patchify_dense(z + (size_t)i * 3 * 128 * 128, 128, 1, m->zop.p + (size_t)slots[i] * zrow, st, E))) return rc;
+        if ((rc = patchify_dense(z + (size_t)i * 3 * TZ * TZ, TZ, 1, m->zop.p + (size_t)slots[i] * zrow, st, E))) return rc;
     }
     return VT_OK;
 }
@@ -495,6 +529,7 @@ int stem_rows(VbModel* m, ZSrc zsrc, const float* z, const float* x, const unsig
     if (rc || (rc = check_slice(m, B, sl, E))) return rc;
     if ((x != nullptr) == (xu8 != nullptr)) return E.fail(VT_ERR_ARG, "stem_rows: one of the fp32 crop and the uint8 patch");
     if (xu8 && (reinterpret_cast<uintptr_t>(xu8) & 15)) return E.fail(VT_ERR_ARG, "the uint8 patch must be 16-byte aligned on the ViT-Base path");
+    const int L = m->L, LZ = m->LZ, LX = m->LX;
     const size_t f0 = sl ? sl->f0 : 0, r0 = f0 * L;
     const int cus = sl ? sl->cus : 0;
     bf16* const xn = m->xn.p + r0 * C;
@@ -503,29 +538,35 @@ int stem_rows(VbModel* m, ZSrc zsrc, const float* z, const float* x, const unsig
     const bf16* zop = m->zop.p + f0 * LZ * PATCH_K;
     if (zsrc == Z_GIVEN) {      // not through the cache: a call with its own template leaves vt_set_template's rows alone
         bf16* const ztmp = m->hid.p + r0 * HID;
-        if ((rc = patchify_dense(z, 128, B, ztmp, st, E))) return rc;
+        if ((rc = patchify_dense(z, m->TZ, B, ztmp, st, E))) return rc;
         zop = ztmp;
     }
     if (xu8) {
         const size_t items = (size_t)B * LX * 16;
-        hipLaunchKernelGGL(vbm::patchify_u8_kernel, dim3((unsigned)std::min<size_t>((items + 255) / 256, 16384)), dim3(256), 0, st, xu8, xop, B, 256,
+        hipLaunchKernelGGL(vbm::patchify_u8_kernel, dim3((unsigned)std::min<size_t>((items + 255) / 256, 16384)), dim3(256), 0, st, xu8, xop, B, m->TX,
                            m->u8_centre);
         VB_HIP(hipGetLastError());
-    } else if ((rc = patchify_dense(x, 256, B, xop, st, E))) return rc;
+    } else if ((rc = patchify_dense(x, m->TX, B, xop, st, E))) return rc;
     vbg::Args a{};
     a.resid = resid; a.pos = m->pos.p; a.N = C; a.K = PATCH_K; a.L = L;
     if (m->fold) { a.xb = xn; a.stats = m->stats.p + r0; a.ldstats = (int)(m->stats.n / STAT_P); }
+    // operand rows -> (frame, token): a shift at 64 / 256 rows per frame, the rows themselves at 144 / 576 (EPI_PATCH_ROWS_N)
+    auto rows_gemm = [&](vbg::Args& g, int rows, int shift) {
+        g.row_shift = shift < 0 ? rows : shift;
+        return shift < 0 ? launch_gemm<256, 256, 2, 4, vbg::A_PLAIN, vbg::EPI_PATCH_ROWS_N>(g, 1, st, E, cus)
+                       : launch_gemm<256, 256, 2, 4, vbg::A_PLAIN, vbg::EPI_PATCH_ROWS>(g, 1, st, E, cus);
+    };
     if (zsrc != Z_NONE) {
         vbg::Args az = a;
-        az.X = zop; az.W = m->wpatch.p; az.bias = m->bpatch.p; az.M = B * LZ; az.row_shift = 6; az.row_o0 = 0;
+        az.X = zop; az.W = m->wpatch.p; az.bias = m->bpatch.p; az.M = B * LZ; az.row_o0 = 0;
         if (m->fold && m->center) az.cm = m->cpos.p;
-        if ((rc = launch_gemm<256, 256, 2, 4, vbg::A_PLAIN, vbg::EPI_PATCH_ROWS>(az, 1, st, E, cus))) return rc;
+        if ((rc = rows_gemm(az, LZ, m->zshift))) return rc;
     }
-    a.X = xop; a.M = B * LX; a.row_shift = 8; a.row_o0 = LZ;
+    a.X = xop; a.M = B * LX; a.row_o0 = LZ;
     a.W = xu8 ? m->wpatch_u8.p : m->wpatch.p;
     a.bias = xu8 ? m->bpatch_u8.p : m->bpatch.p;
     if (m->fold && m->center) a.cm = xu8 ? m->cpos_u8.p : m->cpos.p;
-    if ((rc = launch_gemm<256, 256, 2, 4, vbg::A_PLAIN, vbg::EPI_PATCH_ROWS>(a, 1, st, E, cus))) return rc;
+    if ((rc = rows_gemm(a, LX, m->xshift))) return rc;
     if (m->fold && (rc = run_finalize(m, r0, B * L, st, E))) return rc;
     if (x_tokens_out)
         VB_HIP(hipMemcpy2DAsync(x_tokens_out + (size_t)LZ * C, (size_t)L * C * 4, resid + (size_t)LZ * C, (size_t)L * C * 4, (size_t)LX * C * 4, B,
@@ -538,7 +579,7 @@ int blocks(VbModel* m, const float* tokens_in, int B, int nblocks, hipStream_t s
     const Err E{err};
     int rc = check(m, B, E);
     if (rc || (rc = check_slice(m, B, sl, E))) return rc;
-    const int M = B * L;
+    const int L = m->L, F = m->F, M = B * L;
     const size_t f0 = sl ? sl->f0 : 0, r0 = f0 * L;
     const int cus = sl ? sl->cus : 0;
     bf16* const xn = m->xn.p + r0 * C;
@@ -557,11 +598,11 @@ int blocks(VbModel* m, const float* tokens_in, int B, int nblocks, hipStream_t s
     const int ldstats = (int)(m->stats.n / STAT_P);
     // folded LayerNorms: a residual stream from outside has no bf16 copy / rstd yet (vb::stem leaves both behind its GEMM)
     const float* const cmean = (fold && m->center) ? m->rmean.p + r0 : nullptr;
-    if (fold && tokens_in && nblocks > 0 && (rc = run_layernorm(resid, nullptr, nullptr, B, st, nullptr, nullptr, nullptr, E, xn, rstd, m->rmean.p + r0))) return rc;
+    if (fold && tokens_in && nblocks > 0 && (rc = run_layernorm(m, resid, nullptr, nullptr, B, st, nullptr, nullptr, nullptr, E, xn, rstd, m->rmean.p + r0))) return rc;
     for (int i = 0; i < nblocks; ++i) {
         const BlockW& b = m->blk[i];
-        if (!fold && (rc = run_layernorm(resid, b.ln1g.p, b.ln1b.p, B, st, xn, nullptr, nullptr, E))) return rc;
-        if (m->fused_qkv) {          // projection + attention of a (frame, head) in one workgroup: q / k / v^T never leave the CU
+        if (!fold && (rc = run_layernorm(m, resid, b.ln1g.p, b.ln1b.p, B, st, xn, nullptr, nullptr, E))) return rc;
+        if (m->fused_qkv && !m->g384) {          // projection + attention of a (frame, head) in one workgroup: q / k / v^T never leave the CU
             vbq::Args qa{};
             qa.X = xn; qa.W = b.wqkv.p; qa.bias = b.bqkv.p; qa.rstd = rstd; qa.out = ao; qa.B = B; qa.heads = HEADS;
             { static const int hgv = env_int("VB_QA_HGROUP", 6); qa.hgroup = (hgv > 0 && HEADS % hgv == 0) ? hgv : HEADS; }
@@ -578,15 +619,21 @@ int blocks(VbModel* m, const float* tokens_in, int B, int nblocks, hipStream_t s
         v.X = xn; v.W = b.wqkv.p + (size_t)2 * C * C; v.bias = b.bqkv.p + 2 * C; v.vt = vt;   // v: rows 2C .. 3C, stored transposed
         v.M = M; v.N = C; v.K = C; v.L = L; v.rstd = rstd;
         if ((rc = launch_gemm<256, 256, 2, 4, vbg::A_PLAIN, vbg::EPI_VT>(v, 1, st, E, cus))) return rc;
-        constexpr int attn_lds = vba::Geo<L, HD>::LDS_BYTES;
-        hipLaunchKernelGGL((vba::attn_kernel<L, HD>), dim3(B * HEADS), dim3(256), attn_lds, st, qk, vt, ao, HEADS);
+        if (m->g384)
+            hipLaunchKernelGGL((vbs::attn_stream_kernel<L384>), dim3(B * HEADS * vbs::splits<L384>()), dim3(256), vbs::LDS_BYTES, st, qk, vt, ao, HEADS);
+        else if (m->attn_stream)
+            hipLaunchKernelGGL((vbs::attn_stream_kernel<L256>), dim3(B * HEADS * vbs::splits<L256>()), dim3(256), vbs::LDS_BYTES, st, qk, vt, ao, HEADS);
+        else {
+        constexpr int attn_lds = vba::Geo<L256, HD>::LDS_BYTES;
+        hipLaunchKernelGGL((vba::attn_kernel<L256, HD>), dim3(B * HEADS), dim3(256), attn_lds, st, qk, vt, ao, HEADS);
+        }
         VB_HIP(hipGetLastError());
         }
         vbg::Args p{};
         p.X = ao; p.W = b.wproj.p; p.bias = b.bproj.p; p.resid = resid; p.M = M; p.N = C; p.K = C;
         if (fold) { p.xb = xn; p.stats = stats; p.ldstats = ldstats; p.cm = cmean; }
         if ((rc = launch_gemm<256, 256, 2, 4, vbg::A_PLAIN, vbg::EPI_RESID>(p, 1, st, E, cus))) return rc;
-        if (fold ? (rc = run_finalize(m, r0, M, st, E)) : (rc = run_layernorm(resid, b.ln2g.p, b.ln2b.p, B, st, xn, nullptr, nullptr, E))) return rc;
+        if (fold ? (rc = run_finalize(m, r0, M, st, E)) : (rc = run_layernorm(m, resid, b.ln2g.p, b.ln2b.p, B, st, xn, nullptr, nullptr, E))) return rc;
         vbg::Args f1{};
         f1.rstd = rstd;
         f1.X = xn; f1.W = b.w1.p; f1.bias = b.b1.p; f1.out = hid; f1.M = M; f1.N = HID; f1.K = C; f1.ldo = HID; f1.rb = 4;
@@ -599,7 +646,7 @@ int blocks(VbModel* m, const float* tokens_in, int B, int nblocks, hipStream_t s
         if (feeds_ln && (rc = run_finalize(m, r0, M, st, E))) return rc;
     }
     if (resid_out) VB_HIP(hipMemcpyAsync(resid_out, resid, (size_t)M * C * 4, hipMemcpyDeviceToDevice, st));
-    return run_layernorm(resid, m->ng.p, m->nb.p, B, st, nullptr, map0, feat_out, E);
+    return run_layernorm(m, resid, m->ng.p, m->nb.p, B, st, nullptr, map0, feat_out, E);
 }
 
 int head(VbModel* m, const float* feat_in, int B, hipStream_t st, float* score, float* size, float* offset, std::string* err,
@@ -607,6 +654,7 @@ int head(VbModel* m, const float* feat_in, int B, hipStream_t st, float* score, 
     const Err E{err};
     int rc = check(m, B, E);
     if (rc || (rc = check_slice(m, B, sl, E))) return rc;
+    const int LX = m->LX, F = m->F;
     const size_t f0 = sl ? sl->f0 : 0;
     const long long Bt = sl ? sl->Btot : B;              // tower-major buffers: [tower][Bt frames]...
     const int cus = sl ? sl->cus : 0;
