@@ -7,8 +7,9 @@
 
 --matrix: one child process per (library, environment); the current build against OTHER.  Environments: the default, every entry of
 VARIANTS in tests/test_gpu_variants.py, VT_TRACK_U8=0, VT_GRAPH_CHAINS=2 and 3, and the crop forms tests/test_gpu_patch_u8.py forces
-(crop_bytes, crop_fast_off, crop_band_off, crop_band4, crop_band2, crop_band4_unaligned).  Configs: g128, g256, generic (112, 224), f16 (the f16
-build at G128, needs --f16), vitb.  Batches 1, 7, 96, 256 (ViT-Base 1, 96).  Entries: forward, forward on the cached template, forward_u8,
+(crop_bytes, crop_fast_off, crop_band_off, crop_band4, crop_band2, crop_band4_unaligned), and the ViT-Base attention routes the default never
+takes: vb_unfused (attn_kernel<320, 64>), vb_stream (attn_stream_kernel<320>), vb_nofold.  Configs: g128, g256, generic (112, 224), f16 (the f16
+build at G128, needs --f16), vitb, vitb384 (192 / 384, depth 12).  Batches 1, 5, 7, 96, 256 (vitb 1, 96; vitb384 1, 5).  Entries: forward, forward on the cached template, forward_u8,
 capture + replay, track_step, track_step_frames, track_step_images (NV12, and I420 under BT.709: the other body of the band image kernel)
 -- four steps each for the tracker entries, so the state
 feeds back.  A child prints sha256 over the bytes of all six outputs (+ states and record) per case, or the library's error code where it
@@ -16,6 +17,7 @@ refuses the case: both libraries must refuse with the same code.  Children run o
 import argparse, json, os, subprocess, sys
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 KEYS = ("score_map", "size_map", "offset_map", "pred_boxes", "hann_boxes", "conf")
+VITB_BATCHES = {"vitb": (1, 96), "vitb384": (1, 5)}      # the ViT-Base configs and the batches of --batches each of them runs
 
 VITB_CHILD = r"""
 import sys, json, hashlib
@@ -65,14 +67,14 @@ def child(configs, batches):
             res[name] = "refused " + (code.group(1) if code else str(e)[:60])
 
     for cfg in configs:
-        tz, tx = {"g128": (64, 128), "g256": (128, 256), "generic": (112, 224), "f16": (64, 128), "vitb": (128, 256)}[cfg]
-        if cfg == "vitb":
-            sd = synth.synth_vitb_state_dict(26)
-            make = lambda B: native.Model(128, 256, channels=768, heads=12, depth=12, head_channels=256, max_batch=B)
+        tz, tx = {"g128": (64, 128), "g256": (128, 256), "generic": (112, 224), "f16": (64, 128), "vitb": (128, 256), "vitb384": (192, 384)}[cfg]
+        if cfg in VITB_BATCHES:
+            sd = synth.synth_vitb_state_dict(26, len_z=(tz // 16) ** 2, len_x=(tx // 16) ** 2)
+            make = lambda B: native.Model(tz, tx, channels=768, heads=12, depth=12, head_channels=256, max_batch=B)
         else:
             sd = synth.synth_state_dict(5, len_z=(tz // 16) ** 2, len_x=(tx // 16) ** 2)
             make = lambda B: native.Model(tz, tx, max_batch=B, precision="f16" if cfg == "f16" else "f32")
-        for B in ([b for b in batches if b in (1, 96)] if cfg == "vitb" else batches):
+        for B in ([b for b in batches if b in VITB_BATCHES[cfg]] if cfg in VITB_BATCHES else batches):
             m = make(B)
             m.load_state_dict(sd)
             z, x = synth.synth_inputs(40 + B, B, tz, tx)
@@ -153,6 +155,8 @@ def environments():
     envs.update({"crop_bytes": {"VT_CROP_BYTES": "1"}, "crop_fast_off": {"VT_CROP_FAST": "0"}, "crop_band_off": {"VT_CROP_BAND": "0"},
                  "crop_band4": {"VT_CROP_BAND": "-4"}, "crop_band2": {"VT_CROP_BAND": "-2"},
                  "crop_band4_unaligned": {"VT_CROP_BAND": "-4", "VT_CROP_ALIGNED": "0"}})
+    envs.update({"vb_unfused": {"VB_FUSED_QKV": "0"}, "vb_stream": {"VB_FUSED_QKV": "0", "VB_ATTN_STREAM": "1"},
+                 "vb_nofold": {"VB_LN_FOLD": "0", "VB_FUSED_QKV": "0"}})
     return envs
 
 
@@ -171,8 +175,8 @@ def main():
     ap.add_argument("--matrix", action="store_true")
     ap.add_argument("--f16", default="")
     ap.add_argument("--envs", default="")
-    ap.add_argument("--configs", default="g128,g256,generic,f16,vitb")
-    ap.add_argument("--batches", default="1,7,96,256")
+    ap.add_argument("--configs", default="g128,g256,generic,f16,vitb,vitb384")
+    ap.add_argument("--batches", default="1,5,7,96,256")
     ap.add_argument("--out", default="")
     a = ap.parse_args()
     other = os.path.abspath(a.other)

@@ -19,7 +19,7 @@
 // under it.
 //
 // Registers per wave (NQ = 3): S 3 x 16 + O 3 x 16 + q fragments 3 x 8 + m, l 6 + K / V^T fragment and P operands + addresses:
-// measured 172 VGPRs at L = 720 and 166 at L = 320 of the 256 the two-workgroup occupancy allows, ScratchSize 0
+// measured 168 VGPRs at L = 720 and 166 at L = 320 of the 256 the two-workgroup occupancy allows, ScratchSize 0
 // (profiles/r6_resource_usage.txt).  Every K / V^T fragment read from LDS feeds NQ = 3 MFMAs.
 //
 // The partial last chunk (L % 32 = 16).  A lane's eight scores of a 32-key sub-chunk are keys 32 c + 8 (lane >> 4) + {0..7}: those
@@ -79,9 +79,7 @@ __global__ __launch_bounds__(256, 2) void attn_stream_kernel(const bf16* __restr
     for (int u = 0; u < NQ; ++u) {
         qts[u] = sp * QT_PER_WG + w * NQ + u;
         const int qt = qts[u] < NT ? qts[u] : NT - 1;
-#pragma unroll
-        for (int ks = 0; ks < KS; ++ks)
-            qfrag[u][ks] = *reinterpret_cast<const bf16x8*>(qf + (size_t)(qt * 16 + l15) * 2 * C + ks * 32 + q * 8);
+        vba::load_q(qfrag[u], qf, qt, l15, q, C);
     }
 
     // ---- staging: chunk c's K rows (permuted) and V^T columns into buffer `b`, nsub 32-key sub-chunks of it; 2 nsub pieces per wave
@@ -91,8 +89,7 @@ __global__ __launch_bounds__(256, 2) void attn_stream_kernel(const bf16* __restr
         char* Vimg = Kimg + KC * HD * 2;
         for (int s = w; s < nsub * 2 * KS; s += WAVES) {           // K sub-tile s = key tile t (of this chunk) x k-step
             const int t = s / KS, ks = s - t * KS;
-            const int key = c * KC + 32 * (t >> 1) + 8 * (prow >> 2) + (prow & 3) + 4 * (t & 1);
-            vbg::glds16(kf + (size_t)key * 2 * C + ks * 32 + pk, Kimg + s * 1024 + lane * 16);
+            vbg::glds16(kf + (size_t)(c * KC + vba::perm_key(t, prow)) * 2 * C + ks * 32 + pk, Kimg + s * 1024 + lane * 16);
         }
         for (int s = w; s < nsub * DT; s += WAVES) {               // V^T sub-tile s = d tile x sub-chunk (sub-chunk fastest)
             const int dt = s / nsub, sc = s - dt * nsub;
@@ -101,7 +98,6 @@ __global__ __launch_bounds__(256, 2) void attn_stream_kernel(const bf16* __restr
     };
 
     const int fr = vbg::swz_byte(l15 * 64 + q * 16);
-    constexpr float LOG2E = 1.4426950408889634f;
     float mrun[NQ], lsum[NQ];
     f4 O[NQ][DT];
 #pragma unroll
@@ -119,17 +115,7 @@ __global__ __launch_bounds__(256, 2) void attn_stream_kernel(const bf16* __restr
         const char* Kimg = smem + b * CHUNK_BYTES;
         const char* Vimg = Kimg + KC * HD * 2;
         f4 S[NQ][2 * NS];
-#pragma unroll
-        for (int t = 0; t < 2 * NS; ++t) {
-#pragma unroll
-            for (int u = 0; u < NQ; ++u) S[u][t] = splat4(0.f);
-#pragma unroll
-            for (int ks = 0; ks < KS; ++ks) {
-                const bf16x8 kf8 = *reinterpret_cast<const bf16x8*>(Kimg + (t * KS + ks) * 1024 + fr);
-#pragma unroll
-                for (int u = 0; u < NQ; ++u) S[u][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf8, qfrag[u][ks], S[u][t], 0, 0, 0);
-            }
-        }
+        vba::qk_tiles(S, Kimg, fr, qfrag);
         if constexpr (MASK) {      // the last sub-chunk: this lane's keys are base + {0..3} (even tile) and base + 4 + {0..3} (odd tile)
             const int base = c * KC + (NS - 1) * 32 + 8 * q;
 #pragma unroll
@@ -142,27 +128,14 @@ __global__ __launch_bounds__(256, 2) void attn_stream_kernel(const bf16* __restr
         }
 #pragma unroll
         for (int u = 0; u < NQ; ++u) {
-            float m0 = fmaxf(S[u][0].x, S[u][0].y), m1 = fmaxf(S[u][0].z, S[u][0].w);
-#pragma unroll
-            for (int t = 1; t < 2 * NS; ++t) {
-                m0 = fmaxf(fmaxf(m0, S[u][t].x), S[u][t].y);
-                m1 = fmaxf(fmaxf(m1, S[u][t].z), S[u][t].w);
-            }
-            const float mx = fmaxf(mrun[u], quad_max(fmaxf(m0, m1)));      // finite: every chunk holds an existing key
-            const float alpha = __builtin_amdgcn_exp2f((mrun[u] - mx) * LOG2E);
+            const float mx = fmaxf(mrun[u], quad_max(vba::lane_max(S[u])));      // finite: every chunk holds an existing key
+            const float alpha = __builtin_amdgcn_exp2f((mrun[u] - mx) * vba::LOG2E);
             mrun[u] = mx;
-            const vbg::f2 l2 = {LOG2E, LOG2E}, nmb = {-mx * LOG2E, -mx * LOG2E};
+            // vba::exp_rows(S[u], mx), its loop written out: with the loop inside a helper attn_stream_kernel<320> takes 168 VGPRs for 166
+            const vbg::f2 l2 = {vba::LOG2E, vba::LOG2E}, nmb = {-mx * vba::LOG2E, -mx * vba::LOG2E};
             vbg::f2 s0 = {0.f, 0.f}, s1 = {0.f, 0.f};
 #pragma unroll
-            for (int t = 0; t < 2 * NS; ++t) {
-                const vbg::f2 a = __builtin_elementwise_fma(vbg::f2{S[u][t].x, S[u][t].y}, l2, nmb);
-                const vbg::f2 b2 = __builtin_elementwise_fma(vbg::f2{S[u][t].z, S[u][t].w}, l2, nmb);
-                const vbg::f2 pa = {__builtin_amdgcn_exp2f(a.x), __builtin_amdgcn_exp2f(a.y)};
-                const vbg::f2 pb = {__builtin_amdgcn_exp2f(b2.x), __builtin_amdgcn_exp2f(b2.y)};
-                S[u][t] = f4{pa.x, pa.y, pb.x, pb.y};
-                s0 += pa;
-                s1 += pb;
-            }
+            for (int t = 0; t < 2 * NS; ++t) vba::exp_tile(S[u][t], l2, nmb, s0, s1);
             const vbg::f2 st = s0 + s1;
             lsum[u] = fmaf(lsum[u], alpha, st.x + st.y);      // this lane's keys only: the four lane groups are summed once, at the end
 #pragma unroll
@@ -170,26 +143,14 @@ __global__ __launch_bounds__(256, 2) void attn_stream_kernel(const bf16* __restr
         }
 #pragma unroll
         for (int sc = 0; sc < NS; ++sc) {
-            bf16x8 p[NQ];
+            if (MASK && sc == NS - 1) {      // this lane's V^T columns are keys base + {0..7}: those past the frame are not the frame's, so they are 0
+                const int base = c * KC + sc * 32 + 8 * q;
+                vba::pv_chunk(O, S, sc, Vimg, 2, fr, [&](bf16x8& vf8) {
 #pragma unroll
-            for (int u = 0; u < NQ; ++u) {
-                const bf16x4 lo = vbg::to_bf16x4(S[u][2 * sc]), hi = vbg::to_bf16x4(S[u][2 * sc + 1]);
-                p[u] = bf16x8{lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
-            }
-#pragma unroll
-            for (int dt = 0; dt < DT; ++dt) {
-                bf16x8 vf8 = *reinterpret_cast<const bf16x8*>(Vimg + (dt * 2 + sc) * 1024 + fr);
-                if constexpr (MASK) {      // this lane's V^T columns are keys base + {0..7}: those past the frame are not the frame's, so they are 0
-                    if (sc == NS - 1) {
-                        const int base = c * KC + sc * 32 + 8 * q;
-#pragma unroll
-                        for (int j = 0; j < 8; ++j)
-                            if (base + j >= L) vf8[j] = (bf16)0.0f;
-                    }
-                }
-#pragma unroll
-                for (int u = 0; u < NQ; ++u) O[u][dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vf8, p[u], O[u][dt], 0, 0, 0);
-            }
+                    for (int j = 0; j < 8; ++j)
+                        if (base + j >= L) vf8[j] = (bf16)0.0f;
+                });
+            } else vba::pv_chunk(O, S, sc, Vimg, 2, fr);
         }
     };
 
@@ -210,11 +171,7 @@ __global__ __launch_bounds__(256, 2) void attn_stream_kernel(const bf16* __restr
 #pragma unroll
     for (int u = 0; u < NQ; ++u) {
         const float inv = 1.0f / quad_sum(lsum[u]);
-        if (qts[u] < NT) {
-            bf16* o = out + (size_t)(f * L + qts[u] * 16 + l15) * C + h * HD + q * 4;
-#pragma unroll
-            for (int dt = 0; dt < DT; ++dt) *reinterpret_cast<bf16x4*>(o + dt * 16) = vbg::to_bf16x4(O[u][dt] * splat4(inv));
-        }
+        if (qts[u] < NT) vba::store_tile(out, (size_t)(f * L + qts[u] * 16 + l15), C, h * HD + q * 4, O[u], inv);
     }
 }
 

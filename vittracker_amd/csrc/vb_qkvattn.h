@@ -16,9 +16,11 @@
 // has the same tile pattern (which tiles swap is a compile-time property of the tile index): with a wave-uniform branch between two
 // operand orders hipcc spilled 300 registers around the k-loop.
 // Attention: vb_attn.h's arithmetic (S^T = K q^T with keys on the MFMA rows, softmax rows in registers, O^T = V^T P^T, two query tiles
-// per pass), on 8 waves, q from LDS like K.  The three images alias the projection's staging buffers.
+// per pass) through vb_attn.h's helpers -- nothing of it is written here --, on 8 waves, q from LDS like K; the epilogue places the K
+// rows by vba::perm_tile / perm_row, the inverse of the staging kernels' vba::perm_key.  The three images alias the projection's
+// staging buffers.
 #pragma once
-#include "vb_gemm.h"
+#include "vb_attn.h"
 
 #ifndef VB_QA_DBG
 #define VB_QA_DBG 0         // timing experiments only (wrong results): 1 = projection + epilogue only (no attention), 2 = attention only (no k-loop),
@@ -217,8 +219,8 @@ __global__ __launch_bounds__(512) void qkv_attn_kernel(const Args a) {
                         const bf16x4 y = vbg::to_bf16x4(vbg::fma4(acc[i][j], splat4(rs[j]), bv));
                         if (ft < 4) {
                             *reinterpret_cast<bf16x4*>(Qimg + (tj * KS + ks) * 1024 + swz_byte(l15 * 64 + kb)) = y;
-                        } else {           // K rows permuted: token 32 c + 8 a + b -> tile 2 c + (b >> 2), row 4 a + (b & 3)   (vb_attn.h)
-                            const int c = m >> 5, aa = (m & 31) >> 3, b = m & 7, t = 2 * c + (b >> 2), row = 4 * aa + (b & 3);
+                        } else {           // K rows permuted: token m where the attention expects key m (the inverse of vba::perm_key)
+                            const int t = vba::perm_tile(m), row = vba::perm_row(m);
                             *reinterpret_cast<bf16x4*>(Kimg + (t * KS + ks) * 1024 + swz_byte(row * 64 + kb)) = y;
                         }
                     }
@@ -236,7 +238,6 @@ __global__ __launch_bounds__(512) void qkv_attn_kernel(const Args a) {
         }
         __syncthreads();
         // ---- attention of the frame's 20 query tiles: wave w takes tiles w, w + 8 (and w + 16 for w < 4); two tiles per pass
-        constexpr float LOG2E = 1.4426950408889634f;
         auto pass = [&](auto nq_tag, int qt0, int qt1) {
             constexpr int NQ = decltype(nq_tag)::value;
             const int qts[2] = {qt0, qt1};
@@ -250,41 +251,12 @@ __global__ __launch_bounds__(512) void qkv_attn_kernel(const Args a) {
 #pragma unroll
                 for (int ks = 0; ks < KS; ++ks) qf[u][ks] = *reinterpret_cast<const bf16x8*>(Qimg + (qts[u] * KS + ks) * 1024 + frq);
             f4 S[NQ][NT];
-#pragma unroll
-            for (int t = 0; t < NT; ++t) {
-#pragma unroll
-                for (int u = 0; u < NQ; ++u) S[u][t] = splat4(0.f);
-#pragma unroll
-                for (int ks = 0; ks < KS; ++ks) {
-                    const bf16x8 kf8 = *reinterpret_cast<const bf16x8*>(Kimg + (t * KS + ks) * 1024 + frq);
-#pragma unroll
-                    for (int u = 0; u < NQ; ++u) S[u][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf8, qf[u][ks], S[u][t], 0, 0, 0);
-                }
-            }
+            vba::qk_tiles(S, Kimg, frq, qf);
             float inv[NQ];
 #pragma unroll
             for (int u = 0; u < NQ; ++u) {
-                float m0 = fmaxf(S[u][0].x, S[u][0].y), m1 = fmaxf(S[u][0].z, S[u][0].w);
-#pragma unroll
-                for (int t = 1; t < NT; ++t) {
-                    m0 = fmaxf(fmaxf(m0, S[u][t].x), S[u][t].y);
-                    m1 = fmaxf(fmaxf(m1, S[u][t].z), S[u][t].w);
-                }
-                const float mx = quad_max(fmaxf(m0, m1));
-                const vbg::f2 l2 = {LOG2E, LOG2E}, nmb = {-mx * LOG2E, -mx * LOG2E};
-                vbg::f2 s0 = {0.f, 0.f}, s1 = {0.f, 0.f};
-#pragma unroll
-                for (int t = 0; t < NT; ++t) {
-                    const vbg::f2 x0 = __builtin_elementwise_fma(vbg::f2{S[u][t].x, S[u][t].y}, l2, nmb);
-                    const vbg::f2 x1 = __builtin_elementwise_fma(vbg::f2{S[u][t].z, S[u][t].w}, l2, nmb);
-                    const vbg::f2 pa = {__builtin_amdgcn_exp2f(x0.x), __builtin_amdgcn_exp2f(x0.y)};
-                    const vbg::f2 pb = {__builtin_amdgcn_exp2f(x1.x), __builtin_amdgcn_exp2f(x1.y)};
-                    S[u][t] = f4{pa.x, pa.y, pb.x, pb.y};
-                    s0 += pa;
-                    s1 += pb;
-                }
-                const vbg::f2 st = s0 + s1;
-                inv[u] = 1.0f / quad_sum(st.x + st.y);
+                const float mx = quad_max(vba::lane_max(S[u]));
+                inv[u] = 1.0f / quad_sum(vba::exp_rows(S[u], mx));
             }
             f4 O[NQ][DT];
 #pragma unroll
@@ -292,26 +264,9 @@ __global__ __launch_bounds__(512) void qkv_attn_kernel(const Args a) {
 #pragma unroll
                 for (int dt = 0; dt < DT; ++dt) O[u][dt] = splat4(0.f);
 #pragma unroll
-            for (int c = 0; c < NC; ++c) {
-                bf16x8 p[NQ];
+            for (int c = 0; c < NC; ++c) vba::pv_chunk(O, S, c, Vimg, NC, frq);
 #pragma unroll
-                for (int u = 0; u < NQ; ++u) {
-                    const bf16x4 lo = vbg::to_bf16x4(S[u][2 * c]), hi = vbg::to_bf16x4(S[u][2 * c + 1]);
-                    p[u] = bf16x8{lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
-                }
-#pragma unroll
-                for (int dt = 0; dt < DT; ++dt) {
-                    const bf16x8 vf8 = *reinterpret_cast<const bf16x8*>(Vimg + (dt * NC + c) * 1024 + frq);
-#pragma unroll
-                    for (int u = 0; u < NQ; ++u) O[u][dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vf8, p[u], O[u][dt], 0, 0, 0);
-                }
-            }
-#pragma unroll
-            for (int u = 0; u < NQ; ++u) {
-                bf16* o = a.out + (size_t)(f * L + qts[u] * 16 + l15) * DM + h * HD + q * 4;
-#pragma unroll
-                for (int dt = 0; dt < DT; ++dt) *reinterpret_cast<bf16x4*>(o + dt * 16) = vbg::to_bf16x4(O[u][dt] * splat4(inv[u]));
-            }
+            for (int u = 0; u < NQ; ++u) vba::store_tile(a.out, (size_t)(f * L + qts[u] * 16 + l15), DM, h * HD + q * 4, O[u], inv[u]);
         };
         if (VB_QA_DBG != 1 && VB_QA_DBG < 3) {
             pass(std::integral_constant<int, 2>{}, w, w + 8);

@@ -1,7 +1,9 @@
 // vitb.hip -- host side of the ViT-Base OSTrack path (BASELINE config 4): weight packing (bf16, BatchNorm folded, conv
-// weights as [cout][tap][cin], attention scale folded into W_q), workspace, launch sequence.  Kernels: vb_gemm.h,
-// vb_attn.h, vb_qkvattn.h, vb_attn_stream.h (the 384 geometry's attention), vb_misc.h.  Reached through the same C ABI as the
-// vit_48 path (vt_create with channels = 768).
+// weights as [cout][tap][cin], attention scale folded into W_q), workspace, launch sequence.  Kernels: vb_gemm.h, vb_misc.h and the
+// three attention kernels vb_attn.h, vb_qkvattn.h, vb_attn_stream.h (the 384 geometry's), whose shared arithmetic lives in vb_attn.h.
+// Reached through the same C ABI as the vit_48 path (vt_create with channels = 768).
+// Layout of this file: Buf owns device memory (a model is freed by deleting it); Hooks holds the experiment switches, read once;
+// SliceView holds what a frame slice addresses, built once per entry; run_attention launches one of the four attention forms.
 #include "vb_api.h"
 
 #include <algorithm>
@@ -46,9 +48,13 @@ uint16_t f2bf(float f) {   // round to nearest even, NaN kept quiet
 }
 
 template <typename T>
-struct Buf {
+struct Buf {      // owns its device memory; movable (std::vector<BlockW> is resized), not copyable
     T* p = nullptr;
     size_t n = 0;
+    Buf() = default;
+    Buf(Buf&& o) noexcept : p(o.p), n(o.n) { o.p = nullptr; }
+    Buf& operator=(Buf&& o) noexcept { std::swap(p, o.p); std::swap(n, o.n); return *this; }
+    ~Buf() { release(); }
     hipError_t alloc(size_t count) { n = count; return hipMalloc(reinterpret_cast<void**>(&p), count * sizeof(T)); }
     void release() { if (p) (void)hipFree(p); p = nullptr; }
 };
@@ -73,7 +79,7 @@ struct VbModel {
     std::vector<BlockW> blk;
     Buf<bf16> wc[4]; Buf<float> bc[4], w5, b5;     // head: conv1 (towers along N), conv2..4 ([3][cout_padded][9 cin])
     // workspace
-    Buf<bf16> xn, qk, vt, ao, hid, map0, map1, map2, map3, t4;
+    Buf<bf16> xn, qk, vt, ao, hid, map[4], t4;      // map[i]: the head's zero-bordered maps of HEAD_CH[i] channels (1-3: three towers)
     Buf<float> resid;
     // LayerNorm folded into qkv / fc1 (vb_gemm.h): xn then holds the RAW residual rows in bf16, written by the GEMM epilogues that
     // produce them, rstd their 1 / sqrt(var + eps), stats the epilogues' per-slice (sum, M2) pairs [C / 64][max rows]
@@ -122,6 +128,20 @@ int upload_bf16(Buf<bf16>& d, const std::vector<float>& h, const Err& E) {
 }
 int upload_f32(Buf<float>& d, const float* h, size_t n, const Err& E) { return upload(d, h, n, E); }
 
+// a state-dict tensor as it is: looked up, checked and uploaded, one helper per element type (*host: the tensor's host values)
+int load_f32(Buf<float>& d, const vb::TensorMap& tm, const std::string& name, int64_t numel, const Err& E, const float** host = nullptr) {
+    const float* p;
+    if (int rc = need(tm, name, numel, &p, E)) return rc;
+    if (host) *host = p;
+    return upload_f32(d, p, (size_t)numel, E);
+}
+int load_bf16(Buf<bf16>& d, const vb::TensorMap& tm, const std::string& name, int64_t numel, const Err& E, const float** host = nullptr) {
+    const float* p;
+    if (int rc = need(tm, name, numel, &p, E)) return rc;
+    if (host) *host = p;
+    return upload_bf16(d, std::vector<float>(p, p + numel), E);
+}
+
 int num_cus() {
     static int n = 0;
     if (!n) {
@@ -133,36 +153,46 @@ int num_cus() {
 
 inline int env_int(const char* name, int dflt) { const char* v = std::getenv(name); return v ? std::atoi(v) : dflt; }
 
+// The experiment hooks (tools/gpu_vbdbg.sh, gpu_vbexp.sh, gpu_vbchains.sh), read once, at the first GEMM launch:
+//   VB_DBG                              vbg::Args::dbg of every GEMM
+//   VB_RB_<epilogue id>=rows            overrides the tile-row block of that GEMM kind
+//   VB_DESYNC_<epilogue id>=<us>[:groups]   phase groups of workgroups (Args::desync_ticks)
+//   VB_MAX_CUS                          persistent grids of at most this many workgroups
+struct Hooks {
+    int dbg, max_cus, rb[8], desync_us[8], desync_groups[8];
+    Hooks() : dbg(env_int("VB_DBG", 0)), max_cus(env_int("VB_MAX_CUS", 0)) {
+        for (int e = 0; e < 8; ++e) {
+            rb[e] = env_int(("VB_RB_" + std::to_string(e)).c_str(), -1);
+            const char* v = std::getenv(("VB_DESYNC_" + std::to_string(e)).c_str());
+            desync_us[e] = v ? std::atoi(v) : 0;
+            const char* c = v ? std::strchr(v, ':') : nullptr;
+            desync_groups[e] = c ? std::max(2, std::atoi(c + 1)) : 2;
+        }
+    }
+};
+const Hooks& hooks() { static const Hooks h; return h; }
+
+// workgroups of a persistent kernel: one per CU, at most `cus` (0 = all), in whole XCD rounds of 8
+int persistent_grid(int cus, int groups = 1) { return std::max(8, (cus > 0 ? std::min(cus, num_cus()) : num_cus()) / groups / 8 * 8); }
+
+// grid of a grid-stride elementwise kernel of 256 threads
+unsigned grid256(size_t items) { return (unsigned)std::min<size_t>((items + 255) / 256, 16384); }
+
 template <int BM, int BN, int WM, int WN, int AMODE, int EPI>
 int launch_gemm(const vbg::Args& a, int groups, hipStream_t st, const Err& E, int cus = 0) {
     if (a.M < 1 || a.K % vbg::BK != 0 || a.N % 8 != 0)
         return E.fail(VT_ERR_ARG, "gemm shape: K must be a multiple of 64 and N of 8 (got M=" + std::to_string(a.M) + " N=" +
                                       std::to_string(a.N) + " K=" + std::to_string(a.K) + ")");
     if (BM == 256 && BN == 256 && a.K % (2 * vbg::BK) != 0) return E.fail(VT_ERR_ARG, "gemm shape: the 256 x 256 tile needs K to be a multiple of 128");
-    static const int dbg = [] { const char* v = std::getenv("VB_DBG"); return v ? std::atoi(v) : 0; }();
+    const Hooks& H = hooks();
     vbg::Args ad = a;
-    ad.dbg = dbg;
-    {   // experiment hook: VB_RB_<epilogue id>=rows overrides the tile-row block of that GEMM kind
-        static const int rbs[8] = {env_int("VB_RB_0", -1), env_int("VB_RB_1", -1), env_int("VB_RB_2", -1), env_int("VB_RB_3", -1),
-                                   env_int("VB_RB_4", -1), env_int("VB_RB_5", -1), env_int("VB_RB_6", -1), env_int("VB_RB_7", -1)};
-        if (rbs[EPI] >= 0) ad.rb = rbs[EPI];
-    }
-    {   // experiment hook: VB_DESYNC_<epilogue id>=<us>[:groups] -- phase groups of workgroups (Args::desync_ticks)
-        static const struct D { int us[8], g[8]; D() {
-            for (int e = 0; e < 8; ++e) {
-                const std::string n = "VB_DESYNC_" + std::to_string(e);
-                const char* v = std::getenv(n.c_str());
-                us[e] = v ? std::atoi(v) : 0;
-                const char* c = v ? std::strchr(v, ':') : nullptr;
-                g[e] = c ? std::max(2, std::atoi(c + 1)) : 2;
-            } } } ds;
-        if (ds.us[EPI] > 0) { ad.desync_ticks = ds.us[EPI] * 100; ad.desync_groups = ds.g[EPI]; }
-    }
+    ad.dbg = H.dbg;
+    if (H.rb[EPI] >= 0) ad.rb = H.rb[EPI];
+    if (H.desync_us[EPI] > 0) { ad.desync_ticks = H.desync_us[EPI] * 100; ad.desync_groups = H.desync_groups[EPI]; }
     // persistent workgroups: one per CU, each walks tiles blockIdx.x, blockIdx.x + grid, ...
     const int ntiles = ((a.M + BM - 1) / BM) * ((a.N + BN - 1) / BN);
-    static const int max_cus = env_int("VB_MAX_CUS", 0);      // experiment hook: persistent grid of at most this many workgroups
-    if (max_cus > 0) cus = cus > 0 ? std::min(cus, max_cus) : max_cus;
-    const int tiles = std::min(ntiles, std::max(8, (cus > 0 ? std::min(cus, num_cus()) : num_cus()) / groups / 8 * 8));
+    if (H.max_cus > 0) cus = cus > 0 ? std::min(cus, H.max_cus) : H.max_cus;
+    const int tiles = std::min(ntiles, persistent_grid(cus, groups));
     constexpr int lds = vbg::lds_bytes<BM, BN>();
     hipLaunchKernelGGL((vbg::gemm_kernel<BM, BN, WM, WN, AMODE, EPI>), dim3(tiles, groups), dim3(512), lds, st, ad);
     VB_HIP(hipGetLastError());
@@ -170,9 +200,7 @@ int launch_gemm(const vbg::Args& a, int groups, hipStream_t st, const Err& E, in
 }
 
 template <typename K>
-hipError_t allow_lds(K kernel, int bytes) {
-    return hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-}
+const void* kernel_ptr(K kernel) { return reinterpret_cast<const void*>(kernel); }
 
 int run_layernorm(const VbModel* m, const float* resid, const float* g, const float* b, int B, hipStream_t st, bf16* xn, bf16* map, float* feat,
                   const Err& E, bf16* xb = nullptr, float* rstd = nullptr, float* mean = nullptr) {
@@ -185,9 +213,30 @@ int run_layernorm(const VbModel* m, const float* resid, const float* g, const fl
 
 constexpr int STAT_P = C / 64;       // (sum, M2) pairs per residual row: one per 64-column wave slice of the 256-wide GEMM tiles
 
-int run_finalize(const VbModel* m, size_t r0, int M, hipStream_t st, const Err& E) {
-    hipLaunchKernelGGL(vbm::ln_finalize_kernel<STAT_P>, dim3((M + 255) / 256), dim3(256), 0, st, m->stats.p + r0, (int)(m->stats.n / STAT_P), M, LN_EPS,
-                       m->rstd.p + r0, m->rmean.p + r0);
+// What an entry addresses for the frame slice [f0, f0 + B) of a batch of Bt frames (vb_api.h Slice; none: the whole batch from frame 0):
+// the slice's first token row, its CU budget and every workspace at that frame.
+struct SliceView {
+    size_t f0, r0;           // first frame, first token row
+    int cus;                 // workgroups of a persistent kernel (0 = one per CU)
+    long long Bt;            // frames of the whole batch: the stride of tower-major buffers
+    bf16 *xn, *qk, *vt, *ao, *hid, *map[5];      // vt: [frame][C][L]; map[0..3]: the head's padded maps, map[4]: conv4's dense output
+    float *resid, *rstd, *rmean;
+    vbg::f2* stats;
+    int ldstats;
+    SliceView(const VbModel* m, int B, const vb::Slice* sl)
+        : f0(sl ? sl->f0 : 0), r0(f0 * m->L), cus(sl ? sl->cus : 0), Bt(sl ? sl->Btot : B), xn(m->xn.p + r0 * C), qk(m->qk.p + r0 * 2 * C),
+          vt(m->vt.p + r0 * C), ao(m->ao.p + r0 * C), hid(m->hid.p + r0 * HID), resid(m->resid.p + r0 * C), rstd(m->rstd.p + r0),
+          rmean(m->rmean.p + r0), stats(m->stats.p + r0), ldstats((int)(m->stats.n / STAT_P)) {
+        const size_t P2 = (size_t)(m->F + 2) * (m->F + 2);
+        for (int i = 0; i < 4; ++i) map[i] = m->map[i].p + f0 * P2 * HEAD_CH[i];
+        map[4] = m->t4.p + f0 * (size_t)m->LX * HEAD_CH[4];
+    }
+    // a GEMM that writes residual rows also leaves their bf16 copy and LayerNorm statistics (the folded LayerNorms, vb_gemm.h)
+    void stats_of(vbg::Args& a) const { a.xb = xn; a.stats = stats; a.ldstats = ldstats; }
+};
+
+int run_finalize(const SliceView& v, int M, hipStream_t st, const Err& E) {
+    hipLaunchKernelGGL(vbm::ln_finalize_kernel<STAT_P>, dim3((M + 255) / 256), dim3(256), 0, st, v.stats, v.ldstats, M, LN_EPS, v.rstd, v.rmean);
     VB_HIP(hipGetLastError());
     return VT_OK;
 }
@@ -212,9 +261,20 @@ void fold_layernorm(std::vector<float>& w, std::vector<float>& b, const float* g
 // errors of a row of W' meet a common mode of ~2 sigma of the patch and the tokens leave the 3.2e-3 the stage is held to (3.3e-3 on
 // noise patches; centred 1.7e-3; the fp32 route 2.3-2.6e-3: NOTES R7-1, tests/test_vitb_track_host.py).  Compensating with the ROUNDED
 // weights instead is algebraically the uncentred form again.  The centring table of the search rows (Args::cm) follows b'.
+// The patch GEMM's centring constants, [L]: a token row is patches W^T + bias + pos row; what is known of its mean before the GEMM runs is
+// mean(bias) + mean(pos row) (the projection of a normalised patch is zero-mean over channels to first order).  bias_sum: over channels
+int upload_centring(Buf<float>& d, const std::vector<float>& pos, double bias_sum, const Err& E) {
+    std::vector<float> cpos(pos.size() / C);
+    for (size_t t = 0; t < cpos.size(); ++t) {
+        double s = 0;
+        for (int k = 0; k < C; ++k) s += pos[t * C + k];
+        cpos[t] = (float)((s + bias_sum) / C);
+    }
+    return upload_f32(d, cpos.data(), cpos.size(), E);
+}
+
 int fold_patch_u8(VbModel* m, const Err& E) {
-    const int L = m->L;
-    std::vector<float> w((size_t)C * PATCH_K), b(C), cpos(L);
+    std::vector<float> w((size_t)C * PATCH_K), b(C);
     double k255[3], ms[3], bsum = 0;
     for (int c = 0; c < 3; ++c) { k255[c] = 1.0 / (255.0 * (double)m->norm_std[c]); ms[c] = (double)m->norm_mean[c] / (double)m->norm_std[c]; }
     for (int n = 0; n < C; ++n) {
@@ -231,14 +291,9 @@ int fold_patch_u8(VbModel* m, const Err& E) {
         b[n] = (float)bd;
         bsum += bd;
     }
-    for (int t = 0; t < L; ++t) {
-        double s = 0;
-        for (int k = 0; k < C; ++k) s += m->h_pos[(size_t)t * C + k];
-        cpos[t] = (float)((s + bsum) / C);
-    }
     int rc;
     if ((rc = upload_bf16(m->wpatch_u8, w, E)) || (rc = upload_f32(m->bpatch_u8, b.data(), b.size(), E))) return rc;
-    return upload_f32(m->cpos_u8, cpos.data(), cpos.size(), E);
+    return upload_centring(m->cpos_u8, m->h_pos, bsum, E);
 }
 
 }  // namespace
@@ -283,36 +338,41 @@ int create(const vt_config* cfg, VbModel** out, std::string* err) {
     m->attn_stream = env_int("VB_ATTN_STREAM", 0) != 0;
     const size_t B = (size_t)cfg->max_batch, M = B * L, P2 = (size_t)(F + 2) * (F + 2);
     hipError_t e = hipSuccess;
-    auto A = [&](auto& buf, size_t n) { if (e == hipSuccess) e = buf.alloc(n); };
     // the streaming attention kernel's last key chunk reads up to PAD_TOKENS rows (qk) / elements (vt) past a frame's last token: the
     // workspaces carry that tail so the reads stay inside them, and are zero-filled ONCE, here.  Nothing read there is used: the kernel
     // masks those keys' scores and zeroes their V^T columns in registers (vb_attn_stream.h)
     constexpr size_t PAD = vbs::PAD_TOKENS;
-    A(m->xn, M * C); A(m->resid, M * C); A(m->qk, (M + PAD) * 2 * C); A(m->vt, M * C + PAD); A(m->ao, M * C); A(m->hid, M * HID);
-    A(m->map0, B * P2 * C); A(m->map1, 3 * B * P2 * HEAD_CH[1]); A(m->map2, 3 * B * P2 * HEAD_CH[2]);
-    A(m->map3, 3 * B * P2 * HEAD_CH[3]); A(m->t4, 3 * B * LX * HEAD_CH[4]);
-    A(m->rstd, M); A(m->stats, (size_t)STAT_P * M); A(m->rmean, M); A(m->zop, B * LZ * PATCH_K);
-    // zero borders of the padded maps (kernels only ever write interiors)
-    if (e == hipSuccess) e = hipMemset(m->map0.p, 0, m->map0.n * 2);
-    if (e == hipSuccess) e = hipMemset(m->map1.p, 0, m->map1.n * 2);
-    if (e == hipSuccess) e = hipMemset(m->map2.p, 0, m->map2.n * 2);
-    if (e == hipSuccess) e = hipMemset(m->map3.p, 0, m->map3.n * 2);
-    if (e == hipSuccess) e = hipMemset(m->qk.p, 0, m->qk.n * 2);
-    if (e == hipSuccess) e = hipMemset(m->vt.p, 0, m->vt.n * 2);
+    auto alloc_all = [&](auto list) {
+        for (const auto& w : list)
+            if (e == hipSuccess) e = w.first->alloc(w.second);
+    };
+    alloc_all(std::initializer_list<std::pair<Buf<bf16>*, size_t>>{
+        {&m->xn, M * C}, {&m->qk, (M + PAD) * 2 * C}, {&m->vt, M * C + PAD}, {&m->ao, M * C}, {&m->hid, M * HID}, {&m->map[0], B * P2 * C},
+        {&m->map[1], 3 * B * P2 * HEAD_CH[1]}, {&m->map[2], 3 * B * P2 * HEAD_CH[2]}, {&m->map[3], 3 * B * P2 * HEAD_CH[3]},
+        {&m->t4, 3 * B * LX * HEAD_CH[4]}, {&m->zop, B * LZ * PATCH_K}});
+    alloc_all(std::initializer_list<std::pair<Buf<float>*, size_t>>{{&m->resid, M * C}, {&m->rstd, M}, {&m->rmean, M}});
+    alloc_all(std::initializer_list<std::pair<Buf<vbg::f2>*, size_t>>{{&m->stats, (size_t)STAT_P * M}});
+    // zero borders of the padded maps (kernels only ever write interiors), and the two tails
+    Buf<bf16>* const zeroed[] = {&m->map[0], &m->map[1], &m->map[2], &m->map[3], &m->qk, &m->vt};
+    for (Buf<bf16>* b : zeroed)
+        if (e == hipSuccess) e = hipMemset(b->p, 0, b->n * 2);
     using namespace vbg;
-    if (e == hipSuccess) e = allow_lds(gemm_kernel<256, 256, 2, 4, A_PLAIN, EPI_PATCH>, lds_bytes<256, 256>());
-    if (e == hipSuccess) e = allow_lds(gemm_kernel<256, 256, 2, 4, A_PLAIN, EPI_PATCH_ROWS>, lds_bytes<256, 256>());
-    if (e == hipSuccess) e = allow_lds(gemm_kernel<256, 256, 2, 4, A_PLAIN, EPI_PATCH_ROWS_N>, lds_bytes<256, 256>());
-    if (e == hipSuccess) e = allow_lds(gemm_kernel<256, 256, 2, 4, A_PLAIN, EPI_BF16>, lds_bytes<256, 256>());
-    if (e == hipSuccess) e = allow_lds(gemm_kernel<256, 256, 2, 4, A_PLAIN, EPI_VT>, lds_bytes<256, 256>());
-    if (e == hipSuccess) e = allow_lds(gemm_kernel<256, 256, 2, 4, A_PLAIN, EPI_RESID>, lds_bytes<256, 256>());
-    if (e == hipSuccess) e = allow_lds(gemm_kernel<256, 256, 2, 4, A_PLAIN, EPI_GELU>, lds_bytes<256, 256>());
-    if (e == hipSuccess) e = allow_lds(gemm_kernel<256, 256, 2, 4, A_CONV, EPI_CONV>, lds_bytes<256, 256>());
-    if (e == hipSuccess) e = allow_lds(gemm_kernel<256, 64, 8, 1, A_CONV, EPI_CONV>, lds_bytes<256, 64>());
-    if (e == hipSuccess) e = allow_lds(vba::attn_kernel<L256, HD>, vba::Geo<L256, HD>::LDS_BYTES);
-    if (e == hipSuccess) e = allow_lds(vbs::attn_stream_kernel<L256>, vbs::LDS_BYTES);
-    if (e == hipSuccess) e = allow_lds(vbs::attn_stream_kernel<L384>, vbs::LDS_BYTES);
-    if (e == hipSuccess) e = allow_lds(vbq::qkv_attn_kernel, vbq::LDS_BYTES);
+    const struct { const void* kernel; int lds; } dynamic_lds[] = {
+        {kernel_ptr(gemm_kernel<256, 256, 2, 4, A_PLAIN, EPI_PATCH>), lds_bytes<256, 256>()},
+        {kernel_ptr(gemm_kernel<256, 256, 2, 4, A_PLAIN, EPI_PATCH_ROWS>), lds_bytes<256, 256>()},
+        {kernel_ptr(gemm_kernel<256, 256, 2, 4, A_PLAIN, EPI_PATCH_ROWS_N>), lds_bytes<256, 256>()},
+        {kernel_ptr(gemm_kernel<256, 256, 2, 4, A_PLAIN, EPI_BF16>), lds_bytes<256, 256>()},
+        {kernel_ptr(gemm_kernel<256, 256, 2, 4, A_PLAIN, EPI_VT>), lds_bytes<256, 256>()},
+        {kernel_ptr(gemm_kernel<256, 256, 2, 4, A_PLAIN, EPI_RESID>), lds_bytes<256, 256>()},
+        {kernel_ptr(gemm_kernel<256, 256, 2, 4, A_PLAIN, EPI_GELU>), lds_bytes<256, 256>()},
+        {kernel_ptr(gemm_kernel<256, 256, 2, 4, A_CONV, EPI_CONV>), lds_bytes<256, 256>()},
+        {kernel_ptr(gemm_kernel<256, 64, 8, 1, A_CONV, EPI_CONV>), lds_bytes<256, 64>()},
+        {kernel_ptr(vba::attn_kernel<L256, HD>), vba::Geo<L256, HD>::LDS_BYTES},
+        {kernel_ptr(vbs::attn_stream_kernel<L256>), vbs::LDS_BYTES},
+        {kernel_ptr(vbs::attn_stream_kernel<L384>), vbs::LDS_BYTES},
+        {kernel_ptr(vbq::qkv_attn_kernel), vbq::LDS_BYTES}};
+    for (const auto& k : dynamic_lds)
+        if (e == hipSuccess) e = hipFuncSetAttribute(k.kernel, hipFuncAttributeMaxDynamicSharedMemorySize, k.lds);
     if (e != hipSuccess) {
         destroy(m);
         return E.fail(VT_ERR_HIP, std::string("ViT-Base workspace: ") + hipGetErrorString(e));
@@ -321,21 +381,7 @@ int create(const vt_config* cfg, VbModel** out, std::string* err) {
     return VT_OK;
 }
 
-void destroy(VbModel* m) {
-    if (!m) return;
-    m->wpatch.release(); m->bpatch.release(); m->pos.release(); m->ng.release(); m->nb.release();
-    for (BlockW& b : m->blk) {
-        b.ln1g.release(); b.ln1b.release(); b.ln2g.release(); b.ln2b.release(); b.bqkv.release(); b.bproj.release();
-        b.b1.release(); b.b2.release(); b.wqkv.release(); b.wproj.release(); b.w1.release(); b.w2.release();
-    }
-    for (int i = 0; i < 4; ++i) { m->wc[i].release(); m->bc[i].release(); }
-    m->w5.release(); m->b5.release();
-    m->xn.release(); m->qk.release(); m->vt.release(); m->ao.release(); m->hid.release(); m->map0.release();
-    m->map1.release(); m->map2.release(); m->map3.release(); m->t4.release(); m->resid.release();
-    m->rstd.release(); m->stats.release(); m->rmean.release(); m->cpos.release();
-    m->wpatch_u8.release(); m->bpatch_u8.release(); m->cpos_u8.release(); m->zop.release();
-    delete m;
-}
+void destroy(VbModel* m) { delete m; }      // every Buf frees its own
 
 // Key layout: the reference's OSTrack ckpt['net'] -- backbone.{patch_embed.proj, pos_embed_z, pos_embed_x, blocks.N.*, norm},
 // box_head.* (lib/models/ostrack/vit.py:94-139, base_backbone.py:83-84, lib/models/layers/head.py:98-128).
@@ -345,75 +391,45 @@ int load_weights(VbModel* m, const TensorMap& tm, std::string* err) {
     const float* p;
     const std::string bb = "backbone.";
     const int L = m->L, LZ = m->LZ, LX = m->LX;
-    if ((rc = need(tm, bb + "patch_embed.proj.weight", (int64_t)C * PATCH_K, &p, E))) return rc;
-    if ((rc = upload_bf16(m->wpatch, std::vector<float>(p, p + (size_t)C * PATCH_K), E))) return rc;
-    if ((rc = need(tm, bb + "patch_embed.proj.bias", C, &p, E))) return rc;
-    if ((rc = upload_f32(m->bpatch, p, C, E))) return rc;
-    m->h_bpatch.assign(p, p + C);
-    if ((rc = need(tm, bb + "patch_embed.proj.weight", (int64_t)C * PATCH_K, &p, E))) return rc;
-    m->h_wpatch.assign(p, p + (size_t)C * PATCH_K);
-    {
-        std::vector<float> pos((size_t)L * C);
-        if ((rc = need(tm, bb + "pos_embed_z", (int64_t)LZ * C, &p, E))) return rc;
-        std::memcpy(pos.data(), p, (size_t)LZ * C * 4);
-        if ((rc = need(tm, bb + "pos_embed_x", (int64_t)LX * C, &p, E))) return rc;
-        std::memcpy(pos.data() + (size_t)LZ * C, p, (size_t)LX * C * 4);
-        if ((rc = upload_f32(m->pos, pos.data(), pos.size(), E))) return rc;
-        // the patch GEMM's centring constants: a token row is patches W^T + bias + pos row; what is known of its mean before the GEMM runs
-        // is mean(bias) + mean(pos row) (the projection of a normalised patch is zero-mean over channels to first order)
-        const float* bp = nullptr;
-        if ((rc = need(tm, bb + "patch_embed.proj.bias", C, &bp, E))) return rc;
-        double bmean = 0;
-        for (int k = 0; k < C; ++k) bmean += bp[k];
-        std::vector<float> cpos(L);
-        for (int t = 0; t < L; ++t) {
-            double s = 0;
-            for (int k = 0; k < C; ++k) s += pos[(size_t)t * C + k];
-            cpos[t] = (float)((s + bmean) / C);
-        }
-        if ((rc = upload_f32(m->cpos, cpos.data(), cpos.size(), E))) return rc;
-        m->h_pos = pos;
-        if ((rc = fold_patch_u8(m, E))) return rc;
-    }
+    const float *wp, *bp;
+    if ((rc = load_bf16(m->wpatch, tm, bb + "patch_embed.proj.weight", (int64_t)C * PATCH_K, E, &wp))) return rc;
+    if ((rc = load_f32(m->bpatch, tm, bb + "patch_embed.proj.bias", C, E, &bp))) return rc;
+    m->h_wpatch.assign(wp, wp + (size_t)C * PATCH_K);
+    m->h_bpatch.assign(bp, bp + C);
+    m->h_pos.resize((size_t)L * C);
+    if ((rc = need(tm, bb + "pos_embed_z", (int64_t)LZ * C, &p, E))) return rc;
+    std::memcpy(m->h_pos.data(), p, (size_t)LZ * C * 4);
+    if ((rc = need(tm, bb + "pos_embed_x", (int64_t)LX * C, &p, E))) return rc;
+    std::memcpy(m->h_pos.data() + (size_t)LZ * C, p, (size_t)LX * C * 4);
+    if ((rc = upload_f32(m->pos, m->h_pos.data(), m->h_pos.size(), E))) return rc;
+    double bsum = 0;
+    for (int k = 0; k < C; ++k) bsum += bp[k];
+    if ((rc = upload_centring(m->cpos, m->h_pos, bsum, E)) || (rc = fold_patch_u8(m, E))) return rc;
     const float scale = 1.0f / std::sqrt((float)HD);     // 0.125: a power of two, folding it into W_q / b_q is exact
     for (int i = 0; i < m->depth; ++i) {
         BlockW& b = m->blk[i];
         const std::string pre = bb + "blocks." + std::to_string(i) + ".";
-        struct V { const char* name; Buf<float>* dst; int n; };
-        const V vecs[] = {{"norm1.weight", &b.ln1g, C}, {"norm1.bias", &b.ln1b, C}, {"norm2.weight", &b.ln2g, C}, {"norm2.bias", &b.ln2b, C},
-                          {"attn.proj.bias", &b.bproj, C}, {"mlp.fc2.bias", &b.b2, C}};
-        for (const V& v : vecs) {
-            if ((rc = need(tm, pre + v.name, v.n, &p, E))) return rc;
-            if ((rc = upload_f32(*v.dst, p, v.n, E))) return rc;
-        }
         const float *g1, *be1, *g2, *be2;
-        if ((rc = need(tm, pre + "norm1.weight", C, &g1, E)) || (rc = need(tm, pre + "norm1.bias", C, &be1, E))) return rc;
-        if ((rc = need(tm, pre + "norm2.weight", C, &g2, E)) || (rc = need(tm, pre + "norm2.bias", C, &be2, E))) return rc;
-        if ((rc = need(tm, pre + "attn.qkv.weight", (int64_t)3 * C * C, &p, E))) return rc;
-        std::vector<float> w(p, p + (size_t)3 * C * C);
-        if ((rc = need(tm, pre + "attn.qkv.bias", 3 * C, &p, E))) return rc;
-        std::vector<float> bq(p, p + 3 * C);
-        if (m->fold) fold_layernorm(w, bq, g1, be1, 3 * C, C);
-        for (size_t k = 0; k < (size_t)C * C; ++k) w[k] *= scale;
-        for (int k = 0; k < C; ++k) bq[k] *= scale;
-        if ((rc = upload_bf16(b.wqkv, w, E))) return rc;
-        if ((rc = upload_f32(b.bqkv, bq.data(), bq.size(), E))) return rc;
-        if ((rc = need(tm, pre + "attn.proj.weight", (int64_t)C * C, &p, E))) return rc;
-        if ((rc = upload_bf16(b.wproj, std::vector<float>(p, p + (size_t)C * C), E))) return rc;
-        if ((rc = need(tm, pre + "mlp.fc1.weight", (int64_t)HID * C, &p, E))) return rc;
-        std::vector<float> w1(p, p + (size_t)HID * C);
-        if ((rc = need(tm, pre + "mlp.fc1.bias", HID, &p, E))) return rc;
-        std::vector<float> b1(p, p + HID);
-        if (m->fold) fold_layernorm(w1, b1, g2, be2, HID, C);
-        if ((rc = upload_bf16(b.w1, w1, E))) return rc;
-        if ((rc = upload_f32(b.b1, b1.data(), b1.size(), E))) return rc;
-        if ((rc = need(tm, pre + "mlp.fc2.weight", (int64_t)HID * C, &p, E))) return rc;
-        if ((rc = upload_bf16(b.w2, std::vector<float>(p, p + (size_t)HID * C), E))) return rc;
+        if ((rc = load_f32(b.ln1g, tm, pre + "norm1.weight", C, E, &g1)) || (rc = load_f32(b.ln1b, tm, pre + "norm1.bias", C, E, &be1))) return rc;
+        if ((rc = load_f32(b.ln2g, tm, pre + "norm2.weight", C, E, &g2)) || (rc = load_f32(b.ln2b, tm, pre + "norm2.bias", C, E, &be2))) return rc;
+        if ((rc = load_f32(b.bproj, tm, pre + "attn.proj.bias", C, E)) || (rc = load_f32(b.b2, tm, pre + "mlp.fc2.bias", C, E))) return rc;
+        // a Linear behind a LayerNorm: the norm folded in (VB_LN_FOLD), its first `nscaled` output rows times the attention scale
+        auto folded = [&](const std::string& name, int N, const float* g, const float* be, int nscaled, Buf<bf16>& W, Buf<float>& Bv) {
+            const float *pw, *pb;
+            if ((rc = need(tm, pre + name + ".weight", (int64_t)N * C, &pw, E)) || (rc = need(tm, pre + name + ".bias", N, &pb, E))) return rc;
+            std::vector<float> w(pw, pw + (size_t)N * C), bias(pb, pb + N);
+            if (m->fold) fold_layernorm(w, bias, g, be, N, C);
+            for (size_t k = 0; k < (size_t)nscaled * C; ++k) w[k] *= scale;
+            for (int k = 0; k < nscaled; ++k) bias[k] *= scale;
+            if ((rc = upload_bf16(W, w, E))) return rc;
+            return upload_f32(Bv, bias.data(), bias.size(), E);
+        };
+        if ((rc = folded("attn.qkv", 3 * C, g1, be1, C, b.wqkv, b.bqkv))) return rc;
+        if ((rc = load_bf16(b.wproj, tm, pre + "attn.proj.weight", (int64_t)C * C, E))) return rc;
+        if ((rc = folded("mlp.fc1", HID, g2, be2, 0, b.w1, b.b1))) return rc;
+        if ((rc = load_bf16(b.w2, tm, pre + "mlp.fc2.weight", (int64_t)HID * C, E))) return rc;
     }
-    if ((rc = need(tm, bb + "norm.weight", C, &p, E))) return rc;
-    if ((rc = upload_f32(m->ng, p, C, E))) return rc;
-    if ((rc = need(tm, bb + "norm.bias", C, &p, E))) return rc;
-    if ((rc = upload_f32(m->nb, p, C, E))) return rc;
+    if ((rc = load_f32(m->ng, tm, bb + "norm.weight", C, E)) || (rc = load_f32(m->nb, tm, bb + "norm.bias", C, E))) return rc;
     // ---- head: Conv3x3(+bias) + BatchNorm(eval, eps 1e-5) folded in double (head.py:8-21), weights as [cout][tap][cin]
     const char* towers[3] = {"ctr", "offset", "size"};
     for (int li = 0; li < 4; ++li) {
@@ -425,13 +441,11 @@ int load_weights(VbModel* m, const TensorMap& tm, std::string* err) {
         std::vector<float> w((size_t)3 * rows * K, 0.f), bias((size_t)3 * cout);
         for (int t = 0; t < 3; ++t) {
             const std::string cn = std::string("box_head.conv") + std::to_string(li + 1) + "_" + towers[t];
-            const float *pw, *pb, *g, *beta, *mu, *var;
-            if ((rc = need(tm, cn + ".0.weight", (int64_t)cout * cin * 9, &pw, E))) return rc;
-            if ((rc = need(tm, cn + ".0.bias", cout, &pb, E))) return rc;
-            if ((rc = need(tm, cn + ".1.weight", cout, &g, E))) return rc;
-            if ((rc = need(tm, cn + ".1.bias", cout, &beta, E))) return rc;
-            if ((rc = need(tm, cn + ".1.running_mean", cout, &mu, E))) return rc;
-            if ((rc = need(tm, cn + ".1.running_var", cout, &var, E))) return rc;
+            const char* keys[6] = {".0.weight", ".0.bias", ".1.weight", ".1.bias", ".1.running_mean", ".1.running_var"};
+            const float* t6[6];
+            for (int k = 0; k < 6; ++k)
+                if ((rc = need(tm, cn + keys[k], k ? cout : (int64_t)cout * cin * 9, &t6[k], E))) return rc;
+            const float *pw = t6[0], *pb = t6[1], *g = t6[2], *beta = t6[3], *mu = t6[4], *var = t6[5];
             for (int o = 0; o < cout; ++o) {
                 const double k = (double)g[o] / std::sqrt((double)var[o] + 1e-5);
                 float* dst = w.data() + ((size_t)t * rows + o) * K;
@@ -480,30 +494,24 @@ int stem(VbModel* m, const float* z, const float* x, int B, hipStream_t st, floa
     int rc = check(m, B, E);
     if (rc || (rc = check_slice(m, B, sl, E))) return rc;
     const int L = m->L, M = B * L;
-    const size_t r0 = (sl ? sl->f0 : 0) * L;          // first token row of the slice
-    const int cus = sl ? sl->cus : 0;
-    bf16* const xn = m->xn.p + r0 * C;
-    bf16* const patches = (m->fold ? m->ao.p : m->xn.p) + r0 * C;     // folded: xn receives the tokens' bf16 copy from the GEMM epilogue
-    float* const resid = m->resid.p + r0 * C;
-    const size_t items = (size_t)M * 96;
-    hipLaunchKernelGGL(vbm::patchify_kernel, dim3((unsigned)std::min<size_t>((items + 255) / 256, 16384)), dim3(256), 0, st, z, x, patches,
-                       B, m->TZ, m->TX);
+    const SliceView v(m, B, sl);
+    bf16* const patches = m->fold ? v.ao : v.xn;     // folded: xn receives the tokens' bf16 copy from the GEMM epilogue
+    hipLaunchKernelGGL(vbm::patchify_kernel, dim3(grid256((size_t)M * 96)), dim3(256), 0, st, z, x, patches, B, m->TZ, m->TX);
     VB_HIP(hipGetLastError());
     vbg::Args a{};
-    a.X = patches; a.W = m->wpatch.p; a.bias = m->bpatch.p; a.resid = resid; a.pos = m->pos.p;
+    a.X = patches; a.W = m->wpatch.p; a.bias = m->bpatch.p; a.resid = v.resid; a.pos = m->pos.p;
     a.M = M; a.N = C; a.K = PATCH_K; a.L = L;
-    if (m->fold) { a.xb = xn; a.stats = m->stats.p + r0; a.ldstats = (int)(m->stats.n / STAT_P); }
+    if (m->fold) v.stats_of(a);
     if (m->fold && m->center) { a.cm = m->cpos.p; a.cm_mod = L; }
-    if ((rc = launch_gemm<256, 256, 2, 4, vbg::A_PLAIN, vbg::EPI_PATCH>(a, 1, st, E, cus))) return rc;
-    if (m->fold && (rc = run_finalize(m, r0, M, st, E))) return rc;
-    if (tokens_out) VB_HIP(hipMemcpyAsync(tokens_out, resid, (size_t)M * C * 4, hipMemcpyDeviceToDevice, st));
+    if ((rc = launch_gemm<256, 256, 2, 4, vbg::A_PLAIN, vbg::EPI_PATCH>(a, 1, st, E, v.cus))) return rc;
+    if (m->fold && (rc = run_finalize(v, M, st, E))) return rc;
+    if (tokens_out) VB_HIP(hipMemcpyAsync(tokens_out, v.resid, (size_t)M * C * 4, hipMemcpyDeviceToDevice, st));
     return VT_OK;
 }
 
 // one token kind's rows of a crop batch as a dense operand: patchify_kernel with no template (Tz = 0) walks (B, 3, T, T) alone
 static int patchify_dense(const float* img, int T, int B, bf16* P, hipStream_t st, const Err& E) {
-    const size_t items = (size_t)B * (T / 16) * (T / 16) * 96;
-    hipLaunchKernelGGL(vbm::patchify_kernel, dim3((unsigned)std::min<size_t>((items + 255) / 256, 16384)), dim3(256), 0, st, nullptr, img, P, B, 0, T);
+    hipLaunchKernelGGL(vbm::patchify_kernel, dim3(grid256((size_t)B * (T / 16) * (T / 16) * 96)), dim3(256), 0, st, nullptr, img, P, B, 0, T);
     VB_HIP(hipGetLastError());
     return VT_OK;
 }
@@ -530,31 +538,25 @@ int stem_rows(VbModel* m, ZSrc zsrc, const float* z, const float* x, const unsig
     if ((x != nullptr) == (xu8 != nullptr)) return E.fail(VT_ERR_ARG, "stem_rows: one of the fp32 crop and the uint8 patch");
     if (xu8 && (reinterpret_cast<uintptr_t>(xu8) & 15)) return E.fail(VT_ERR_ARG, "the uint8 patch must be 16-byte aligned on the ViT-Base path");
     const int L = m->L, LZ = m->LZ, LX = m->LX;
-    const size_t f0 = sl ? sl->f0 : 0, r0 = f0 * L;
-    const int cus = sl ? sl->cus : 0;
-    bf16* const xn = m->xn.p + r0 * C;
-    float* const resid = m->resid.p + r0 * C;
-    bf16* const xop = (m->fold ? m->ao.p : m->xn.p) + r0 * C;      // B * LX dense rows inside the slice's B * L (as vb::stem's operand)
-    const bf16* zop = m->zop.p + f0 * LZ * PATCH_K;
+    const SliceView v(m, B, sl);
+    bf16* const xop = m->fold ? v.ao : v.xn;      // B * LX dense rows inside the slice's B * L (as vb::stem's operand)
+    const bf16* zop = m->zop.p + v.f0 * LZ * PATCH_K;
     if (zsrc == Z_GIVEN) {      // not through the cache: a call with its own template leaves vt_set_template's rows alone
-        bf16* const ztmp = m->hid.p + r0 * HID;
-        if ((rc = patchify_dense(z, m->TZ, B, ztmp, st, E))) return rc;
-        zop = ztmp;
+        if ((rc = patchify_dense(z, m->TZ, B, v.hid, st, E))) return rc;
+        zop = v.hid;
     }
     if (xu8) {
-        const size_t items = (size_t)B * LX * 16;
-        hipLaunchKernelGGL(vbm::patchify_u8_kernel, dim3((unsigned)std::min<size_t>((items + 255) / 256, 16384)), dim3(256), 0, st, xu8, xop, B, m->TX,
-                           m->u8_centre);
+        hipLaunchKernelGGL(vbm::patchify_u8_kernel, dim3(grid256((size_t)B * LX * 16)), dim3(256), 0, st, xu8, xop, B, m->TX, m->u8_centre);
         VB_HIP(hipGetLastError());
     } else if ((rc = patchify_dense(x, m->TX, B, xop, st, E))) return rc;
     vbg::Args a{};
-    a.resid = resid; a.pos = m->pos.p; a.N = C; a.K = PATCH_K; a.L = L;
-    if (m->fold) { a.xb = xn; a.stats = m->stats.p + r0; a.ldstats = (int)(m->stats.n / STAT_P); }
+    a.resid = v.resid; a.pos = m->pos.p; a.N = C; a.K = PATCH_K; a.L = L;
+    if (m->fold) v.stats_of(a);
     // operand rows -> (frame, token): a shift at 64 / 256 rows per frame, the rows themselves at 144 / 576 (EPI_PATCH_ROWS_N)
     auto rows_gemm = [&](vbg::Args& g, int rows, int shift) {
         g.row_shift = shift < 0 ? rows : shift;
-        return shift < 0 ? launch_gemm<256, 256, 2, 4, vbg::A_PLAIN, vbg::EPI_PATCH_ROWS_N>(g, 1, st, E, cus)
-                       : launch_gemm<256, 256, 2, 4, vbg::A_PLAIN, vbg::EPI_PATCH_ROWS>(g, 1, st, E, cus);
+        return shift < 0 ? launch_gemm<256, 256, 2, 4, vbg::A_PLAIN, vbg::EPI_PATCH_ROWS_N>(g, 1, st, E, v.cus)
+                       : launch_gemm<256, 256, 2, 4, vbg::A_PLAIN, vbg::EPI_PATCH_ROWS>(g, 1, st, E, v.cus);
     };
     if (zsrc != Z_NONE) {
         vbg::Args az = a;
@@ -567,10 +569,45 @@ int stem_rows(VbModel* m, ZSrc zsrc, const float* z, const float* x, const unsig
     a.bias = xu8 ? m->bpatch_u8.p : m->bpatch.p;
     if (m->fold && m->center) a.cm = xu8 ? m->cpos_u8.p : m->cpos.p;
     if ((rc = rows_gemm(a, LX, m->xshift))) return rc;
-    if (m->fold && (rc = run_finalize(m, r0, B * L, st, E))) return rc;
+    if (m->fold && (rc = run_finalize(v, B * L, st, E))) return rc;
     if (x_tokens_out)
-        VB_HIP(hipMemcpy2DAsync(x_tokens_out + (size_t)LZ * C, (size_t)L * C * 4, resid + (size_t)LZ * C, (size_t)L * C * 4, (size_t)LX * C * 4, B,
+        VB_HIP(hipMemcpy2DAsync(x_tokens_out + (size_t)LZ * C, (size_t)L * C * 4, v.resid + (size_t)LZ * C, (size_t)L * C * 4, (size_t)LX * C * 4, B,
                                 hipMemcpyDeviceToDevice, st));
+    return VT_OK;
+}
+
+// One block's attention into v.ao, in one of four forms:
+//   fused (the default at 320 tokens)       vbq::qkv_attn_kernel: projection + attention of a (frame, head) in one workgroup, q / k / v^T never leave the CU
+//   otherwise qk GEMM + v GEMM (V^T) and    vbs::attn_stream_kernel<720> (the 384 geometry), vbs::attn_stream_kernel<320> (VB_ATTN_STREAM) or
+//                                           vba::attn_kernel<320, 64>
+static int run_attention(const VbModel* m, const SliceView& v, const BlockW& b, const float* rstd, int B, hipStream_t st, const Err& E) {
+    int rc;
+    if (m->fused_qkv && !m->g384) {
+        vbq::Args qa{};
+        qa.X = v.xn; qa.W = b.wqkv.p; qa.bias = b.bqkv.p; qa.rstd = rstd; qa.out = v.ao; qa.B = B; qa.heads = HEADS;
+        static const int hgv = env_int("VB_QA_HGROUP", 6);
+        qa.hgroup = (hgv > 0 && HEADS % hgv == 0) ? hgv : HEADS;
+        hipLaunchKernelGGL(vbq::qkv_attn_kernel, dim3(persistent_grid(v.cus)), dim3(512), vbq::LDS_BYTES, st, qa);
+        VB_HIP(hipGetLastError());
+        return VT_OK;
+    }
+    const int L = m->L, M = B * L;
+    vbg::Args a{};
+    a.rstd = rstd;
+    a.X = v.xn; a.W = b.wqkv.p; a.bias = b.bqkv.p; a.out = v.qk;          // q | k: rows 0 .. 2C of W_qkv
+    a.M = M; a.N = 2 * C; a.K = C; a.ldo = 2 * C; a.rb = 4;    // 4 tile rows x 8 columns per XCD: measured 4 % faster than row-major
+    if ((rc = launch_gemm<256, 256, 2, 4, vbg::A_PLAIN, vbg::EPI_BF16>(a, 1, st, E, v.cus))) return rc;
+    vbg::Args w{};
+    w.X = v.xn; w.W = b.wqkv.p + (size_t)2 * C * C; w.bias = b.bqkv.p + 2 * C; w.vt = v.vt;   // v: rows 2C .. 3C, stored transposed
+    w.M = M; w.N = C; w.K = C; w.L = L; w.rstd = rstd;
+    if ((rc = launch_gemm<256, 256, 2, 4, vbg::A_PLAIN, vbg::EPI_VT>(w, 1, st, E, v.cus))) return rc;
+    if (m->g384)
+        hipLaunchKernelGGL((vbs::attn_stream_kernel<L384>), dim3(B * HEADS * vbs::splits<L384>()), dim3(256), vbs::LDS_BYTES, st, v.qk, v.vt, v.ao, HEADS);
+    else if (m->attn_stream)
+        hipLaunchKernelGGL((vbs::attn_stream_kernel<L256>), dim3(B * HEADS * vbs::splits<L256>()), dim3(256), vbs::LDS_BYTES, st, v.qk, v.vt, v.ao, HEADS);
+    else
+        hipLaunchKernelGGL((vba::attn_kernel<L256, HD>), dim3(B * HEADS), dim3(256), (vba::Geo<L256, HD>::LDS_BYTES), st, v.qk, v.vt, v.ao, HEADS);
+    VB_HIP(hipGetLastError());
     return VT_OK;
 }
 
@@ -579,74 +616,38 @@ int blocks(VbModel* m, const float* tokens_in, int B, int nblocks, hipStream_t s
     const Err E{err};
     int rc = check(m, B, E);
     if (rc || (rc = check_slice(m, B, sl, E))) return rc;
-    const int L = m->L, F = m->F, M = B * L;
-    const size_t f0 = sl ? sl->f0 : 0, r0 = f0 * L;
-    const int cus = sl ? sl->cus : 0;
-    bf16* const xn = m->xn.p + r0 * C;
-    float* const resid = m->resid.p + r0 * C;
-    bf16* const qk = m->qk.p + r0 * 2 * C;
-    bf16* const vt = m->vt.p + r0 * C;                 // [frame][C][L]
-    bf16* const ao = m->ao.p + r0 * C;
-    bf16* const hid = m->hid.p + r0 * HID;
-    bf16* const map0 = m->map0.p + f0 * (size_t)(F + 2) * (F + 2) * C;
+    const int M = B * m->L;
+    const SliceView v(m, B, sl);
     if (nblocks < 0 || nblocks > m->depth) nblocks = m->depth;
-    if (tokens_in && tokens_in != resid)
-        VB_HIP(hipMemcpyAsync(resid, tokens_in, (size_t)M * C * 4, hipMemcpyDeviceToDevice, st));
+    if (tokens_in && tokens_in != v.resid)
+        VB_HIP(hipMemcpyAsync(v.resid, tokens_in, (size_t)M * C * 4, hipMemcpyDeviceToDevice, st));
     const bool fold = m->fold;
-    float* const rstd = fold ? m->rstd.p + r0 : nullptr;
-    vbg::f2* const stats = m->stats.p + r0;
-    const int ldstats = (int)(m->stats.n / STAT_P);
+    float* const rstd = fold ? v.rstd : nullptr;
     // folded LayerNorms: a residual stream from outside has no bf16 copy / rstd yet (vb::stem leaves both behind its GEMM)
-    const float* const cmean = (fold && m->center) ? m->rmean.p + r0 : nullptr;
-    if (fold && tokens_in && nblocks > 0 && (rc = run_layernorm(m, resid, nullptr, nullptr, B, st, nullptr, nullptr, nullptr, E, xn, rstd, m->rmean.p + r0))) return rc;
+    const float* const cmean = (fold && m->center) ? v.rmean : nullptr;
+    if (fold && tokens_in && nblocks > 0 && (rc = run_layernorm(m, v.resid, nullptr, nullptr, B, st, nullptr, nullptr, nullptr, E, v.xn, rstd, v.rmean))) return rc;
+    // a GEMM onto the residual stream; feeds_ln: a folded LayerNorm reads what it leaves (bf16 copy centred on cmean + statistics, then finalize)
+    auto resid_gemm = [&](const bf16* X, const bf16* W, const float* bias, int K, bool feeds_ln) {
+        vbg::Args p{};
+        p.X = X; p.W = W; p.bias = bias; p.resid = v.resid; p.M = M; p.N = C; p.K = K;
+        if (feeds_ln) { v.stats_of(p); p.cm = cmean; }
+        if (int r = launch_gemm<256, 256, 2, 4, vbg::A_PLAIN, vbg::EPI_RESID>(p, 1, st, E, v.cus)) return r;
+        return feeds_ln ? run_finalize(v, M, st, E) : VT_OK;
+    };
     for (int i = 0; i < nblocks; ++i) {
         const BlockW& b = m->blk[i];
-        if (!fold && (rc = run_layernorm(m, resid, b.ln1g.p, b.ln1b.p, B, st, xn, nullptr, nullptr, E))) return rc;
-        if (m->fused_qkv && !m->g384) {          // projection + attention of a (frame, head) in one workgroup: q / k / v^T never leave the CU
-            vbq::Args qa{};
-            qa.X = xn; qa.W = b.wqkv.p; qa.bias = b.bqkv.p; qa.rstd = rstd; qa.out = ao; qa.B = B; qa.heads = HEADS;
-            { static const int hgv = env_int("VB_QA_HGROUP", 6); qa.hgroup = (hgv > 0 && HEADS % hgv == 0) ? hgv : HEADS; }
-            const int grid = std::max(8, (cus > 0 ? std::min(cus, num_cus()) : num_cus()) / 8 * 8);
-            hipLaunchKernelGGL(vbq::qkv_attn_kernel, dim3(grid), dim3(512), vbq::LDS_BYTES, st, qa);
-            VB_HIP(hipGetLastError());
-        } else {
-        vbg::Args a{};
-        a.rstd = rstd;
-        a.X = xn; a.W = b.wqkv.p; a.bias = b.bqkv.p; a.out = qk;          // q | k: rows 0 .. 2C of W_qkv
-        a.M = M; a.N = 2 * C; a.K = C; a.ldo = 2 * C; a.rb = 4;    // 4 tile rows x 8 columns per XCD: measured 4 % faster than row-major
-        if ((rc = launch_gemm<256, 256, 2, 4, vbg::A_PLAIN, vbg::EPI_BF16>(a, 1, st, E, cus))) return rc;
-        vbg::Args v{};
-        v.X = xn; v.W = b.wqkv.p + (size_t)2 * C * C; v.bias = b.bqkv.p + 2 * C; v.vt = vt;   // v: rows 2C .. 3C, stored transposed
-        v.M = M; v.N = C; v.K = C; v.L = L; v.rstd = rstd;
-        if ((rc = launch_gemm<256, 256, 2, 4, vbg::A_PLAIN, vbg::EPI_VT>(v, 1, st, E, cus))) return rc;
-        if (m->g384)
-            hipLaunchKernelGGL((vbs::attn_stream_kernel<L384>), dim3(B * HEADS * vbs::splits<L384>()), dim3(256), vbs::LDS_BYTES, st, qk, vt, ao, HEADS);
-        else if (m->attn_stream)
-            hipLaunchKernelGGL((vbs::attn_stream_kernel<L256>), dim3(B * HEADS * vbs::splits<L256>()), dim3(256), vbs::LDS_BYTES, st, qk, vt, ao, HEADS);
-        else {
-        constexpr int attn_lds = vba::Geo<L256, HD>::LDS_BYTES;
-        hipLaunchKernelGGL((vba::attn_kernel<L256, HD>), dim3(B * HEADS), dim3(256), attn_lds, st, qk, vt, ao, HEADS);
-        }
-        VB_HIP(hipGetLastError());
-        }
-        vbg::Args p{};
-        p.X = ao; p.W = b.wproj.p; p.bias = b.bproj.p; p.resid = resid; p.M = M; p.N = C; p.K = C;
-        if (fold) { p.xb = xn; p.stats = stats; p.ldstats = ldstats; p.cm = cmean; }
-        if ((rc = launch_gemm<256, 256, 2, 4, vbg::A_PLAIN, vbg::EPI_RESID>(p, 1, st, E, cus))) return rc;
-        if (fold ? (rc = run_finalize(m, r0, M, st, E)) : (rc = run_layernorm(m, resid, b.ln2g.p, b.ln2b.p, B, st, xn, nullptr, nullptr, E))) return rc;
+        if (!fold && (rc = run_layernorm(m, v.resid, b.ln1g.p, b.ln1b.p, B, st, v.xn, nullptr, nullptr, E))) return rc;
+        if ((rc = run_attention(m, v, b, rstd, B, st, E))) return rc;
+        if ((rc = resid_gemm(v.ao, b.wproj.p, b.bproj.p, C, fold))) return rc;
+        if (!fold && (rc = run_layernorm(m, v.resid, b.ln2g.p, b.ln2b.p, B, st, v.xn, nullptr, nullptr, E))) return rc;
         vbg::Args f1{};
         f1.rstd = rstd;
-        f1.X = xn; f1.W = b.w1.p; f1.bias = b.b1.p; f1.out = hid; f1.M = M; f1.N = HID; f1.K = C; f1.ldo = HID; f1.rb = 4;
-        if ((rc = launch_gemm<256, 256, 2, 4, vbg::A_PLAIN, vbg::EPI_GELU>(f1, 1, st, E, cus))) return rc;
-        vbg::Args f2{};
-        f2.X = hid; f2.W = b.w2.p; f2.bias = b.b2.p; f2.resid = resid; f2.M = M; f2.N = C; f2.K = HID;
-        const bool feeds_ln = fold && i + 1 < nblocks;            // the final norm reads the f32 stream itself
-        if (feeds_ln) { f2.xb = xn; f2.stats = stats; f2.ldstats = ldstats; f2.cm = cmean; }
-        if ((rc = launch_gemm<256, 256, 2, 4, vbg::A_PLAIN, vbg::EPI_RESID>(f2, 1, st, E, cus))) return rc;
-        if (feeds_ln && (rc = run_finalize(m, r0, M, st, E))) return rc;
+        f1.X = v.xn; f1.W = b.w1.p; f1.bias = b.b1.p; f1.out = v.hid; f1.M = M; f1.N = HID; f1.K = C; f1.ldo = HID; f1.rb = 4;
+        if ((rc = launch_gemm<256, 256, 2, 4, vbg::A_PLAIN, vbg::EPI_GELU>(f1, 1, st, E, v.cus))) return rc;
+        if ((rc = resid_gemm(v.hid, b.w2.p, b.b2.p, HID, fold && i + 1 < nblocks))) return rc;      // the final norm reads the f32 stream itself
     }
-    if (resid_out) VB_HIP(hipMemcpyAsync(resid_out, resid, (size_t)M * C * 4, hipMemcpyDeviceToDevice, st));
-    return run_layernorm(m, resid, m->ng.p, m->nb.p, B, st, nullptr, map0, feat_out, E);
+    if (resid_out) VB_HIP(hipMemcpyAsync(resid_out, v.resid, (size_t)M * C * 4, hipMemcpyDeviceToDevice, st));
+    return run_layernorm(m, v.resid, m->ng.p, m->nb.p, B, st, nullptr, v.map[0], feat_out, E);
 }
 
 int head(VbModel* m, const float* feat_in, int B, hipStream_t st, float* score, float* size, float* offset, std::string* err,
@@ -654,39 +655,31 @@ int head(VbModel* m, const float* feat_in, int B, hipStream_t st, float* score, 
     const Err E{err};
     int rc = check(m, B, E);
     if (rc || (rc = check_slice(m, B, sl, E))) return rc;
-    const int LX = m->LX, F = m->F;
-    const size_t f0 = sl ? sl->f0 : 0;
-    const long long Bt = sl ? sl->Btot : B;              // tower-major buffers: [tower][Bt frames]...
-    const int cus = sl ? sl->cus : 0;
-    bf16* const map0 = m->map0.p + f0 * (size_t)(F + 2) * (F + 2) * C;
+    const int LX = m->LX, F = m->F, M = B * LX;
+    const SliceView v(m, B, sl);
+    const long long Bt = v.Bt, P2 = (long long)(F + 2) * (F + 2);              // tower-major buffers: [tower][Bt frames]...
     if (feat_in) {
-        const size_t items = (size_t)B * LX * (C / 4);
-        hipLaunchKernelGGL(vbm::feat_to_map_kernel, dim3((unsigned)std::min<size_t>((items + 255) / 256, 16384)), dim3(256), 0, st, feat_in,
-                           map0, B, F, C);
+        hipLaunchKernelGGL(vbm::feat_to_map_kernel, dim3(grid256((size_t)B * LX * (C / 4))), dim3(256), 0, st, feat_in, v.map[0], B, F, C);
         VB_HIP(hipGetLastError());
     }
-    const int M = B * LX;
-    const long long P2 = (long long)(F + 2) * (F + 2);
     {   // conv1 of the three towers as one GEMM: N = 3 x 256, K = 9 x 768
         vbg::Args a{};
-        a.X = map0; a.W = m->wc[0].p; a.bias = m->bc[0].p; a.out = m->map1.p + f0 * (size_t)P2 * HEAD_CH[1];
+        a.X = v.map[0]; a.W = m->wc[0].p; a.bias = m->bc[0].p; a.out = v.map[1];
         a.M = M; a.N = 3 * HEAD_CH[1]; a.K = 9 * HEAD_CH[0]; a.ldo = HEAD_CH[1]; a.C = HEAD_CH[0]; a.F = F; a.out_padded = 1;
         a.n_split = HEAD_CH[1]; a.gOut = Bt * P2 * HEAD_CH[1];
-        if ((rc = launch_gemm<256, 256, 2, 4, vbg::A_CONV, vbg::EPI_CONV>(a, 1, st, E, cus))) return rc;
+        if ((rc = launch_gemm<256, 256, 2, 4, vbg::A_CONV, vbg::EPI_CONV>(a, 1, st, E, v.cus))) return rc;
     }
-    bf16* maps[4] = {m->map1.p + f0 * (size_t)P2 * HEAD_CH[1], m->map2.p + f0 * (size_t)P2 * HEAD_CH[2],
-                     m->map3.p + f0 * (size_t)P2 * HEAD_CH[3], m->t4.p + f0 * (size_t)LX * HEAD_CH[4]};
     for (int li = 1; li < 4; ++li) {   // conv2..4: one launch per layer, blockIdx.y = tower
         const int cin = HEAD_CH[li], cout = HEAD_CH[li + 1], rows = li == 1 ? 256 : (cout < 64 ? 64 : cout);
         vbg::Args a{};
-        a.X = maps[li - 1]; a.W = m->wc[li].p; a.bias = m->bc[li].p; a.out = maps[li];
+        a.X = v.map[li]; a.W = m->wc[li].p; a.bias = m->bc[li].p; a.out = v.map[li + 1];
         a.M = M; a.N = cout; a.K = 9 * cin; a.ldo = cout; a.C = cin; a.F = F; a.out_padded = li < 3;
         a.gX = Bt * P2 * cin; a.gW = (long long)rows * 9 * cin; a.gBias = cout;
         a.gOut = li < 3 ? Bt * P2 * cout : Bt * LX * cout;
-        if (li == 1 ? (rc = launch_gemm<256, 256, 2, 4, vbg::A_CONV, vbg::EPI_CONV>(a, 3, st, E, cus))
-                    : (rc = launch_gemm<256, 64, 8, 1, vbg::A_CONV, vbg::EPI_CONV>(a, 3, st, E, cus))) return rc;
+        if (li == 1 ? (rc = launch_gemm<256, 256, 2, 4, vbg::A_CONV, vbg::EPI_CONV>(a, 3, st, E, v.cus))
+                    : (rc = launch_gemm<256, 64, 8, 1, vbg::A_CONV, vbg::EPI_CONV>(a, 3, st, E, v.cus))) return rc;
     }
-    hipLaunchKernelGGL((vbm::conv5_kernel<32>), dim3((M + 255) / 256), dim3(256), 0, st, maps[3], m->w5.p, m->b5.p, M, LX,
+    hipLaunchKernelGGL((vbm::conv5_kernel<32>), dim3((M + 255) / 256), dim3(256), 0, st, v.map[4], m->w5.p, m->b5.p, M, LX,
                        (size_t)(Bt * LX * HEAD_CH[4]), score, size, offset);
     VB_HIP(hipGetLastError());
     return VT_OK;
