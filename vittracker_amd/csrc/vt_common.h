@@ -183,6 +183,7 @@ __device__ __forceinline__ f4 gelu4(f4 u) {
 __device__ __forceinline__ float hardswish(float y) {
     return y * __builtin_fminf(__builtin_fmaxf(__builtin_fmaf(y, 1.0f / 6.0f, 0.5f), 0.0f), 1.0f);
 }
+__device__ __forceinline__ f4 hardswish4(f4 v) { return f4{hardswish(v.x), hardswish(v.y), hardswish(v.z), hardswish(v.w)}; }
 __device__ __forceinline__ float sigmoid_clamped(float v) {
     // torch.clamp(x.sigmoid_(), 1e-4, 1 - 1e-4)   (lib/models/layers/head.py:177-179)
     float y = 1.0f / (1.0f + expf(-v));

@@ -114,6 +114,142 @@ __device__ __forceinline__ f4 l1_channel(const u3v& d, int c) {
     return f4{ub(c), ub(3 + c), ub(6 + c), ub(9 + c)};
 }
 
+// ---- pieces of layers 1 and 2 written once under stem_a / stem_a2 (below), stem_fused / stem_pipe (vt_stem_fused.h) and stem_stream
+// No helper reads threadIdx or derives a lane index: a call site computes pair / lr / qp / q / px from its own copy of the thread's
+// index (a FRESH one where the kernel needs that: stem_fused_kernel) and passes values in; s_setprio, waits and barriers stay there too.
+// Layer 1's ARITHMETIC (bias start, nine double-buffered weight sections, operand select, 2 x 3 x 6 fmaf block, Hardswish) is NOT
+// among them: as a helper (`l1_pair`) it cost registers in one instantiation or another of every kernel, whatever its form
+// (NOTES.md, "Stem kernels"), so stem_a, stem_a2, stem_fused, stem_pipe and stem_stream each keep their copy.  Change all five together.
+//
+// stem_a / stem_a2: a pair into its row `dst` of a parity-split layer-1 map (planes of npix1 entries, HALF even columns | column -1 | HALF odd columns)
+__device__ __forceinline__ void l1_store(f4* dst, int qp, int npix1, int HALF, const float (&a0)[6], const float (&a1)[6]) {
+    dst += qp;
+    dst[0] = f4{a0[0], a0[1], a0[2], a0[3]};                // even column 2 qp, channels 0-3
+    dst[npix1] = f4{a0[4], a0[5], 0.f, 0.f};                //                   channels 4-5 (+ padding)
+    dst[HALF + 1] = f4{a1[0], a1[1], a1[2], a1[3]};         // odd column 2 qp + 1
+    dst[npix1 + HALF + 1] = f4{a1[4], a1[5], 0.f, 0.f};
+}
+
+// ---- the band kernels (stem_fused, stem_pipe, stem_stream): a band = 512 layer-1 pixel pairs, one per thread of eight waves -----
+// Frame b's crop as a buffer descriptor: (3, T, T) fp32 planes, or the (T, T, 3) uint8 patch (U8).  Buffer loads take the scalar
+// descriptor + one 32-bit offset VGPR (kernel rows 1 and 2 are offsets of the same register, the channel plane is the scalar
+// offset): a fetch holds 2 address registers instead of 9 64-bit pairs.
+template <bool U8>
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t crop_rsrc(const float* crops, int b, int T) {
+    constexpr int ESZ = U8 ? 1 : 4;
+    return __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(reinterpret_cast<const char*>(crops) + (size_t)b * 3 * T * T * ESZ), 0, 3 * T * T * ESZ, 0x00020000);
+}
+// Input of layer-1 row p1 (>= 0), pixel pair qp.  Raw loads only: nothing here may depend on the loaded data, so the requests stay
+// in flight across whatever follows (the image top reads row 0 instead of row -1; layer 1 replaces it).
+template <bool U8>
+__device__ __forceinline__ void l1_fetch(__amdgpu_buffer_rsrc_t rsrc_z, __amdgpu_buffer_rsrc_t rsrc_x, bool is_z, int lgT, int p1, int qp, L1In<U8>& vin) {
+    if constexpr (U8) {     // row y, pixels 4 qp .. 4 qp + 3 of the uint8 patch = bytes 12 (y T / 4 + qp) .. + 11: one load per kernel row
+        const unsigned o1 = 12u * ((((unsigned)(2 * p1)) << (lgT - 2)) + (unsigned)qp);
+        const unsigned o0 = p1 > 0 ? o1 - (3u << lgT) : o1;
+        vin.v[0] = __builtin_amdgcn_raw_buffer_load_b96(rsrc_x, o0, 0, 0);
+        vin.v[1] = __builtin_amdgcn_raw_buffer_load_b96(rsrc_x, o1, 0, 0);
+        vin.v[2] = __builtin_amdgcn_raw_buffer_load_b96(rsrc_x, o1 + (3u << lgT), 0, 0);
+    } else {
+        typedef unsigned u4 __attribute__((ext_vector_type(4)));
+        const unsigned off1 = ((((unsigned)(2 * p1)) << lgT) + 4u * (unsigned)qp) << 2;      // input row 2 p1 (kernel row 1), bytes
+        const unsigned off0 = p1 > 0 ? off1 - (4u << lgT) : off1;
+        const unsigned off2 = off1 + (4u << lgT);
+#pragma unroll
+        for (int r = 0; r < 3; ++r)
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                const unsigned vo = r == 0 ? off0 : (r == 1 ? off1 : off2), so = (unsigned)c << (2 * lgT + 2);
+                const u4 t = is_z ? __builtin_amdgcn_raw_buffer_load_b128(rsrc_z, vo, so, 0) : __builtin_amdgcn_raw_buffer_load_b128(rsrc_x, vo, so, 0);
+                vin.v[r][c] = __builtin_bit_cast(f4, t);
+            }
+    }
+}
+// Housekeeping of a band's layer-1 ring by a few of its 512 threads: column -1 of every row, and row 0 = the last row of the band
+// above (it is in the other ring) or, at the top of a crop, zeros.  ZERO_TOP = false: the top row is cleared elsewhere (stem_fused).
+template <bool ZERO_TOP, typename Band>
+__device__ __forceinline__ void ring_edges(f4* ring, const f4* other_ring, int pair, const Band& J, bool halo) {
+    const int nrow = 2 * J.R2 + 1;
+    if (pair < 2 * nrow) {
+        const int plane = pair >= nrow ? 1 : 0;
+        ring[plane * J.npix1 + (pair - plane * nrow) * J.PITCH + J.HALF] = splat4(0.f);
+    }
+    if ((ZERO_TOP || halo) && pair >= 128 && pair < 128 + 2 * J.PITCH) {
+        const int e = pair - 128, plane = e >= J.PITCH ? 1 : 0, col = e - plane * J.PITCH;
+        ring[plane * J.npix1 + col] = halo ? other_ring[plane * J.npix1 + 2 * J.R2 * J.PITCH + col] : splat4(0.f);
+    }
+}
+
+#ifndef VT_F16
+// Layer 2 (6 -> 12) on v_mfma_f32_16x16x1_4B_f32: four 16x16 blocks per instruction, K = 1.  Its 6 input channels make 54 real
+// k-steps; on the 16x16x4 form (k in quads of 4 channels, chunks of 4 quads) they pad to 80.  Block b = pixel tile 4 gw + b of the
+// band's 16: lane (b, px) SUPPLIES pixel px of that tile as B, every lane supplies W[oc = px][k] as A (the same for the four
+// blocks), and lane (q, px) RECEIVES channels 4q..4q+3 of pixel px of all four tiles (tools/src/probe_mfma4b.hip).
+// cw2: [tap][channels 0-3 | 4-5][16 output channels] float4 in LDS (16 lanes read 16 consecutive entries), cb2: the 16 biases.
+typedef float f16v __attribute__((ext_vector_type(16)));
+template <typename Band>
+__device__ __forceinline__ f16v l2_tile4(const f4* ring, const Band& J, const f4* cw2, const float* cb2, int gw, int q, int px) {
+    const int op = 16 * (4 * gw + q) + px, yy = op >> J.lgW2, xx = op & ((1 << J.lgW2) - 1);
+    const f4* src = ring + 2 * yy * J.PITCH + xx;                     // tap (0,0) of this lane's pixel, channel quad 0
+    const f4* wk = cw2 + px;
+    const f4 bv2 = ld4(cb2 + 4 * q);
+    f16v acc = {bv2.x, bv2.y, bv2.z, bv2.w, bv2.x, bv2.y, bv2.z, bv2.w, bv2.x, bv2.y, bv2.z, bv2.w, bv2.x, bv2.y, bv2.z, bv2.w};
+    auto tapoff = [&](int tap) {
+        const int dy = tap / 3, dx = tap - 3 * dy;
+        return dy * J.PITCH + (dx == 1 ? 0 : (dx == 0 ? J.HALF : J.HALF + 1));
+    };
+    f4 a0 = src[tapoff(0)], a1 = src[J.npix1 + tapoff(0)], w0 = wk[0], w1 = wk[16];
+#pragma unroll
+    for (int tap = 0; tap < 9; ++tap) {
+        f4 na0 = a0, na1 = a1, nw0 = w0, nw1 = w1;
+        if (tap + 1 < 9) {
+            na0 = src[tapoff(tap + 1)]; na1 = src[J.npix1 + tapoff(tap + 1)];
+            nw0 = wk[32 * (tap + 1)]; nw1 = wk[32 * (tap + 1) + 16];
+            __builtin_amdgcn_sched_barrier(0);        // keep the next tap's reads ahead of this tap's MFMAs
+        }
+        acc = __builtin_amdgcn_mfma_f32_16x16x1f32(w0.x, a0.x, acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_16x16x1f32(w0.y, a0.y, acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_16x16x1f32(w0.z, a0.z, acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_16x16x1f32(w0.w, a0.w, acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_16x16x1f32(w1.x, a1.x, acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_16x16x1f32(w1.y, a1.y, acc, 0, 0, 0);
+        a0 = na0; a1 = na1; w0 = nw0; w1 = nw1;
+    }
+    return acc;
+}
+// channels 4q..4q+3 of this lane's pixel of block bb, after Hardswish
+__device__ __forceinline__ f4 l2_result(const f16v& acc, int bb) {
+    return hardswish4(f4{acc[4 * bb], acc[4 * bb + 1], acc[4 * bb + 2], acc[4 * bb + 3]});
+}
+#else
+// f16 build: layer 2 as an implicit GEMM on the 16x16x16 form (vt_conv.h), tiles gw and gw + 8 of the band's 16 on each of the group's
+// eight waves.  cw2: the [5][64] weight images in LDS.  store(y, x, v): pixel (y, x) of the band, channels 4q..4q+3 after Hardswish (q < 3).
+template <typename Band, typename Store>
+__device__ __forceinline__ void l2_tiles_f16(const f4* ring, const Band& J, const f4* cw2, const float* cb2, int lane, int gw, int q, int px, Store store) {
+    f4 w2a[5][1];
+#pragma unroll
+    for (int c = 0; c < 5; ++c) w2a[c][0] = cw2[c * 64 + lane];
+    const f4 bv2 = ld4(cb2 + 4 * q);
+    int base[2], yy[2], xx[2];
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+        const int op = 16 * (gw + 8 * i) + px;
+        yy[i] = op >> J.lgW2; xx[i] = op & ((1 << J.lgW2) - 1);
+        base[i] = 2 * yy[i] * J.PITCH + xx[i];
+    }
+    f4 acc[2][1] = {{bv2}, {bv2}};
+    auto off2 = [&](int c) { return s2_chunk_off<2>(c, q, J.npix1, J.PITCH, J.HALF); };
+    vtc::mma_pass<1, 2, 5, 5, true>(ring, base, w2a, 0, off2, acc);
+    if (q < 3) {
+#pragma unroll
+        for (int i = 0; i < 2; ++i) store(yy[i], xx[i], hardswish4(acc[i][0]));
+    }
+}
+#endif
+
+// stem_pipe, stem_stream: a crop of side T is cut into bands of 512 layer-1 pixel pairs.
+constexpr int band_r2(int T) { return 1024 / T; }                    // layer-2 rows of a band
+constexpr int band_npix1(int T) { return stem_a_npix1(T, band_r2(T)); }      // one plane of a band's layer-1 ring
+
 // w1g: [r][c][s][6] scalar sections (layer 1, VALU); w2img: [1][5][64][4] MFMA image of layer 2 with
 // the input channels padded 6 -> 8; b2: 16 (12 used).
 // U8: the crops are uint8 (T, T, 3) patches, w1g / b1 point into the folded image w1u (see L1In above).
@@ -166,6 +302,7 @@ __global__ __launch_bounds__(256, VT_STEM_A_WAVES_PER_SIMD) void stem_a_kernel(
         i = in_range ? i : npairs - 1;
         const int lr = i / HALF, qp = i - lr * HALF;
         const int p1 = 2 * p0 - 1 + lr;
+        // layer-1 arithmetic, copy 1 of 5 (through a helper: f16 build <true> 75 -> 79 VGPRs)
         float a0[6], a1[6];
 #pragma unroll
         for (int j = 0; j < 6; ++j) a0[j] = a1[j] = b1[j];
@@ -200,13 +337,7 @@ __global__ __launch_bounds__(256, VT_STEM_A_WAVES_PER_SIMD) void stem_a_kernel(
         const float live = p1 < 0 ? 0.f : 1.f;      // row -1 of the layer-1 map = layer 2's zero padding
 #pragma unroll
         for (int j = 0; j < 6; ++j) { a0[j] = hardswish(a0[j]) * live; a1[j] = hardswish(a1[j]) * live; }
-        if (in_range) {
-            f4* dst = map1 + lr * PITCH;
-            dst[qp] = f4{a0[0], a0[1], a0[2], a0[3]};                   // even column 2*qp, channels 0-3
-            dst[npix1 + qp] = f4{a0[4], a0[5], 0.f, 0.f};               //                   channels 4-5 (+ padding)
-            dst[HALF + 1 + qp] = f4{a1[0], a1[1], a1[2], a1[3]};        // odd column 2*qp+1
-            dst[npix1 + HALF + 1 + qp] = f4{a1[4], a1[5], 0.f, 0.f};
-        }
+        if (in_range) l1_store(map1 + lr * PITCH, qp, npix1, HALF, a0, a1);
     };
     if (!(skip & 1)) {
         L1In<U8> va, vb;
@@ -232,8 +363,7 @@ __global__ __launch_bounds__(256, VT_STEM_A_WAVES_PER_SIMD) void stem_a_kernel(
         if (q < 3) {
             const int op = 16 * t + px;
             const int y = op >> w2_log2, x = op - (y << w2_log2);
-            v.x = hardswish(v.x); v.y = hardswish(v.y); v.z = hardswish(v.z); v.w = hardswish(v.w);
-            st4(out + ((((size_t)b * 3 + q) * W2 + p0 + y) * W2 + x) * 4, v);     // quad plane q: 16 lanes = 256 contiguous bytes
+            st4(out + ((((size_t)b * 3 + q) * W2 + p0 + y) * W2 + x) * 4, hardswish4(v));     // quad plane q: 16 lanes = 256 contiguous bytes
         }
     };
     if (!(skip & 2)) {
@@ -315,6 +445,7 @@ __global__ __launch_bounds__(256, VT_STEM_A_WAVES_PER_SIMD) void stem_a2_kernel(
         const int lr = i >> J.lgHALF, qp = i & (J.HALF - 1);
         const int p1 = 2 * J.p0 - 1 + lr;
         float a0[6], a1[6];
+        // layer-1 arithmetic, copy 2 of 5 (a helper costs this kernel 109 VGPRs against its row of 103: NOTES.md)
 #pragma unroll
         for (int j = 0; j < 6; ++j) a0[j] = a1[j] = b1[j];
         float wa[18], wb[18];
@@ -339,13 +470,7 @@ __global__ __launch_bounds__(256, VT_STEM_A_WAVES_PER_SIMD) void stem_a2_kernel(
         const float live = p1 < 0 ? 0.f : 1.f;      // row -1 of the layer-1 map = layer 2's zero padding
 #pragma unroll
         for (int j = 0; j < 6; ++j) { a0[j] = hardswish(a0[j]) * live; a1[j] = hardswish(a1[j]) * live; }
-        if (in_range) {
-            f4* dst = maps + J.map_off + lr * J.PITCH;
-            dst[qp] = f4{a0[0], a0[1], a0[2], a0[3]};
-            dst[J.npix1 + qp] = f4{a0[4], a0[5], 0.f, 0.f};
-            dst[J.HALF + 1 + qp] = f4{a1[0], a1[1], a1[2], a1[3]};
-            dst[J.npix1 + J.HALF + 1 + qp] = f4{a1[4], a1[5], 0.f, 0.f};
-        }
+        if (in_range) l1_store(maps + J.map_off + lr * J.PITCH, qp, J.npix1, J.HALF, a0, a1);
     };
     if (!(skip & 1)) {
         f4 va[3][3], vb[3][3];
@@ -394,8 +519,7 @@ __global__ __launch_bounds__(256, VT_STEM_A_WAVES_PER_SIMD) void stem_a2_kernel(
                 for (int i = 0; i < NPT; ++i) {
                     const int op = 16 * (t0 + tstride * i) + px;
                     const int y = op >> J.lgW2, x = op & ((1 << J.lgW2) - 1);
-                    f4 v = acc[i][0];
-                    v.x = hardswish(v.x); v.y = hardswish(v.y); v.z = hardswish(v.z); v.w = hardswish(v.w);
+                    const f4 v = hardswish4(acc[i][0]);
                     st4(J.out + ((((size_t)q << (2 * J.lgW2)) + (((size_t)J.p0 + y) << J.lgW2) + x) << 2), v);   // quad plane q
                 }
             }
@@ -530,8 +654,7 @@ __global__ __launch_bounds__(256) void stem_b_kernel(CropB cx, CropB cz, const f
                 for (int i = 0; i < NPT; ++i) {
                     const int op = 16 * (tb + 2 * i) + px;
                     const int y = op >> w3_log2, x = op - (y << w3_log2);
-                    f4 v = acc[i][0];
-                    v.x = hardswish(v.x); v.y = hardswish(v.y); v.z = hardswish(v.z); v.w = hardswish(v.w);
+                    const f4 v = hardswish4(acc[i][0]);
                     map3[(4 * ot3 + q) * npix3 + (y + lr_first) * pitch3 + ((x & 1) ? half3 + 1 + (x >> 1) : (x >> 1))] = v;
                 }
             }

@@ -33,6 +33,20 @@
 
 namespace vts {
 
+// Diagnostic time stamps (VT_DBG_STAMPS; DIAG instantiations only): wave `wave` of frame b records s_memtime as its nstamp-th entry of
+// stamps[B][16][32]; entries past the 32nd are dropped.
+template <bool DIAG>
+__device__ __forceinline__ void stamp_wave(unsigned long long* stamps, int b, int wave, int lane, int& nstamp) {
+    if constexpr (DIAG) {
+        if (stamps != nullptr && nstamp < 32) {
+            unsigned long long tt;
+            asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(tt)::"memory");
+            if (lane == 0) stamps[((size_t)b * 16 + wave) * 32 + nstamp] = tt;
+            ++nstamp;
+        }
+    }
+}
+
 struct FusedGeo {                       // TX = 128, TZ = 64
     static constexpr int TX = 128, TZ = 64;
     static constexpr int R2X = 8, NBX = (TX / 4) / R2X;            // 4 search bands of 8 layer-2 rows
@@ -152,37 +166,13 @@ __global__ __launch_bounds__(1024) void stem_fused_kernel(
     // those sub-expressions between the five bands' phases, keeps them all live from the first use on and runs out of registers
     // (36 B/lane of scratch, with the spill's wait in front of the first band's loads).
     auto fresh = [](int v) { asm volatile("" : "+v"(v)); return v; };
-    // Raw loads only: nothing here may depend on the loaded data, so the requests stay in flight across
-    // the layer-2 work and the barrier that follow (the top-of-image zeroing is applied in layer1).
-    // Buffer loads (scalar descriptor + one 32-bit offset VGPR; kernel rows 1 and 2 are immediate offsets of the same register,
-    // the channel plane is the scalar offset): a fetch holds 2 address registers instead of 9 64-bit pairs.
-    const auto rsrc_z = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(zin_b), 0, 3 * G::TZ * G::TZ * 4, 0x00020000);
-    const auto rsrc_x = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(xin_b), 0, 3 * G::TX * G::TX * (U8 ? 1 : 4), 0x00020000);
+    // Raw loads only (l1_fetch): the requests stay in flight across the layer-2 work and the barrier that follow; the top-of-image
+    // padding is applied in layer1.
+    const auto rsrc_z = crop_rsrc<false>(zin, b, G::TZ), rsrc_x = crop_rsrc<U8>(xin, b, G::TX);
     auto fetch = [&](const auto& J, L1In<U8>& vin) {
-        typedef unsigned u4 __attribute__((ext_vector_type(4)));
         const int pair = fresh(pair_);
         const int lr = 1 + (pair >> J.lgHALF), qp = pair & (J.HALF - 1);
-        const int p1 = 2 * J.p0 - 1 + lr;                    // layer-1 row (>= 0)
-        if constexpr (U8) {     // the uint8 patch: row y, pixels 4 qp .. 4 qp + 3 = bytes 12 (y T / 4 + qp) .. + 11, one load per kernel row
-            const unsigned o1 = 12u * ((((unsigned)(2 * p1)) << (J.lgT - 2)) + (unsigned)qp);
-            const unsigned o0 = p1 > 0 ? o1 - (3u << J.lgT) : o1;                              // the image top reads row 0 (replaced in layer1)
-            vin.v[0] = __builtin_amdgcn_raw_buffer_load_b96(rsrc_x, o0, 0, 0);
-            vin.v[1] = __builtin_amdgcn_raw_buffer_load_b96(rsrc_x, o1, 0, 0);
-            vin.v[2] = __builtin_amdgcn_raw_buffer_load_b96(rsrc_x, o1 + (3u << J.lgT), 0, 0);
-            return;
-        } else {
-        auto& v = vin.v;
-        const unsigned off1 = ((((unsigned)(2 * p1)) << J.lgT) + 4u * (unsigned)qp) << 2;      // input row 2 p1 (kernel row 1), bytes
-        const unsigned off0 = p1 > 0 ? off1 - (4u << J.lgT) : off1;                            // row 2 p1 - 1; the image top reads row 0 (zeroed in layer1)
-#pragma unroll
-        for (int r = 0; r < 3; ++r)
-#pragma unroll
-            for (int c = 0; c < 3; ++c) {
-                const u4 t = __builtin_amdgcn_raw_buffer_load_b128(J.is_z ? rsrc_z : rsrc_x, r == 0 ? off0 : off1 + (r == 2 ? (4u << J.lgT) : 0u),
-                                                                   c << (2 * J.lgT + 2), 0);
-                v[r][c] = __builtin_bit_cast(f4, t);
-            }
-        }
+        l1_fetch<U8>(rsrc_z, rsrc_x, J.is_z, J.lgT, 2 * J.p0 - 1 + lr, qp, vin);      // layer-1 row 2 p0 - 1 + lr >= 0
     };
     auto layer1 = [&](const auto& J, const L1In<U8>& vin) {
         // layer 1 is the long pole of an interval (VALU-bound); without this the issue arbiter favours the
@@ -191,16 +181,8 @@ __global__ __launch_bounds__(1024) void stem_fused_kernel(
         const int pair = fresh(pair_);
         const int lr = 1 + (pair >> J.lgHALF), qp = pair & (J.HALF - 1);
         const float keep0 = (2 * J.p0 - 1 + lr) > 0 ? 1.f : 0.f;   // kernel row 0 of layer-1 row 0 is the zero padding
-        // housekeeping by a few threads: column -1 of every ring row, and the halo row
-        const int nrow = 2 * J.R2 + 1;
-        if (pair < 2 * nrow) {
-            const int plane = pair >= nrow ? 1 : 0;
-            ring[plane * J.npix1 + (pair - plane * nrow) * J.PITCH + J.HALF] = splat4(0.f);
-        }
-        if (J.halo && pair >= 128 && pair < 128 + 2 * J.PITCH) {
-            const int e = pair - 128, plane = e >= J.PITCH ? 1 : 0, col = e - plane * J.PITCH;
-            ring[plane * J.npix1 + col] = other_ring[plane * J.npix1 + 2 * J.R2 * J.PITCH + col];
-        }
+        ring_edges<false>(ring, other_ring, pair, J, J.halo);     // row 0 at the image top was cleared at the start
+        // layer-1 arithmetic, copy 3 of 5, and its own four stores (through helpers: f16 build <1, false, *, true> 75 -> 81 VGPRs, <0 | 1 | 2> +2)
         float a0[6], a1[6];
 #pragma unroll
         for (int j = 0; j < 6; ++j) a0[j] = a1[j] = b1[j];
@@ -244,88 +226,27 @@ __global__ __launch_bounds__(1024) void stem_fused_kernel(
     // ---- layer 2: this group's ring -> the frame's layer-2 map ------------------------------------------
     auto layer2 = [&](const auto& J) {
 #ifndef VT_F16
-        // Layer 2 on v_mfma_f32_16x16x1_4B_f32: four 16x16 blocks per instruction, K = 1.  Its 6 input channels make 54 real
-        // k-steps; on the 16x16x4 form (k in quads of 4 channels, chunks of 4 quads) they pad to 80.  Block b = pixel tile 4 gw + b:
-        // lane (b, px) SUPPLIES pixel px of that tile as B, every lane supplies W[oc = px][k] as A (the same for the four
-        // blocks), and lane (q, px) RECEIVES channels 4q..4q+3 of pixel px of all four tiles (tools/src/probe_mfma4b.hip).
-        // Four waves of the group (one per SIMD) cover the band's 16 tiles; the other four go straight to the barrier.
+        // l2_tile4: four waves of the group (one per SIMD) cover the band's 16 tiles; the other four go straight to the barrier.
         if (gw < 4) {
-            typedef float f16v __attribute__((ext_vector_type(16)));
             const int ln = fresh(lane), q = ln >> 4, px = ln & 15;
-            const int op = 16 * (4 * gw + q) + px, yy = op >> J.lgW2, xx = op & ((1 << J.lgW2) - 1);
-            const f4* src = ring + 2 * yy * J.PITCH + xx;                     // tap (0,0) of this lane's pixel, channel quad 0
-            const f4* wk = cw2 + px;                                          // [tap][channels 0-3 | 4-5][16 output channels] float4: 16 lanes read 16 consecutive entries
-            const f4 bv2 = ld4(cb2 + 4 * q);
-            f16v acc = {bv2.x, bv2.y, bv2.z, bv2.w, bv2.x, bv2.y, bv2.z, bv2.w, bv2.x, bv2.y, bv2.z, bv2.w, bv2.x, bv2.y, bv2.z, bv2.w};
-            auto tapoff = [&](int tap) {
-                const int dy = tap / 3, dx = tap - 3 * dy;
-                return dy * J.PITCH + (dx == 1 ? 0 : (dx == 0 ? J.HALF : J.HALF + 1));
-            };
-            f4 a0 = src[tapoff(0)], a1 = src[J.npix1 + tapoff(0)], w0 = wk[0], w1 = wk[16];
-#pragma unroll
-            for (int tap = 0; tap < 9; ++tap) {
-                f4 na0 = a0, na1 = a1, nw0 = w0, nw1 = w1;
-                if (tap + 1 < 9) {
-                    na0 = src[tapoff(tap + 1)]; na1 = src[J.npix1 + tapoff(tap + 1)];
-                    nw0 = wk[32 * (tap + 1)]; nw1 = wk[32 * (tap + 1) + 16];
-                    __builtin_amdgcn_sched_barrier(0);        // keep the next tap's reads ahead of this tap's MFMAs
-                }
-                acc = __builtin_amdgcn_mfma_f32_16x16x1f32(w0.x, a0.x, acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_16x16x1f32(w0.y, a0.y, acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_16x16x1f32(w0.z, a0.z, acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_16x16x1f32(w0.w, a0.w, acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_16x16x1f32(w1.x, a1.x, acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_16x16x1f32(w1.y, a1.y, acc, 0, 0, 0);
-                a0 = na0; a1 = na1; w0 = nw0; w1 = nw1;
-            }
+            const f16v acc = l2_tile4(ring, J, cw2, cb2, gw, q, px);
             if (q < 3) {
 #pragma unroll
                 for (int bb = 0; bb < 4; ++bb) {
                     const int ob = 16 * (4 * gw + bb) + px, y = ob >> J.lgW2, x = ob & ((1 << J.lgW2) - 1);
-                    f4 r = {acc[4 * bb], acc[4 * bb + 1], acc[4 * bb + 2], acc[4 * bb + 3]};
-                    r.x = hardswish(r.x); r.y = hardswish(r.y); r.z = hardswish(r.z); r.w = hardswish(r.w);
-                    m2[J.m2_off + q * J.npix2 + (J.p0 + y + 1) * J.pitch2 + ((x & 1) ? J.half2 + 1 + (x >> 1) : (x >> 1))] = r;
+                    m2[J.m2_off + q * J.npix2 + (J.p0 + y + 1) * J.pitch2 + ((x & 1) ? J.half2 + 1 + (x >> 1) : (x >> 1))] = l2_result(acc, bb);
                 }
             }
         }
 #else
-        f4 w2a[5][1];
-#pragma unroll
-        for (int c = 0; c < 5; ++c) w2a[c][0] = cw2[c * 64 + lane];
-        const f4 bv2 = ld4(cb2 + 4 * q);
-        int base[2], yy[2], xx[2];
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            const int op = 16 * (gw + 8 * i) + px;                       // 16 tiles per band: tiles gw and gw + 8
-            yy[i] = op >> J.lgW2; xx[i] = op & ((1 << J.lgW2) - 1);
-            base[i] = 2 * yy[i] * J.PITCH + xx[i];
-        }
-        f4 acc[2][1] = {{bv2}, {bv2}};
-        auto off2 = [&](int c) { return s2_chunk_off<2>(c, q, J.npix1, J.PITCH, J.HALF); };
-        vtc::mma_pass<1, 2, 5, 5, true>(ring, base, w2a, 0, off2, acc);
-        if (q < 3) {
-#pragma unroll
-            for (int i = 0; i < 2; ++i) {
-                f4 v = acc[i][0];
-                v.x = hardswish(v.x); v.y = hardswish(v.y); v.z = hardswish(v.z); v.w = hardswish(v.w);
-                const int x = xx[i];
-                m2[J.m2_off + q * J.npix2 + (J.p0 + yy[i] + 1) * J.pitch2 + ((x & 1) ? J.half2 + 1 + (x >> 1) : (x >> 1))] = v;
-            }
-        }
+        l2_tiles_f16(ring, J, cw2, cb2, lane, gw, q, px, [&](int y, int x, f4 v) {
+            m2[J.m2_off + q * J.npix2 + (J.p0 + y + 1) * J.pitch2 + ((x & 1) ? J.half2 + 1 + (x >> 1) : (x >> 1))] = v;
+        });
 #endif
     };
 
     int nstamp = 0;
-    auto stamp = [&]() {
-        if constexpr (DIAG) {
-            if (stamps != nullptr) {
-                unsigned long long tt;
-                asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(tt)::"memory");
-                if (lane == 0) stamps[((size_t)b * 16 + wave) * 32 + nstamp] = tt;
-                ++nstamp;
-            }
-        }
-    };
+    auto stamp = [&]() { stamp_wave<DIAG>(stamps, b, wave, lane, nstamp); };
     stamp();
     // ---- start ---------------------------------------------------------------------------------------------------------
     // Order in the memory queue: (1) this thread's constant (tiny, cache-resident), (2) group A's first band -- the template
@@ -527,8 +448,7 @@ __global__ __launch_bounds__(1024) void stem_fused_kernel(
 #pragma unroll
                 for (int ot = 0; ot < 2; ++ot)
                     if (16 * ot + 4 * q < 24) {
-                        f4 r = acc[ot];
-                        r.x = hardswish(r.x); r.y = hardswish(r.y); r.z = hardswish(r.z); r.w = hardswish(r.w);
+                        const f4 r = hardswish4(acc[ot]);
                         u32x2 pcs[3];
                         vt3::split3(r, pcs[0], pcs[1], pcs[2]);        // split ONCE where it is produced: layer 4 reads pieces
 #pragma unroll
@@ -544,8 +464,7 @@ __global__ __launch_bounds__(1024) void stem_fused_kernel(
 #pragma unroll
                 for (int ot = 0; ot < 2; ++ot)
                     if (16 * ot + 4 * q < 24) {
-                        f4 r = acc[ot];
-                        r.x = hardswish(r.x); r.y = hardswish(r.y); r.z = hardswish(r.z); r.w = hardswish(r.w);
+                        const f4 r = hardswish4(acc[ot]);
                         u32x2 pcs[3];
                         vt3::split3(r, pcs[0], pcs[1], pcs[2]);
 #pragma unroll
@@ -574,8 +493,7 @@ __global__ __launch_bounds__(1024) void stem_fused_kernel(
                 if (16 * ot3 + 4 * q < 24) {
 #pragma unroll
                     for (int i = 0; i < 2; ++i) {
-                        f4 r = acc[i][0];
-                        r.x = hardswish(r.x); r.y = hardswish(r.y); r.z = hardswish(r.z); r.w = hardswish(r.w);
+                        const f4 r = hardswish4(acc[i][0]);
                         const int y = (wave >> 1) + 8 * i;
                         // the store must wait until every wave has finished reading the rings?  No: layer 3 reads
                         // only the layer-2 maps; the rings died at the pipeline's last barrier.
@@ -597,8 +515,7 @@ __global__ __launch_bounds__(1024) void stem_fused_kernel(
                 auto off3 = [&](int c) { return o3[c]; };
                 vtc::mma_pass<1, 1, NCH3, NCH3>(m2 + M2Z_OFF, base, w3a, 0, off3, acc);
                 if (16 * ot3 + 4 * q < 24) {
-                    f4 r = acc[0][0];
-                    r.x = hardswish(r.x); r.y = hardswish(r.y); r.z = hardswish(r.z); r.w = hardswish(r.w);
+                    const f4 r = hardswish4(acc[0][0]);
                     m3z[(4 * ot3 + q) * G::NPIX3Z + (y + 1) * P3 + ((x & 1) ? H3 + 1 + (x >> 1) : (x >> 1))] = r;
                 }
             }
@@ -697,12 +614,10 @@ __global__ __launch_bounds__(1024) void stem_fused_kernel(
 // Replaces stem_a, whose four workgroups per CU run the two layers in lock step (their times add up).
 template <int TX, int TZ>
 struct PipeGeo {
-    static constexpr int R2X = 1024 / TX, R2Z = 1024 / TZ;       // 512 pixel pairs per band = one per thread of a group
+    static constexpr int R2X = band_r2(TX), R2Z = band_r2(TZ);   // 512 pixel pairs per band = one per thread of a group
     static constexpr int NBX = (TX / 4) / R2X, NBZ = (TZ / 4) / R2Z, NB = NBX + NBZ;
-    static constexpr int NPIX1X = round16((2 * R2X + 1) * (TX / 2 + 1));
-    static constexpr int NPIX1Z = round16((2 * R2Z + 1) * (TZ / 2 + 1));
-    static constexpr int RING = 2 * (NPIX1X > NPIX1Z ? NPIX1X : NPIX1Z);
-    static constexpr int CONST_F4 = 5 * 64 + 4;                  // layer-2 weight images, b2
+    static constexpr int RING = 2 * (band_npix1(TX) > band_npix1(TZ) ? band_npix1(TX) : band_npix1(TZ));
+    static constexpr int CONST_F4 = 5 * 64 + 4;                 // layer-2 weight images, b2
     static constexpr int LDS_BYTES = (2 * RING + CONST_F4) * 16;
     static_assert(NB % 2 == 0 && NBZ % 2 == 0, "bands alternate between the two groups, crop by crop");
     static_assert((R2X * (TX / 4)) == 256 && (R2Z * (TZ / 4)) == 256, "16 layer-2 tiles per band");
@@ -734,7 +649,7 @@ __global__ __launch_bounds__(1024) void stem_pipe_kernel(
     const int pair = gw * 64 + lane;
 
     struct Band {
-        const float* in; float* out;
+        const float* in; float* out;      // `in` is never read (the fetch goes through crop_rsrc): without the field <.., 2, ..> takes 107 VGPRs against 105
         int lgT, HALF, lgHALF, PITCH, npix1, p0, R2, lgW2;
         bool halo, is_z;
     };
@@ -747,53 +662,21 @@ __global__ __launch_bounds__(1024) void stem_pipe_kernel(
         J.in = is_z ? zin + (size_t)b * 3 * TZ * TZ : xin + (size_t)b * 3 * TX * TX;
         J.out = is_z ? act_z + (size_t)b * 3 * (TZ / 4) * (TZ / 4) * 4 : act_x + (size_t)b * 3 * (TX / 4) * (TX / 4) * 4;
         J.lgT = is_z ? lgTZ : lgTX; J.HALF = (is_z ? TZ : TX) >> 2; J.lgHALF = J.lgT - 2; J.PITCH = ((is_z ? TZ : TX) >> 1) + 1;
-        J.npix1 = is_z ? G::NPIX1Z : G::NPIX1X; J.R2 = is_z ? G::R2Z : G::R2X; J.p0 = kb * J.R2; J.lgW2 = J.lgT - 2;
+        J.npix1 = is_z ? band_npix1(TZ) : band_npix1(TX); J.R2 = is_z ? G::R2Z : G::R2X; J.p0 = kb * J.R2; J.lgW2 = J.lgT - 2;
         J.halo = kb > 0; J.is_z = is_z;
         return J;
     };
-    // buffer loads: scalar descriptor + one 32-bit offset register per kernel row pair (see stem_fused_kernel)
-    const auto rsrc_z = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(zin + (size_t)b * 3 * TZ * TZ), 0, 3 * TZ * TZ * 4, 0x00020000);
-    const auto rsrc_x = U8 ? __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned char*>(reinterpret_cast<const unsigned char*>(xin) + (size_t)b * 3 * TX * TX), 0, 3 * TX * TX, 0x00020000)
-                           : __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(xin + (size_t)b * 3 * TX * TX), 0, 3 * TX * TX * 4, 0x00020000);
+    const auto rsrc_z = crop_rsrc<false>(zin, b, TZ), rsrc_x = crop_rsrc<U8>(xin, b, TX);
     auto fetch = [&](const Band& J, L1In<U8>& vin) {           // raw loads only (see stem_fused_kernel)
-        typedef unsigned u4 __attribute__((ext_vector_type(4)));
         const int lr = 1 + (pair >> J.lgHALF), qp = pair & (J.HALF - 1);
-        const int p1 = 2 * J.p0 - 1 + lr;
-        if constexpr (U8) {     // row y, pixels 4 qp .. 4 qp + 3 of the uint8 patch = bytes 12 (y T / 4 + qp) .. + 11: one load per kernel row
-            const unsigned o1 = 12u * ((((unsigned)(2 * p1)) << (J.lgT - 2)) + (unsigned)qp);
-            const unsigned o0 = p1 > 0 ? o1 - (3u << J.lgT) : o1;
-            vin.v[0] = __builtin_amdgcn_raw_buffer_load_b96(rsrc_x, o0, 0, 0);
-            vin.v[1] = __builtin_amdgcn_raw_buffer_load_b96(rsrc_x, o1, 0, 0);
-            vin.v[2] = __builtin_amdgcn_raw_buffer_load_b96(rsrc_x, o1 + (3u << J.lgT), 0, 0);
-            return;
-        } else {
-        auto& v = vin.v;
-        const unsigned off1 = ((((unsigned)(2 * p1)) << J.lgT) + 4u * (unsigned)qp) << 2;
-        const unsigned off0 = p1 > 0 ? off1 - (4u << J.lgT) : off1;
-        const unsigned off2 = off1 + (4u << J.lgT);
-#pragma unroll
-        for (int r = 0; r < 3; ++r)
-#pragma unroll
-            for (int c = 0; c < 3; ++c) {
-                const unsigned vo = r == 0 ? off0 : (r == 1 ? off1 : off2), so = (unsigned)c << (2 * J.lgT + 2);
-                const u4 t = J.is_z ? __builtin_amdgcn_raw_buffer_load_b128(rsrc_z, vo, so, 0) : __builtin_amdgcn_raw_buffer_load_b128(rsrc_x, vo, so, 0);
-                v[r][c] = __builtin_bit_cast(f4, t);
-            }
-        }
+        l1_fetch<U8>(rsrc_z, rsrc_x, J.is_z, J.lgT, 2 * J.p0 - 1 + lr, qp, vin);
     };
     auto layer1 = [&](const Band& J, const L1In<U8>& vin) {
         __builtin_amdgcn_s_setprio(3);
         const int lr = 1 + (pair >> J.lgHALF), qp = pair & (J.HALF - 1);
         const float keep0 = (2 * J.p0 - 1 + lr) > 0 ? 1.f : 0.f;
-        const int nrow = 2 * J.R2 + 1;
-        if (pair < 2 * nrow) {                                  // column -1 of every ring row
-            const int plane = pair >= nrow ? 1 : 0;
-            ring[plane * J.npix1 + (pair - plane * nrow) * J.PITCH + J.HALF] = splat4(0.f);
-        }
-        if (pair >= 128 && pair < 128 + 2 * J.PITCH) {          // row 0: the previous band's last row, or the image top
-            const int e = pair - 128, plane = e >= J.PITCH ? 1 : 0, col = e - plane * J.PITCH;
-            ring[plane * J.npix1 + col] = J.halo ? other_ring[plane * J.npix1 + 2 * J.R2 * J.PITCH + col] : splat4(0.f);
-        }
+        ring_edges<true>(ring, other_ring, pair, J, J.halo);
+        // layer-1 arithmetic, copy 4 of 5, and its own four stores (through helpers: <.., 1, false, true> 89 -> 96 VGPRs, <.., 2, ..> 105 -> 107)
         float a0[6], a1[6];
 #pragma unroll
         for (int j = 0; j < 6; ++j) a0[j] = a1[j] = b1[j];
@@ -835,86 +718,25 @@ __global__ __launch_bounds__(1024) void stem_pipe_kernel(
     };
     auto layer2 = [&](const Band& J) {
 #ifndef VT_F16
-        // Layer 2 on v_mfma_f32_16x16x1_4B_f32: four 16x16 blocks per instruction, K = 1.  Its 6 input channels make 54 real
-        // k-steps; on the 16x16x4 form (k in quads of 4 channels, chunks of 4 quads) they pad to 80.  Block b = pixel tile 4 gw + b:
-        // lane (b, px) SUPPLIES pixel px of that tile as B, every lane supplies W[oc = px][k] as A (the same for the four
-        // blocks), and lane (q, px) RECEIVES channels 4q..4q+3 of pixel px of all four tiles (tools/src/probe_mfma4b.hip).
-        // Four waves of the group (one per SIMD) cover the band's 16 tiles; the other four go straight to the barrier.
-        if (gw < 4) {
-            typedef float f16v __attribute__((ext_vector_type(16)));
-            const int op = 16 * (4 * gw + q) + px, yy = op >> J.lgW2, xx = op & ((1 << J.lgW2) - 1);
-            const f4* src = ring + 2 * yy * J.PITCH + xx;                     // tap (0,0) of this lane's pixel, channel quad 0
-            const f4* wk = cw2 + px;                                          // [tap][channels 0-3 | 4-5][16 output channels] float4: 16 lanes read 16 consecutive entries
-            const f4 bv2 = ld4(cb2 + 4 * q);
-            f16v acc = {bv2.x, bv2.y, bv2.z, bv2.w, bv2.x, bv2.y, bv2.z, bv2.w, bv2.x, bv2.y, bv2.z, bv2.w, bv2.x, bv2.y, bv2.z, bv2.w};
-            auto tapoff = [&](int tap) {
-                const int dy = tap / 3, dx = tap - 3 * dy;
-                return dy * J.PITCH + (dx == 1 ? 0 : (dx == 0 ? J.HALF : J.HALF + 1));
-            };
-            f4 a0 = src[tapoff(0)], a1 = src[J.npix1 + tapoff(0)], w0 = wk[0], w1 = wk[16];
-#pragma unroll
-            for (int tap = 0; tap < 9; ++tap) {
-                f4 na0 = a0, na1 = a1, nw0 = w0, nw1 = w1;
-                if (tap + 1 < 9) {
-                    na0 = src[tapoff(tap + 1)]; na1 = src[J.npix1 + tapoff(tap + 1)];
-                    nw0 = wk[32 * (tap + 1)]; nw1 = wk[32 * (tap + 1) + 16];
-                    __builtin_amdgcn_sched_barrier(0);        // keep the next tap's reads ahead of this tap's MFMAs
-                }
-                acc = __builtin_amdgcn_mfma_f32_16x16x1f32(w0.x, a0.x, acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_16x16x1f32(w0.y, a0.y, acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_16x16x1f32(w0.z, a0.z, acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_16x16x1f32(w0.w, a0.w, acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_16x16x1f32(w1.x, a1.x, acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_16x16x1f32(w1.y, a1.y, acc, 0, 0, 0);
-                a0 = na0; a1 = na1; w0 = nw0; w1 = nw1;
-            }
+        if (gw < 4) {                             // l2_tile4: four waves of the group, as in stem_fused_kernel
+            const f16v acc = l2_tile4(ring, J, cw2, cb2, gw, q, px);
             if (q < 3) {
 #pragma unroll
                 for (int bb = 0; bb < 4; ++bb) {
                     const int ob = 16 * (4 * gw + bb) + px, y = ob >> J.lgW2, x = ob & ((1 << J.lgW2) - 1);
-                    f4 r = {acc[4 * bb], acc[4 * bb + 1], acc[4 * bb + 2], acc[4 * bb + 3]};
-                    r.x = hardswish(r.x); r.y = hardswish(r.y); r.z = hardswish(r.z); r.w = hardswish(r.w);
-                    st4(J.out + ((((size_t)q << (2 * J.lgW2)) + (((size_t)J.p0 + y) << J.lgW2) + x) << 2), r);   // quad plane q
+                    st4(J.out + ((((size_t)q << (2 * J.lgW2)) + (((size_t)J.p0 + y) << J.lgW2) + x) << 2), l2_result(acc, bb));   // quad plane q
                 }
             }
         }
 #else
-        f4 w2a[5][1];
-#pragma unroll
-        for (int c = 0; c < 5; ++c) w2a[c][0] = cw2[c * 64 + lane];
-        const f4 bv2 = ld4(cb2 + 4 * q);
-        int base[2], yy[2], xx[2];
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            const int op = 16 * (gw + 8 * i) + px;
-            yy[i] = op >> J.lgW2; xx[i] = op & ((1 << J.lgW2) - 1);
-            base[i] = 2 * yy[i] * J.PITCH + xx[i];
-        }
-        f4 acc[2][1] = {{bv2}, {bv2}};
-        auto off2 = [&](int c) { return s2_chunk_off<2>(c, q, J.npix1, J.PITCH, J.HALF); };
-        vtc::mma_pass<1, 2, 5, 5, true>(ring, base, w2a, 0, off2, acc);
-        if (q < 3) {
-#pragma unroll
-            for (int i = 0; i < 2; ++i) {
-                f4 r = acc[i][0];
-                r.x = hardswish(r.x); r.y = hardswish(r.y); r.z = hardswish(r.z); r.w = hardswish(r.w);
-                st4(J.out + ((((size_t)q << (2 * J.lgW2)) + (((size_t)J.p0 + yy[i]) << J.lgW2) + xx[i]) << 2), r);   // quad plane q
-            }
-        }
+        l2_tiles_f16(ring, J, cw2, cb2, lane, gw, q, px, [&](int y, int x, f4 v) {
+            st4(J.out + ((((size_t)q << (2 * J.lgW2)) + (((size_t)J.p0 + y) << J.lgW2) + x) << 2), v);   // quad plane q
+        });
 #endif
     };
 
     int nstamp = 0;
-    auto stamp = [&]() {
-        if constexpr (DIAG) {
-            if (stamps != nullptr && nstamp < 32) {
-                unsigned long long tt;
-                asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(tt)::"memory");
-                if (lane == 0) stamps[((size_t)b * 16 + wave) * 32 + nstamp] = tt;
-                ++nstamp;
-            }
-        }
-    };
+    auto stamp = [&]() { stamp_wave<DIAG>(stamps, b, wave, lane, nstamp); };
     stamp();
     L1In<U8> v;
     fetch(band(2 * s_lo + grp), v);

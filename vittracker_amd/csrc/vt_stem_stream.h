@@ -37,13 +37,11 @@ namespace vts {
 
 template <int TX, int TZ>
 struct StreamGeo {
-    static constexpr int r2(int T) { return 1024 / T; }
-    static constexpr int NBX = (TX / 4) / r2(TX), NBZ = (TZ / 4) / r2(TZ), NB = NBX + NBZ;
-    static constexpr int npix1(int T) { return round16((2 * r2(T) + 1) * (T / 2 + 1)); }
-    static constexpr int np2(int T) { return round16((r2(T) + 1) * (T / 4 + 1)); }          // one plane of an L2 slot
-    static constexpr int np3(int T) { return round16((r2(T) / 2 + 1) * (T / 8 + 1)); }      // one plane of an L3 slot
+    static constexpr int NBX = (TX / 4) / band_r2(TX), NBZ = (TZ / 4) / band_r2(TZ), NB = NBX + NBZ;
+    static constexpr int np2(int T) { return round16((band_r2(T) + 1) * (T / 4 + 1)); }          // one plane of an L2 slot
+    static constexpr int np3(int T) { return round16((band_r2(T) / 2 + 1) * (T / 8 + 1)); }      // one plane of an L3 slot
     static constexpr int imax(int a, int b) { return a > b ? a : b; }
-    static constexpr int RING = 2 * imax(npix1(TX), npix1(TZ));                              // f4 per L1 ring (2 planes)
+    static constexpr int RING = 2 * imax(band_npix1(TX), band_npix1(TZ));                    // f4 per L1 ring (2 planes)
     static constexpr int SLOT2 = 3 * imax(np2(TX), np2(TZ));                                 // f4 per L2 slot (3 planes)
     static constexpr int SLOT3 = 6 * imax(np3(TX), np3(TZ));                                 // f4 per L3 slot (6 planes)
     static constexpr int CONST_F4 = 9 * 32 + 4 + 8 + 12;                                     // layer-2 weights for the 4-block MFMA, b2, b3, b4
@@ -58,7 +56,7 @@ struct StreamGeo {
     static constexpr int LDS_F4 = 2 * RING + 3 * SLOT2 + 3 * SLOT3 + CONST_F4 + OFFTAB_F4 + W4L_F4;
     static constexpr int LDS_BYTES = LDS_F4 * 16;
     static_assert(LDS_BYTES <= 160 * 1024, "LDS");
-    static_assert(r2(TX) % 4 == 0 && r2(TZ) % 4 == 0, "a band holds whole token rows");
+    static_assert(band_r2(TX) % 4 == 0 && band_r2(TZ) % 4 == 0, "a band holds whole token rows");
 };
 
 // ZMODE 0: both crops; 1: search bands only (the template's token rows are cached in `tokens`); 2: template bands only.
@@ -111,7 +109,7 @@ __global__ __launch_bounds__(1024) void stem_stream_kernel(
         J.nb = J.is_z ? G::NBZ : G::NBX;
         const int T = J.is_z ? TZ : TX;
         J.lgT = J.is_z ? lgTZ : lgTX; J.HALF = T >> 2; J.lgHALF = J.lgT - 2; J.PITCH = (T >> 1) + 1;
-        J.npix1 = J.is_z ? G::npix1(TZ) : G::npix1(TX); J.R2 = J.is_z ? G::r2(TZ) : G::r2(TX); J.lgW2 = J.lgT - 2;
+        J.npix1 = J.is_z ? band_npix1(TZ) : band_npix1(TX); J.R2 = J.is_z ? band_r2(TZ) : band_r2(TX); J.lgW2 = J.lgT - 2;
         J.pitch2 = (T >> 2) + 1; J.half2 = T >> 3; J.np2 = J.is_z ? G::np2(TZ) : G::np2(TX);
         J.lgW3 = J.lgT - 3; J.R3 = J.R2 >> 1; J.pitch3 = (T >> 3) + 1; J.half3 = T >> 4; J.np3 = J.is_z ? G::np3(TZ) : G::np3(TX);
         J.lgW4 = J.lgT - 4;
@@ -144,35 +142,11 @@ __global__ __launch_bounds__(1024) void stem_stream_kernel(
     if (wave < 8) {
         // =============================================================== layer 1: waves 0-7 =====================================
         const int pair_ = wave * 64 + lane;                      // this thread's pixel pair of a band (0..511)
-        const auto rsrc_z = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(zin + (size_t)b * 3 * TZ * TZ), 0, 3 * TZ * TZ * 4, 0x00020000);
-        const auto rsrc_x = U8 ? __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned char*>(reinterpret_cast<const unsigned char*>(xin) + (size_t)b * 3 * TX * TX), 0, 3 * TX * TX, 0x00020000)
-                               : __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(xin + (size_t)b * 3 * TX * TX), 0, 3 * TX * TX * 4, 0x00020000);
+        const auto rsrc_z = crop_rsrc<false>(zin, b, TZ), rsrc_x = crop_rsrc<U8>(xin, b, TX);
         auto fetch = [&](const Band& J, L1In<U8>& vin) {           // raw loads only: nothing here depends on the loaded data
-            typedef unsigned u4 __attribute__((ext_vector_type(4)));
             const int pair = fresh(pair_);
             const int lr = 1 + (pair >> J.lgHALF), qp = pair & (J.HALF - 1);
-            const int p1 = 2 * J.kb * J.R2 - 1 + lr;               // layer-1 row (>= 0)
-            if constexpr (U8) {     // row y, pixels 4 qp .. 4 qp + 3 of the uint8 patch = bytes 12 (y T / 4 + qp) .. + 11: one load per kernel row
-                const unsigned o1 = 12u * ((((unsigned)(2 * p1)) << (J.lgT - 2)) + (unsigned)qp);
-                const unsigned o0 = p1 > 0 ? o1 - (3u << J.lgT) : o1;                              // the image top reads row 0 (replaced in layer1)
-                vin.v[0] = __builtin_amdgcn_raw_buffer_load_b96(rsrc_x, o0, 0, 0);
-                vin.v[1] = __builtin_amdgcn_raw_buffer_load_b96(rsrc_x, o1, 0, 0);
-                vin.v[2] = __builtin_amdgcn_raw_buffer_load_b96(rsrc_x, o1 + (3u << J.lgT), 0, 0);
-                return;
-            } else {
-            auto& v = vin.v;
-            const unsigned off1 = ((((unsigned)(2 * p1)) << J.lgT) + 4u * (unsigned)qp) << 2;
-            const unsigned off0 = p1 > 0 ? off1 - (4u << J.lgT) : off1;   // the image top reads row 0 (zeroed in layer1)
-            const unsigned off2 = off1 + (4u << J.lgT);
-#pragma unroll
-            for (int r = 0; r < 3; ++r)
-#pragma unroll
-                for (int c = 0; c < 3; ++c) {
-                    const unsigned vo = r == 0 ? off0 : (r == 1 ? off1 : off2), so = (unsigned)c << (2 * J.lgT + 2);
-                    const u4 t = J.is_z ? __builtin_amdgcn_raw_buffer_load_b128(rsrc_z, vo, so, 0) : __builtin_amdgcn_raw_buffer_load_b128(rsrc_x, vo, so, 0);
-                    v[r][c] = __builtin_bit_cast(f4, t);
-                }
-            }
+            l1_fetch<U8>(rsrc_z, rsrc_x, J.is_z, J.lgT, 2 * J.kb * J.R2 - 1 + lr, qp, vin);      // layer-1 row >= 0
         };
         auto layer1 = [&](const Band& J, int g, const L1In<U8>& vin) {
             f4* const ring = ring0 + (g & 1) * G::RING;
@@ -180,15 +154,8 @@ __global__ __launch_bounds__(1024) void stem_stream_kernel(
             const int pair = fresh(pair_);
             const int lr = 1 + (pair >> J.lgHALF), qp = pair & (J.HALF - 1);
             const float keep0 = (2 * J.kb * J.R2 - 1 + lr) > 0 ? 1.f : 0.f;   // kernel row 0 of layer-1 row 0 is the zero padding
-            const int nrow = 2 * J.R2 + 1;
-            if (pair < 2 * nrow) {                                  // column -1 of every ring row
-                const int plane = pair >= nrow ? 1 : 0;
-                ring[plane * J.npix1 + (pair - plane * nrow) * J.PITCH + J.HALF] = splat4(0.f);
-            }
-            if (pair >= 128 && pair < 128 + 2 * J.PITCH) {          // row 0: the previous band's last row, or the image top
-                const int e = pair - 128, plane = e >= J.PITCH ? 1 : 0, col = e - plane * J.PITCH;
-                ring[plane * J.npix1 + col] = J.kb > 0 ? other_ring[plane * J.npix1 + 2 * J.R2 * J.PITCH + col] : splat4(0.f);
-            }
+            ring_edges<true>(ring, other_ring, pair, J, J.kb > 0);
+            // layer-1 arithmetic, copy 5 of 5, and its own four stores (through helpers: <256, 128, 0> 127 -> 128 VGPRs, three more +1 with l1_store alone)
             float a0[6], a1[6];
 #pragma unroll
             for (int j = 0; j < 6; ++j) a0[j] = a1[j] = b1[j];
@@ -244,7 +211,6 @@ __global__ __launch_bounds__(1024) void stem_stream_kernel(
     } else if (wave < 12) {
         // =============================================================== layer 2: waves 8-11 ====================================
         const int gw = wave - 8;
-        typedef float f16v __attribute__((ext_vector_type(16)));
         auto layer2 = [&](const Band& J, int g) {
             const int ln = fresh(lane), q = ln >> 4, px = ln & 15, tid2 = gw * 64 + ln;
             const f4* const ring = ring0 + (g & 1) * G::RING;
@@ -260,39 +226,13 @@ __global__ __launch_bounds__(1024) void stem_stream_kernel(
                     const int plane = e / J.pitch2, col = e - plane * J.pitch2;
                     slot[plane * J.np2 + col] = splat4(0.f);
                 }
-            const int op = 16 * (4 * gw + q) + px, yy = op >> J.lgW2, xx = op & ((1 << J.lgW2) - 1);
-            const f4* src = ring + 2 * yy * J.PITCH + xx;                     // tap (0,0) of this lane's pixel, channel quad 0
-            const f4* wk = cw2 + px;
-            const f4 bv2 = ld4(cb2 + 4 * q);
-            f16v acc = {bv2.x, bv2.y, bv2.z, bv2.w, bv2.x, bv2.y, bv2.z, bv2.w, bv2.x, bv2.y, bv2.z, bv2.w, bv2.x, bv2.y, bv2.z, bv2.w};
-            auto tapoff = [&](int tap) {
-                const int dy = tap / 3, dx = tap - 3 * dy;
-                return dy * J.PITCH + (dx == 1 ? 0 : (dx == 0 ? J.HALF : J.HALF + 1));
-            };
-            f4 a0 = src[tapoff(0)], a1 = src[J.npix1 + tapoff(0)], w0 = wk[0], w1 = wk[16];
-#pragma unroll
-            for (int tap = 0; tap < 9; ++tap) {
-                f4 na0 = a0, na1 = a1, nw0 = w0, nw1 = w1;
-                if (tap + 1 < 9) {
-                    na0 = src[tapoff(tap + 1)]; na1 = src[J.npix1 + tapoff(tap + 1)];
-                    nw0 = wk[32 * (tap + 1)]; nw1 = wk[32 * (tap + 1) + 16];
-                    __builtin_amdgcn_sched_barrier(0);        // keep the next tap's reads ahead of this tap's MFMAs
-                }
-                acc = __builtin_amdgcn_mfma_f32_16x16x1f32(w0.x, a0.x, acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_16x16x1f32(w0.y, a0.y, acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_16x16x1f32(w0.z, a0.z, acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_16x16x1f32(w0.w, a0.w, acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_16x16x1f32(w1.x, a1.x, acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_16x16x1f32(w1.y, a1.y, acc, 0, 0, 0);
-                a0 = na0; a1 = na1; w0 = nw0; w1 = nw1;
-            }
+            const f16v acc = l2_tile4(ring, J, cw2, cb2, gw, q, px);
             if (q < 3) {
                 const bool copy_down = J.kb + 1 < J.nb;       // the band below is of the same crop: it needs this band's last row
 #pragma unroll
                 for (int bb = 0; bb < 4; ++bb) {
                     const int ob = 16 * (4 * gw + bb) + px, y = ob >> J.lgW2, x = ob & ((1 << J.lgW2) - 1);
-                    f4 r = {acc[4 * bb], acc[4 * bb + 1], acc[4 * bb + 2], acc[4 * bb + 3]};
-                    r.x = hardswish(r.x); r.y = hardswish(r.y); r.z = hardswish(r.z); r.w = hardswish(r.w);
+                    const f4 r = l2_result(acc, bb);
                     const int col = (x & 1) ? J.half2 + 1 + (x >> 1) : (x >> 1);
                     slot[q * J.np2 + (y + 1) * J.pitch2 + col] = r;
                     if (copy_down && y == J.R2 - 1) nslot[q * J.np2 + col] = r;
@@ -354,8 +294,7 @@ __global__ __launch_bounds__(1024) void stem_stream_kernel(
                 const bool copy_down = J.kb + 1 < J.nb;
 #pragma unroll
                 for (int i = 0; i < 2; ++i) {
-                    f4 r = acc[i][0];
-                    r.x = hardswish(r.x); r.y = hardswish(r.y); r.z = hardswish(r.z); r.w = hardswish(r.w);
+                    const f4 r = hardswish4(acc[i][0]);
                     const int col = (xx[i] & 1) ? J.half3 + 1 + (xx[i] >> 1) : (xx[i] >> 1);
                     slot[(4 * ot3 + q) * J.np3 + (yy[i] + 1) * J.pitch3 + col] = r;
                     if (copy_down && yy[i] == J.R3 - 1) nslot[(4 * ot3 + q) * J.np3 + col] = r;
