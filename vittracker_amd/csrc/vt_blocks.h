@@ -230,8 +230,16 @@ __device__ __forceinline__ void gemm_stage(OpA opa, OpS ops, f4 (&acc)[N]) {
 //
 // BAL (G128: 5 tiles on a CU's 4 SIMDs).  One wave per tile puts two tile-waves on SIMD0, which then
 // carries 2/5 of the MFMAs and sets the kernel time.  The balanced variant runs 8 waves: waves 0-3
-// ("owners", one per SIMD) own tiles 0-3 exactly as before; waves 4-7 ("guests", again one per SIMD)
-// share tile 4 four ways and keep its residual stream redundantly in registers:
+// ("owners", one per SIMD) own four tiles; waves 4-7 ("guests", again one per SIMD) share the fifth
+// ("the guests' tile") four ways and keep its residual stream redundantly in registers.
+// Role map (from len_z, wave-uniform): a template of exactly one tile (G128 as shipped) -- the guests'
+// tile is the TEMPLATE tile 0 and owner wave w owns search tile w + 1; any other len_z -- the guests'
+// tile is the last tile and owner wave w owns tile w.  With the template as the guests' tile, the last
+// block's skip of the template rows (they only matter as keys / values there) drops guest work on all
+// four SIMDs -- guest 0's q, the partial attention and its rendezvous, proj, the MLP, the fc2 partial
+// sums -- and that block runs four search tiles on four SIMDs with nothing beside them; the template
+// cache (ZC) skips the guests' LN1 + qkv in block 0, and only owners write feat rows.
+// The guests' split of the work (the key-tile split is independent of which tile they own):
 //     LN1 + QKV   guest 0: q -> Qg (LDS), guest 1: k -> Kimg, guest 2: v -> Vimg          (36 MFMAs each)
 //     attention   guest g: keys of tile g (guest 3: tiles 3 and 4) -> partial (max, sum, P.V) in LDS,
 //                 guests-only rendezvous on an LDS counter, flash-style merge               (24 / 48)
@@ -274,7 +282,11 @@ __global__ __launch_bounds__(NW * 64, (NW == 5 && !WLDS) ? 3 : 1) void blocks_ke
     constexpr int KV_UNITS = A3 ? NT * KP_T16 + (VP3 ? NC * VP_T16 : NC * NT * 64) : 2 * NT * NC * 64;
     constexpr int L = NT * 16;
     constexpr int NOWN = BAL ? NT - 1 : NT;                // tiles handled by owner waves
-    constexpr int GT = NT - 1;                             // BAL: the guests' tile
+    // BAL role map (wave-uniform, from len_z: scalar registers).  A template of exactly one tile: the guests share tile 0 and owner
+    // wave w owns search tile w + 1, so the last block's skip of the template rows takes the guests' work, not an owner's.
+    // Any other len_z: the guests share the last tile, owner wave w owns tile w.
+    const int toff = (BAL && len_z == 16) ? 1 : 0;         // owner wave w <-> tile w + toff
+    const int GT = toff ? 0 : NT - 1;                      // BAL: the guests' tile
     extern __shared__ __attribute__((aligned(16))) float lds[];
     f4* Kimg = reinterpret_cast<f4*>(lds);                 // [NT][NC][64]   (BF3L: also fc2's third output tile, as pieces)
     f4* Vimg = Kimg + (A3 ? NT * KP_T16 : NT * NC * 64);   // [NC][NT][64]   (A3: behind the K pieces; VP3: pieces, addressed from Kimg)
@@ -335,14 +347,17 @@ __global__ __launch_bounds__(NW * 64, (NW == 5 && !WLDS) ? 3 : 1) void blocks_ke
     f4 x[TPW][NC];
 #pragma unroll
     for (int i = 0; i < TPW; ++i) {
-        const int T = w + NW * i;
-        if (T < NOWN && T != dbg_skip_tile) {
+        const int T = w + NW * i + toff;
+        if (T - toff < NOWN && T != dbg_skip_tile) {
             const float* src = tokens + ((size_t)b * L + 16 * T + tok) * C + 4 * q;
 #pragma unroll
             for (int c = 0; c < NC; ++c) x[i][c] = ld4(src + 16 * c);
         }
     }
-    f4 x4[NC];                                   // BAL: every guest's copy of the guest tile's residual stream
+    // BAL: every guest's copy of the guest tile's residual stream.  A wave is an owner (x[0]) or a guest (x4), never both: the forms
+    // on the fp32 / f16 pipes say so by sharing the registers (10 VGPRs; the three-piece forms, tuned at the register cap, keep theirs)
+    f4 x4s[NC];
+    f4 (&x4)[NC] = (BAL && !BF3) ? x[0] : x4s;
     if constexpr (BAL) {
         if (w >= NOWN) {
             const float* src = tokens + ((size_t)b * L + 16 * GT + tok) * C + 4 * q;
@@ -364,6 +379,17 @@ __global__ __launch_bounds__(NW * 64, (NW == 5 && !WLDS) ? 3 : 1) void blocks_ke
         int lane_s = lane_k;
         if constexpr (BF3) asm volatile("" : "+v"(lane_s));
         const int lane = lane_s, tok = lane & 15, q = lane >> 4;
+        // In the last block the template rows only matter as keys / values: their attention
+        // output, proj and MLP never reach the head (vit_dist.py:126 keeps the search rows only),
+        // so those tiles stop after publishing K / V -- unless the caller asked for the residual.
+        const bool last_skip_z = (blk == depth_total - 1) && (resid == nullptr);
+        // BAL with the template as the guests' tile: that skip is the guests'.  Guest 1 still publishes k and guest 2 v^T; guest 0's
+        // q, the partial attention with its rendezvous, proj, the MLP and the fc2 partial sums are dropped, and the block runs the
+        // four search tiles on four SIMDs with nothing beside them.  One wave-uniform value for all four guests (none of them
+        // then waits on the counter); every guest still reaches every workgroup barrier.
+        const bool guest_skip = BAL && last_skip_z && toff != 0;
+        // ZC, block 0: the guests' tile is the template tile -- its q / k / v^T images go to / come from the cache on the guest path
+        const bool zg_tile = BAL && ZC && blk == 0 && toff != 0;
         const float* __restrict__ P = params + (size_t)blk * BLOCK_STRIDE;
         const float* S = Sp + blk * SMALL_STRIDE;
         // weight operand image `t` of each GEMM: from the staging buffers (WLDS) or straight from L2
@@ -510,14 +536,14 @@ __global__ __launch_bounds__(NW * 64, (NW == 5 && !WLDS) ? 3 : 1) void blocks_ke
         // ---- LN1 + QKV; publish K / V^T images ------------------------------------------------
 #pragma unroll
         for (int i = 0; i < TPW; ++i) {
-            const int T = w + NW * i;
+            const int T = w + NW * i + toff;
             const bool z_tile = ZC && blk == 0 && 16 * T < len_z;       // wave-uniform; compiled out of the default kernel
             // the cache pointer is rebuilt from a fresh copy of the lane index where it is used (block 0 only): as a loop invariant
             // of the block loop it stayed in registers for the whole kernel (the G256 variant spilled 68 B / lane)
             int lane_z = lane;
             if constexpr (ZC) asm volatile("" : "+v"(lane_z));
             f4* const zc = reinterpret_cast<f4*>(zcache) + (((size_t)b * (len_z >> 4) + T) * 3 * NC) * 64 + lane_z;
-            if (VT_BLK_OWNERS && T < NOWN && T != dbg_skip_tile && z_tile && zcache_mode == 2) {
+            if (VT_BLK_OWNERS && T - toff < NOWN && T != dbg_skip_tile && z_tile && zcache_mode == 2) {
 #pragma unroll
                 for (int ot = 0; ot < NC; ++ot) {
                     qr[i][ot] = zc[ot * 64];
@@ -532,7 +558,7 @@ __global__ __launch_bounds__(NW * 64, (NW == 5 && !WLDS) ? 3 : 1) void blocks_ke
                     for (int ot = 0; ot < NC; ++ot) kr[ot] = zc[(NC + ot) * 64];
                     store_k3(Kimg + T * KP_T16, kr);
                 }
-            } else if (VT_BLK_OWNERS && T < NOWN && T != dbg_skip_tile) {
+            } else if (VT_BLK_OWNERS && T - toff < NOWN && T != dbg_skip_tile) {
                 f4 h[NC];
                 layer_norm_plain(x[i], h);
                 fstamp();
@@ -629,76 +655,120 @@ __global__ __launch_bounds__(NW * 64, (NW == 5 && !WLDS) ? 3 : 1) void blocks_ke
             }
         }
         if constexpr (BAL) {
-            if (BF3L && VT_BLK_GUESTS && w >= NOWN && g < 3) {
-                f4 h[NC];
-                layer_norm_plain(x4, h);
-                u32x4 hb[3];
-                u32x2 hc[3];
-                split_h3(h, hb, hc);
-                u32x4 a0[NC][3];
-                u32x2 a2[NC][3];
-#pragma unroll
-                for (int j = 0; j < NC; ++j) w1_load3(NC * g + j, a0[j], a2[j]);
+            // guest g's cache images of the guests' tile (ZC, block 0; tile 0 of a one-tile template): q / k / v^T = images 3 g .. 3 g + 2
+            // of the tile's nine; the pointer is built where it is used, from a fresh copy of the lane index (see the owners' zc)
+            auto zc_guest = [&]() {
+                int lane_z = lane;
+                asm volatile("" : "+v"(lane_z));
+                return reinterpret_cast<f4*>(zcache) + ((size_t)b * 3 * NC + NC * g) * 64 + lane_z;
+            };
+            // the guests' tile as a constant (0 or NT - 1) at their publish sites: the images' tile offsets then sit in the instructions'
+            // offset fields as before, behind one scalar branch
+            auto with_gt = [&](auto f) {
+                if (toff) f(std::integral_constant<int, 0>{});
+                else f(std::integral_constant<int, NT - 1>{});
+            };
+            const bool guest_qkv = VT_BLK_GUESTS && w >= NOWN && g < 3 && !(guest_skip && g == 0);
+            if (BF3L && guest_qkv) {
                 f4 r[NC];
-                if (g < 2) {
-                    f4 bias[NC];
+                if (zg_tile && zcache_mode == 2) {
+                    const f4* const zc = zc_guest();
 #pragma unroll
-                    for (int j = 0; j < NC; ++j) bias[j] = ld4(S + S_BQKV + 16 * (g * NC + j) + 4 * q);
-                    __builtin_amdgcn_sched_barrier(0);
+                    for (int j = 0; j < NC; ++j) r[j] = zc[j * 64];
+                } else {
+                    f4 h[NC];
+                    layer_norm_plain(x4, h);
+                    u32x4 hb[3];
+                    u32x2 hc[3];
+                    split_h3(h, hb, hc);
+                    u32x4 a0[NC][3];
+                    u32x2 a2[NC][3];
 #pragma unroll
-                    for (int j = 0; j < NC; ++j) r[j] = tile48(std::false_type{}, a0[j], a2[j], hb, hc, bias[j]);
-                    if constexpr (A3) {
-                        store_k3(g == 0 ? Qg : Kimg + GT * KP_T16, r);
+                    for (int j = 0; j < NC; ++j) w1_load3(NC * g + j, a0[j], a2[j]);
+                    if (g < 2) {
+                        f4 bias[NC];
+#pragma unroll
+                        for (int j = 0; j < NC; ++j) bias[j] = ld4(S + S_BQKV + 16 * (g * NC + j) + 4 * q);
+                        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                        for (int j = 0; j < NC; ++j) r[j] = tile48(std::false_type{}, a0[j], a2[j], hb, hc, bias[j]);
+                    } else {
+                        f4 bias[NC];
+#pragma unroll
+                        for (int j = 0; j < NC; ++j) bias[j] = splat4(S[S_BQKV + 2 * C + 16 * j + tok]);
+                        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                        for (int j = 0; j < NC; ++j) r[j] = tile48(std::true_type{}, a0[j], a2[j], hb, hc, bias[j]);
+                    }
+                    if (zg_tile && zcache_mode == 1) {
+                        f4* const zc = zc_guest();
+#pragma unroll
+                        for (int j = 0; j < NC; ++j) zc[j * 64] = r[j];
+                    }
+                }
+                with_gt([&](auto gt) {
+                    constexpr int GTc = decltype(gt)::value;
+                    if (g < 2) {
+                        if constexpr (A3) {
+                            store_k3(g == 0 ? Qg : Kimg + GTc * KP_T16, r);
+                        } else {
+#pragma unroll
+                            for (int j = 0; j < NC; ++j) {
+                                if (g == 0) Qg[j * 64 + lane] = r[j];
+                                else Ko[(GTc * NC + j) * 64 + lane] = to_opnd(r[j]);
+                            }
+                        }
                     } else {
 #pragma unroll
                         for (int j = 0; j < NC; ++j) {
-                            if (g == 0) Qg[j * 64 + lane] = r[j];
-                            else Ko[(GT * NC + j) * 64 + lane] = to_opnd(r[j]);
+                            if constexpr (A3) store_v3(GTc, j, r[j]);
+                            else Vo[(j * NT + GTc) * 64 + lane] = to_opnd(r[j]);
                         }
                     }
+                });
+            } else if (guest_qkv) {      // guest 0: q, guest 1: k, guest 2: v of the guest tile
+                f4 acc[NC];
+                if (zg_tile && zcache_mode == 2) {
+                    const f4* const zc = zc_guest();
+#pragma unroll
+                    for (int ot = 0; ot < NC; ++ot) acc[ot] = zc[ot * 64];
                 } else {
-                    f4 bias[NC];
+                    f4 h[NC];
+                    layer_norm_plain(x4, h);
+                    if (g < 2) {
 #pragma unroll
-                    for (int j = 0; j < NC; ++j) bias[j] = splat4(S[S_BQKV + 2 * C + 16 * j + tok]);
-                    __builtin_amdgcn_sched_barrier(0);
+                        for (int ot = 0; ot < NC; ++ot) acc[ot] = ld4(S + S_BQKV + 16 * (g * NC + ot) + 4 * q);
+                        gemm_stage<NC, NC, true, true>(
+                            [&](int c, opnd (&a)[NC]) {
 #pragma unroll
-                    for (int j = 0; j < NC; ++j) r[j] = tile48(std::true_type{}, a0[j], a2[j], hb, hc, bias[j]);
+                                for (int ot = 0; ot < NC; ++ot) a[ot] = w_qkv((g * NC + ot) * NC + c);
+                            },
+                            [&](int c) { return h[c]; }, acc);
+                    } else {
 #pragma unroll
-                    for (int j = 0; j < NC; ++j) {
-                        if constexpr (A3) store_v3(GT, j, r[j]);
-                        else Vo[(j * NT + GT) * 64 + lane] = to_opnd(r[j]);
+                        for (int ot = 0; ot < NC; ++ot) acc[ot] = splat4(S[S_BQKV + 2 * C + 16 * ot + tok]);
+                        gemm_stage<NC, NC, false, true>(
+                            [&](int c, opnd (&bw)[NC]) {
+#pragma unroll
+                                for (int ot = 0; ot < NC; ++ot) bw[ot] = w_qkv((2 * NC + ot) * NC + c);
+                            },
+                            [&](int c) { return h[c]; }, acc);
+                    }
+                    if (zg_tile && zcache_mode == 1) {
+                        f4* const zc = zc_guest();
+#pragma unroll
+                        for (int ot = 0; ot < NC; ++ot) zc[ot * 64] = acc[ot];
                     }
                 }
-            } else if (VT_BLK_GUESTS && w >= NOWN && g < 3) {      // guest 0: q, guest 1: k, guest 2: v of the guest tile
-                f4 h[NC];
-                layer_norm_plain(x4, h);
-                f4 acc[NC];
-                if (g < 2) {
-#pragma unroll
-                    for (int ot = 0; ot < NC; ++ot) acc[ot] = ld4(S + S_BQKV + 16 * (g * NC + ot) + 4 * q);
-                    gemm_stage<NC, NC, true, true>(
-                        [&](int c, opnd (&a)[NC]) {
-#pragma unroll
-                            for (int ot = 0; ot < NC; ++ot) a[ot] = w_qkv((g * NC + ot) * NC + c);
-                        },
-                        [&](int c) { return h[c]; }, acc);
+                with_gt([&](auto gt) {
+                    constexpr int GTc = decltype(gt)::value;
 #pragma unroll
                     for (int ot = 0; ot < NC; ++ot) {
                         if (g == 0) Qg[ot * 64 + lane] = acc[ot];
-                        else Ko[(GT * NC + ot) * 64 + lane] = to_opnd(acc[ot]);
+                        else if (g == 1) Ko[(GTc * NC + ot) * 64 + lane] = to_opnd(acc[ot]);
+                        else Vo[(ot * NT + GTc) * 64 + lane] = to_opnd(acc[ot]);
                     }
-                } else {
-#pragma unroll
-                    for (int ot = 0; ot < NC; ++ot) acc[ot] = splat4(S[S_BQKV + 2 * C + 16 * ot + tok]);
-                    gemm_stage<NC, NC, false, true>(
-                        [&](int c, opnd (&bw)[NC]) {
-#pragma unroll
-                            for (int ot = 0; ot < NC; ++ot) bw[ot] = w_qkv((2 * NC + ot) * NC + c);
-                        },
-                        [&](int c) { return h[c]; }, acc);
-#pragma unroll
-                    for (int ot = 0; ot < NC; ++ot) Vo[(ot * NT + GT) * 64 + lane] = to_opnd(acc[ot]);
-                }
+                });
             }
         }
         stamp();            // QKV done
@@ -708,15 +778,11 @@ __global__ __launch_bounds__(NW * 64, (NW == 5 && !WLDS) ? 3 : 1) void blocks_ke
         if constexpr (BF3L) {
             stage_tiles(Wa, P3, W3_FC1_TILES, w, NW, lane, blk == 0);
         } else if constexpr (WLDS) stage_img(Wa, O_W1, NH * NC, blk);      // fc1 weights
-        // In the last block the template rows only matter as keys / values: their attention
-        // output, proj and MLP never reach the head (vit_dist.py:126 keeps the search rows only),
-        // so those tiles stop after publishing K / V -- unless the caller asked for the residual.
-        const bool last_skip_z = (blk == depth_total - 1) && (resid == nullptr);
         // ---- attention + proj (residual add) --------------------------------------------------
 #pragma unroll
         for (int i = 0; i < TPW; ++i) {
-            const int T = w + NW * i;
-            if (A3 && VT_BLK_OWNERS && T < NOWN && T != dbg_skip_tile && !(last_skip_z && 16 * T < len_z)) {
+            const int T = w + NW * i + toff;
+            if (A3 && VT_BLK_OWNERS && T - toff < NOWN && T != dbg_skip_tile && !(last_skip_z && 16 * T < len_z)) {
                 // A3: the same attention + proj as six-term bf16 products.  q is split here (it stayed fp32 across the barrier: 12 instead
                 // of 18 registers), the scores' exponentials are split as they are produced, o after its normalisation.
                 constexpr int TW[6] = {2, 0, 1, 1, 0, 0}, TX[6] = {0, 2, 1, 0, 1, 0};
@@ -903,7 +969,7 @@ __global__ __launch_bounds__(NW * 64, (NW == 5 && !WLDS) ? 3 : 1) void blocks_ke
                     x[i][ot] = tile48(std::false_type{}, wa0[ot % NWB], wa2[ot % NWB], ob, oc, x[i][ot] + ld4(S + S_BPROJ + 16 * ot + 4 * q));
                     __builtin_amdgcn_sched_barrier(0);
                 }
-            } else if (!A3 && VT_BLK_OWNERS && T < NOWN && T != dbg_skip_tile && !(last_skip_z && 16 * T < len_z)) {
+            } else if (!A3 && VT_BLK_OWNERS && T - toff < NOWN && T != dbg_skip_tile && !(last_skip_z && 16 * T < len_z)) {
                 // softmax((q k^T) * scale) (attn.py:40-41) as exp2(raw * (scale log2 e) - max_raw * (scale log2 e)): the scale, the
                 // subtraction and exp's own log2 e factor become ONE packed fma per two scores, the row maximum runs on v_max3 and the
                 // row sum on packed adds -- 10 instead of 22 VALU instructions per score tile (scale > 0: the raw maximum is the maximum)
@@ -970,7 +1036,7 @@ __global__ __launch_bounds__(NW * 64, (NW == 5 && !WLDS) ? 3 : 1) void blocks_ke
             }
         }
         if constexpr (BAL) {
-            if (VT_BLK_GUESTS && w >= NOWN) {
+            if (VT_BLK_GUESTS && w >= NOWN && !guest_skip) {
                 // partial attention of the guest queries over this guest's key tiles
                 auto attn_part = [&](auto njc, int J0) {
                     constexpr int NJ = decltype(njc)::value;
@@ -1384,11 +1450,11 @@ __global__ __launch_bounds__(NW * 64, (NW == 5 && !WLDS) ? 3 : 1) void blocks_ke
         if constexpr (BF3L) {
 #pragma unroll
             for (int i = 0; i < TPW; ++i) {
-                const int T = w + NW * i;
-                if (VT_BLK_OWNERS && T < NOWN && T != dbg_skip_tile && !(last_skip_z && 16 * T < len_z)) mlp_first3(i, i);
+                const int T = w + NW * i + toff;
+                if (VT_BLK_OWNERS && T - toff < NOWN && T != dbg_skip_tile && !(last_skip_z && 16 * T < len_z)) mlp_first3(i, i);
             }
             u32x2 gq[NC][3];     // the guest's GELU(fc1) tiles 3 g .. 3 g + 2 as pieces
-            if (VT_BLK_GUESTS && w >= NOWN) {
+            if (VT_BLK_GUESTS && w >= NOWN && !guest_skip) {
 #pragma unroll
                 for (int ot = 0; ot < NC; ++ot) x4[ot] = x4[ot] + ld4(S + S_BPROJ + 16 * ot + 4 * q) + Dg[ot * 64 + lane];
                 f4 h[NC];
@@ -1416,10 +1482,10 @@ __global__ __launch_bounds__(NW * 64, (NW == 5 && !WLDS) ? 3 : 1) void blocks_ke
             stamp();
 #pragma unroll
             for (int i = 0; i < TPW; ++i) {
-                const int T = w + NW * i;
-                if (VT_BLK_OWNERS && T < NOWN && T != dbg_skip_tile && !(last_skip_z && 16 * T < len_z)) mlp_second3(i, i);
+                const int T = w + NW * i + toff;
+                if (VT_BLK_OWNERS && T - toff < NOWN && T != dbg_skip_tile && !(last_skip_z && 16 * T < len_z)) mlp_second3(i, i);
             }
-            if (VT_BLK_GUESTS && w >= NOWN) {
+            if (VT_BLK_GUESTS && w >= NOWN && !guest_skip) {
                 // fc2 restricted to this guest's hidden tiles 3 g .. 3 g + 2 = one whole chunk pair and half of another (the other
                 // half of that pair belongs to the neighbouring guest: zeros in this guest's B operand)
                 const bool odd = g & 1;
@@ -1470,12 +1536,12 @@ __global__ __launch_bounds__(NW * 64, (NW == 5 && !WLDS) ? 3 : 1) void blocks_ke
         } else if constexpr (WLDS) {
 #pragma unroll
             for (int i = 0; i < TPW; ++i) {
-                const int T = w + NW * i;
-                if (VT_BLK_OWNERS && T < NOWN && T != dbg_skip_tile && !(last_skip_z && 16 * T < len_z)) mlp_first(i, i);
+                const int T = w + NW * i + toff;
+                if (VT_BLK_OWNERS && T - toff < NOWN && T != dbg_skip_tile && !(last_skip_z && 16 * T < len_z)) mlp_first(i, i);
             }
             f4 ghid[NC];        // BAL: GELU(fc1) of this guest's three hidden tiles
             if constexpr (BAL) {
-                if (VT_BLK_GUESTS && w >= NOWN) {
+                if (VT_BLK_GUESTS && w >= NOWN && !guest_skip) {
 #pragma unroll
                     for (int ot = 0; ot < NC; ++ot) x4[ot] = x4[ot] + ld4(S + S_BPROJ + 16 * ot + 4 * q) + Dg[ot * 64 + lane];
                     f4 h[NC];
@@ -1501,11 +1567,11 @@ __global__ __launch_bounds__(NW * 64, (NW == 5 && !WLDS) ? 3 : 1) void blocks_ke
             stamp();
 #pragma unroll
             for (int i = 0; i < TPW; ++i) {
-                const int T = w + NW * i;
-                if (VT_BLK_OWNERS && T < NOWN && T != dbg_skip_tile && !(last_skip_z && 16 * T < len_z)) mlp_second(i, i);
+                const int T = w + NW * i + toff;
+                if (VT_BLK_OWNERS && T - toff < NOWN && T != dbg_skip_tile && !(last_skip_z && 16 * T < len_z)) mlp_second(i, i);
             }
             if constexpr (BAL) {
-                if (VT_BLK_GUESTS && w >= NOWN) {   // fc2 restricted to this guest's hidden tiles: a partial sum of the update
+                if (VT_BLK_GUESTS && w >= NOWN && !guest_skip) {   // fc2 restricted to this guest's hidden tiles: a partial sum of the update
                     f4 part[NC];
 #pragma unroll
                     for (int ot = 0; ot < NC; ++ot) part[ot] = splat4(0.f);
@@ -1625,7 +1691,7 @@ __global__ __launch_bounds__(NW * 64, (NW == 5 && !WLDS) ? 3 : 1) void blocks_ke
         stamp();            // MLP done
         if constexpr (WLDS) barrier_publish<true>();   // buffer B free; next qkv weights landed
         if constexpr (BAL) {
-            if (w >= NOWN) {
+            if (w >= NOWN && !guest_skip) {
 #pragma unroll
                 for (int k = 0; k < 4; ++k)
 #pragma unroll
@@ -1649,17 +1715,19 @@ __global__ __launch_bounds__(NW * 64, (NW == 5 && !WLDS) ? 3 : 1) void blocks_ke
 #pragma unroll
                 for (int c = 0; c < NC; ++c) st4(dst + 16 * c, x4[c]);
             }
-            f4 h[NC];
-            layer_norm_img(x4, h, PF, PF + C, q_e);
-            float* dst = feat + ((size_t)b * Lx + (16 * GT - len_z) + tok_e) * C + 4 * q_e;
+            if (16 * GT >= len_z) {      // the guests' tile is a search tile (the old role map); else the owners write every feat row
+                f4 h[NC];
+                layer_norm_img(x4, h, PF, PF + C, q_e);
+                float* dst = feat + ((size_t)b * Lx + (16 * GT - len_z) + tok_e) * C + 4 * q_e;
 #pragma unroll
-            for (int c = 0; c < NC; ++c) st4(dst + 16 * c, h[c]);
+                for (int c = 0; c < NC; ++c) st4(dst + 16 * c, h[c]);
+            }
         }
     }
 #pragma unroll
     for (int i = 0; i < TPW; ++i) {
-        const int T = w + NW * i;
-        if (T < NOWN) {
+        const int T = w + NW * i + toff;
+        if (T - toff < NOWN) {
             if (resid != nullptr) {
                 float* dst = resid + ((size_t)b * L + 16 * T + tok_e) * C + 4 * q_e;
 #pragma unroll
