@@ -53,6 +53,8 @@ typedef struct vt_graph vt_graph;
  *     uint8 patches).
  *     channels 768, heads 12, head_channels 256, stride 16, depth 1..24 (12), (template, search) = (128, 256) or (192, 384) -- ViT-Base:
  *         OSTrack-256 (64 + 256 = 320 tokens, 16 x 16 maps) and OSTrack-384 (144 + 576 = 720 tokens, 24 x 24 maps)
+ *     channels 1024, heads 16, head_channels 256, stride 16, depth 1..24 (24), the same two (template, search) pairs -- ViT-Large: the same
+ *         kernels at the second width.  This exact tuple is the ViT-Large model; any other 1024-wide configuration is a shape-generic one.
  * and rejects everything else with VT_ERR_ARG and a message naming these.  The tuned kernels are specialised on their tile
  * counts (token tiles per frame, feature chunks, map sides are template parameters -- that is where their register blocking comes
  * from), so widths and crop sizes are NOT run-time parameters of THOSE kernels. */
@@ -98,7 +100,10 @@ const char* vt_version(void);
  * the qkv projection unless VB_FUSED_QKV=0) and, at (192,384), always qk GEMM + v GEMM + the key-streaming kernel of vb_attn_stream.h
  * (VB_FUSED_QKV has no effect there; VB_ATTN_STREAM=1 with VB_FUSED_QKV=0 selects that kernel at (128,256) too).  Crops are 192 px /
  * 384 px, uint8 patches (B,384,384,3) with 1152-byte rows, the template cache max_batch x 144 operand rows, the Hann window 576 values.
- * Any other ViT-Base geometry or width: VT_ERR_ARG, "unsupported ViT-Base configuration" naming both. */
+ * Any other ViT-Base geometry or width: VT_ERR_ARG, "unsupported ViT-Base configuration" naming both.
+ * channels 1024, heads 16, head_channels 256, stride 16 at the same two geometries: the ViT-Large OSTrack (vit_large_patch16_224: MLP 4096,
+ * depth up to 24) on the same code with the same routes per geometry; vt_query reports channels = 1024, stage tensors are (B, L, 1024).
+ * A depth outside 1..24 there: VT_ERR_ARG, "unsupported ViT-Large configuration". */
 int vt_create(const vt_config* cfg, vt_model** out);
 void vt_destroy(vt_model* m);
 

@@ -58,12 +58,13 @@ def _child(geom, B):
     print("CHILD-OK")
 
 
-def _split(geom, B):
-    """{kernel: us per step} of one geometry's step from a rocprofv3 child, or a string saying why not."""
+def _split(geom, B, script=None):
+    """{kernel: us per step} of one geometry's step from a rocprofv3 child, or a string saying why not.  script: the file whose
+    `--child <geom> --batch B` replays the step (this one; tools/vitl_time.py passes itself)."""
     if shutil.which("rocprofv3") is None:
         return "rocprofv3 not on PATH"
     with tempfile.TemporaryDirectory() as d:
-        p = subprocess.run(["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", d, "--", sys.executable, os.path.abspath(__file__),
+        p = subprocess.run(["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", d, "--", sys.executable, os.path.abspath(script or __file__),
                             "--child", geom, "--batch", str(B)], capture_output=True, text=True, timeout=900, cwd=d)
         if p.returncode != 0 or "CHILD-OK" not in p.stdout:
             return "child failed: " + (p.stdout + p.stderr)[-400:]

@@ -1,4 +1,4 @@
-// vb_api.h -- internal interface between the C-ABI layer (vittrack.hip) and the ViT-Base runtime (vitb.hip).
+// vb_api.h -- internal interface between the C-ABI layer (vittrack.hip) and the ViT-Base / ViT-Large runtime (vitb.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -25,8 +25,8 @@ struct Slice {
 };
 
 // Every function returns VT_OK or a VT_ERR_* code and fills *err.
-// create: channels 768, heads 12, head_channels 256, stride 16 at (template, search) = (128, 256) or (192, 384); the model carries its
-// token counts and map side, every function below works on them.
+// create: channels 768, heads 12 (ViT-Base) or channels 1024, heads 16 (ViT-Large), head_channels 256, stride 16 at (template, search) =
+// (128, 256) or (192, 384); the model carries its width C, its token counts and map side, every function below works on them.
 int create(const vt_config* cfg, VbModel** out, std::string* err);
 void destroy(VbModel* m);
 int load_weights(VbModel* m, const TensorMap& tm, std::string* err);
@@ -36,7 +36,7 @@ int stem(VbModel* m, const float* z, const float* x, int B, hipStream_t st, floa
 // operand can be cached and the search rows can come from a uint8 patch under their own (normalisation-folded) weights.
 //   zsrc  Z_GIVEN: z is the fp32 template crop;  Z_CACHED: the operand rows set_template left (z unused);  Z_NONE: search rows only
 //   x / xu8 (exactly one): fp32 (B,3,Tx,Tx) crop, or the uint8 (B,Tx,Tx,3) patch of vt_crop_u8* (16-byte aligned); Tx = 256 or 384
-//   x_tokens_out (optional): the search rows are copied into rows [Lz, L) of this (B,L,768) matrix (L = 320: Lz = 64; L = 720: Lz = 144)
+//   x_tokens_out (optional): the search rows are copied into rows [Lz, L) of this (B,L,C) matrix (L = 320: Lz = 64; L = 720: Lz = 144)
 enum ZSrc { Z_GIVEN = 0, Z_CACHED = 1, Z_NONE = 2 };
 int stem_rows(VbModel* m, ZSrc zsrc, const float* z, const float* x, const unsigned char* xu8, int B, hipStream_t st, float* x_tokens_out,
               std::string* err, const Slice* sl = nullptr);

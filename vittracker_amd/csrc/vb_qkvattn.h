@@ -36,7 +36,7 @@ using vbg::bf16x8;
 using vbg::glds16;
 using vbg::swz_byte;
 
-constexpr int L = 320, HD = 64, DM = 768, NT = L / 16, NC = L / 32, KS = HD / 32, DT = HD / 16;
+constexpr int L = 320, HD = 64, NT = L / 16, NC = L / 32, KS = HD / 32, DT = HD / 16;
 constexpr int XP = L / 8, WP = 3 * HD / 8;                  // 1 KiB DMA pieces per k-tile: 40 + 24
 constexpr int STAGE_BYTES = (XP + WP) * 1024;               // 64 KiB
 constexpr int IMG_BYTES = NT * KS * 1024;                   // q, K, V^T images: 40 KiB each
@@ -53,7 +53,11 @@ struct Args {
     int hgroup;           // heads walked together (see the item order in the kernel); divides heads
 };
 
-__global__ __launch_bounds__(512) void qkv_attn_kernel(const Args a) {
+// The kernel's body at model width DM (768: ViT-Base, 1024: ViT-Large).  DM sets the row pitch of X / W / out, the distance between the q, k
+// and v sections of W and bias, and the number of k-tiles (DM / 64); the stages and the images hold 64-deep k-tiles of one head and do not
+// depend on it.
+template <int DM>
+__device__ __forceinline__ void qkv_attn_body(const Args& a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int lane_k = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int wm = w >> 1, wn = w & 1;
@@ -275,5 +279,11 @@ __global__ __launch_bounds__(512) void qkv_attn_kernel(const Args a) {
         __syncthreads();             // the images are dead: the next item's staging may overwrite them
     }
 }
+
+__global__ __launch_bounds__(512) void qkv_attn_kernel(const Args a) { qkv_attn_body<768>(a); }
+
+// the same kernel at another width (ViT-Large: DM = 1024, 16 k-tiles, 16 heads)
+template <int DM>
+__global__ __launch_bounds__(512) void qkv_attn_wide_kernel(const Args a) { qkv_attn_body<DM>(a); }
 
 }  // namespace vbq

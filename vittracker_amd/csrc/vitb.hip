@@ -1,7 +1,9 @@
-// vitb.hip -- host side of the ViT-Base OSTrack path (BASELINE config 4): weight packing (bf16, BatchNorm folded, conv
+// vitb.hip -- host side of the plain-ViT OSTrack path (ViT-Base, BASELINE config 4, and ViT-Large): weight packing (bf16, BatchNorm folded, conv
 // weights as [cout][tap][cin], attention scale folded into W_q), workspace, launch sequence.  Kernels: vb_gemm.h, vb_misc.h and the
 // three attention kernels vb_attn.h, vb_qkvattn.h, vb_attn_stream.h (the 384 geometry's), whose shared arithmetic lives in vb_attn.h.
-// Reached through the same C ABI as the vit_48 path (vt_create with channels = 768).
+// Reached through the same C ABI as the vit_48 path (vt_create with channels = 768, or the ViT-Large tuple at channels = 1024).  The two
+// model points differ in width, head count and hidden width alone (VbModel::C / HEADS / HID); the kernels take them at run time except
+// the three that compile the width in (dispatch_width below).
 // Layout of this file: Buf owns device memory (a model is freed by deleting it); Hooks holds the experiment switches, read once;
 // SliceView holds what a frame slice addresses, built once per entry; run_attention launches one of the four attention forms.
 #include "vb_api.h"
@@ -22,12 +24,14 @@ using vbg::bf16;
 
 namespace {
 
-constexpr int C = 768, HEADS = 12, HD = 64, HID = 3072, PATCH_K = 768, HW = 256 /* head width */;
+constexpr int HD = 64, PATCH_K = 768, HW = 256 /* head width */;
+// the two model points (lib/models/ostrack/vit.py:393-400): width, heads of 64, MLP width = 4 x width
+constexpr int C_BASE = 768, HEADS_BASE = 12, C_LARGE = 1024, HEADS_LARGE = 16;
 // The two geometries (template / search crop -> tokens at stride 16): OSTrack-256 = 128 / 256 -> 64 + 256 = 320, OSTrack-384 = 192 / 384 ->
 // 144 + 576 = 720.  The model carries its own (VbModel::L, LZ, LX, F, TZ, TX); the token counts below are the attention kernels' template arguments.
 constexpr int L256 = 320, L384 = 720;
 constexpr float LN_EPS = 1e-6f;
-constexpr int HEAD_CH[5] = {768, 256, 128, 64, 32};
+constexpr int HEAD_CH[5] = {0 /* the model's width: VbModel::head_ch */, 256, 128, 64, 32};
 
 struct Err {
     std::string* e;
@@ -69,6 +73,9 @@ struct BlockW {
 struct VbModel {
     vt_config cfg{};
     int depth = 12, maxB = 0;
+    int C = C_BASE, HEADS = HEADS_BASE, HID = 4 * C_BASE;      // width, heads, MLP width: ViT-Base, or 1024 / 16 / 4096 (ViT-Large)
+    int head_ch(int i) const { return i ? HEAD_CH[i] : C; }    // channels of the head's map i
+    int stat_p() const { return C / 64; }      // (sum, M2) pairs per residual row: one per 64-column wave slice of the 256-wide GEMM tiles
     int TZ = 128, TX = 256, LZ = 64, LX = 256, L = 320, F = 16;      // crop sides, template / search / all tokens per frame, head map side
     int zshift = 6, xshift = 8;     // log2(LZ), log2(LX) where they are powers of two (EPI_PATCH_ROWS); -1 otherwise (EPI_PATCH_ROWS_N)
     bool g384 = false;              // OSTrack-384: always qk GEMM + v GEMM + vbs::attn_stream_kernel (VB_FUSED_QKV has no effect)
@@ -82,7 +89,7 @@ struct VbModel {
     Buf<bf16> xn, qk, vt, ao, hid, map[4], t4;      // map[i]: the head's zero-bordered maps of HEAD_CH[i] channels (1-3: three towers)
     Buf<float> resid;
     // LayerNorm folded into qkv / fc1 (vb_gemm.h): xn then holds the RAW residual rows in bf16, written by the GEMM epilogues that
-    // produce them, rstd their 1 / sqrt(var + eps), stats the epilogues' per-slice (sum, M2) pairs [C / 64][max rows]
+    // produce them, rstd their 1 / sqrt(var + eps), stats the epilogues' per-slice (sum, M2) pairs [stat_p()][max rows]
     bool fold = true;
     bool fused_qkv = true;          // VB_FUSED_QKV: the qkv projection inside the attention kernel (vb_qkvattn.h) instead of qk GEMM + v GEMM + attention
     Buf<float> rstd;
@@ -199,19 +206,27 @@ int launch_gemm(const vbg::Args& a, int groups, hipStream_t st, const Err& E, in
     return VT_OK;
 }
 
+// The kernels that compile the width in (vbm::layernorm_kernel<C>, vbm::ln_finalize_kernel<C / 64>, the fused qkv + attention kernel): f
+// is called with the model's width as a std::integral_constant.  vb::create admits no third width.
+template <typename F>
+void dispatch_width(int C, F&& f) {
+    if (C == C_LARGE) f(std::integral_constant<int, C_LARGE>{});
+    else f(std::integral_constant<int, C_BASE>{});
+}
+
 template <typename K>
 const void* kernel_ptr(K kernel) { return reinterpret_cast<const void*>(kernel); }
 
 int run_layernorm(const VbModel* m, const float* resid, const float* g, const float* b, int B, hipStream_t st, bf16* xn, bf16* map, float* feat,
                   const Err& E, bf16* xb = nullptr, float* rstd = nullptr, float* mean = nullptr) {
     const int M = B * m->L;
-    hipLaunchKernelGGL((vbm::layernorm_kernel<C>), dim3((M + 3) / 4), dim3(256), 0, st, resid, g, b, LN_EPS, M, m->L, m->LZ, m->F, xn, map, feat, xb,
-                       rstd, mean);
+    dispatch_width(m->C, [&](auto W) {
+        hipLaunchKernelGGL((vbm::layernorm_kernel<decltype(W)::value>), dim3((M + 3) / 4), dim3(256), 0, st, resid, g, b, LN_EPS, M, m->L, m->LZ, m->F,
+                           xn, map, feat, xb, rstd, mean);
+    });
     VB_HIP(hipGetLastError());
     return VT_OK;
 }
-
-constexpr int STAT_P = C / 64;       // (sum, M2) pairs per residual row: one per 64-column wave slice of the 256-wide GEMM tiles
 
 // What an entry addresses for the frame slice [f0, f0 + B) of a batch of Bt frames (vb_api.h Slice; none: the whole batch from frame 0):
 // the slice's first token row, its CU budget and every workspace at that frame.
@@ -224,19 +239,22 @@ struct SliceView {
     vbg::f2* stats;
     int ldstats;
     SliceView(const VbModel* m, int B, const vb::Slice* sl)
-        : f0(sl ? sl->f0 : 0), r0(f0 * m->L), cus(sl ? sl->cus : 0), Bt(sl ? sl->Btot : B), xn(m->xn.p + r0 * C), qk(m->qk.p + r0 * 2 * C),
-          vt(m->vt.p + r0 * C), ao(m->ao.p + r0 * C), hid(m->hid.p + r0 * HID), resid(m->resid.p + r0 * C), rstd(m->rstd.p + r0),
-          rmean(m->rmean.p + r0), stats(m->stats.p + r0), ldstats((int)(m->stats.n / STAT_P)) {
+        : f0(sl ? sl->f0 : 0), r0(f0 * m->L), cus(sl ? sl->cus : 0), Bt(sl ? sl->Btot : B), xn(m->xn.p + r0 * m->C), qk(m->qk.p + r0 * 2 * m->C),
+          vt(m->vt.p + r0 * m->C), ao(m->ao.p + r0 * m->C), hid(m->hid.p + r0 * m->HID), resid(m->resid.p + r0 * m->C), rstd(m->rstd.p + r0),
+          rmean(m->rmean.p + r0), stats(m->stats.p + r0), ldstats((int)(m->stats.n / m->stat_p())) {
         const size_t P2 = (size_t)(m->F + 2) * (m->F + 2);
-        for (int i = 0; i < 4; ++i) map[i] = m->map[i].p + f0 * P2 * HEAD_CH[i];
+        for (int i = 0; i < 4; ++i) map[i] = m->map[i].p + f0 * P2 * m->head_ch(i);
         map[4] = m->t4.p + f0 * (size_t)m->LX * HEAD_CH[4];
     }
     // a GEMM that writes residual rows also leaves their bf16 copy and LayerNorm statistics (the folded LayerNorms, vb_gemm.h)
     void stats_of(vbg::Args& a) const { a.xb = xn; a.stats = stats; a.ldstats = ldstats; }
 };
 
-int run_finalize(const SliceView& v, int M, hipStream_t st, const Err& E) {
-    hipLaunchKernelGGL(vbm::ln_finalize_kernel<STAT_P>, dim3((M + 255) / 256), dim3(256), 0, st, v.stats, v.ldstats, M, LN_EPS, v.rstd, v.rmean);
+int run_finalize(const VbModel* m, const SliceView& v, int M, hipStream_t st, const Err& E) {
+    dispatch_width(m->C, [&](auto W) {
+        hipLaunchKernelGGL(vbm::ln_finalize_kernel<decltype(W)::value / 64>, dim3((M + 255) / 256), dim3(256), 0, st, v.stats, v.ldstats, M, LN_EPS, v.rstd,
+                           v.rmean);
+    });
     VB_HIP(hipGetLastError());
     return VT_OK;
 }
@@ -263,7 +281,7 @@ void fold_layernorm(std::vector<float>& w, std::vector<float>& b, const float* g
 // weights instead is algebraically the uncentred form again.  The centring table of the search rows (Args::cm) follows b'.
 // The patch GEMM's centring constants, [L]: a token row is patches W^T + bias + pos row; what is known of its mean before the GEMM runs is
 // mean(bias) + mean(pos row) (the projection of a normalised patch is zero-mean over channels to first order).  bias_sum: over channels
-int upload_centring(Buf<float>& d, const std::vector<float>& pos, double bias_sum, const Err& E) {
+int upload_centring(Buf<float>& d, const std::vector<float>& pos, int C, double bias_sum, const Err& E) {
     std::vector<float> cpos(pos.size() / C);
     for (size_t t = 0; t < cpos.size(); ++t) {
         double s = 0;
@@ -274,6 +292,7 @@ int upload_centring(Buf<float>& d, const std::vector<float>& pos, double bias_su
 }
 
 int fold_patch_u8(VbModel* m, const Err& E) {
+    const int C = m->C;
     std::vector<float> w((size_t)C * PATCH_K), b(C);
     double k255[3], ms[3], bsum = 0;
     for (int c = 0; c < 3; ++c) { k255[c] = 1.0 / (255.0 * (double)m->norm_std[c]); ms[c] = (double)m->norm_mean[c] / (double)m->norm_std[c]; }
@@ -293,7 +312,7 @@ int fold_patch_u8(VbModel* m, const Err& E) {
     }
     int rc;
     if ((rc = upload_bf16(m->wpatch_u8, w, E)) || (rc = upload_f32(m->bpatch_u8, b.data(), b.size(), E))) return rc;
-    return upload_centring(m->cpos_u8, m->h_pos, bsum, E);
+    return upload_centring(m->cpos_u8, m->h_pos, C, bsum, E);
 }
 
 }  // namespace
@@ -310,7 +329,15 @@ int set_normalization(VbModel* m, const float* mean3, const float* std3, std::st
 int create(const vt_config* cfg, VbModel** out, std::string* err) {
     const Err E{err};
     const bool g256 = cfg->template_size == 128 && cfg->search_size == 256, g384 = cfg->template_size == 192 && cfg->search_size == 384;
-    if (cfg->channels != C || cfg->heads != HEADS || cfg->head_channels != HW || cfg->stride != 16 || !(g256 || g384))
+    const bool large = cfg->channels == C_LARGE;
+    if (large) {       // vt_create sends only the exact ViT-Large tuple here; the depth is what is left to refuse
+        if (cfg->heads != HEADS_LARGE || cfg->head_channels != HW || cfg->stride != 16 || !(g256 || g384) || cfg->depth < 1 || cfg->depth > 24)
+            return E.fail(VT_ERR_ARG, "unsupported ViT-Large configuration: this build implements CHANNELS=1024, HEADS=16, HEAD.NUM_CHANNELS=256, "
+                                      "STRIDE=16, 1 <= depth <= 24, template 128 / search 256 or template 192 / search 384; got channels=" +
+                                      std::to_string(cfg->channels) + " heads=" + std::to_string(cfg->heads) + " depth=" + std::to_string(cfg->depth) +
+                                      " head_channels=" + std::to_string(cfg->head_channels) + " stride=" + std::to_string(cfg->stride) +
+                                      " template=" + std::to_string(cfg->template_size) + " search=" + std::to_string(cfg->search_size));
+    } else if (cfg->channels != C_BASE || cfg->heads != HEADS_BASE || cfg->head_channels != HW || cfg->stride != 16 || !(g256 || g384))
         return E.fail(VT_ERR_ARG, "unsupported ViT-Base configuration: this build implements CHANNELS=768, HEADS=12, "
                                   "HEAD.NUM_CHANNELS=256, STRIDE=16, template 128 / search 256 (OSTrack-256) or template 192 / search 384 "
                                   "(OSTrack-384); got channels=" + std::to_string(cfg->channels) + " heads=" + std::to_string(cfg->heads) +
@@ -319,10 +346,18 @@ int create(const vt_config* cfg, VbModel** out, std::string* err) {
     if (cfg->depth < 1 || cfg->depth > 24 || cfg->max_batch < 1) return E.fail(VT_ERR_ARG, "bad depth / max_batch");
     // the EPI_PATCH_ROWS_N epilogue finds a row's frame by a multiply-high that is exact while rows * rows-per-frame < 2^32
     if (g384 && (uint64_t)cfg->max_batch * 576 * 576 >= (1ull << 32)) return E.fail(VT_ERR_ARG, "max_batch too large for the 192 / 384 geometry");
+    // the GEMMs address their operands by 32-bit byte offsets from the operand's base: the widest one, the MLP's hidden rows, has to fit
+    {
+        const uint64_t Lc = (uint64_t)(cfg->template_size / 16) * (cfg->template_size / 16) + (uint64_t)(cfg->search_size / 16) * (cfg->search_size / 16);
+        if ((uint64_t)cfg->max_batch * Lc * (4 * (uint64_t)cfg->channels) * 2 >= (1ull << 32))
+            return E.fail(VT_ERR_ARG, "max_batch too large: the MLP's hidden rows of a batch must stay below 4 GiB");
+    }
     VbModel* m = new VbModel();
     m->cfg = *cfg;
     m->depth = cfg->depth;
     m->maxB = cfg->max_batch;
+    m->C = cfg->channels; m->HEADS = cfg->heads; m->HID = 4 * cfg->channels;
+    const int C = m->C, HID = m->HID;
     m->blk.resize(m->depth);
     m->g384 = g384;
     m->TZ = cfg->template_size; m->TX = cfg->search_size;
@@ -347,11 +382,11 @@ int create(const vt_config* cfg, VbModel** out, std::string* err) {
             if (e == hipSuccess) e = w.first->alloc(w.second);
     };
     alloc_all(std::initializer_list<std::pair<Buf<bf16>*, size_t>>{
-        {&m->xn, M * C}, {&m->qk, (M + PAD) * 2 * C}, {&m->vt, M * C + PAD}, {&m->ao, M * C}, {&m->hid, M * HID}, {&m->map[0], B * P2 * C},
+        {&m->xn, M * C}, {&m->qk, (M + PAD) * 2 * C}, {&m->vt, M * C + PAD}, {&m->ao, M * C}, {&m->hid, M * HID}, {&m->map[0], B * P2 * (size_t)C},
         {&m->map[1], 3 * B * P2 * HEAD_CH[1]}, {&m->map[2], 3 * B * P2 * HEAD_CH[2]}, {&m->map[3], 3 * B * P2 * HEAD_CH[3]},
         {&m->t4, 3 * B * LX * HEAD_CH[4]}, {&m->zop, B * LZ * PATCH_K}});
     alloc_all(std::initializer_list<std::pair<Buf<float>*, size_t>>{{&m->resid, M * C}, {&m->rstd, M}, {&m->rmean, M}});
-    alloc_all(std::initializer_list<std::pair<Buf<vbg::f2>*, size_t>>{{&m->stats, (size_t)STAT_P * M}});
+    alloc_all(std::initializer_list<std::pair<Buf<vbg::f2>*, size_t>>{{&m->stats, (size_t)m->stat_p() * M}});
     // zero borders of the padded maps (kernels only ever write interiors), and the two tails
     Buf<bf16>* const zeroed[] = {&m->map[0], &m->map[1], &m->map[2], &m->map[3], &m->qk, &m->vt};
     for (Buf<bf16>* b : zeroed)
@@ -370,12 +405,13 @@ int create(const vt_config* cfg, VbModel** out, std::string* err) {
         {kernel_ptr(vba::attn_kernel<L256, HD>), vba::Geo<L256, HD>::LDS_BYTES},
         {kernel_ptr(vbs::attn_stream_kernel<L256>), vbs::LDS_BYTES},
         {kernel_ptr(vbs::attn_stream_kernel<L384>), vbs::LDS_BYTES},
-        {kernel_ptr(vbq::qkv_attn_kernel), vbq::LDS_BYTES}};
+        {kernel_ptr(vbq::qkv_attn_kernel), vbq::LDS_BYTES},
+        {kernel_ptr(vbq::qkv_attn_wide_kernel<C_LARGE>), vbq::LDS_BYTES}};
     for (const auto& k : dynamic_lds)
         if (e == hipSuccess) e = hipFuncSetAttribute(k.kernel, hipFuncAttributeMaxDynamicSharedMemorySize, k.lds);
     if (e != hipSuccess) {
         destroy(m);
-        return E.fail(VT_ERR_HIP, std::string("ViT-Base workspace: ") + hipGetErrorString(e));
+        return E.fail(VT_ERR_HIP, std::string("ViT workspace: ") + hipGetErrorString(e));
     }
     *out = m;
     return VT_OK;
@@ -390,7 +426,7 @@ int load_weights(VbModel* m, const TensorMap& tm, std::string* err) {
     int rc;
     const float* p;
     const std::string bb = "backbone.";
-    const int L = m->L, LZ = m->LZ, LX = m->LX;
+    const int L = m->L, LZ = m->LZ, LX = m->LX, C = m->C, HID = m->HID;
     const float *wp, *bp;
     if ((rc = load_bf16(m->wpatch, tm, bb + "patch_embed.proj.weight", (int64_t)C * PATCH_K, E, &wp))) return rc;
     if ((rc = load_f32(m->bpatch, tm, bb + "patch_embed.proj.bias", C, E, &bp))) return rc;
@@ -404,7 +440,7 @@ int load_weights(VbModel* m, const TensorMap& tm, std::string* err) {
     if ((rc = upload_f32(m->pos, m->h_pos.data(), m->h_pos.size(), E))) return rc;
     double bsum = 0;
     for (int k = 0; k < C; ++k) bsum += bp[k];
-    if ((rc = upload_centring(m->cpos, m->h_pos, bsum, E)) || (rc = fold_patch_u8(m, E))) return rc;
+    if ((rc = upload_centring(m->cpos, m->h_pos, C, bsum, E)) || (rc = fold_patch_u8(m, E))) return rc;
     const float scale = 1.0f / std::sqrt((float)HD);     // 0.125: a power of two, folding it into W_q / b_q is exact
     for (int i = 0; i < m->depth; ++i) {
         BlockW& b = m->blk[i];
@@ -433,8 +469,8 @@ int load_weights(VbModel* m, const TensorMap& tm, std::string* err) {
     // ---- head: Conv3x3(+bias) + BatchNorm(eval, eps 1e-5) folded in double (head.py:8-21), weights as [cout][tap][cin]
     const char* towers[3] = {"ctr", "offset", "size"};
     for (int li = 0; li < 4; ++li) {
-        const int cin = HEAD_CH[li], cout = HEAD_CH[li + 1], K = 9 * cin;
-        // conv1: towers along N.  conv2 (N = 128 per tower, K = 2304) runs on the 256 x 256 software-pipelined tile, one group per tower, with
+        const int cin = m->head_ch(li), cout = HEAD_CH[li + 1], K = 9 * cin;
+        // conv1: towers along N (K = 9 x the model's width).  conv2 (N = 128 per tower, K = 2304) runs on the 256 x 256 software-pipelined tile, one group per tower, with
         // its weight rows zero-padded to 256 (half of every MFMA column block is padding, and it still beats the two-buffer 256 x 64 loop:
         // 268 -> ~180 us, round 5); conv3 / conv4 keep the narrow tile (BN = 64: rows padded to 64)
         const int rows = li == 0 ? cout : (li == 1 ? 256 : (cout < 64 ? 64 : cout));
@@ -493,7 +529,7 @@ int stem(VbModel* m, const float* z, const float* x, int B, hipStream_t st, floa
     const Err E{err};
     int rc = check(m, B, E);
     if (rc || (rc = check_slice(m, B, sl, E))) return rc;
-    const int L = m->L, M = B * L;
+    const int L = m->L, M = B * L, C = m->C;
     const SliceView v(m, B, sl);
     bf16* const patches = m->fold ? v.ao : v.xn;     // folded: xn receives the tokens' bf16 copy from the GEMM epilogue
     hipLaunchKernelGGL(vbm::patchify_kernel, dim3(grid256((size_t)M * 96)), dim3(256), 0, st, z, x, patches, B, m->TZ, m->TX);
@@ -504,7 +540,7 @@ int stem(VbModel* m, const float* z, const float* x, int B, hipStream_t st, floa
     if (m->fold) v.stats_of(a);
     if (m->fold && m->center) { a.cm = m->cpos.p; a.cm_mod = L; }
     if ((rc = launch_gemm<256, 256, 2, 4, vbg::A_PLAIN, vbg::EPI_PATCH>(a, 1, st, E, v.cus))) return rc;
-    if (m->fold && (rc = run_finalize(v, M, st, E))) return rc;
+    if (m->fold && (rc = run_finalize(m, v, M, st, E))) return rc;
     if (tokens_out) VB_HIP(hipMemcpyAsync(tokens_out, v.resid, (size_t)M * C * 4, hipMemcpyDeviceToDevice, st));
     return VT_OK;
 }
@@ -537,7 +573,7 @@ int stem_rows(VbModel* m, ZSrc zsrc, const float* z, const float* x, const unsig
     if (rc || (rc = check_slice(m, B, sl, E))) return rc;
     if ((x != nullptr) == (xu8 != nullptr)) return E.fail(VT_ERR_ARG, "stem_rows: one of the fp32 crop and the uint8 patch");
     if (xu8 && (reinterpret_cast<uintptr_t>(xu8) & 15)) return E.fail(VT_ERR_ARG, "the uint8 patch must be 16-byte aligned on the ViT-Base path");
-    const int L = m->L, LZ = m->LZ, LX = m->LX;
+    const int L = m->L, LZ = m->LZ, LX = m->LX, C = m->C;
     const SliceView v(m, B, sl);
     bf16* const xop = m->fold ? v.ao : v.xn;      // B * LX dense rows inside the slice's B * L (as vb::stem's operand)
     const bf16* zop = m->zop.p + v.f0 * LZ * PATCH_K;
@@ -569,7 +605,7 @@ int stem_rows(VbModel* m, ZSrc zsrc, const float* z, const float* x, const unsig
     a.bias = xu8 ? m->bpatch_u8.p : m->bpatch.p;
     if (m->fold && m->center) a.cm = xu8 ? m->cpos_u8.p : m->cpos.p;
     if ((rc = rows_gemm(a, LX, m->xshift))) return rc;
-    if (m->fold && (rc = run_finalize(v, B * L, st, E))) return rc;
+    if (m->fold && (rc = run_finalize(m, v, B * L, st, E))) return rc;
     if (x_tokens_out)
         VB_HIP(hipMemcpy2DAsync(x_tokens_out + (size_t)LZ * C, (size_t)L * C * 4, v.resid + (size_t)LZ * C, (size_t)L * C * 4, (size_t)LX * C * 4, B,
                                 hipMemcpyDeviceToDevice, st));
@@ -582,12 +618,17 @@ int stem_rows(VbModel* m, ZSrc zsrc, const float* z, const float* x, const unsig
 //                                           vba::attn_kernel<320, 64>
 static int run_attention(const VbModel* m, const SliceView& v, const BlockW& b, const float* rstd, int B, hipStream_t st, const Err& E) {
     int rc;
+    const int C = m->C, HEADS = m->HEADS;
     if (m->fused_qkv && !m->g384) {
         vbq::Args qa{};
         qa.X = v.xn; qa.W = b.wqkv.p; qa.bias = b.bqkv.p; qa.rstd = rstd; qa.out = v.ao; qa.B = B; qa.heads = HEADS;
-        static const int hgv = env_int("VB_QA_HGROUP", 6);
-        qa.hgroup = (hgv > 0 && HEADS % hgv == 0) ? hgv : HEADS;
-        hipLaunchKernelGGL(vbq::qkv_attn_kernel, dim3(persistent_grid(v.cus)), dim3(512), vbq::LDS_BYTES, st, qa);
+        // heads walked together: 6 of 12 measured best at width 768 (vb_qkvattn.h); 16 heads of width 1024 take 4, the divisor whose group of
+        // weight rows (4 x 384 KiB) is nearest to that one's (6 x 288 KiB)
+        static const int hgv = env_int("VB_QA_HGROUP", -1);
+        const int hg = hgv < 0 ? (C == C_LARGE ? 4 : 6) : hgv;
+        qa.hgroup = (hg > 0 && HEADS % hg == 0) ? hg : HEADS;
+        if (C == C_LARGE) hipLaunchKernelGGL(vbq::qkv_attn_wide_kernel<C_LARGE>, dim3(persistent_grid(v.cus)), dim3(512), vbq::LDS_BYTES, st, qa);
+        else hipLaunchKernelGGL(vbq::qkv_attn_kernel, dim3(persistent_grid(v.cus)), dim3(512), vbq::LDS_BYTES, st, qa);
         VB_HIP(hipGetLastError());
         return VT_OK;
     }
@@ -616,7 +657,7 @@ int blocks(VbModel* m, const float* tokens_in, int B, int nblocks, hipStream_t s
     const Err E{err};
     int rc = check(m, B, E);
     if (rc || (rc = check_slice(m, B, sl, E))) return rc;
-    const int M = B * m->L;
+    const int M = B * m->L, C = m->C, HID = m->HID;
     const SliceView v(m, B, sl);
     if (nblocks < 0 || nblocks > m->depth) nblocks = m->depth;
     if (tokens_in && tokens_in != v.resid)
@@ -632,7 +673,7 @@ int blocks(VbModel* m, const float* tokens_in, int B, int nblocks, hipStream_t s
         p.X = X; p.W = W; p.bias = bias; p.resid = v.resid; p.M = M; p.N = C; p.K = K;
         if (feeds_ln) { v.stats_of(p); p.cm = cmean; }
         if (int r = launch_gemm<256, 256, 2, 4, vbg::A_PLAIN, vbg::EPI_RESID>(p, 1, st, E, v.cus)) return r;
-        return feeds_ln ? run_finalize(v, M, st, E) : VT_OK;
+        return feeds_ln ? run_finalize(m, v, M, st, E) : VT_OK;
     };
     for (int i = 0; i < nblocks; ++i) {
         const BlockW& b = m->blk[i];
@@ -655,17 +696,17 @@ int head(VbModel* m, const float* feat_in, int B, hipStream_t st, float* score, 
     const Err E{err};
     int rc = check(m, B, E);
     if (rc || (rc = check_slice(m, B, sl, E))) return rc;
-    const int LX = m->LX, F = m->F, M = B * LX;
+    const int LX = m->LX, F = m->F, M = B * LX, C = m->C;
     const SliceView v(m, B, sl);
     const long long Bt = v.Bt, P2 = (long long)(F + 2) * (F + 2);              // tower-major buffers: [tower][Bt frames]...
     if (feat_in) {
         hipLaunchKernelGGL(vbm::feat_to_map_kernel, dim3(grid256((size_t)B * LX * (C / 4))), dim3(256), 0, st, feat_in, v.map[0], B, F, C);
         VB_HIP(hipGetLastError());
     }
-    {   // conv1 of the three towers as one GEMM: N = 3 x 256, K = 9 x 768
+    {   // conv1 of the three towers as one GEMM: N = 3 x 256, K = 9 x the width
         vbg::Args a{};
         a.X = v.map[0]; a.W = m->wc[0].p; a.bias = m->bc[0].p; a.out = v.map[1];
-        a.M = M; a.N = 3 * HEAD_CH[1]; a.K = 9 * HEAD_CH[0]; a.ldo = HEAD_CH[1]; a.C = HEAD_CH[0]; a.F = F; a.out_padded = 1;
+        a.M = M; a.N = 3 * HEAD_CH[1]; a.K = 9 * C; a.ldo = HEAD_CH[1]; a.C = C; a.F = F; a.out_padded = 1;
         a.n_split = HEAD_CH[1]; a.gOut = Bt * P2 * HEAD_CH[1];
         if ((rc = launch_gemm<256, 256, 2, 4, vbg::A_CONV, vbg::EPI_CONV>(a, 1, st, E, v.cus))) return rc;
     }

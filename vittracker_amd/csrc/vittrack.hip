@@ -180,7 +180,7 @@ const CropSwitches& crop_switches() {
 }  // namespace
 
 struct vt_model {
-    VbModel* vb = nullptr;           // ViT-Base path (channels = 768): backbone + head towers live in vitb.hip
+    VbModel* vb = nullptr;           // ViT-Base / ViT-Large path (channels = 768 / 1024): backbone + head towers live in vitb.hip
     // any other stride-16 geometry of the vit_48_h32 surface: the shape-generic kernels of vt_generic.h
     bool generic = false;
     vtg::Dims gd{48, 1, 32};         // widths of the shape-generic path (round 6: any CHANNELS / HEADS / HEAD.NUM_CHANNELS)
@@ -1198,7 +1198,7 @@ int init_model(vt_model* m, const vt_config* cfg, bool vitb) {
     return VT_OK;
 }
 
-// ViT-Base model: the shared part of vt_model is the output scratch, the window and the streams
+// ViT-Base or ViT-Large model: the shared part of vt_model is the output scratch, the window and the streams
 int create_vitb(const vt_config* cfg, vt_model** out) {
     std::string err;
     VbModel* vbm = nullptr;
@@ -1223,6 +1223,11 @@ const char* vt_version(void) { return "vittrack-hip 0.2 (gfx950, " VT_PRECISION_
 int vt_create(const vt_config* cfg, vt_model** out) {
     if (!cfg || !out) return fail(VT_ERR_ARG, "null argument");
     if (cfg->channels == 768) return create_vitb(cfg, out);
+    // ViT-Large OSTrack: this exact tuple leaves the shape-generic surface for the bf16 path of vitb.hip (which checks the depth); every other
+    // 1024-wide configuration goes on below
+    if (cfg->channels == 1024 && cfg->heads == 16 && cfg->head_channels == 256 && cfg->stride == 16 &&
+        ((cfg->template_size == 128 && cfg->search_size == 256) || (cfg->template_size == 192 && cfg->search_size == 384)))
+        return create_vitb(cfg, out);
     // build_ostrack_dist takes embed_dim / num_heads / the head width from the YAML (vit_dist.py:159-164; head.py:352-359): the shipped widths
     // (48, 1, 32) at the two geometries of the repository's configs run the tuned kernels, everything else the shape-generic ones
     const bool shipped_widths = cfg->channels == 48 && cfg->heads == 1 && cfg->head_channels == 32;

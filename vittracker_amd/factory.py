@@ -1,4 +1,4 @@
-"""One place that turns a config tree into a network: ``build_network(cfg)`` picks the ViT-Base OSTrack model
+"""One place that turns a config tree into a network: ``build_network(cfg)`` picks the ViT-Base / ViT-Large OSTrack model
 (:mod:`vittracker_amd.model_vitb`, ``lib/models/ostrack/ostrack.py:164``) or the distilled vit_48 one (:mod:`vittracker_amd.model`,
 ``lib/models/vit_dist/vit_dist.py:159``) from ``MODEL.BACKBONE.TYPE`` / ``CHANNELS``, so that every tracker front end
 (``BatchedVitTracker`` and what stands on it, the plugins' host-crop path) serves both YAML families."""
@@ -8,11 +8,14 @@ from __future__ import annotations
 def network_builder(cfg):
     """The build function of cfg's model family.  The vit_dist YAMLs keep the config default ``TYPE: vit_base_patch16_224`` (the
     reference's vit_dist builder never reads it), so the width decides: 768 channels is the ViT-Base backbone, anything else
-    the distilled stem + blocks of that width."""
+    the distilled stem + blocks of that width.  No vit_dist YAML names ``vit_large_patch16_224``: that TYPE alone selects the ViT-Large
+    backbone (its width comes from the TYPE, as in the reference's build_ostrack)."""
     from .model import build_ostrack_dist
     from .model_vitb import build_ostrack
     bb = cfg.MODEL.BACKBONE
     if int(bb.CHANNELS) == 768 and str(bb.TYPE).startswith("vit_base_patch16_224"):
+        return build_ostrack
+    if str(bb.TYPE).startswith("vit_large_patch16_224"):
         return build_ostrack
     return build_ostrack_dist
 

@@ -1,7 +1,7 @@
-"""Model-level drop-in for the ViT-Base OSTrack path (BASELINE config 4): ``build_ostrack(cfg, training=False) -> OSTrack``
+"""Model-level drop-in for the plain-ViT OSTrack path (ViT-Base, BASELINE config 4, and ViT-Large): ``build_ostrack(cfg, training=False) -> OSTrack``
 with the surface the reference's callers use (``lib/models/ostrack/ostrack.py:22-151,164-286``):
 
-    net = build_ostrack(cfg, training=False)            # MODEL.BACKBONE.TYPE = vit_base_patch16_224, HEAD = CENTER / 256
+    net = build_ostrack(cfg, training=False)            # MODEL.BACKBONE.TYPE = vit_base_patch16_224 | vit_large_patch16_224, HEAD = CENTER / 256
     net.load_state_dict(ckpt['net'], strict=False)      # keys backbone.* / box_head.*
     net = net.cuda(); net.eval()
     out = net.forward(template=z, search=x)             # {'pred_boxes','score_map','size_map','offset_map'}
@@ -19,13 +19,24 @@ from .config import geometry
 from .model import CenterHead, OstrackDist
 
 
+#: what MODEL.BACKBONE.TYPE fixes for the large backbone (lib/models/ostrack/vit.py:393-400: embed_dim, num_heads, depth).  As in the
+#: reference the TYPE decides: CHANNELS / HEADS of the YAML are not read for it.
+VIT_LARGE = {"channels": 1024, "heads": 16, "depth": 24}
+
+
 class OSTrack(OstrackDist):
-    def __init__(self, cfg, depth=12, max_batch=1):
+    def __init__(self, cfg, depth=None, max_batch=1):
         g = geometry(cfg)
         if g["head_type"] != "CENTER":
             raise ValueError("HEAD TYPE %s is not supported." % g["head_type"])
-        if str(cfg.MODEL.BACKBONE.TYPE) != "vit_base_patch16_224":
-            raise NotImplementedError(f"backbone {cfg.MODEL.BACKBONE.TYPE!r}: only vit_base_patch16_224 is implemented")
+        bb_type = str(cfg.MODEL.BACKBONE.TYPE)
+        if bb_type == "vit_large_patch16_224":
+            g["channels"], g["heads"] = VIT_LARGE["channels"], VIT_LARGE["heads"]
+            depth = VIT_LARGE["depth"] if depth is None else depth
+        elif bb_type == "vit_base_patch16_224":
+            depth = 12 if depth is None else depth
+        else:
+            raise NotImplementedError(f"backbone {cfg.MODEL.BACKBONE.TYPE!r}: only vit_base_patch16_224 and vit_large_patch16_224 are implemented")
         if str(cfg.MODEL.BACKBONE.CAT_MODE) != "direct":
             raise NotImplementedError("only CAT_MODE 'direct' (template tokens first) is implemented")
         self.geom, self.depth, self.mode, self.head_type, self.max_batch = g, depth, "eval", "CENTER", max_batch

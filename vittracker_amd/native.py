@@ -710,7 +710,8 @@ class Model:
     def __init__(self, template_size, search_size, channels=48, heads=1, depth=3, head_channels=32, stride=16,
                  max_batch=1, precision="f32"):
         """precision: 'f32' (exact fp32 contractions, the parity path) or 'f16' (vit_48 contractions on f16 MFMA,
-        BASELINE config 5).  The ViT-Base path (channels=768) always contracts in bf16."""
+        BASELINE config 5).  The ViT-Base path (channels=768, heads=12) and the ViT-Large one (channels=1024, heads=16, head_channels=256
+        at 128 / 256 or 192 / 384) always contract in bf16."""
         self.precision = precision
         self._L = lib(precision)
         self.cfg = VtConfig(template_size, search_size, channels, heads, depth, head_channels, stride, max_batch)
@@ -797,7 +798,7 @@ class Model:
     # ---- whole step
     def set_template(self, z, stream=None):
         """Exact template cache (vt_set_template): afterwards ``forward(None, x)`` / ``capture(None, x)`` skip the
-        template's patch embedding and block 0's LayerNorm-1 + qkv of its rows.  On a ViT-Base model (channels=768) the cache holds the
+        template's patch embedding and block 0's LayerNorm-1 + qkv of its rows.  On a ViT-Base / ViT-Large model (channels=768 / 1024) the cache holds the
         templates' bf16 patch-GEMM operand rows; forward(None, x), forward_u8(None, patch) and track_step* read it, bit-identical to the
         same call with z."""
         B, tz = z.shape[0], self.template_size
@@ -1030,7 +1031,7 @@ class Model:
 
     def forward_u8(self, z, x_patch, out: Outputs | None = None, stream=None) -> Outputs:
         """Preprocessor.process + forward on the uint8 search patch of crop_u8; z: fp32 template crop or None (cached template).
-        ViT-Base models take it at every batch size; the patch must be 16-byte aligned there (any torch allocation is)."""
+        ViT-Base and ViT-Large models take it at every batch size; the patch must be 16-byte aligned there (any torch allocation is)."""
         B = self._check_patch(x_patch)
         if z is None:
             if getattr(self, "_tmpl_B", 0) < B:
