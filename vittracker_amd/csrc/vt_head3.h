@@ -18,6 +18,9 @@
 //     8 values are its quad of chunk 2 p and its quad of chunk 2 p + 1 (the K order inside an MFMA is free as long as both
 //     operands agree), so the fp32 kernels' 16-deep chunks, quad decoding and tap offsets carry over unchanged.
 //   * an odd last chunk pairs with zero weights (the activation read for it clamps to a valid quad, as pad quads always did).
+//   * conv3 (16 -> 8) and conv4 (8 -> 4) of the two fused heads (head_fused3, head_seq3) are NOT three-piece products: on the
+//     16 x 16 MFMA they fill 8 and 4 of 16 output rows, so they run on v_mfma_f32_4x4x1 at fp32 from fp32 maps (quad_taps,
+//     FusedConvQ / SeqConvQ); the per-tower form head_towers3 keeps pieces for all four layers.
 #pragma once
 #include "vt_bf3.h"
 #include "vt_head.h"
@@ -163,15 +166,16 @@ struct HeadConv3 {
         }
     }
     // ---- the same layer with its weights shared by the tower's four waves through LDS (1-output-tile layers, one pixel tile per
-    // wave): every wave of a tower needs the WHOLE image, so streamed per wave it crosses the L2 -> CU path four times.  The images
-    // of conv2-4 move as one sequence of staged passes of <= SP chunk pairs (WeightPipe below): pass j is fetched by the tower's 256
+    // wave): every wave of a tower needs the WHOLE image, so streamed per wave it crosses the L2 -> CU path four times.  The image
+    // moves as a sequence of staged passes of <= SP chunk pairs (WeightPipe below): pass j is fetched by the tower's 256
     // threads at the start of pass j - 2, parked in staging buffer j & 1 at the end of pass j - 1 and read by all four waves in
     // pass j; one workgroup barrier per pass, which is also the layer's barrier after its last pass.  (Fetched only one pass ahead
-    // every pass waited for its own L2 round trip: 6 passes x ~1 us.)
+    // every pass waited for its own L2 round trip.)  The ReLU'd result is stored as fp32, quad-planar f4 out_map[quad][G::NPIX]: its
+    // reader is the 4 x 4-block fp32 MFMA layer (FusedConvQ), not another three-piece product.
     static constexpr int SP = 3, NSP = (NCP + SP - 1) / SP, SBUF16 = SP * 192;       // staging buffer: 9 KiB
     static constexpr int pass_n16(int p) { return (p + 1 < NSP ? SP : NCP - (NSP - 1) * SP) * 192; }
     template <typename Pipe>
-    __device__ __forceinline__ void run_staged(const u32x2* in_map, u32x2* out_map, const float* __restrict__ bias, int wave, int lane,
+    __device__ __forceinline__ void run_staged(const u32x2* in_map, f4* out_map, const float* __restrict__ bias, int wave, int lane,
                                                int g0, Pipe& pipe) {
         static_assert(NOT == 1 && NPT == 1 && ACT == NW, "staged form: one output tile, one pixel tile per wave");
         const int q = lane >> 4;
@@ -223,10 +227,7 @@ struct HeadConv3 {
             if (p == NSP - 1 && 4 * q < COUT) {
                 f4 v = acc;
                 v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f);
-                u32x2 h, m, l;
-                split3(v, h, m, l);
-                const int e = q * G::NPIX + centre;
-                out_map[e] = h; out_map[PS_OUT + e] = m; out_map[2 * PS_OUT + e] = l;
+                out_map[q * G::NPIX + centre] = v;
             }
             pipe.park(g + 1);
             __syncthreads();
@@ -234,28 +235,98 @@ struct HeadConv3 {
     }
 };
 
-// LDS entries (uint2) of the maps: input 3 x 12 planes, per tower m1 3 x 8 and m2 3 x 4 planes
+// ---- v_mfma_f32_4x4x1_16B_f32 with the A broadcast (cbsz = 4: every one of the sixteen 4 x 4 blocks multiplies by block `abid`'s
+// rows), the instruction of conv3 / conv4 in both fused heads: SeqConvQ below (F = 16) describes the operand layout.
+template <int AB>
+__device__ __forceinline__ f4 mfma4x4_bcast(float a, float b, f4 c) { return __builtin_amdgcn_mfma_f32_4x4x1f32(a, b, c, 4, AB, 0); }
+__device__ __forceinline__ f4 mfma4x4_bcast(float a, float b, f4 c, int ab) {      // ab is a constant after unrolling
+    switch (ab) {
+        case 0: return mfma4x4_bcast<0>(a, b, c);   case 1: return mfma4x4_bcast<1>(a, b, c);
+        case 2: return mfma4x4_bcast<2>(a, b, c);   case 3: return mfma4x4_bcast<3>(a, b, c);
+        case 4: return mfma4x4_bcast<4>(a, b, c);   case 5: return mfma4x4_bcast<5>(a, b, c);
+        case 6: return mfma4x4_bcast<6>(a, b, c);   case 7: return mfma4x4_bcast<7>(a, b, c);
+        case 8: return mfma4x4_bcast<8>(a, b, c);   case 9: return mfma4x4_bcast<9>(a, b, c);
+        case 10: return mfma4x4_bcast<10>(a, b, c); case 11: return mfma4x4_bcast<11>(a, b, c);
+        case 12: return mfma4x4_bcast<12>(a, b, c); case 13: return mfma4x4_bcast<13>(a, b, c);
+        case 14: return mfma4x4_bcast<14>(a, b, c); default: return mfma4x4_bcast<15>(a, b, c);
+    }
+}
+constexpr int quad_nkr(int nq) { return (9 * nq * 4 + 15) / 16; }      // weight registers of a group of four output channels over 9 taps x nq quads
+// The tap loop of a 3 x 3 conv on that instruction, for one lane's pixel and one group of four output channels: over
+// k = (tap NQ + icq) 4 + c it adds w[k] x (channel c of the lane's quad icq at tap `tap`) into acc[k mod 4] -- four accumulators keep
+// dependent MFMAs four instructions apart.  in0[icq * PLANE + off(tap)] is the lane's f4 of quad icq at that tap (fp32 quad-planar
+// map; the next tap's reads are requested before this tap's MFMAs); register k >> 4 holds, in lane l, w[16 (k >> 4) + (l >> 2)][output
+// channel l & 3].
+template <int NQ, int PLANE, typename Off>
+__device__ __forceinline__ void quad_taps(const f4* in0, Off off, const float (&wr)[quad_nkr(NQ)], f4 (&acc)[4]) {
+    f4 bv[2][NQ];
+    auto fetch = [&](int tap, f4 (&bd)[NQ]) {
+        const int o = off(tap);
+#pragma unroll
+        for (int icq = 0; icq < NQ; ++icq) bd[icq] = in0[icq * PLANE + o];
+        __builtin_amdgcn_sched_barrier(0);
+    };
+    fetch(0, bv[0]);
+#pragma unroll
+    for (int tap = 0; tap < 9; ++tap) {
+        if (tap + 1 < 9) fetch(tap + 1, bv[(tap + 1) & 1]);
+#pragma unroll
+        for (int icq = 0; icq < NQ; ++icq)
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+                const int k = (tap * NQ + icq) * 4 + c;
+                acc[c] = mfma4x4_bcast(wr[k >> 4], bv[tap & 1][icq][c], acc[c], k & 15);
+            }
+    }
+}
+
+// conv3 (16 -> 8) / conv4 (8 -> 4) of head_fused3 (F = 8) on the 4 x 4-block MFMA: ONE wave covers the map's 64 pixels, lane = pixel
+// (row lane >> 3, column lane & 7), reads its own pixel's activations from fp32 quad-planar maps f4 map[quad][G::NPIX] and ends with
+// its pixel's four output channels in registers.  A job is one group of four output channels over NQ consecutive channel quads of the
+// input (a slice of K when NQ < CIN / 4: the partial sums are then added by the caller).  Geo<8> stores no halo columns: the taps at
+// dx = +-1 of columns 0 / 7 read the plane's zero tail, the rows above / below its zero border rows (Geo<8>::tap_cols).
+template <int NQ>
+struct FusedConvQ {
+    static constexpr int NKR = quad_nkr(NQ);
+    float wr[NKR];
+    // from the [group][k = tap CIN + ic, padded to 16][4] image (vth::O_W3Q / O_W4Q): group g, input channels ic0 .. ic0 + 4 NQ - 1.
+    // One dword load per register (with 4 NQ = CIN: lane l reads float 64 kr + l of the group's image).
+    template <int CIN>
+    __device__ __forceinline__ void prefetch(const float* __restrict__ wq, int g, int ic0, int lane) {
+#pragma unroll
+        for (int kr = 0; kr < NKR; ++kr) {
+            const int kk = 16 * kr + (lane >> 2), tap = kk / (4 * NQ), i = kk % (4 * NQ);
+            wr[kr] = tap < 9 ? wq[((size_t)g * vth::kpad16(CIN) + tap * CIN + ic0 + i) * 4 + (lane & 3)] : 0.f;
+        }
+    }
+    // in: the first of the job's NQ planes; cb: G::tap_cols(lane >> 4, lane, cb), the lane's pixel
+    __device__ __forceinline__ void taps(const f4* in, const int (&cb)[3], f4 (&acc)[4]) const {
+        quad_taps<NQ, G::NPIX>(in, [&](int tap) { const int dy = tap / 3, dx = tap - 3 * dy; return dy * G::P + (dx == 0 ? cb[0] : (dx == 1 ? cb[1] : cb[2])); }, wr, acc);
+    }
+};
+__device__ __forceinline__ f4 relu4(f4 v) { return f4{fmaxf(v.x, 0.f), fmaxf(v.y, 0.f), fmaxf(v.z, 0.f), fmaxf(v.w, 0.f)}; }
+
+// LDS entries (uint2) of the maps: input 3 x 12 planes, per tower m1 3 x 8 and (per-tower form) m2 3 x 4 planes
 constexpr int IN_E = 3 * (C / 4) * G::NPIX, M1_E = 3 * (W1 / 4) * G::NPIX, M2_E = 3 * 4 * G::NPIX;
 constexpr int TOWERS3_LDS_BYTES = (IN_E + M1_E + M2_E) * 8;
 constexpr int SBUF_BYTES = 3 * 192 * 16;                        // one staged pass of weights (HeadConv3::run_staged): 9 KiB
 static_assert(IN_E * 8 / 3 >= SBUF_BYTES, "a tower's second staging buffer is its third of the input map (dead after conv1)");
-constexpr int FUSED3_LDS_BYTES = (IN_E + 3 * (M1_E + M2_E)) * 8 + 5 * 64 * 4 + 3 * SBUF_BYTES;
+// head_fused3: conv2's output m2 is fp32, 4 quad planes of f4 (7 KiB per tower); conv3's output m3 (2 planes) and conv3's exchange
+// area live in the tower's m1 region, dead once conv2 has read it
+constexpr int M2F_E = 4 * G::NPIX * 2, TOWER_E = M1_E + M2F_E;       // in 8-byte entries
+constexpr int FUSED3_LDS_BYTES = (IN_E + 3 * TOWER_E) * 8 + 5 * 64 * 4 + 3 * SBUF_BYTES;
 static_assert(FUSED3_LDS_BYTES <= 160 * 1024, "LDS");
 
-// The staged passes of conv2, conv3, conv4 of one tower, in order (3 + 2 + 1 passes), two register slots and two LDS buffers.
+// The staged passes of conv2 of one tower, in order, two register slots and two LDS buffers.
 struct WeightPipe {
-    static constexpr int N2 = HeadConv3<W1, 16>::NSP, N3 = HeadConv3<16, 8>::NSP, N4 = HeadConv3<8, 4>::NSP, NP = N2 + N3 + N4;
+    static constexpr int NP = HeadConv3<W1, 16>::NSP;
     const u32x4* tw3;
     u32x4 *buf0, *buf1;
     int tid;
     u32x4 r[2][3];
-    // 16-byte offset (inside the tower's images) and size of global pass j
-    static constexpr int off16(int j) {
-        return j < N2 ? O3_W2 + j * HeadConv3<W1, 16>::SBUF16 : j < N2 + N3 ? O3_W3 + (j - N2) * HeadConv3<16, 8>::SBUF16 : O3_W4 + (j - N2 - N3) * HeadConv3<8, 4>::SBUF16;
-    }
-    static constexpr int n16(int j) {
-        return j < N2 ? HeadConv3<W1, 16>::pass_n16(j) : j < N2 + N3 ? HeadConv3<16, 8>::pass_n16(j - N2) : HeadConv3<8, 4>::pass_n16(j - N2 - N3);
-    }
+    // 16-byte offset (inside the tower's images) and size of pass j
+    static constexpr int off16(int j) { return O3_W2 + j * HeadConv3<W1, 16>::SBUF16; }
+    static constexpr int n16(int j) { return HeadConv3<W1, 16>::pass_n16(j); }
     __device__ __forceinline__ const u32x4* buf(int j) const { return (j & 1) ? buf1 : buf0; }
     __device__ __forceinline__ void fetch(int j) {           // j compile-time at every call site (the pass loops are unrolled)
         if (j >= NP) return;
@@ -345,15 +416,15 @@ __global__ __launch_bounds__(768) void head_fused3_kernel(const float* __restric
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int t = wave >> 2, wv = wave & 3, tid = threadIdx.x - 256 * t;
-    u32x2* m1 = in_map + IN_E + t * (M1_E + M2_E);
-    u32x2* m2 = m1 + M1_E;
-    float* outs = reinterpret_cast<float*>(in_map + IN_E + 3 * (M1_E + M2_E));     // [5][64]
+    u32x2* m1 = in_map + IN_E + t * TOWER_E;
+    f4* const m2 = reinterpret_cast<f4*>(m1 + M1_E);      // conv2's output, fp32, 4 quad planes
+    f4* const m3 = reinterpret_cast<f4*>(m1);             // conv3's output, fp32, 2 quad planes: m1's bytes, dead after conv2
+    f4* const xch = m3 + 2 * G::NPIX;                     // conv3's partial sums on their way to the summing wave (m1's bytes too)
+    float* outs = reinterpret_cast<float*>(in_map + IN_E + 3 * TOWER_E);     // [5][64]
     const float* __restrict__ tw = hw + (size_t)t * vth::TOWER_STRIDE;
     const u32x4* __restrict__ tw3 = hw3 + (size_t)t * TOWER3_STRIDE;
-    HeadConv3<C, W1, 4, 4, 1> c1;          // one pair per register pass: the staged layers' two fetch slots are live across conv1
+    HeadConv3<C, W1, 4, 4, 1> c1;          // one pair per register pass: conv2's two fetch slots are live across conv1
     HeadConv3<W1, 16> c2;
-    HeadConv3<16, 8> c3;
-    HeadConv3<8, 4> c4;
     c1.prefetch(tw3 + O3_W1, wv, lane);        // flies during the map set-up
     static_assert(64 * (C / 4) == 768, "one staged element per thread");
     const f4 fv = ld4(feat + ((size_t)b * 64 + (threadIdx.x & 63)) * C + 4 * (threadIdx.x >> 6));     // requested before the LDS is cleared
@@ -362,12 +433,21 @@ __global__ __launch_bounds__(768) void head_fused3_kernel(const float* __restric
     // zero what is read without ever being written: per plane the border rows (entries [0, P) and [(F + 1) P, (F + 2) P)) and the zero tail
     // behind them -- 48 of a plane's 112 entries; the interiors are written (staging, layer epilogues) before they are read.  No barrier
     // between this and the staging: they touch different entries.
+    // The piece planes (8-byte entries) of the input map and of the three m1; then the fp32 planes (16-byte entries) of the three m2.
+    // m3's borders are zeroed where m1 dies (below).
+    constexpr int ZQ = G::NPIX - F * G::P;      // entries to zero per plane; the first G::P of them are the top row
     {
-        constexpr int NPL = (IN_E + 3 * (M1_E + M2_E)) / G::NPIX, ZU = (G::NPIX - F * G::P) / 2, TOPU = G::P / 2;     // planes; 16-byte units to zero per plane; of them the top row
+        constexpr int NPL_IN = IN_E / G::NPIX, NPL_M1 = M1_E / G::NPIX, NPL = NPL_IN + 3 * NPL_M1, ZU = ZQ / 2, TOPU = G::P / 2;     // 16-byte units
         static_assert(G::P % 2 == 0 && G::NPIX % 2 == 0 && ((F + 1) * G::P) % 2 == 0, "16-byte units");
         for (int j = threadIdx.x; j < NPL * ZU; j += 768) {
-            const int pl = j / ZU, u = j - pl * ZU;
-            reinterpret_cast<u32x4*>(in_map + pl * G::NPIX)[u < TOPU ? u : (F + 1) * G::P / 2 + (u - TOPU)] = u32x4{0, 0, 0, 0};
+            const int pl = j / ZU, u = j - pl * ZU, pm = pl - NPL_IN;
+            u32x2* plane = pm < 0 ? in_map + pl * G::NPIX : in_map + IN_E + (pm / NPL_M1) * TOWER_E + (pm % NPL_M1) * G::NPIX;
+            reinterpret_cast<u32x4*>(plane)[u < TOPU ? u : (F + 1) * G::P / 2 + (u - TOPU)] = u32x4{0, 0, 0, 0};
+        }
+        static_assert(3 * 4 * ZQ <= 768, "one thread per zeroed entry of the fp32 planes");
+        if (threadIdx.x < 3 * 4 * ZQ) {
+            const int pl = threadIdx.x / ZQ, u = threadIdx.x - pl * ZQ;       // plane = (tower pl >> 2, quad pl & 3)
+            reinterpret_cast<f4*>(in_map + IN_E + (pl >> 2) * TOWER_E + M1_E)[(pl & 3) * G::NPIX + (u < G::P ? u : F * G::P + u)] = splat4(0.f);
         }
     }
     {
@@ -378,8 +458,8 @@ __global__ __launch_bounds__(768) void head_fused3_kernel(const float* __restric
         in_map[e] = h; in_map[(C / 4) * G::NPIX + e] = m; in_map[2 * (C / 4) * G::NPIX + e] = l;
     }
     __syncthreads();
-    // conv2-4: weights through the tower's two LDS staging buffers (run_staged): buffer 0 behind the output rows, buffer 1 the
-    // tower's third of the input map once conv1 is done with it.  conv2's first pass is fetched before conv1 and parked after it.
+    // conv2: weights through the tower's two LDS staging buffers (run_staged): buffer 0 behind the output rows, buffer 1 the
+    // tower's third of the input map once conv1 is done with it.  Its first pass is fetched before conv1 and parked after it.
     u32x4* const sbuf0 = reinterpret_cast<u32x4*>(outs + 5 * 64) + t * (SBUF_BYTES / 16);
     u32x4* const sbuf1 = reinterpret_cast<u32x4*>(in_map) + t * (IN_E / 6);          // IN_E / 3 entries of 8 bytes = IN_E / 6 x 16 bytes
     WeightPipe pipe{tw3, sbuf0, sbuf1, tid, {}};
@@ -388,12 +468,38 @@ __global__ __launch_bounds__(768) void head_fused3_kernel(const float* __restric
     if (!(VT_H3_SKIP & 1)) c1.run(in_map, m1, tw3 + O3_W1, tw + vth::O_B1, wv, lane);
     pipe.park(0);
     __syncthreads();
+    // conv3 / conv4 on the 4 x 4-block fp32 MFMA (FusedConvQ): lane = pixel, weights in registers, requested a layer early
+    int cb[3];
+    G::tap_cols(lane >> 4, lane, cb);
+    const int centre = cb[1] + G::P;            // = G::interior(lane >> 3, lane & 7)
+    // conv3 = 2 output groups x 2 halves of K (input quads 0-1 / 2-3) over the tower's four waves, 72 MFMAs each; the upper half's
+    // partial sum goes through xch to the lower half's wave, which adds it to its own (bias included) -- a fixed order -- and applies
+    // the ReLU.  (Measured against K-quarters with both groups per wave and against two whole-K jobs per tower: NOTES.)
+    const int g3 = wv & 1, h3 = wv >> 1;
+    FusedConvQ<2> c3;
+    c3.prefetch<16>(tw + vth::O_W3Q, g3, 8 * h3, lane);
     c2.run_staged(m1, m2, tw + vth::O_B2, wv, lane, 0, pipe);
-    c3.run_staged(m2, m1, tw + vth::O_B3, wv, lane, WeightPipe::N2, pipe);
-    c4.run_staged(m1, m2, tw + vth::O_B4, wv, lane, WeightPipe::N2 + WeightPipe::N3, pipe);
-    if (tid < F * F) {
-        const int pix = tid, e = G::interior(pix >> 3, pix & 7);
-        const f4 v = join3(m2[e], m2[G::NPIX + e], m2[2 * G::NPIX + e]);
+    FusedConvQ<2> c4;                        // one job per tower, on wave slot t: three different SIMDs
+    if (wv == t) c4.prefetch<8>(tw + vth::O_W4Q, 0, 0, lane);
+    if (tid < 2 * ZQ) {                         // m3's border rows and zero tail: these bytes held conv1's pieces until conv2's last barrier
+        const int pl = tid / ZQ, u = tid - pl * ZQ;
+        m3[pl * G::NPIX + (u < G::P ? u : F * G::P + u)] = splat4(0.f);
+    }
+    {
+        f4 acc[4] = {h3 == 0 ? ld4(tw + vth::O_B3 + 4 * g3) : splat4(0.f), splat4(0.f), splat4(0.f), splat4(0.f)};
+        if (!(VT_H3_SKIP & 2)) c3.taps(m2 + 2 * h3 * G::NPIX, cb, acc);
+        const f4 v = (acc[0] + acc[1]) + (acc[2] + acc[3]);
+        if (h3 == 1) xch[g3 * 64 + lane] = v;
+        __syncthreads();
+        if (h3 == 0) m3[g3 * G::NPIX + centre] = relu4(v + xch[g3 * 64 + lane]);
+    }
+    __syncthreads();
+    // conv4 and the 1 x 1 conv + activation in one go: the lane ends conv4 with its pixel's four channels, all the 1 x 1 stage reads
+    if (wv == t) {
+        f4 acc[4] = {ld4(tw + vth::O_B4), splat4(0.f), splat4(0.f), splat4(0.f)};
+        if (!(VT_H3_SKIP & 2)) c4.taps(m3, cb, acc);
+        const f4 v = relu4((acc[0] + acc[1]) + (acc[2] + acc[3]));
+        const int pix = lane;
         const int nout = (t == 0) ? 1 : 2;
         for (int o = 0; o < nout; ++o) {
             const f4 w5 = ld4(tw + vth::O_W5 + 4 * o);
@@ -568,20 +674,7 @@ __device__ __forceinline__ int seq_halo_pix(int k) {
 // output channel l & 3 at k = 16 kg + (l >> 2), so a layer's whole [k][oc] image is 9 (conv3) / 5 (conv4) registers, loaded
 // a layer early by one coalesced dword load each.  Jobs = pixel groups (4) x output-channel groups: conv3 keeps all eight waves
 // busy, conv4 four (one per SIMD).  Four accumulators (k mod 4) keep dependent MFMAs 35 cycles apart (14.6 needed).
-template <int AB>
-__device__ __forceinline__ f4 mfma4x4_bcast(float a, float b, f4 c) { return __builtin_amdgcn_mfma_f32_4x4x1f32(a, b, c, 4, AB, 0); }
-__device__ __forceinline__ f4 mfma4x4_bcast(float a, float b, f4 c, int ab) {      // ab is a constant after unrolling
-    switch (ab) {
-        case 0: return mfma4x4_bcast<0>(a, b, c);   case 1: return mfma4x4_bcast<1>(a, b, c);
-        case 2: return mfma4x4_bcast<2>(a, b, c);   case 3: return mfma4x4_bcast<3>(a, b, c);
-        case 4: return mfma4x4_bcast<4>(a, b, c);   case 5: return mfma4x4_bcast<5>(a, b, c);
-        case 6: return mfma4x4_bcast<6>(a, b, c);   case 7: return mfma4x4_bcast<7>(a, b, c);
-        case 8: return mfma4x4_bcast<8>(a, b, c);   case 9: return mfma4x4_bcast<9>(a, b, c);
-        case 10: return mfma4x4_bcast<10>(a, b, c); case 11: return mfma4x4_bcast<11>(a, b, c);
-        case 12: return mfma4x4_bcast<12>(a, b, c); case 13: return mfma4x4_bcast<13>(a, b, c);
-        case 14: return mfma4x4_bcast<14>(a, b, c); default: return mfma4x4_bcast<15>(a, b, c);
-    }
-}
+// (the instruction wrapper and the tap loop, quad_taps, stand above head_fused3_kernel, whose conv3 / conv4 share them)
 template <int CIN, int COUT, int NW>
 struct SeqConvQ {
     static constexpr int NQ = CIN / 4, NG = COUT / 4, NPG = 16 * 16 / 64, JOBS = NG * NPG, KP = vth::kpad16(CIN), NKR = KP / 16;
@@ -604,25 +697,7 @@ struct SeqConvQ {
         const int p = pixel_of(pg, lane), y = p >> 4, x = p & 15;
         const f4* in0 = in_map + y * G16::P + x;                                 // tap (0, 0) of this lane's pixel
         f4 acc[4] = {ld4(bias + 4 * g), splat4(0.f), splat4(0.f), splat4(0.f)};
-        f4 bv[2][NQ];
-        auto fetch = [&](int tap, f4 (&bd)[NQ]) {
-            const int dy = tap / 3, dx = tap - 3 * dy;
-#pragma unroll
-            for (int icq = 0; icq < NQ; ++icq) bd[icq] = in0[icq * G16::NPIX + dy * G16::P + dx];
-            __builtin_amdgcn_sched_barrier(0);
-        };
-        fetch(0, bv[0]);
-#pragma unroll
-        for (int tap = 0; tap < 9; ++tap) {
-            if (tap + 1 < 9) fetch(tap + 1, bv[(tap + 1) & 1]);
-#pragma unroll
-            for (int icq = 0; icq < NQ; ++icq)
-#pragma unroll
-                for (int c = 0; c < 4; ++c) {
-                    const int k = (tap * NQ + icq) * 4 + c;
-                    acc[c] = mfma4x4_bcast(wr[k >> 4], bv[tap & 1][icq][c], acc[c], k & 15);
-                }
-        }
+        quad_taps<NQ, G16::NPIX>(in0, [](int tap) { const int dy = tap / 3, dx = tap - 3 * dy; return dy * G16::P + dx; }, wr, acc);
         f4 v = (acc[0] + acc[1]) + (acc[2] + acc[3]);
         v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f);
         return v;
