@@ -181,6 +181,29 @@ int vt_crop_u8(vt_model* m, const uint8_t* frames_dev, int32_t H, int32_t W, con
  * W' = W / (255 std_c), b' = b - sum W mean_c / std_c + 128 sum W' from the unrounded fp64 W' (uncentred, the rounding of W' multiplies
  * the patch's common mode and the tokens leave their 3.2e-3 bound; VB_U8_CENTER=0 restores that form to show it). */
 int vt_set_normalization(vt_model* m, const float* mean3, const float* std3);
+/* OSTrack candidate elimination (MODEL.BACKBONE.TYPE vit_base_patch16_224_ce: lib/models/ostrack/vit_ce.py:151-186,
+ * lib/models/layers/attn_blocks.py:20-85) on a ViT-Base model, by KEY MASKING: after the attention of block loc[k] the search tokens are
+ * ranked by the attention they receive from the selected template rows (mean over heads and rows of the softmax weights) and the
+ * stage keeps ceil(keep_ratio[k] * kept so far) of them, the product in double as math.ceil(keep_ratio * lens_s) takes it (0.7, 0.7, 0.7:
+ * 180 / 126 / 89 of 256, 404 / 283 / 199 of 576).  No token is moved: every matrix keeps its B x L rows, later attentions treat the removed
+ * tokens as absent keys, and the search rows of removed tokens are exact zeros after the final norm (feat_dev of vt_blocks, the head's
+ * input), as in the reference.  The kept tokens' values are the reference's; there is no speed-up.
+ *   n, loc, keep_ratio: 1 <= n <= depth stages, loc strictly increasing in [0, depth), 0 < keep_ratio <= 1 (host arrays)
+ *   template_rows: Lz host bytes, non-zero = the template row takes part in the score (CE_TEMPLATE_RANGE: lib/utils/ce_utils.py:15-49), at
+ *       least one set; NULL = all rows.  One selection per model, not per frame.
+ * A stage whose count equals the previous stage's is a no-op; a configuration of no-ops only leaves the model a plain one, bit for bit.
+ * Ties in the ranking go to the lower token index (the reference's torch.sort leaves them unspecified).
+ * From block loc[0] on attention runs as qk GEMM + v GEMM + the key-streaming kernel at both geometries (the score reads the q | k rows).
+ * Call it before or after vt_load_weights, before any graph is captured: VT_ERR_STATE afterwards, as vt_set_normalization.  Anything but a
+ * ViT-Base model, or arguments outside the above: VT_ERR_ARG.  Synchronises the device and allocates; not capturable.
+ * With nblocks < depth vt_blocks runs the stages inside [0, nblocks) and the final norm zeroes what they removed.  resid_dev rows of
+ * removed tokens are unspecified (finite in practice: they go on being computed and are never read by a kept row). */
+int vt_set_candidate_elimination(vt_model* m, int32_t n, const int32_t* loc, const double* keep_ratio, const uint8_t* template_rows);
+/* What the last vt_forward* / vt_track_step* / vt_blocks / graph launch of B frames left: removed_stage_dev (B,Lx) bytes, 0 = kept to the
+ * end, k = removed at stage k (1-based); scores_dev (n,B,Lx) fp32, the ranking score of each stage, NaN for tokens removed earlier and for
+ * stages that did not run (no-ops; stages at or past nblocks keep what an earlier call left).  Either pointer may be NULL.  Capturable.
+ * VT_ERR_STATE before vt_set_candidate_elimination. */
+int vt_ce_result(vt_model* m, int32_t B, void* stream, uint8_t* removed_stage_dev, float* scores_dev);
 /* Preprocessor.process + OstrackDist.forward on a uint8 search patch (lib/test/tracker/data_utils.py:11-17 +
  * lib/models/vit_dist/vit_dist.py:77-100): x_patch_dev (B,S,S,3) uint8 as vt_crop_u8 writes it; z_dev (B,3,Tz,Tz) fp32 as in
  * vt_forward, or NULL after vt_set_template.  Results agree with vt_forward on the normalised fp32 crop to fp32 rounding (the

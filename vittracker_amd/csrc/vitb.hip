@@ -1,6 +1,7 @@
 // vitb.hip -- host side of the plain-ViT OSTrack path (ViT-Base, BASELINE config 4, and ViT-Large): weight packing (bf16, BatchNorm folded, conv
 // weights as [cout][tap][cin], attention scale folded into W_q), workspace, launch sequence.  Kernels: vb_gemm.h, vb_misc.h and the
-// three attention kernels vb_attn.h, vb_qkvattn.h, vb_attn_stream.h (the 384 geometry's), whose shared arithmetic lives in vb_attn.h.
+// three attention kernels vb_attn.h, vb_qkvattn.h, vb_attn_stream.h (the 384 geometry's), whose shared arithmetic lives in vb_attn.h;
+// vb_ce.h: OSTrack candidate elimination by key masking (the stages' score / select kernels; vb::blocks routes them).
 // Reached through the same C ABI as the vit_48 path (vt_create with channels = 768, or the ViT-Large tuple at channels = 1024).  The two
 // model points differ in width, head count and hidden width alone (VbModel::C / HEADS / HID); the kernels take them at run time except
 // the three that compile the width in (dispatch_width below).
@@ -16,6 +17,7 @@
 
 #include "vb_attn.h"
 #include "vb_attn_stream.h"
+#include "vb_ce.h"
 #include "vb_gemm.h"
 #include "vb_misc.h"
 #include "vb_qkvattn.h"
@@ -104,6 +106,20 @@ struct VbModel {
     Buf<bf16> zop;           // template cache: the templates' operand rows [max_batch * LZ][PATCH_K]
     bool center = true;      // VB_LN_CENTER
     Buf<vbg::f2> stats;
+    // candidate elimination by key masking (vb_ce.h; vb::set_candidate_elimination).  ce_loc / ce_keep: per stage its block and its count of
+    // kept search tokens (a count equal to the previous one: the stage is a no-op and runs nothing); ce_first: the block of the first stage
+    // that removes something, -1 = a plain model.  Device buffers, all indexed by absolute frame: ce_bits [stage][max_batch][ceil(L / 32)] the
+    // key bitmap each stage leaves, ce_removed [max_batch][LX], ce_scores [stage][max_batch][LX], ce_part [max_batch][HEADS][LX] the
+    // per-head sums between the two kernels of a stage, ce_rows the selected template rows
+    std::vector<int> ce_loc, ce_keep;
+    int ce_first = -1, ce_nrows = 0;
+    bool ce_set = false;
+    bool ce_plain = false;          // VB_CE_SCORE_PLAIN=1: the plain score loop for ALL too (the MFMA form's yardstick; tests)
+    Buf<uint32_t> ce_bits;
+    Buf<uint8_t> ce_removed;
+    Buf<float> ce_scores, ce_part;
+    Buf<int32_t> ce_rows;
+    int ce_words() const { return (L + 31) / 32; }
 };
 
 namespace {
@@ -371,6 +387,7 @@ int create(const vt_config* cfg, VbModel** out, std::string* err) {
     m->fused_qkv = env_int("VB_FUSED_QKV", 1) != 0;
     m->u8_centre = env_int("VB_U8_CENTER", 1) != 0 ? 128.f : 0.f;
     m->attn_stream = env_int("VB_ATTN_STREAM", 0) != 0;
+    m->ce_plain = env_int("VB_CE_SCORE_PLAIN", 0) != 0;
     const size_t B = (size_t)cfg->max_batch, M = B * L, P2 = (size_t)(F + 2) * (F + 2);
     hipError_t e = hipSuccess;
     // the streaming attention kernel's last key chunk reads up to PAD_TOKENS rows (qk) / elements (vt) past a frame's last token: the
@@ -405,6 +422,8 @@ int create(const vt_config* cfg, VbModel** out, std::string* err) {
         {kernel_ptr(vba::attn_kernel<L256, HD>), vba::Geo<L256, HD>::LDS_BYTES},
         {kernel_ptr(vbs::attn_stream_kernel<L256>), vbs::LDS_BYTES},
         {kernel_ptr(vbs::attn_stream_kernel<L384>), vbs::LDS_BYTES},
+        {kernel_ptr(vbs::attn_stream_masked_kernel<L256>), vbs::LDS_BYTES},
+        {kernel_ptr(vbs::attn_stream_masked_kernel<L384>), vbs::LDS_BYTES},
         {kernel_ptr(vbq::qkv_attn_kernel), vbq::LDS_BYTES},
         {kernel_ptr(vbq::qkv_attn_wide_kernel<C_LARGE>), vbq::LDS_BYTES}};
     for (const auto& k : dynamic_lds)
@@ -418,6 +437,75 @@ int create(const vt_config* cfg, VbModel** out, std::string* err) {
 }
 
 void destroy(VbModel* m) { delete m; }      // every Buf frees its own
+
+int check_ce_args(int n, const int32_t* loc, const double* keep_ratio, std::string* err) {
+    const Err E{err};
+    if (!loc || !keep_ratio) return E.fail(VT_ERR_ARG, "candidate elimination: null loc / keep_ratio");
+    if (n < 1) return E.fail(VT_ERR_ARG, "candidate elimination: at least one stage (n >= 1), got n=" + std::to_string(n));
+    for (int k = 0; k < n; ++k) {
+        if (loc[k] < 0 || (k > 0 && loc[k] <= loc[k - 1]))
+            return E.fail(VT_ERR_ARG, "candidate elimination: loc must be strictly increasing block indices >= 0 (stage " + std::to_string(k) + ": " +
+                                          std::to_string(loc[k]) + ")");
+        if (!(keep_ratio[k] > 0.0 && keep_ratio[k] <= 1.0))
+            return E.fail(VT_ERR_ARG, "candidate elimination: keep_ratio must lie in (0, 1] (stage " + std::to_string(k) + ": " + std::to_string(keep_ratio[k]) + ")");
+    }
+    return VT_OK;
+}
+
+int set_candidate_elimination(VbModel* m, int n, const int32_t* loc, const double* keep_ratio, const uint8_t* template_rows, std::string* err) {
+    const Err E{err};
+    if (int rc = check_ce_args(n, loc, keep_ratio, err)) return rc;
+    if (m->C != C_BASE) return E.fail(VT_ERR_ARG, "candidate elimination is implemented for ViT-Base models (channels 768) only");
+    if (n > m->depth || loc[n - 1] >= m->depth)
+        return E.fail(VT_ERR_ARG, "candidate elimination: " + std::to_string(n) + " stages up to block " + std::to_string(loc[n - 1]) + " do not fit depth " +
+                                      std::to_string(m->depth) + " (1 <= n <= depth, loc in [0, depth))");
+    std::vector<int32_t> rows;
+    for (int r = 0; r < m->LZ; ++r)
+        if (!template_rows || template_rows[r]) rows.push_back(r);
+    if (rows.empty()) return E.fail(VT_ERR_ARG, "candidate elimination: template_rows selects no template row");
+    std::vector<int> keep(n);
+    int prev = m->LX, first = -1;
+    for (int k = 0; k < n; ++k) {       // math.ceil(keep_ratio * lens_s) of attn_blocks.py:39, the product in double
+        keep[k] = std::min(prev, std::max(1, (int)std::ceil(keep_ratio[k] * (double)prev)));
+        if (keep[k] < prev && first < 0) first = loc[k];
+        prev = keep[k];
+    }
+    VB_HIP(hipDeviceSynchronize());      // no step may be reading the buffers that are about to be replaced
+    // an earlier configuration is gone from here on: if an allocation below fails the model is a plain one, never old stages on new buffers
+    m->ce_set = false;
+    m->ce_first = -1;
+    m->ce_loc.clear();
+    m->ce_keep.clear();
+    const size_t B = (size_t)m->maxB, W = (size_t)m->ce_words(), LX = (size_t)m->LX;
+    auto fresh = [](auto& buf, size_t count, int byte) {
+        buf.release();
+        hipError_t e = buf.alloc(count);
+        return e != hipSuccess ? e : hipMemset(buf.p, byte, count * sizeof(*buf.p));
+    };
+    VB_HIP(fresh(m->ce_bits, (size_t)n * B * W, 0));
+    VB_HIP(fresh(m->ce_removed, B * LX, 0));
+    VB_HIP(fresh(m->ce_scores, (size_t)n * B * LX, 0xff));      // NaN: what a stage that never runs (a no-op) reports
+    VB_HIP(fresh(m->ce_part, B * (size_t)m->HEADS * LX, 0));
+    if (int rc = upload(m->ce_rows, rows.data(), rows.size(), E)) return rc;
+    m->ce_loc.assign(loc, loc + n);
+    m->ce_keep = keep;
+    m->ce_nrows = (int)rows.size();
+    m->ce_first = first;
+    m->ce_set = true;
+    return VT_OK;
+}
+
+int ce_result(VbModel* m, int B, hipStream_t st, uint8_t* removed_stage, float* scores, std::string* err) {
+    const Err E{err};
+    if (!m->ce_set) return E.fail(VT_ERR_STATE, "vt_set_candidate_elimination has not been called");
+    if (B < 1 || B > m->maxB) return E.fail(VT_ERR_STATE, "batch " + std::to_string(B) + " outside [1, max_batch=" + std::to_string(m->maxB) + "]");
+    const size_t LX = (size_t)m->LX;
+    if (removed_stage) VB_HIP(hipMemcpyAsync(removed_stage, m->ce_removed.p, (size_t)B * LX, hipMemcpyDeviceToDevice, st));
+    if (scores)
+        VB_HIP(hipMemcpy2DAsync(scores, (size_t)B * LX * 4, m->ce_scores.p, (size_t)m->maxB * LX * 4, (size_t)B * LX * 4, m->ce_loc.size(),
+                                hipMemcpyDeviceToDevice, st));
+    return VT_OK;
+}
 
 // Key layout: the reference's OSTrack ckpt['net'] -- backbone.{patch_embed.proj, pos_embed_z, pos_embed_x, blocks.N.*, norm},
 // box_head.* (lib/models/ostrack/vit.py:94-139, base_backbone.py:83-84, lib/models/layers/head.py:98-128).
@@ -616,10 +704,13 @@ int stem_rows(VbModel* m, ZSrc zsrc, const float* z, const float* x, const unsig
 //   fused (the default at 320 tokens)       vbq::qkv_attn_kernel: projection + attention of a (frame, head) in one workgroup, q / k / v^T never leave the CU
 //   otherwise qk GEMM + v GEMM (V^T) and    vbs::attn_stream_kernel<720> (the 384 geometry), vbs::attn_stream_kernel<320> (VB_ATTN_STREAM) or
 //                                           vba::attn_kernel<320, 64>
-static int run_attention(const VbModel* m, const SliceView& v, const BlockW& b, const float* rstd, int B, hipStream_t st, const Err& E) {
+// ce: a block from the first candidate-elimination stage on -- always qk GEMM + v GEMM + the streaming kernel at either geometry (the stage's
+// score reads the q | k rows the qk GEMM leaves in v.qk); keys: the slice's key bitmap (vb_ce.h), nullptr = every key (the first stage's block)
+static int run_attention(const VbModel* m, const SliceView& v, const BlockW& b, const float* rstd, int B, hipStream_t st, const Err& E,
+                         bool ce = false, const uint32_t* keys = nullptr) {
     int rc;
     const int C = m->C, HEADS = m->HEADS;
-    if (m->fused_qkv && !m->g384) {
+    if (m->fused_qkv && !m->g384 && !ce) {
         vbq::Args qa{};
         qa.X = v.xn; qa.W = b.wqkv.p; qa.bias = b.bqkv.p; qa.rstd = rstd; qa.out = v.ao; qa.B = B; qa.heads = HEADS;
         // heads walked together: 6 of 12 measured best at width 768 (vb_qkvattn.h); 16 heads of width 1024 take 4, the divisor whose group of
@@ -642,9 +733,13 @@ static int run_attention(const VbModel* m, const SliceView& v, const BlockW& b, 
     w.X = v.xn; w.W = b.wqkv.p + (size_t)2 * C * C; w.bias = b.bqkv.p + 2 * C; w.vt = v.vt;   // v: rows 2C .. 3C, stored transposed
     w.M = M; w.N = C; w.K = C; w.L = L; w.rstd = rstd;
     if ((rc = launch_gemm<256, 256, 2, 4, vbg::A_PLAIN, vbg::EPI_VT>(w, 1, st, E, v.cus))) return rc;
-    if (m->g384)
+    if (keys && m->g384)
+        hipLaunchKernelGGL((vbs::attn_stream_masked_kernel<L384>), dim3(B * HEADS * vbs::splits<L384>()), dim3(256), vbs::LDS_BYTES, st, v.qk, v.vt, v.ao, HEADS, keys);
+    else if (keys)
+        hipLaunchKernelGGL((vbs::attn_stream_masked_kernel<L256>), dim3(B * HEADS * vbs::splits<L256>()), dim3(256), vbs::LDS_BYTES, st, v.qk, v.vt, v.ao, HEADS, keys);
+    else if (m->g384)
         hipLaunchKernelGGL((vbs::attn_stream_kernel<L384>), dim3(B * HEADS * vbs::splits<L384>()), dim3(256), vbs::LDS_BYTES, st, v.qk, v.vt, v.ao, HEADS);
-    else if (m->attn_stream)
+    else if (m->attn_stream || ce)
         hipLaunchKernelGGL((vbs::attn_stream_kernel<L256>), dim3(B * HEADS * vbs::splits<L256>()), dim3(256), vbs::LDS_BYTES, st, v.qk, v.vt, v.ao, HEADS);
     else
         hipLaunchKernelGGL((vba::attn_kernel<L256, HD>), dim3(B * HEADS), dim3(256), (vba::Geo<L256, HD>::LDS_BYTES), st, v.qk, v.vt, v.ao, HEADS);
@@ -675,10 +770,39 @@ int blocks(VbModel* m, const float* tokens_in, int B, int nblocks, hipStream_t s
         if (int r = launch_gemm<256, 256, 2, 4, vbg::A_PLAIN, vbg::EPI_RESID>(p, 1, st, E, v.cus)) return r;
         return feeds_ln ? run_finalize(m, v, M, st, E) : VT_OK;
     };
+    // candidate elimination (vb_ce.h): from the first stage's block on the attention is the streaming kernel, under the key bitmap the
+    // stages so far have left for this slice's frames; a stage runs behind its block's attention: score, then select
+    const bool ce = m->ce_first >= 0;
+    const size_t ceW = (size_t)m->ce_words(), LX = (size_t)m->LX;
+    const uint32_t* keys = nullptr;
+    int stage = 0, kept = m->LX;
+    auto ce_stage = [&](int k) {
+        uint32_t* next = m->ce_bits.p + ((size_t)k * m->maxB + v.f0) * ceW;
+        float* part = m->ce_part.p + v.f0 * m->HEADS * LX;
+        if (m->ce_nrows == m->LZ && !m->ce_plain) {      // every template row (CE_TEMPLATE_RANGE ALL): whole query tiles on the MFMA
+            if (m->g384) hipLaunchKernelGGL(vbc::ce_score_all_kernel<L384>, dim3(B * m->HEADS), dim3(256), 0, st, v.qk, keys, part, m->HEADS, m->LZ);
+            else hipLaunchKernelGGL(vbc::ce_score_all_kernel<L256>, dim3(B * m->HEADS), dim3(256), 0, st, v.qk, keys, part, m->HEADS, m->LZ);
+        } else if (m->g384)
+            hipLaunchKernelGGL(vbc::ce_score_kernel<L384>, dim3(B * m->HEADS), dim3(256), 0, st, v.qk, keys, m->ce_rows.p, m->ce_nrows, part, m->HEADS, m->LZ);
+        else
+            hipLaunchKernelGGL(vbc::ce_score_kernel<L256>, dim3(B * m->HEADS), dim3(256), 0, st, v.qk, keys, m->ce_rows.p, m->ce_nrows, part, m->HEADS, m->LZ);
+        hipLaunchKernelGGL(vbc::ce_select_kernel, dim3(B), dim3(256), 0, st, part, keys, next, m->ce_removed.p + v.f0 * LX,
+                           m->ce_scores.p + ((size_t)k * m->maxB + v.f0) * LX, m->HEADS, 1.0f / (float)(m->HEADS * m->ce_nrows), k + 1, m->ce_keep[k],
+                           m->L, m->LZ);
+        keys = next;
+    };
     for (int i = 0; i < nblocks; ++i) {
         const BlockW& b = m->blk[i];
         if (!fold && (rc = run_layernorm(m, v.resid, b.ln1g.p, b.ln1b.p, B, st, v.xn, nullptr, nullptr, E))) return rc;
-        if ((rc = run_attention(m, v, b, rstd, B, st, E))) return rc;
+        if ((rc = run_attention(m, v, b, rstd, B, st, E, ce && i >= m->ce_first, keys))) return rc;
+        if (ce && stage < (int)m->ce_loc.size() && m->ce_loc[stage] == i) {
+            if (m->ce_keep[stage] < kept) {      // a stage that keeps every token it meets is a no-op, as attn_blocks.py:40-41 returns early
+                ce_stage(stage);
+                VB_HIP(hipGetLastError());
+                kept = m->ce_keep[stage];
+            }
+            ++stage;
+        }
         if ((rc = resid_gemm(v.ao, b.wproj.p, b.bproj.p, C, fold))) return rc;
         if (!fold && (rc = run_layernorm(m, v.resid, b.ln2g.p, b.ln2b.p, B, st, v.xn, nullptr, nullptr, E))) return rc;
         vbg::Args f1{};
@@ -688,7 +812,13 @@ int blocks(VbModel* m, const float* tokens_in, int B, int nblocks, hipStream_t s
         if ((rc = resid_gemm(v.hid, b.w2.p, b.b2.p, HID, fold && i + 1 < nblocks))) return rc;      // the final norm reads the f32 stream itself
     }
     if (resid_out) VB_HIP(hipMemcpyAsync(resid_out, v.resid, (size_t)M * C * 4, hipMemcpyDeviceToDevice, st));
-    return run_layernorm(m, v.resid, m->ng.p, m->nb.p, B, st, nullptr, v.map[0], feat_out, E);
+    if ((rc = run_layernorm(m, v.resid, m->ng.p, m->nb.p, B, st, nullptr, v.map[0], feat_out, E))) return rc;
+    if (keys) {      // the removed tokens' rows of the final norm are zeros (vit_ce.py:170-181)
+        hipLaunchKernelGGL(vbc::ce_zero_rows_kernel, dim3(grid256((size_t)B * LX * (C / 4))), dim3(256), 0, st, keys, v.map[0], feat_out, B, m->L, m->LZ, m->F, C);
+        VB_HIP(hipGetLastError());
+    } else if (m->ce_set)      // no stage ran in [0, nblocks) (or every stage is a no-op): nothing is removed
+        VB_HIP(hipMemsetAsync(m->ce_removed.p + v.f0 * LX, 0, (size_t)B * LX, st));
+    return VT_OK;
 }
 
 int head(VbModel* m, const float* feat_in, int B, hipStream_t st, float* score, float* size, float* offset, std::string* err,

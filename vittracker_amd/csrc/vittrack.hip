@@ -1555,6 +1555,25 @@ int vt_set_normalization(vt_model* m, const float* mean3, const float* std3) {
     return fold_w1u(m, mean3, std3);
 }
 
+int vt_set_candidate_elimination(vt_model* m, int32_t n, const int32_t* loc, const double* keep_ratio, const uint8_t* template_rows) {
+    std::string err;
+    if (int rc = vb::check_ce_args(n, loc, keep_ratio, &err)) return fail(rc, err);      // what needs no model comes first
+    if (!m) return fail(VT_ERR_ARG, "null model");
+    if (!m->vb) return fail(VT_ERR_ARG, "candidate elimination is implemented for ViT-Base models (channels 768) only");
+    if (m->graphs_captured > 0)
+        return fail(VT_ERR_STATE, "captured graphs hold the routes and stage buffers of their capture: set the candidate elimination before capturing");
+    if (int rc = vb::set_candidate_elimination(m->vb, n, loc, keep_ratio, template_rows, &err)) return fail(rc, err);
+    return VT_OK;
+}
+
+int vt_ce_result(vt_model* m, int32_t B, void* stream, uint8_t* removed_stage_dev, float* scores_dev) {
+    if (!m) return fail(VT_ERR_ARG, "null model");
+    if (!m->vb) return fail(VT_ERR_ARG, "candidate elimination is implemented for ViT-Base models (channels 768) only");
+    std::string err;
+    if (int rc = vb::ce_result(m->vb, B, static_cast<hipStream_t>(stream), removed_stage_dev, scores_dev, &err)) return fail(rc, err);
+    return VT_OK;
+}
+
 int vt_patch_u8_supported(const vt_model* m, int32_t B) {
     if (!m) return 0;
     return stem_takes_u8(m, B) ? 1 : 0;

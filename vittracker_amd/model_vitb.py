@@ -1,15 +1,21 @@
 """Model-level drop-in for the plain-ViT OSTrack path (ViT-Base, BASELINE config 4, and ViT-Large): ``build_ostrack(cfg, training=False) -> OSTrack``
 with the surface the reference's callers use (``lib/models/ostrack/ostrack.py:22-151,164-286``):
 
-    net = build_ostrack(cfg, training=False)            # MODEL.BACKBONE.TYPE = vit_base_patch16_224 | vit_large_patch16_224, HEAD = CENTER / 256
+    net = build_ostrack(cfg, training=False)            # MODEL.BACKBONE.TYPE = vit_base_patch16_224[_ce] | vit_large_patch16_224, HEAD = CENTER / 256
     net.load_state_dict(ckpt['net'], strict=False)      # keys backbone.* / box_head.*
     net = net.cuda(); net.eval()
     out = net.forward(template=z, search=x)             # {'pred_boxes','score_map','size_map','offset_map'}
     net.box_head.cal_bbox(score, size, offset)
 
 Arithmetic runs in ``libvittrack_hip.so`` (bf16 MFMA contractions, f32 accumulate / LayerNorm / softmax / residual stream);
-no CPU execution path.  Only what the CENTER-head inference graph needs is accepted: the candidate-elimination / prompt /
-draw variants of the reference (``vit_ce.py``, ``MODEL.PROCESS.*``) raise NotImplementedError."""
+no CPU execution path.
+
+The candidate-elimination backbone ``vit_base_patch16_224_ce`` (``lib/models/ostrack/vit_ce.py``; every published OSTrack checkpoint) is
+accepted with a non-empty ``CE_LOC`` of the length of ``CE_KEEP_RATIO`` and runs by key masking (``native.Model.set_candidate_elimination``,
+DESIGN.md 11.4): the kept tokens take the reference's values, removed tokens come back as zeros, nothing is faster.  The template rows of
+the score come from ``CE_TEMPLATE_RANGE`` as ``lib/utils/ce_utils.py:15-49`` picks them (``ALL``, ``CTR_POINT``, ``CTR_REC``), one
+selection per model.  Not implemented (NotImplementedError): ViT-Large CE, ``CE_TEMPLATE_RANGE: GT_BOX``, a ``ce_keep_rate`` argument
+of ``forward``, a ``_ce`` TYPE without ``CE_LOC``, and the prompt / draw variants (``MODEL.PROCESS.*``)."""
 from __future__ import annotations
 
 from collections import OrderedDict
@@ -23,6 +29,28 @@ from .model import CenterHead, OstrackDist
 #: reference the TYPE decides: CHANNELS / HEADS of the YAML are not read for it.
 VIT_LARGE = {"channels": 1024, "heads": 16, "depth": 24}
 
+#: generate_mask_cond (lib/utils/ce_utils.py:22-49): the slice of template map rows AND columns that is set, per template map side of the two geometries (8: 128 px, 12: 192 px)
+CE_RANGE_SLICES = {"CTR_POINT": {8: (3, 4), 12: (5, 6)}, "CTR_REC": {8: (3, 5), 12: (5, 7)}}
+
+
+def ce_template_rows(template_range: str, feat_sz_z: int):
+    """box_mask_z of generate_mask_cond (lib/utils/ce_utils.py:15-49) for one sample, as a list of feat_sz_z ** 2 booleans; None for ALL
+    (every row).  CTR_POINT: row 27 at 8 x 8, row 65 at 12 x 12; CTR_REC: rows 27, 28, 35, 36 and 65, 66, 77, 78."""
+    template_range = str(template_range)
+    if template_range == "ALL":
+        return None
+    if template_range == "GT_BOX":
+        raise NotImplementedError("CE_TEMPLATE_RANGE GT_BOX (a template mask per frame from the ground-truth box) is not implemented: "
+                                  "ALL, CTR_POINT and CTR_REC are")
+    sl = CE_RANGE_SLICES.get(template_range, {}).get(int(feat_sz_z))
+    if sl is None:
+        raise NotImplementedError(f"CE_TEMPLATE_RANGE {template_range!r} at a {feat_sz_z} x {feat_sz_z} template map")      # ce_utils.py:32,46,63
+    rows = [False] * (feat_sz_z * feat_sz_z)
+    for y in range(*sl):
+        for x in range(*sl):
+            rows[y * feat_sz_z + x] = True
+    return rows
+
 
 class OSTrack(OstrackDist):
     def __init__(self, cfg, depth=None, max_batch=1):
@@ -30,13 +58,25 @@ class OSTrack(OstrackDist):
         if g["head_type"] != "CENTER":
             raise ValueError("HEAD TYPE %s is not supported." % g["head_type"])
         bb_type = str(cfg.MODEL.BACKBONE.TYPE)
+        self.ce_loc, self.ce_keep_ratio, self.ce_rows = [], [], None
         if bb_type == "vit_large_patch16_224":
             g["channels"], g["heads"] = VIT_LARGE["channels"], VIT_LARGE["heads"]
             depth = VIT_LARGE["depth"] if depth is None else depth
         elif bb_type == "vit_base_patch16_224":
             depth = 12 if depth is None else depth
+        elif bb_type == "vit_base_patch16_224_ce":
+            depth = 12 if depth is None else depth
+            self.ce_loc = [int(v) for v in cfg.MODEL.BACKBONE.CE_LOC]
+            self.ce_keep_ratio = [float(v) for v in cfg.MODEL.BACKBONE.CE_KEEP_RATIO]
+            if not self.ce_loc or not self.ce_keep_ratio:
+                raise NotImplementedError("backbone 'vit_base_patch16_224_ce' without CE_LOC / CE_KEEP_RATIO: give MODEL.BACKBONE.CE_LOC and "
+                                          "CE_KEEP_RATIO (the published models: [3, 6, 9] and [0.7, 0.7, 0.7]) or use TYPE vit_base_patch16_224")
+            if len(self.ce_loc) != len(self.ce_keep_ratio):
+                raise ValueError(f"CE_LOC {self.ce_loc} and CE_KEEP_RATIO {self.ce_keep_ratio} must have the same length")
+            self.ce_rows = ce_template_rows(cfg.MODEL.BACKBONE.CE_TEMPLATE_RANGE, g["template_size"] // g["stride"])
         else:
-            raise NotImplementedError(f"backbone {cfg.MODEL.BACKBONE.TYPE!r}: only vit_base_patch16_224 and vit_large_patch16_224 are implemented")
+            raise NotImplementedError(f"backbone {cfg.MODEL.BACKBONE.TYPE!r}: only vit_base_patch16_224, vit_base_patch16_224_ce and "
+                                      "vit_large_patch16_224 are implemented")
         if str(cfg.MODEL.BACKBONE.CAT_MODE) != "direct":
             raise NotImplementedError("only CAT_MODE 'direct' (template tokens first) is implemented")
         self.geom, self.depth, self.mode, self.head_type, self.max_batch = g, depth, "eval", "CENTER", max_batch
@@ -46,12 +86,60 @@ class OSTrack(OstrackDist):
                                                               head_ch=g["head_channels"], len_z=g["len_z"], len_x=g["len_x"]))
         self._nat, self._device, self.training = None, None, False
 
-    def forward(self, template, search, **unused):
-        """OSTrack.forward (ostrack.py:47-120) for the plain backbone: no CE mask, no template / search pre-processing."""
+    def _native(self) -> native.Model:
+        fresh = self._nat is None
+        nat = OstrackDist._native(self)
+        if fresh and self.ce_loc:      # every entry point of the native model (forward, forward_u8, track_step*, captures) then runs with it
+            nat.set_candidate_elimination(self.ce_loc, self.ce_keep_ratio, self.ce_rows)
+        return nat
+
+    def _check_ce_mask(self, mask, B):
+        """The model has ONE selection of template rows (per-frame masks are not implemented): `mask` must repeat it for every sample."""
+        import torch
+        lz = self.geom["len_z"]
+        want = torch.tensor(self.ce_rows if self.ce_rows is not None else [True] * lz, dtype=torch.bool)
+        if not (isinstance(mask, torch.Tensor) and mask.dtype == torch.bool and tuple(mask.shape) == (B, lz)):
+            raise ValueError(f"ce_template_mask must be None or a ({B}, {lz}) bool tensor, got {type(mask).__name__} "
+                             f"{tuple(getattr(mask, 'shape', ()))} {getattr(mask, 'dtype', '')}")
+        if not bool((mask.cpu() == want[None]).all()):
+            raise ValueError("ce_template_mask differs from the model's template rows (CE_TEMPLATE_RANGE "
+                             "fixes one selection per model; per-frame masks are not implemented)")
+
+    def forward(self, template, search, ce_template_mask=None, ce_keep_rate=None, **unused):
+        """OSTrack.forward (ostrack.py:47-120).  Plain backbone: no CE mask, no template / search pre-processing.  CE backbone:
+        ce_template_mask None or the model's own rows for every sample; the dict gains 'removed_indexes_s', per stage the (B, r_k) int64
+        global search indices removed there, ascending (the reference: descending score, as floats; only its visualisation reads them)."""
         extra = {k: v for k, v in unused.items() if v is not None and v is not False}
+        if not self.ce_loc:
+            if ce_template_mask is not None:
+                extra["ce_template_mask"] = ce_template_mask
+            if ce_keep_rate is not None:
+                extra["ce_keep_rate"] = ce_keep_rate
         if extra:
             raise NotImplementedError(f"OSTrack.forward arguments {sorted(extra)} belong to variants that are not implemented")
-        return OstrackDist.forward(self, template, search)
+        if not self.ce_loc:
+            return OstrackDist.forward(self, template, search)
+        if ce_keep_rate is not None:
+            raise NotImplementedError("ce_keep_rate (the training schedule's keep rate) is not implemented: the model runs CE_KEEP_RATIO")
+        B = search.shape[0]
+        if ce_template_mask is not None:
+            self._check_ce_mask(ce_template_mask, B)
+        out = OstrackDist.forward(self, template, search)
+        out["removed_indexes_s"] = self.removed_indexes(B)
+        return out
+
+    def removed_indexes(self, B):
+        """Per stage the (B, r_k) int64 global search indices the last call removed there, ascending; no host synchronisation."""
+        import torch
+        nat = self._native()
+        removed, _ = nat.ce_result(B)
+        out, prev = [], nat.len_x
+        for k, keep in enumerate(nat.ce_keep):
+            # a stable sort of "not removed at this stage" puts the stage's tokens first, in index order
+            order = torch.sort((removed != k + 1).to(torch.uint8), dim=1, stable=True).indices
+            out.append(order[:, :prev - keep].contiguous())
+            prev = keep
+        return out
 
     __call__ = forward
 

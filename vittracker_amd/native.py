@@ -72,6 +72,8 @@ ABI = {
     "vt_stem_u8": (C.c_int, [_vp, _vp, _i32, _vp, _vp]),
     "vt_patch_u8_supported": (C.c_int, [_vp, _i32]),
     "vt_crop_form": (C.c_int, []),
+    "vt_set_candidate_elimination": (C.c_int, [_vp, _i32, C.POINTER(_i32), C.POINTER(C.c_double), _vp]),
+    "vt_ce_result": (C.c_int, [_vp, _i32, _vp, _vp, _vp]),
 }
 # the three frame sources of the crops and of the step: a dense (B,H,W,3) batch (frames, H, W), a vt_frame table, a vt_image table
 for _sfx, _src in (("", [_vp, _i32, _i32]), ("_frames", [_vp]), ("_images", [_vp])):
@@ -641,6 +643,19 @@ class ImageTable(_DescriptorTable):
 _table_ptr, _image_table_ptr = FrameTable.ptr, ImageTable.ptr
 
 
+def ce_keep_counts(len_x: int, keep_ratio):
+    """Search tokens kept after each candidate-elimination stage: math.ceil(keep_ratio * lens_s) of lib/models/layers/attn_blocks.py:39
+    applied stage after stage (0.7, 0.7, 0.7: 180 / 126 / 89 of 256, 404 / 283 / 199 of 576).  The library computes the same."""
+    import math
+    out, n = [], int(len_x)
+    for r in keep_ratio:
+        if not 0.0 < float(r) <= 1.0:
+            raise VtError(f"keep ratio {r} outside (0, 1]")
+        n = min(n, max(1, math.ceil(float(r) * n)))
+        out.append(n)
+    return out
+
+
 def crop_form() -> int:
     """Which crop kernel form the current device runs: 1 = 8-byte unaligned windows (crop_fast_kernel / crop_kernel<false>), 2 = the
     byte-load fallback the device self test selects on any mismatch."""
@@ -1013,6 +1028,40 @@ class Model:
     def set_normalization(self, mean, std):
         """Preprocessor's mean / std for the uint8 entry points (folded into the stem's first layer; default: ImageNet)."""
         _check(self._L.vt_set_normalization(self._h, _f3(mean), _f3(std)), "vt_set_normalization", self._L)
+
+    def set_candidate_elimination(self, loc, keep_ratio, template_rows=None):
+        """OSTrack candidate elimination by key masking (vt_set_candidate_elimination): after block loc[k] the search tokens are ranked
+        by the attention they receive from the selected template rows and ceil(keep_ratio[k] * kept so far) stay present as keys.
+        template_rows: (len_z,) booleans, None = every row.  Before any capture; ViT-Base models only."""
+        loc, keep_ratio = [int(v) for v in loc], [float(v) for v in keep_ratio]
+        if len(loc) != len(keep_ratio):
+            raise VtError(f"candidate elimination: {len(loc)} blocks (CE_LOC) for {len(keep_ratio)} keep ratios (CE_KEEP_RATIO)")
+        n = len(loc)
+        rows = None
+        if template_rows is not None:
+            rows = np.ascontiguousarray(np.asarray(template_rows).reshape(-1) != 0, dtype=np.uint8)
+            if rows.size != self.len_z:
+                raise VtError(f"template_rows must have {self.len_z} entries, got {rows.size}")
+        _check(self._L.vt_set_candidate_elimination(self._h, n, (C.c_int32 * max(n, 1))(*loc), (C.c_double * max(n, 1))(*keep_ratio),
+                                                    rows.ctypes.data if rows is not None else None),
+               "vt_set_candidate_elimination", self._L)
+        self.ce_stages = n
+        self.ce_keep = ce_keep_counts(self.len_x, keep_ratio)
+
+    def ce_result(self, B=None, stream=None):
+        """(removed_stage (B, len_x) uint8: 0 = kept to the end, k = removed at stage k; scores (n, B, len_x) fp32: each stage's ranking
+        score, NaN for tokens removed earlier) of the last forward / step / blocks call (vt_ce_result).  B: default max_batch."""
+        import torch
+        n = getattr(self, "ce_stages", 0)
+        if not n:
+            raise VtError("ce_result needs set_candidate_elimination() first")
+        B = self.max_batch if B is None else int(B)
+        self._check_batch(B)
+        removed = torch.empty(B, self.len_x, dtype=torch.uint8, device="cuda")
+        scores = torch.empty(n, B, self.len_x, dtype=torch.float32, device="cuda")
+        _check(self._L.vt_ce_result(self._h, B, _stream(stream), C.c_void_p(removed.data_ptr()), C.c_void_p(scores.data_ptr())),
+               "vt_ce_result", self._L)
+        return removed, scores
 
     def set_open_loop(self, on: bool = True):
         """vt_set_open_loop: track_step (and graphs captured from now on) leave `states` untouched; the step's box is in `record`."""

@@ -1,5 +1,6 @@
 """Tracker plugin: ``OSTrack`` -- the ViT-Base / ViT-Large OSTrack tracker with the reference's ``initialize() / track()`` contract
-(``lib/test/tracker/ostrack.py:23-189`` for the plain ``vit_base_patch16_224`` / ``vit_large_patch16_224`` backbones), on the MI355X-native library.
+(``lib/test/tracker/ostrack.py:23-189`` for the ``vit_base_patch16_224`` / ``vit_base_patch16_224_ce`` / ``vit_large_patch16_224`` backbones), on the
+MI355X-native library.
 
 The frame step of the two reference trackers is the same statement -- ``sample_target``, ``Preprocessor.process``, the network,
 the Hann-windowed ``cal_bbox``, ``map_box_back`` + ``clip_box(margin=10)`` -- and they differ in the network behind it.  So this class
@@ -8,8 +9,11 @@ pipeline pool, the device pipeline by default (crop -> uint8 patch -> network on
 library call, ``native.Image`` frames accepted), ``params.host_crop = True`` for the reference's structure, ``save_all_boxes``, and
 ``confidence`` as a Python float where the reference leaves a 0-d tensor.
 
-Not implemented, as in :mod:`vittracker_amd.model_vitb`: the candidate-elimination backbone and its ``box_mask_z``
-(``generate_mask_cond``, :57-62 -- the plain backbone never reads it), ``MODEL.PROCESS.*`` and the debug visualisation."""
+The candidate-elimination backbone (``vit_base_patch16_224_ce``, every published OSTrack checkpoint: ``experiments/ostrack/
+vitb_256_mae_ce_32x4_ep300.yaml`` / ``vitb_384_mae_ce_32x4_ep300.yaml``) runs through the same class: its ``box_mask_z``
+(``generate_mask_cond``, :57-62) is fixed per model from ``CE_TEMPLATE_RANGE`` when the network is built, so ``initialize()`` has nothing
+to generate.  Not implemented, as in :mod:`vittracker_amd.model_vitb`: ViT-Large CE, ``CE_TEMPLATE_RANGE: GT_BOX``, ``ce_keep_rate``,
+``MODEL.PROCESS.*`` and the debug visualisation (``removed_indexes_s`` is returned by the model's ``forward``; nothing draws it)."""
 from __future__ import annotations
 
 from .vit_dist import BaseTracker, Vit_dist  # noqa: F401
