@@ -199,6 +199,16 @@ int vt_set_normalization(vt_model* m, const float* mean3, const float* std3);
  * With nblocks < depth vt_blocks runs the stages inside [0, nblocks) and the final norm zeroes what they removed.  resid_dev rows of
  * removed tokens are unspecified (finite in practice: they go on being computed and are never read by a kept row). */
 int vt_set_candidate_elimination(vt_model* m, int32_t n, const int32_t* loc, const double* keep_ratio, const uint8_t* template_rows);
+/* The form the stages run in.  VT_CE_MASKED (the default): key masking, as above.  VT_CE_COMPACT: behind every stage the kept tokens of a
+ * frame (template rows first, kept search tokens in ascending global index, zero pad rows up to a multiple of 16) are gathered into a
+ * shorter dense sequence and every kernel behind it runs on B x Lp_k rows (0.7, 0.7, 0.7: 256 / 192 / 160 rows of 320, 560 / 432 / 352 of
+ * 720); the final norm scatters the kept rows back to their global positions, removed rows are exact zeros, and resid_dev of vt_blocks is
+ * the dense (B,L,C) stream with zero rows for removed tokens.  Same function, same vt_ce_result (global indices), same tie rule; the first
+ * removing stage selects exactly as the masked form does.  ViT-Base only (VT_ERR_ARG otherwise, and for any other `form`); before or after
+ * vt_set_candidate_elimination, before any graph is captured (VT_ERR_STATE afterwards).  Neither synchronises nor allocates. */
+#define VT_CE_MASKED 0
+#define VT_CE_COMPACT 1
+int vt_set_ce_form(vt_model* m, int32_t form);
 /* What the last vt_forward* / vt_track_step* / vt_blocks / graph launch of B frames left: removed_stage_dev (B,Lx) bytes, 0 = kept to the
  * end, k = removed at stage k (1-based); scores_dev (n,B,Lx) fp32, the ranking score of each stage, NaN for tokens removed earlier and for
  * stages that did not run (no-ops; stages at or past nblocks keep what an earlier call left).  Either pointer may be NULL.  Capturable.

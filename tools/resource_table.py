@@ -24,6 +24,21 @@ def table(src, extra=()):
     return [dict(r) for r in _TABLES[key]]
 
 
+def _qualified(name):
+    """A name c++filt leaves mangled (bf16 pointers in the signature) as namespace::function, when it is a plain (non-template) function
+    of one named namespace: _ZN3vbc16ce_gather_kernelEPKDF16b... -> vbc::ce_gather_kernel.  Anything else is returned as it is."""
+    m = re.match(r"_ZN(\d+)", name)
+    if not m:
+        return name
+    i, n = m.end(), int(m.group(1))
+    ns, rest = name[i:i + n], name[i + n:]
+    m = re.match(r"(\d+)", rest)
+    if not m:
+        return name
+    j, k = m.end(), int(m.group(1))
+    return f"{ns}::{rest[j:j + k]}" if rest[j + k:j + k + 1] == "E" and not ns.startswith("_GLOBAL") else name
+
+
 def _compile(src, extra=()):
     err = subprocess.run(["hipcc"] + FLAGS + list(extra) + ["-Rpass-analysis=kernel-resource-usage", "-c", "-o", "/dev/null", src],
                          cwd=CSRC, capture_output=True, text=True).stderr
@@ -34,7 +49,7 @@ def _compile(src, extra=()):
         m = re.search(r"Function Name: (\S+)", ln)
         if m:
             name = subprocess.run(["c++filt", m.group(1)], capture_output=True, text=True).stdout.strip()
-            cur = {"name": re.sub(r"^void ", "", name.split("(")[0])}
+            cur = {"name": _qualified(re.sub(r"^void ", "", name.split("(")[0]))}
             continue
         for key, pat in pats:
             m = re.search(pat, ln)

@@ -20,19 +20,22 @@ sys.path.insert(0, ROOT)
 
 
 def run_tracker(tracker_name, tracker_param, run_id=None, dataset_name="synthetic", sequence=None, debug=0, threads=0,
-                num_gpus=8, batch=0, synthetic_weights=False, frames_per_launch=1, shards=1, continuous=False):
+                num_gpus=8, batch=0, synthetic_weights=False, frames_per_launch=1, shards=1, continuous=False, ce_form=None):
     from vittracker_amd.evaluation import Tracker, get_dataset
     from vittracker_amd.evaluation.running import run_dataset, run_dataset_batched, run_dataset_continuous
     dataset = get_dataset(dataset_name)
     if sequence is not None:
         dataset = type(dataset)([dataset[sequence]])
     tracker = Tracker(tracker_name, tracker_param, dataset_name, run_id)
-    if synthetic_weights:
+    if synthetic_weights or ce_form is not None:
         _get = tracker.get_parameters
 
         def get_parameters():
             p = _get()
-            p.allow_synthetic_weights = True
+            if synthetic_weights:
+                p.allow_synthetic_weights = True
+            if ce_form is not None:
+                p.ce_form = ce_form
             return p
         tracker.get_parameters = get_parameters
     if batch > 0:
@@ -71,13 +74,16 @@ def main():
     p.add_argument("--continuous", action="store_true",
                    help="with --batch: continuous batching -- B slots across every frame size; a finished sequence's slot takes the next one")
     p.add_argument("--synthetic_weights", action="store_true", help="run on the seeded synthetic weights")
+    p.add_argument("--ce_form", choices=("masked", "compact"), default=None,
+                   help="candidate-elimination models (ostrack *_ce_* YAMLs): key masking, or the kept tokens gathered into shorter "
+                        "frames behind every stage; default: the environment variable VB_CE_FORM, else masked")
     a = p.parse_args()
     try:
         seq = int(a.sequence)
     except (TypeError, ValueError):
         seq = a.sequence
     run_tracker(a.tracker_name, a.tracker_param, a.runid, a.dataset_name, seq, a.debug, a.threads, a.num_gpus, a.batch,
-                a.synthetic_weights, a.frames_per_launch, a.shards, a.continuous)
+                a.synthetic_weights, a.frames_per_launch, a.shards, a.continuous, a.ce_form)
 
 
 if __name__ == "__main__":

@@ -44,11 +44,13 @@ int stem_rows(VbModel* m, ZSrc zsrc, const float* z, const float* x, const unsig
 int set_template(VbModel* m, const float* z, int n, const int32_t* slots, hipStream_t st, std::string* err);
 // Preprocessor.process folded into the uint8 form of the patch-embedding weights (fp64; vitb.hip fold_patch_u8).  Synchronous.
 int set_normalization(VbModel* m, const float* mean3, const float* std3, std::string* err);
-// Candidate elimination by key masking (vb_ce.h; include/vittrack.h vt_set_candidate_elimination / vt_ce_result).  check_ce_args: what
+// Candidate elimination, by key masking or compacted (vb_ce.h; include/vittrack.h vt_set_candidate_elimination / vt_ce_result).  check_ce_args: what
 // can be refused without a model (n, loc, keep_ratio).  set_candidate_elimination synchronises the device and (re)allocates the stage buffers;
 // ViT-Base only.  ce_result copies out what the last blocks() left for frames [0, B): removed_stage (B,LX) bytes, scores (n,B,LX) f32.
 int check_ce_args(int n, const int32_t* loc, const double* keep_ratio, std::string* err);
 int set_candidate_elimination(VbModel* m, int n, const int32_t* loc, const double* keep_ratio, const uint8_t* template_rows, std::string* err);
+// The form the stages run in from the next blocks() on: VT_CE_MASKED (the default) or VT_CE_COMPACT (vb_ce.h); ViT-Base only.
+int set_ce_form(VbModel* m, int form, std::string* err);
 int ce_result(VbModel* m, int B, hipStream_t st, uint8_t* removed_stage, float* scores, std::string* err);
 // blocks[0..nblocks) on the residual stream (tokens_in: optional replacement, copied in first), then the final norm:
 // the search rows go to the head's input map (and to feat_out as f32 (B,Lx,C), optional); resid_out optional copy

@@ -79,4 +79,134 @@ __global__ __launch_bounds__(256, 2) void attn_stream_masked_kernel(const bf16* 
 #include "vb_attn_stream_body.inc"
 }
 
+// The same arithmetic at a RUN-TIME frame length: the compact form of candidate elimination (vb_ce.h), where the kept tokens of a frame
+// are gathered into Lp = round_up(nkeys, 16) rows behind each stage.  Lp: rows of a frame in qk / out and the row length of vt, a multiple
+// of 16, at least 80 (two chunks); nkeys in (Lp - 16, Lp]: the live rows.  Rows [nkeys, Lp) are pad rows: as keys they get the partial
+// last chunk's treatment (-inf before the chunk maximum, V^T columns zeroed in registers) under a plain count -- they all lie in the
+// last 16-key tile, so only the last sub-chunk is touched, as in attn_stream_kernel<720> -- and as queries they compute something finite
+// that nobody reads.  The last chunk holds one or two sub-chunks (Lp % 32 is 0 or 16); chunk and split counts are run-time values, the
+// chunk loop is the one above.  Written out rather than sharing vb_attn_stream_body.inc: the body's token counts are constant expressions,
+// and attn_stream_kernel<L> / attn_stream_masked_kernel<L> must go on compiling exactly as recorded (profiles/r6_resource_usage.txt).
+// What is read past a frame's last row (Lp % 32 = 16: 16 rows / elements) is never used, as above, and is mapped memory: where Lp < L the
+// dense layout leaves it inside the slice's own rows (Lp <= L - 16); where nothing shorter than the full frame results (L = 720 with 561 to
+// 575 kept tokens: Lp = 720) it is the next frame's rows, the next chain's slice or the workspaces' tails -- exactly attn_stream_kernel<720>'s reads.
+inline int splits_rt(int Lp) { return (Lp / 16 + QT_PER_WG - 1) / QT_PER_WG; }
+
+// grid = B * heads * splits_rt(Lp), 256 threads, LDS_BYTES of dynamic LDS
+__global__ __launch_bounds__(256, 2) void attn_stream_rt_kernel(const bf16* __restrict__ qk, const bf16* __restrict__ vt, bf16* __restrict__ out,
+                                                             int heads, int Lp, int nkeys) {
+    constexpr int HD = 64, KS = HD / 32, DT = HD / 16;
+    const int NT = Lp / 16, NSUB = (Lp + 31) / 32, NCH = (NSUB + 1) / 2, LAST_SUB = NSUB - 2 * (NCH - 1);
+    const int SPLITS = (NT + QT_PER_WG - 1) / QT_PER_WG;
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int fh = blockIdx.x / SPLITS, sp = blockIdx.x - fh * SPLITS;
+    const int f = fh / heads, h = fh - f * heads, C = heads * HD;
+    const bf16* qf = qk + (size_t)f * Lp * 2 * C + h * HD;
+    const bf16* kf = qf + C;
+    const bf16* vf = vt + ((size_t)f * C + h * HD) * Lp;
+    const int l15 = lane & 15, q = lane >> 4;
+
+    int qts[NQ];
+    bf16x8 qfrag[NQ][KS];
+#pragma unroll
+    for (int u = 0; u < NQ; ++u) {
+        qts[u] = sp * QT_PER_WG + w * NQ + u;
+        const int qt = qts[u] < NT ? qts[u] : NT - 1;
+        vba::load_q(qfrag[u], qf, qt, l15, q, C);
+    }
+
+    const int pl = vbg::swz_byte(lane * 16), prow = pl >> 6, pk = (pl & 63) >> 1;
+    auto stage = [&](int c, int b, int nsub) {
+        char* Kimg = smem + b * CHUNK_BYTES;
+        char* Vimg = Kimg + KC * HD * 2;
+        for (int s = w; s < nsub * 2 * KS; s += WAVES) {
+            const int t = s / KS, ks = s - t * KS;
+            vbg::glds16(kf + (size_t)(c * KC + vba::perm_key(t, prow)) * 2 * C + ks * 32 + pk, Kimg + s * 1024 + lane * 16);
+        }
+        for (int s = w; s < nsub * DT; s += WAVES) {
+            const int dt = s / nsub, sc = s - dt * nsub;
+            vbg::glds16(vf + (size_t)(dt * 16 + prow) * Lp + c * KC + sc * 32 + pk, Vimg + (dt * 2 + sc) * 1024 + lane * 16);
+        }
+    };
+
+    const int fr = vbg::swz_byte(l15 * 64 + q * 16);
+    float mrun[NQ], lsum[NQ];
+    f4 O[NQ][DT];
+#pragma unroll
+    for (int u = 0; u < NQ; ++u) {
+        mrun[u] = -1e30f;
+        lsum[u] = 0.f;
+#pragma unroll
+        for (int dt = 0; dt < DT; ++dt) O[u][dt] = splat4(0.f);
+    }
+
+    // one chunk, as in the body: MASK = the chunk's last sub-chunk may hold keys at or past nkeys
+    auto compute = [&](auto ns_tag, auto mask_tag, int c, int b) {
+        constexpr int NS = decltype(ns_tag)::value;
+        constexpr bool MASK = decltype(mask_tag)::value;
+        const char* Kimg = smem + b * CHUNK_BYTES;
+        const char* Vimg = Kimg + KC * HD * 2;
+        f4 S[NQ][2 * NS];
+        vba::qk_tiles(S, Kimg, fr, qfrag);
+        const int base = c * KC + (NS - 1) * 32 + 8 * q;      // this lane's keys of the last sub-chunk: base + {0..7}
+        if constexpr (MASK) {
+#pragma unroll
+            for (int u = 0; u < NQ; ++u)
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    if (base + j >= nkeys) S[u][2 * NS - 2][j] = -INFINITY;
+                    if (base + 4 + j >= nkeys) S[u][2 * NS - 1][j] = -INFINITY;
+                }
+        }
+#pragma unroll
+        for (int u = 0; u < NQ; ++u) {
+            const float mx = fmaxf(mrun[u], quad_max(vba::lane_max(S[u])));      // finite: chunk 0 is whole (nkeys > 64)
+            const float alpha = __builtin_amdgcn_exp2f((mrun[u] - mx) * vba::LOG2E);
+            mrun[u] = mx;
+            const vbg::f2 l2 = {vba::LOG2E, vba::LOG2E}, nmb = {-mx * vba::LOG2E, -mx * vba::LOG2E};
+            vbg::f2 s0 = {0.f, 0.f}, s1 = {0.f, 0.f};
+#pragma unroll
+            for (int t = 0; t < 2 * NS; ++t) vba::exp_tile(S[u][t], l2, nmb, s0, s1);
+            const vbg::f2 st = s0 + s1;
+            lsum[u] = fmaf(lsum[u], alpha, st.x + st.y);
+#pragma unroll
+            for (int dt = 0; dt < DT; ++dt) O[u][dt] = O[u][dt] * splat4(alpha);
+        }
+#pragma unroll
+        for (int sc = 0; sc < NS; ++sc) {
+            if (MASK && sc == NS - 1) {
+                vba::pv_chunk(O, S, sc, Vimg, 2, fr, [&](bf16x8& vf8) {
+#pragma unroll
+                    for (int j = 0; j < 8; ++j)
+                        if (base + j >= nkeys) vf8[j] = (bf16)0.0f;
+                });
+            } else vba::pv_chunk(O, S, sc, Vimg, 2, fr);
+        }
+    };
+
+    using I1 = std::integral_constant<int, 1>;
+    using I2 = std::integral_constant<int, 2>;
+    stage(0, 0, 2);
+    for (int c = 0; c + 1 < NCH; ++c) {
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __syncthreads();
+        stage(c + 1, (c + 1) & 1, c + 2 < NCH ? 2 : LAST_SUB);
+        compute(I2{}, std::false_type{}, c, c & 1);
+    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    // The last chunk is always the masked instantiation, also where none of its keys is absent (nkeys = Lp, Lp % 32 = 0: a few compares per
+    // lane that change nothing).  Branching to unmasked instantiations there was tried: with four instantiations of the chunk behind
+    // uniform branches the kernel takes 256 VGPRs and spills 4 of them (20 B scratch) where this form takes 188 and none.
+    if (LAST_SUB == 2) compute(I2{}, std::true_type{}, NCH - 1, (NCH - 1) & 1);
+    else compute(I1{}, std::true_type{}, NCH - 1, (NCH - 1) & 1);
+
+#pragma unroll
+    for (int u = 0; u < NQ; ++u) {
+        const float inv = 1.0f / quad_sum(lsum[u]);
+        if (qts[u] < NT) vba::store_tile(out, (size_t)(f * Lp + qts[u] * 16 + l15), C, h * HD + q * 4, O[u], inv);
+    }
+}
+
 }  // namespace vbs

@@ -1,9 +1,14 @@
-// vb_ce.h -- OSTrack candidate elimination (lib/models/layers/attn_blocks.py:20-85, lib/models/ostrack/vit_ce.py:151-186) by KEY MASKING,
-// gfx950.  The reference gathers the kept search tokens after the attention of blocks CE_LOC and runs the rest of the network on the
+// vb_ce.h -- OSTrack candidate elimination (lib/models/layers/attn_blocks.py:20-85, lib/models/ostrack/vit_ce.py:151-186) by KEY MASKING
+// and COMPACTED, gfx950.  The reference gathers the kept search tokens after the attention of blocks CE_LOC and runs the rest of the network on the
 // shorter sequence.  A removed token can reach a later value of a kept one only as a key / value row of a later attention (LayerNorm, the
 // MLP and every GEMM work per token), so here every matrix keeps its dense B x L rows, removed rows go on being computed and are never read
 // by a kept row: later attentions take a per-frame key bitmap (vbs::attn_stream_masked_kernel) and the final norm's search rows of removed
 // tokens are overwritten with zeros, as the reference's scatter into zeros does.  No token moves, no shape changes, nothing is faster.
+// That is the MASKED form (VT_CE_MASKED, the default).  The COMPACT form (VT_CE_COMPACT, vt_set_ce_form) does what the reference does:
+// behind a stage's selection the kept rows of every frame are gathered into a shorter dense frame -- template rows, kept search tokens in
+// ascending global index, zero pad rows up to a multiple of 16 -- and every kernel behind it runs on B x Lp_k rows; the final norm scatters
+// through the last index table to the tokens' global positions.  Same scores at the first removing stage (it runs before anything moves),
+// same results, same tie rule.  Its kernels are at the end of this file; vbs::attn_stream_rt_kernel is its attention.
 //
 // The key bitmap of a frame: ceil(L / 32) uint32 words, bit (key & 31) of word (key >> 5) set = the key is present.  Template keys
 // [0, Lz) are always present; bits at and past L are 0.  Stage k reads the bitmap stage k - 1 left (none: every key present) and writes its
@@ -259,6 +264,297 @@ __global__ __launch_bounds__(256) void ce_zero_rows_kernel(const uint32_t* __res
         *reinterpret_cast<bf16x4*>(map + ((size_t)(f * P + y + 1) * P + x + 1) * C + c) = bf16x4{(bf16)0.f, (bf16)0.f, (bf16)0.f, (bf16)0.f};
         if (feat) st4(feat + row * C + c, splat4(0.f));
     }
+}
+
+// ------------------------------------------------------------------------------------------------ the COMPACT form
+// Behind a stage's selection the kept tokens of every frame are gathered into a shorter dense sequence and everything behind it runs on
+// B x Lp rows (header comment).  A compacted frame: Lz template rows, the kept search tokens in ascending GLOBAL index, then pad rows up
+// to Lp = round_up(Lz + kept, 16).  Pad rows are zero-filled by the gather, never present as keys (nkeys = Lz + kept is a plain count) and
+// never read.  index [frame][kept]: the global search index of compacted search row i; inv [frame][Lx]: the compacted search row of a
+// global token, -1 = removed.  The kernels below take the frame length at run time.
+
+// ce_score_kernel at a run-time frame length: Lp rows per frame, keys [0, nkeys) present.  KPL: keys per lane, 64 KPL >= Lp.  grid = B * heads,
+// 256 threads, 4 * Lp floats of dynamic LDS; part: [frame][heads][nkeys - Lz].
+template <int KPL>
+__global__ __launch_bounds__(256) void ce_score_rt_kernel(const bf16* __restrict__ qk, int Lp, int nkeys, const int32_t* __restrict__ rows, int nrows,
+                                                          float* __restrict__ part, int heads, int Lz) {
+    constexpr int HD = 64;
+    extern __shared__ float red_rt[];      // [4][Lp]
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const int f = blockIdx.x / heads, h = blockIdx.x - f * heads, C = heads * HD;
+    const bf16* qf = qk + (size_t)f * Lp * 2 * C + h * HD;
+    const bf16* kf = qf + C;
+    float acc[KPL];
+#pragma unroll
+    for (int s = 0; s < KPL; ++s) acc[s] = 0.f;
+    for (int r = w; r < nrows; r += 4) {
+        const bf16* qr = qf + (size_t)rows[r] * 2 * C;
+        float qv[HD];
+#pragma unroll
+        for (int d = 0; d < HD; d += 8) {
+            const bf16x8 t = *reinterpret_cast<const bf16x8*>(qr + d);
+#pragma unroll
+            for (int j = 0; j < 8; ++j) qv[d + j] = (float)t[j];
+        }
+        float sc[KPL], mx = -INFINITY;
+#pragma unroll
+        for (int s = 0; s < KPL; ++s) {
+            sc[s] = -INFINITY;
+            if (lane + 64 * s < nkeys) {
+                const bf16* kr = kf + (size_t)(lane + 64 * s) * 2 * C;
+                float a = 0.f;
+#pragma unroll
+                for (int d = 0; d < HD; d += 8) {
+                    const bf16x8 t = *reinterpret_cast<const bf16x8*>(kr + d);
+#pragma unroll
+                    for (int j = 0; j < 8; ++j) a = fmaf(qv[d + j], (float)t[j], a);
+                }
+                sc[s] = a;
+            }
+            mx = fmaxf(mx, sc[s]);
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o));
+        float sum = 0.f;
+#pragma unroll
+        for (int s = 0; s < KPL; ++s) {
+            sc[s] = __builtin_amdgcn_exp2f((sc[s] - mx) * vba::LOG2E);
+            sum += sc[s];
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o);
+        const float inv = 1.0f / sum;
+#pragma unroll
+        for (int s = 0; s < KPL; ++s) acc[s] = fmaf(sc[s], inv, acc[s]);
+    }
+#pragma unroll
+    for (int s = 0; s < KPL; ++s)
+        if (lane + 64 * s < Lp) red_rt[w * Lp + lane + 64 * s] = acc[s];
+    __syncthreads();
+    const int n = nkeys - Lz;
+    float* out = part + ((size_t)f * heads + h) * n;
+    for (int j = threadIdx.x; j < n; j += 256)
+        out[j] = ((red_rt[Lz + j] + red_rt[Lp + Lz + j]) + red_rt[2 * Lp + Lz + j]) + red_rt[3 * Lp + Lz + j];
+}
+
+// ce_score_all_kernel at a run-time frame length (every template row, on the MFMA).  grid = B * heads, 256 threads, 16 * Lp floats of dynamic
+// LDS.  The pad keys lie in the last key tile; their column gets -inf by the additive form, with the MFMAs outside any branch as above.
+__global__ __launch_bounds__(256) void ce_score_all_rt_kernel(const bf16* __restrict__ qk, int Lp, int nkeys, float* __restrict__ part, int heads, int Lz) {
+    constexpr int HD = 64, KS = HD / 32;
+    extern __shared__ float red_rt[];      // [16][Lp]
+    const int NT = Lp / 16;
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const int f = blockIdx.x / heads, h = blockIdx.x - f * heads, C = heads * HD;
+    const bf16* qf = qk + (size_t)f * Lp * 2 * C + h * HD;
+    const bf16* kf = qf + C;
+    const int l15 = lane & 15, g = lane >> 4;
+    float* const acc = red_rt + (size_t)(w * 4 + g) * Lp + l15;
+    for (int t = 0; t < NT; ++t) acc[16 * t] = 0.f;
+    auto logits = [&](const bf16x8 (&qa)[KS], int t) {
+        bf16x8 kb[KS];
+        vba::load_q(kb, kf, t, l15, g, C);
+        f4 S = splat4(0.f);
+#pragma unroll
+        for (int ks = 0; ks < KS; ++ks) S = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qa[ks], kb[ks], S, 0, 0, 0);
+        const float gone = 16 * t + l15 < nkeys ? 0.f : -INFINITY;
+        return S + splat4(gone);
+    };
+    for (int qt = w; qt < Lz / 16; qt += 4) {
+        bf16x8 qa[KS];
+        vba::load_q(qa, qf, qt, l15, g, C);
+        float m[4], l[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) { m[j] = -1e30f; l[j] = 0.f; }
+        for (int t = 0; t < NT; ++t) {
+            const f4 S = logits(qa, t);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const float mn = fmaxf(m[j], S[j]);
+                l[j] = l[j] * __builtin_amdgcn_exp2f((m[j] - mn) * vba::LOG2E) + __builtin_amdgcn_exp2f((S[j] - mn) * vba::LOG2E);
+                m[j] = mn;
+            }
+        }
+#pragma unroll
+        for (int o = 1; o < 16; o <<= 1)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const float mo = __shfl_xor(m[j], o), lo = __shfl_xor(l[j], o), mn = fmaxf(m[j], mo);
+                {      // one normaliser for all 16 lanes, as in ce_score_all_kernel
+#pragma clang fp contract(off)
+                    const float mine = l[j] * __builtin_amdgcn_exp2f((m[j] - mn) * vba::LOG2E), theirs = lo * __builtin_amdgcn_exp2f((mo - mn) * vba::LOG2E);
+                    l[j] = mine + theirs;
+                }
+                m[j] = mn;
+            }
+        float inv[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) inv[j] = 1.0f / l[j];
+        for (int t = 0; t < NT; ++t) {
+            const f4 S = logits(qa, t);
+            float p[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) p[j] = __builtin_amdgcn_exp2f((S[j] - m[j]) * vba::LOG2E) * inv[j];
+            acc[16 * t] += (p[0] + p[1]) + (p[2] + p[3]);
+        }
+    }
+    __syncthreads();
+    const int n = nkeys - Lz;
+    float* out = part + ((size_t)f * heads + h) * n;
+    for (int j = threadIdx.x; j < n; j += 256) {
+        float s = 0.f;
+#pragma unroll
+        for (int i = 0; i < 16; ++i) s += red_rt[(size_t)i * Lp + Lz + j];
+        out[j] = s;
+    }
+}
+
+// Select on the current candidates.  grid = B, 256 threads.  part: [frame][heads][ncand], candidate i of a frame being global search token
+// prev[frame][i] (prev == nullptr: the uncompacted frame, candidate i = token i).  Ranks the ncand candidates (ties: the lower GLOBAL index wins
+// -- candidates stand in ascending global index, so the lower candidate does) and writes, all at GLOBAL positions: the stage's scores (NaN for
+// tokens removed before), removed_stage, inv; and per kept token, in ascending order: next[frame][j] its global index, src[frame][j] its
+// candidate number (what the gather reads).
+__global__ __launch_bounds__(256) void ce_select_compact_kernel(const float* __restrict__ part, const int32_t* __restrict__ prev, int32_t* __restrict__ next,
+                                                                int32_t* __restrict__ src, int32_t* __restrict__ inv, uint8_t* __restrict__ removed,
+                                                                float* __restrict__ scores, int heads, float scale, int stage, int ncand, int keep, int Lx) {
+    __shared__ float s[MAX_LX];
+    __shared__ uint8_t kept[MAX_LX];
+    __shared__ int wsum[4];
+    const int f = blockIdx.x;
+    const int32_t* pf = prev ? prev + (size_t)f * ncand : nullptr;
+    for (int j = threadIdx.x; j < Lx; j += 256) {
+        if (pf) scores[(size_t)f * Lx + j] = __builtin_nanf("");
+        inv[(size_t)f * Lx + j] = -1;
+    }
+    for (int j = threadIdx.x; j < ncand; j += 256) {
+        float v = 0.f;
+        for (int h = 0; h < heads; ++h) v += part[((size_t)f * heads + h) * ncand + j];
+        s[j] = v * scale;
+    }
+    __syncthreads();      // also orders the NaN / -1 fill before the writes below (the same block, global memory)
+    for (int j = threadIdx.x; j < ncand; j += 256) {
+        const float sj = s[j];
+        int rank = 0;
+        for (int i = 0; i < ncand; ++i) {
+            const float si = s[i];
+            rank += (si > sj || (si == sj && i < j)) ? 1 : 0;
+        }
+        const bool k = rank < keep;
+        const int gidx = pf ? pf[j] : j;
+        scores[(size_t)f * Lx + gidx] = sj;
+        if (!k) removed[(size_t)f * Lx + gidx] = (uint8_t)stage;
+        else if (!pf) removed[(size_t)f * Lx + gidx] = 0;
+        kept[j] = k;
+    }
+    __syncthreads();
+    // stable compaction: thread t owns candidates [t * per, (t + 1) * per); exclusive prefix of the kept counts over the threads
+    const int per = (ncand + 255) / 256, j0 = threadIdx.x * per, j1 = min(ncand, j0 + per);
+    int cnt = 0;
+    for (int j = j0; j < j1; ++j) cnt += kept[j];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    int incl = cnt;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const int up = __shfl_up(incl, o);
+        if (lane >= o) incl += up;
+    }
+    if (lane == 63) wsum[w] = incl;
+    __syncthreads();
+    int pos = incl - cnt;
+    for (int i = 0; i < w; ++i) pos += wsum[i];
+    for (int j = j0; j < j1; ++j)
+        if (kept[j] && pos < keep) {      // pos < keep always, but for NaN scores (every rank 0): the tables' bounds hold whatever the input
+            const int gidx = pf ? pf[j] : j;
+            next[(size_t)f * keep + pos] = gidx;
+            src[(size_t)f * Lx + pos] = j;
+            inv[(size_t)f * Lx + gidx] = pos;
+            ++pos;
+        }
+}
+
+// The gather behind select: frame f's new row i is template row i (i < Lz), candidate src[f][i - Lz] (i < Lz + keep) or a zero pad row.
+// Source rows at stride Lsrc, destination rows at stride Ldst, in OTHER buffers (frames run in parallel and frame f's destination would
+// overlap earlier frames' sources in place).  Moves the attention output (bf16), the residual stream (f32) and the rows' centring mean.
+// One wave per row, 4 rows per block; C a multiple of 256.
+__global__ __launch_bounds__(256) void ce_gather_kernel(const bf16* __restrict__ ao, const float* __restrict__ resid, const float* __restrict__ rmean,
+                                                        const int32_t* __restrict__ src, bf16* __restrict__ ao_out, float* __restrict__ resid_out,
+                                                        float* __restrict__ rmean_out, int B, int Lsrc, int Ldst, int Lz, int keep, int Lx, int C) {
+    const int lane = threadIdx.x & 63;
+    const long long row = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= (long long)B * Ldst) return;
+    const int f = (int)(row / Ldst), i = (int)(row - (long long)f * Ldst);
+    const bool live = i < Lz + keep;
+    const size_t from = (size_t)f * Lsrc + (i < Lz ? i : (live ? Lz + src[(size_t)f * Lx + i - Lz] : 0));
+    for (int c = lane * 4; c < C; c += 256) {
+        const bf16x4 z4 = {(bf16)0.f, (bf16)0.f, (bf16)0.f, (bf16)0.f};
+        *reinterpret_cast<bf16x4*>(ao_out + (size_t)row * C + c) = live ? *reinterpret_cast<const bf16x4*>(ao + from * C + c) : z4;
+        st4(resid_out + (size_t)row * C + c, live ? ld4(resid + from * C + c) : splat4(0.f));
+    }
+    if (lane == 0) rmean_out[row] = live ? rmean[from] : 0.f;
+}
+
+// The final LayerNorm on compacted rows, scattered to the tokens' global positions: one wave per (frame, global search token).  A kept token
+// (inv >= 0) is row f * Lp + Lz + inv of resid: its norm goes to the head's padded map and to feat (optional), as vbm::layernorm_kernel
+// writes them; a removed token's row of both is exactly zero (vit_ce.py:170-181).  Every interior row is written once; the border is not touched.
+template <int C>
+__global__ __launch_bounds__(256) void ce_final_norm_kernel(const float* __restrict__ resid, const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                            float eps, const int32_t* __restrict__ inv, int B, int Lp, int Lz, int Lx, int F,
+                                                            bf16* __restrict__ map, float* __restrict__ feat) {
+    constexpr int NV = C / 256;
+    const int lane = threadIdx.x & 63;
+    const long long o = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (o >= (long long)B * Lx) return;
+    const int f = (int)(o / Lx), tt = (int)(o - (long long)f * Lx);
+    const int p = inv[o];
+    f4 y[NV];
+    if (p >= 0) {
+        const float* r = resid + ((size_t)f * Lp + Lz + p) * C;
+        float s = 0.f;
+#pragma unroll
+        for (int i = 0; i < NV; ++i) {
+            y[i] = ld4(r + i * 256 + lane * 4);
+            s += hsum4(y[i]);
+        }
+#pragma unroll
+        for (int k = 32; k > 0; k >>= 1) s += __shfl_xor(s, k);
+        const float mean = s * (1.0f / C);
+        float ss = 0.f;
+#pragma unroll
+        for (int i = 0; i < NV; ++i) {
+            y[i] = y[i] - splat4(mean);
+            ss += hsum4(y[i] * y[i]);
+        }
+#pragma unroll
+        for (int k = 32; k > 0; k >>= 1) ss += __shfl_xor(ss, k);
+        const float rstd = 1.0f / sqrtf(ss * (1.0f / C) + eps);
+#pragma unroll
+        for (int i = 0; i < NV; ++i) {
+            const int c = i * 256 + lane * 4;
+            y[i] = y[i] * splat4(rstd) * ld4(gamma + c) + ld4(beta + c);
+        }
+    } else {
+#pragma unroll
+        for (int i = 0; i < NV; ++i) y[i] = splat4(0.f);
+    }
+    const int yy = tt / F, xx = tt - yy * F, P = F + 2;
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+        const int c = i * 256 + lane * 4;
+        *reinterpret_cast<bf16x4*>(map + ((size_t)(f * P + yy + 1) * P + xx + 1) * C + c) = vbg::to_bf16x4(y[i]);
+        if (feat) st4(feat + (size_t)o * C + c, y[i]);
+    }
+}
+
+// Compacted f32 rows back to the dense (B, L, C) layout (vb::blocks' resid_out): template rows as they are, kept search rows at their
+// global positions, removed rows zero.  One wave per destination row.
+__global__ __launch_bounds__(256) void ce_scatter_rows_kernel(const float* __restrict__ resid, const int32_t* __restrict__ inv, float* __restrict__ out, int B,
+                                                              int Lp, int L, int Lz, int C) {
+    const int lane = threadIdx.x & 63;
+    const long long row = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= (long long)B * L) return;
+    const int f = (int)(row / L), t = (int)(row - (long long)f * L);
+    const int p = t < Lz ? t : inv[(size_t)f * (L - Lz) + t - Lz];
+    const float* r = resid + ((size_t)f * Lp + (t < Lz ? t : Lz + p)) * C;
+    for (int c = lane * 4; c < C; c += 256) st4(out + (size_t)row * C + c, p >= 0 ? ld4(r + c) : splat4(0.f));
 }
 
 }  // namespace vbc

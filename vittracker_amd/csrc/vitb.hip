@@ -1,7 +1,7 @@
 // vitb.hip -- host side of the plain-ViT OSTrack path (ViT-Base, BASELINE config 4, and ViT-Large): weight packing (bf16, BatchNorm folded, conv
 // weights as [cout][tap][cin], attention scale folded into W_q), workspace, launch sequence.  Kernels: vb_gemm.h, vb_misc.h and the
 // three attention kernels vb_attn.h, vb_qkvattn.h, vb_attn_stream.h (the 384 geometry's), whose shared arithmetic lives in vb_attn.h;
-// vb_ce.h: OSTrack candidate elimination by key masking (the stages' score / select kernels; vb::blocks routes them).
+// vb_ce.h: OSTrack candidate elimination by key masking or compacted (the stages' score / select / gather kernels; vb::blocks routes them).
 // Reached through the same C ABI as the vit_48 path (vt_create with channels = 768, or the ViT-Large tuple at channels = 1024).  The two
 // model points differ in width, head count and hidden width alone (VbModel::C / HEADS / HID); the kernels take them at run time except
 // the three that compile the width in (dispatch_width below).
@@ -120,6 +120,14 @@ struct VbModel {
     Buf<float> ce_scores, ce_part;
     Buf<int32_t> ce_rows;
     int ce_words() const { return (L + 31) / 32; }
+    // the compact form (vb::set_ce_form, vb_ce.h): behind every stage the kept tokens are gathered into frames of ce_lp(k) rows.  ce_index
+    // [stage][max_batch][ce_keep[stage]] (stage k from element ce_index_off[k]): the global search index of every compacted search row;
+    // ce_src [max_batch][LX]: per kept token its number among the stage's candidates (select -> gather); ce_inv [max_batch][LX]: the
+    // compacted search row of a global token after the last stage that ran, -1 = removed (the final norm's scatter)
+    int ce_form = VT_CE_MASKED;
+    Buf<int32_t> ce_index, ce_src, ce_inv;
+    std::vector<size_t> ce_index_off;
+    int ce_lp(int k) const { return (LZ + ce_keep[k] + 15) / 16 * 16; }
 };
 
 namespace {
@@ -233,9 +241,10 @@ void dispatch_width(int C, F&& f) {
 template <typename K>
 const void* kernel_ptr(K kernel) { return reinterpret_cast<const void*>(kernel); }
 
+// rows: the residual rows when they are not B frames of L (the compact form of candidate elimination; then no map / feat)
 int run_layernorm(const VbModel* m, const float* resid, const float* g, const float* b, int B, hipStream_t st, bf16* xn, bf16* map, float* feat,
-                  const Err& E, bf16* xb = nullptr, float* rstd = nullptr, float* mean = nullptr) {
-    const int M = B * m->L;
+                  const Err& E, bf16* xb = nullptr, float* rstd = nullptr, float* mean = nullptr, int rows = 0) {
+    const int M = rows ? rows : B * m->L;
     dispatch_width(m->C, [&](auto W) {
         hipLaunchKernelGGL((vbm::layernorm_kernel<decltype(W)::value>), dim3((M + 3) / 4), dim3(256), 0, st, resid, g, b, LN_EPS, M, m->L, m->LZ, m->F,
                            xn, map, feat, xb, rstd, mean);
@@ -424,6 +433,8 @@ int create(const vt_config* cfg, VbModel** out, std::string* err) {
         {kernel_ptr(vbs::attn_stream_kernel<L384>), vbs::LDS_BYTES},
         {kernel_ptr(vbs::attn_stream_masked_kernel<L256>), vbs::LDS_BYTES},
         {kernel_ptr(vbs::attn_stream_masked_kernel<L384>), vbs::LDS_BYTES},
+        {kernel_ptr(vbs::attn_stream_rt_kernel), vbs::LDS_BYTES},
+        {kernel_ptr(vbc::ce_score_all_rt_kernel), 16 * L384 * 4},
         {kernel_ptr(vbq::qkv_attn_kernel), vbq::LDS_BYTES},
         {kernel_ptr(vbq::qkv_attn_wide_kernel<C_LARGE>), vbq::LDS_BYTES}};
     for (const auto& k : dynamic_lds)
@@ -486,12 +497,27 @@ int set_candidate_elimination(VbModel* m, int n, const int32_t* loc, const doubl
     VB_HIP(fresh(m->ce_removed, B * LX, 0));
     VB_HIP(fresh(m->ce_scores, (size_t)n * B * LX, 0xff));      // NaN: what a stage that never runs (a no-op) reports
     VB_HIP(fresh(m->ce_part, B * (size_t)m->HEADS * LX, 0));
+    m->ce_index_off.assign(n, 0);
+    size_t nindex = 0;
+    for (int k = 0; k < n; ++k) { m->ce_index_off[k] = nindex; nindex += B * (size_t)keep[k]; }
+    VB_HIP(fresh(m->ce_index, nindex, 0));
+    VB_HIP(fresh(m->ce_src, B * LX, 0));
+    VB_HIP(fresh(m->ce_inv, B * LX, 0));
     if (int rc = upload(m->ce_rows, rows.data(), rows.size(), E)) return rc;
     m->ce_loc.assign(loc, loc + n);
     m->ce_keep = keep;
     m->ce_nrows = (int)rows.size();
     m->ce_first = first;
     m->ce_set = true;
+    return VT_OK;
+}
+
+int set_ce_form(VbModel* m, int form, std::string* err) {
+    const Err E{err};
+    if (m->C != C_BASE) return E.fail(VT_ERR_ARG, "candidate elimination is implemented for ViT-Base models (channels 768) only");
+    if (form != VT_CE_MASKED && form != VT_CE_COMPACT)
+        return E.fail(VT_ERR_ARG, "candidate elimination form " + std::to_string(form) + ": VT_CE_MASKED (0) or VT_CE_COMPACT (1)");
+    m->ce_form = form;
     return VT_OK;
 }
 
@@ -747,12 +773,32 @@ static int run_attention(const VbModel* m, const SliceView& v, const BlockW& b, 
     return VT_OK;
 }
 
+// A block's attention behind a compacting stage (the compact form of candidate elimination): qk GEMM + v GEMM on the slice's B * Lp dense
+// rows, then vbs::attn_stream_rt_kernel with the frames' nkeys live rows as keys, at either geometry
+static int run_attention_rt(const VbModel* m, const SliceView& v, const BlockW& b, const float* rstd, int B, int Lp, int nkeys, hipStream_t st, const Err& E) {
+    int rc;
+    const int C = m->C, HEADS = m->HEADS, M = B * Lp;
+    vbg::Args a{};
+    a.rstd = rstd;
+    a.X = v.xn; a.W = b.wqkv.p; a.bias = b.bqkv.p; a.out = v.qk;
+    a.M = M; a.N = 2 * C; a.K = C; a.ldo = 2 * C; a.rb = 4;
+    if ((rc = launch_gemm<256, 256, 2, 4, vbg::A_PLAIN, vbg::EPI_BF16>(a, 1, st, E, v.cus))) return rc;
+    vbg::Args w{};
+    w.X = v.xn; w.W = b.wqkv.p + (size_t)2 * C * C; w.bias = b.bqkv.p + 2 * C; w.vt = v.vt;
+    w.M = M; w.N = C; w.K = C; w.L = Lp; w.rstd = rstd;
+    if ((rc = launch_gemm<256, 256, 2, 4, vbg::A_PLAIN, vbg::EPI_VT>(w, 1, st, E, v.cus))) return rc;
+    hipLaunchKernelGGL(vbs::attn_stream_rt_kernel, dim3(B * HEADS * vbs::splits_rt(Lp)), dim3(256), vbs::LDS_BYTES, st, v.qk, v.vt, v.ao, HEADS, Lp, nkeys);
+    VB_HIP(hipGetLastError());
+    return VT_OK;
+}
+
 int blocks(VbModel* m, const float* tokens_in, int B, int nblocks, hipStream_t st, float* feat_out, float* resid_out, std::string* err,
            const Slice* sl) {
     const Err E{err};
     int rc = check(m, B, E);
     if (rc || (rc = check_slice(m, B, sl, E))) return rc;
-    const int M = B * m->L, C = m->C, HID = m->HID;
+    const int C = m->C, HID = m->HID;
+    int M = B * m->L;      // the slice's residual rows: B frames of L, behind a compacting stage B frames of Lc
     const SliceView v(m, B, sl);
     if (nblocks < 0 || nblocks > m->depth) nblocks = m->depth;
     if (tokens_in && tokens_in != v.resid)
@@ -763,10 +809,10 @@ int blocks(VbModel* m, const float* tokens_in, int B, int nblocks, hipStream_t s
     const float* const cmean = (fold && m->center) ? v.rmean : nullptr;
     if (fold && tokens_in && nblocks > 0 && (rc = run_layernorm(m, v.resid, nullptr, nullptr, B, st, nullptr, nullptr, nullptr, E, v.xn, rstd, v.rmean))) return rc;
     // a GEMM onto the residual stream; feeds_ln: a folded LayerNorm reads what it leaves (bf16 copy centred on cmean + statistics, then finalize)
-    auto resid_gemm = [&](const bf16* X, const bf16* W, const float* bias, int K, bool feeds_ln) {
+    auto resid_gemm = [&](const bf16* X, const bf16* W, const float* bias, int K, bool feeds_ln, const float* cm) {
         vbg::Args p{};
         p.X = X; p.W = W; p.bias = bias; p.resid = v.resid; p.M = M; p.N = C; p.K = K;
-        if (feeds_ln) { v.stats_of(p); p.cm = cmean; }
+        if (feeds_ln) { v.stats_of(p); p.cm = cm; }
         if (int r = launch_gemm<256, 256, 2, 4, vbg::A_PLAIN, vbg::EPI_RESID>(p, 1, st, E, v.cus)) return r;
         return feeds_ln ? run_finalize(m, v, M, st, E) : VT_OK;
     };
@@ -791,25 +837,85 @@ int blocks(VbModel* m, const float* tokens_in, int B, int nblocks, hipStream_t s
                            m->L, m->LZ);
         keys = next;
     };
+    // The compact form: the same score on the current rows (the first removing stage on the full frame, with the <L> kernels; later ones on
+    // the compacted rows at their run-time length), select on the current candidates, then the gather of the kept rows of ao / resid (and the
+    // rows' centring means) to the next stride.  The gather goes through the MLP's hidden workspace, idle between fc2 and the next fc1: frames
+    // are gathered in parallel and a frame's destination overlaps earlier frames' sources.  The residual rows are copied back; the proj
+    // GEMM, which follows, reads the attention rows and the means where the gather left them (proj_x / proj_cm).
+    const bool compact = ce && m->ce_form == VT_CE_COMPACT;
+    int Lc = m->L, nkeys = m->L;            // rows and live rows of a frame at the current stage
+    const int32_t* cidx = nullptr;          // the current index table; nullptr: nothing compacted yet
+    const bf16* proj_x = v.ao;
+    const float* proj_cm = cmean;
+    auto ce_stage_compact = [&](int k) -> int {
+        const int ncand = kept, keep = m->ce_keep[k], H = m->HEADS, LZ = m->LZ;
+        float* part = m->ce_part.p + v.f0 * H * LX;
+        const bool all = m->ce_nrows == LZ && !m->ce_plain;
+        if (!cidx) {
+            if (all && m->g384) hipLaunchKernelGGL(vbc::ce_score_all_kernel<L384>, dim3(B * H), dim3(256), 0, st, v.qk, nullptr, part, H, LZ);
+            else if (all) hipLaunchKernelGGL(vbc::ce_score_all_kernel<L256>, dim3(B * H), dim3(256), 0, st, v.qk, nullptr, part, H, LZ);
+            else if (m->g384) hipLaunchKernelGGL(vbc::ce_score_kernel<L384>, dim3(B * H), dim3(256), 0, st, v.qk, nullptr, m->ce_rows.p, m->ce_nrows, part, H, LZ);
+            else hipLaunchKernelGGL(vbc::ce_score_kernel<L256>, dim3(B * H), dim3(256), 0, st, v.qk, nullptr, m->ce_rows.p, m->ce_nrows, part, H, LZ);
+        } else if (all)
+            hipLaunchKernelGGL(vbc::ce_score_all_rt_kernel, dim3(B * H), dim3(256), 16 * Lc * 4, st, v.qk, Lc, nkeys, part, H, LZ);
+        else if (Lc <= 320)
+            hipLaunchKernelGGL(vbc::ce_score_rt_kernel<5>, dim3(B * H), dim3(256), 4 * Lc * 4, st, v.qk, Lc, nkeys, m->ce_rows.p, m->ce_nrows, part, H, LZ);
+        else
+            hipLaunchKernelGGL(vbc::ce_score_rt_kernel<12>, dim3(B * H), dim3(256), 4 * Lc * 4, st, v.qk, Lc, nkeys, m->ce_rows.p, m->ce_nrows, part, H, LZ);
+        VB_HIP(hipGetLastError());
+        int32_t* next = m->ce_index.p + m->ce_index_off[k] + v.f0 * keep;
+        int32_t* src = m->ce_src.p + v.f0 * LX;
+        hipLaunchKernelGGL(vbc::ce_select_compact_kernel, dim3(B), dim3(256), 0, st, part, cidx, next, src, m->ce_inv.p + v.f0 * LX, m->ce_removed.p + v.f0 * LX,
+                           m->ce_scores.p + ((size_t)k * m->maxB + v.f0) * LX, H, 1.0f / (float)(H * m->ce_nrows), k + 1, ncand, keep, m->LX);
+        VB_HIP(hipGetLastError());
+        const int Ln = m->ce_lp(k);
+        const size_t rows = (size_t)B * Ln;
+        bf16* gao = v.hid;
+        float* gres = reinterpret_cast<float*>(v.hid + rows * C);
+        float* gmean = gres + rows * C;
+        hipLaunchKernelGGL(vbc::ce_gather_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, v.ao, v.resid, v.rmean, src, gao, gres, gmean, B, Lc, Ln,
+                           LZ, keep, m->LX, C);
+        VB_HIP(hipGetLastError());
+        VB_HIP(hipMemcpyAsync(v.resid, gres, rows * C * 4, hipMemcpyDeviceToDevice, st));
+        Lc = Ln; nkeys = LZ + keep; M = B * Ln; cidx = next;
+        proj_x = gao;
+        if (cmean) proj_cm = gmean;
+        return VT_OK;
+    };
     for (int i = 0; i < nblocks; ++i) {
         const BlockW& b = m->blk[i];
-        if (!fold && (rc = run_layernorm(m, v.resid, b.ln1g.p, b.ln1b.p, B, st, v.xn, nullptr, nullptr, E))) return rc;
-        if ((rc = run_attention(m, v, b, rstd, B, st, E, ce && i >= m->ce_first, keys))) return rc;
+        if (!fold && (rc = run_layernorm(m, v.resid, b.ln1g.p, b.ln1b.p, B, st, v.xn, nullptr, nullptr, E, nullptr, nullptr, nullptr, M))) return rc;
+        if (cidx) rc = run_attention_rt(m, v, b, rstd, B, Lc, nkeys, st, E);
+        else rc = run_attention(m, v, b, rstd, B, st, E, ce && i >= m->ce_first, keys);
+        if (rc) return rc;
+        proj_x = v.ao; proj_cm = cmean;
         if (ce && stage < (int)m->ce_loc.size() && m->ce_loc[stage] == i) {
             if (m->ce_keep[stage] < kept) {      // a stage that keeps every token it meets is a no-op, as attn_blocks.py:40-41 returns early
-                ce_stage(stage);
+                if (compact) { if ((rc = ce_stage_compact(stage))) return rc; }
+                else ce_stage(stage);
                 VB_HIP(hipGetLastError());
                 kept = m->ce_keep[stage];
             }
             ++stage;
         }
-        if ((rc = resid_gemm(v.ao, b.wproj.p, b.bproj.p, C, fold))) return rc;
-        if (!fold && (rc = run_layernorm(m, v.resid, b.ln2g.p, b.ln2b.p, B, st, v.xn, nullptr, nullptr, E))) return rc;
+        if ((rc = resid_gemm(proj_x, b.wproj.p, b.bproj.p, C, fold, proj_cm))) return rc;
+        if (!fold && (rc = run_layernorm(m, v.resid, b.ln2g.p, b.ln2b.p, B, st, v.xn, nullptr, nullptr, E, nullptr, nullptr, nullptr, M))) return rc;
         vbg::Args f1{};
         f1.rstd = rstd;
         f1.X = v.xn; f1.W = b.w1.p; f1.bias = b.b1.p; f1.out = v.hid; f1.M = M; f1.N = HID; f1.K = C; f1.ldo = HID; f1.rb = 4;
         if ((rc = launch_gemm<256, 256, 2, 4, vbg::A_PLAIN, vbg::EPI_GELU>(f1, 1, st, E, v.cus))) return rc;
-        if ((rc = resid_gemm(v.hid, b.w2.p, b.b2.p, HID, fold && i + 1 < nblocks))) return rc;      // the final norm reads the f32 stream itself
+        if ((rc = resid_gemm(v.hid, b.w2.p, b.b2.p, HID, fold && i + 1 < nblocks, cmean))) return rc;      // the final norm reads the f32 stream itself
+    }
+    if (cidx) {      // compacted rows: the final norm scatters through the last stage's table, removed tokens' rows are zeros (vit_ce.py:170-181)
+        const int32_t* inv = m->ce_inv.p + v.f0 * LX;
+        if (resid_out) {
+            hipLaunchKernelGGL(vbc::ce_scatter_rows_kernel, dim3((B * m->L + 3) / 4), dim3(256), 0, st, v.resid, inv, resid_out, B, Lc, m->L, m->LZ, C);
+            VB_HIP(hipGetLastError());
+        }
+        hipLaunchKernelGGL(vbc::ce_final_norm_kernel<C_BASE>, dim3((B * m->LX + 3) / 4), dim3(256), 0, st, v.resid, m->ng.p, m->nb.p, LN_EPS, inv, B, Lc, m->LZ,
+                           m->LX, m->F, v.map[0], feat_out);
+        VB_HIP(hipGetLastError());
+        return VT_OK;
     }
     if (resid_out) VB_HIP(hipMemcpyAsync(resid_out, v.resid, (size_t)M * C * 4, hipMemcpyDeviceToDevice, st));
     if ((rc = run_layernorm(m, v.resid, m->ng.p, m->nb.p, B, st, nullptr, v.map[0], feat_out, E))) return rc;

@@ -1566,6 +1566,16 @@ int vt_set_candidate_elimination(vt_model* m, int32_t n, const int32_t* loc, con
     return VT_OK;
 }
 
+int vt_set_ce_form(vt_model* m, int32_t form) {
+    if (!m) return fail(VT_ERR_ARG, "null model");
+    if (!m->vb) return fail(VT_ERR_ARG, "candidate elimination is implemented for ViT-Base models (channels 768) only");
+    if (m->graphs_captured > 0)
+        return fail(VT_ERR_STATE, "captured graphs hold the routes and stage buffers of their capture: set the candidate-elimination form before capturing");
+    std::string err;
+    if (int rc = vb::set_ce_form(m->vb, form, &err)) return fail(rc, err);
+    return VT_OK;
+}
+
 int vt_ce_result(vt_model* m, int32_t B, void* stream, uint8_t* removed_stage_dev, float* scores_dev) {
     if (!m) return fail(VT_ERR_ARG, "null model");
     if (!m->vb) return fail(VT_ERR_ARG, "candidate elimination is implemented for ViT-Base models (channels 768) only");

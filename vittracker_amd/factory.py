@@ -20,5 +20,12 @@ def network_builder(cfg):
     return build_ostrack_dist
 
 
-def build_network(cfg, max_batch: int = 1):
-    return network_builder(cfg)(cfg, max_batch=max_batch)
+def build_network(cfg, max_batch: int = 1, ce_form=None):
+    """ce_form: the form a candidate-elimination backbone runs in (model_vitb.build_ostrack); the vit_48 family has none."""
+    from .model_vitb import build_ostrack
+    builder = network_builder(cfg)
+    if builder is build_ostrack:
+        return builder(cfg, max_batch=max_batch, ce_form=ce_form)
+    if ce_form is not None:
+        raise ValueError(f"ce_form={ce_form!r}: the vit_48 family has no candidate elimination")
+    return builder(cfg, max_batch=max_batch)

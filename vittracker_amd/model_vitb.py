@@ -11,8 +11,10 @@ Arithmetic runs in ``libvittrack_hip.so`` (bf16 MFMA contractions, f32 accumulat
 no CPU execution path.
 
 The candidate-elimination backbone ``vit_base_patch16_224_ce`` (``lib/models/ostrack/vit_ce.py``; every published OSTrack checkpoint) is
-accepted with a non-empty ``CE_LOC`` of the length of ``CE_KEEP_RATIO`` and runs by key masking (``native.Model.set_candidate_elimination``,
-DESIGN.md 11.4): the kept tokens take the reference's values, removed tokens come back as zeros, nothing is faster.  The template rows of
+accepted with a non-empty ``CE_LOC`` of the length of ``CE_KEEP_RATIO`` and runs in one of two forms (``native.Model.set_candidate_elimination``,
+DESIGN.md 11.4): by key masking (``ce_form="masked"``, the default: no token moves, nothing is faster) or compacted (``ce_form="compact"``:
+the kept tokens are gathered into shorter frames behind every stage, as the reference does).  Either way the kept tokens take the
+reference's values and removed tokens come back as zeros.  ``ce_form=None`` reads the environment variable ``VB_CE_FORM``.  The template rows of
 the score come from ``CE_TEMPLATE_RANGE`` as ``lib/utils/ce_utils.py:15-49`` picks them (``ALL``, ``CTR_POINT``, ``CTR_REC``), one
 selection per model.  Not implemented (NotImplementedError): ViT-Large CE, ``CE_TEMPLATE_RANGE: GT_BOX``, a ``ce_keep_rate`` argument
 of ``forward``, a ``_ce`` TYPE without ``CE_LOC``, and the prompt / draw variants (``MODEL.PROCESS.*``)."""
@@ -53,12 +55,13 @@ def ce_template_rows(template_range: str, feat_sz_z: int):
 
 
 class OSTrack(OstrackDist):
-    def __init__(self, cfg, depth=None, max_batch=1):
+    def __init__(self, cfg, depth=None, max_batch=1, ce_form=None):
         g = geometry(cfg)
         if g["head_type"] != "CENTER":
             raise ValueError("HEAD TYPE %s is not supported." % g["head_type"])
         bb_type = str(cfg.MODEL.BACKBONE.TYPE)
         self.ce_loc, self.ce_keep_ratio, self.ce_rows = [], [], None
+        self.ce_form = native.ce_form_name(ce_form)      # "masked" | "compact"; read by a candidate-elimination backbone only
         if bb_type == "vit_large_patch16_224":
             g["channels"], g["heads"] = VIT_LARGE["channels"], VIT_LARGE["heads"]
             depth = VIT_LARGE["depth"] if depth is None else depth
@@ -90,7 +93,7 @@ class OSTrack(OstrackDist):
         fresh = self._nat is None
         nat = OstrackDist._native(self)
         if fresh and self.ce_loc:      # every entry point of the native model (forward, forward_u8, track_step*, captures) then runs with it
-            nat.set_candidate_elimination(self.ce_loc, self.ce_keep_ratio, self.ce_rows)
+            nat.set_candidate_elimination(self.ce_loc, self.ce_keep_ratio, self.ce_rows, form=self.ce_form)
         return nat
 
     def _check_ce_mask(self, mask, B):
@@ -144,7 +147,8 @@ class OSTrack(OstrackDist):
     __call__ = forward
 
 
-def build_ostrack(cfg, training=False, max_batch=1):
+def build_ostrack(cfg, training=False, max_batch=1, ce_form=None):
+    """ce_form: "masked" | "compact", the form a candidate-elimination backbone runs in; None: VB_CE_FORM, else "masked"."""
     if training:
         raise NotImplementedError("inference graph only")
-    return OSTrack(cfg, max_batch=max_batch)
+    return OSTrack(cfg, max_batch=max_batch, ce_form=ce_form)

@@ -73,6 +73,7 @@ ABI = {
     "vt_patch_u8_supported": (C.c_int, [_vp, _i32]),
     "vt_crop_form": (C.c_int, []),
     "vt_set_candidate_elimination": (C.c_int, [_vp, _i32, C.POINTER(_i32), C.POINTER(C.c_double), _vp]),
+    "vt_set_ce_form": (C.c_int, [_vp, _i32]),
     "vt_ce_result": (C.c_int, [_vp, _i32, _vp, _vp, _vp]),
 }
 # the three frame sources of the crops and of the step: a dense (B,H,W,3) batch (frames, H, W), a vt_frame table, a vt_image table
@@ -656,6 +657,25 @@ def ce_keep_counts(len_x: int, keep_ratio):
     return out
 
 
+#: the forms candidate elimination runs in (include/vittrack.h VT_CE_MASKED / VT_CE_COMPACT)
+CE_FORMS = {"masked": 0, "compact": 1}
+
+
+def ce_form_name(form=None) -> str:
+    """The form's name: `form`, or without one the environment variable VB_CE_FORM, or "masked"."""
+    if form is None:
+        form = os.environ.get("VB_CE_FORM") or "masked"
+    if form not in CE_FORMS:
+        raise VtError(f"candidate elimination form {form!r}: one of {sorted(CE_FORMS)}")
+    return form
+
+
+def ce_compact_lengths(len_z: int, len_x: int, keep_ratio):
+    """Rows of a frame behind each stage in the compact form: template rows + kept search tokens, rounded up to 16
+    (0.7, 0.7, 0.7: 256 / 192 / 160 at 64 + 256 tokens, 560 / 432 / 352 at 144 + 576)."""
+    return [(int(len_z) + k + 15) // 16 * 16 for k in ce_keep_counts(len_x, keep_ratio)]
+
+
 def crop_form() -> int:
     """Which crop kernel form the current device runs: 1 = 8-byte unaligned windows (crop_fast_kernel / crop_kernel<false>), 2 = the
     byte-load fallback the device self test selects on any mismatch."""
@@ -721,6 +741,8 @@ class Graph:
 
 class Model:
     """Owns one ``vt_model`` (weights + workspace on the current device)."""
+
+    ce_form = "masked"      # the form set_candidate_elimination chose
 
     def __init__(self, template_size, search_size, channels=48, heads=1, depth=3, head_channels=32, stride=16,
                  max_batch=1, precision="f32"):
@@ -1029,10 +1051,13 @@ class Model:
         """Preprocessor's mean / std for the uint8 entry points (folded into the stem's first layer; default: ImageNet)."""
         _check(self._L.vt_set_normalization(self._h, _f3(mean), _f3(std)), "vt_set_normalization", self._L)
 
-    def set_candidate_elimination(self, loc, keep_ratio, template_rows=None):
-        """OSTrack candidate elimination by key masking (vt_set_candidate_elimination): after block loc[k] the search tokens are ranked
-        by the attention they receive from the selected template rows and ceil(keep_ratio[k] * kept so far) stay present as keys.
-        template_rows: (len_z,) booleans, None = every row.  Before any capture; ViT-Base models only."""
+    def set_candidate_elimination(self, loc, keep_ratio, template_rows=None, form=None):
+        """OSTrack candidate elimination (vt_set_candidate_elimination): after block loc[k] the search tokens are ranked by the attention
+        they receive from the selected template rows and ceil(keep_ratio[k] * kept so far) stay.  template_rows: (len_z,) booleans, None =
+        every row.  form (vt_set_ce_form): "masked" -- removed tokens stay in place as absent keys -- or "compact" -- the kept tokens are
+        gathered into shorter frames (ce_compact_lengths) behind every stage; None reads VB_CE_FORM and falls back to "masked".  Same
+        results either way; the chosen form is ``ce_form``.  Before any capture; ViT-Base models only."""
+        form = ce_form_name(form)
         loc, keep_ratio = [int(v) for v in loc], [float(v) for v in keep_ratio]
         if len(loc) != len(keep_ratio):
             raise VtError(f"candidate elimination: {len(loc)} blocks (CE_LOC) for {len(keep_ratio)} keep ratios (CE_KEEP_RATIO)")
@@ -1045,6 +1070,8 @@ class Model:
         _check(self._L.vt_set_candidate_elimination(self._h, n, (C.c_int32 * max(n, 1))(*loc), (C.c_double * max(n, 1))(*keep_ratio),
                                                     rows.ctypes.data if rows is not None else None),
                "vt_set_candidate_elimination", self._L)
+        _check(self._L.vt_set_ce_form(self._h, CE_FORMS[form]), "vt_set_ce_form", self._L)
+        self.ce_form = form
         self.ce_stages = n
         self.ce_keep = ce_keep_counts(self.len_x, keep_ratio)
 

@@ -23,4 +23,6 @@ def parameters(yaml_name: str, env=None):
     params.search_size = cfg.TEST.SEARCH_SIZE
     params.checkpoint = os.path.join(env.save_dir, "checkpoints/train/ostrack/%s/OSTrack_ep%04d.pth.tar" % (yaml_name, cfg.TEST.EPOCH))
     params.save_all_boxes = False
+    #: candidate-elimination YAMLs: "masked" | "compact" (model_vitb.build_ostrack); None: the environment variable VB_CE_FORM, else "masked"
+    params.ce_form = None
     return params
