@@ -231,6 +231,20 @@ int vt_patch_u8_supported(const vt_model* m, int32_t B);
 /* Which crop kernel form the current device runs (decided once per device by a self test against a byte-load twin):
  * 1 = the 8-byte unaligned-window form, 2 = the byte-load form, negative = the self test could not run. */
 int vt_crop_form(void);
+/* Which GEMM kinds of a plain vt_forward of B frames run on the narrow 128 x 64 tile instead of the 256 x 256 one (ViT-Base / ViT-Large
+ * models).  Both tiles sum every output element in one workgroup in the same order, so the results are the same bits; the narrow tile is
+ * chosen per launch where the wide tiles would leave most compute units idle (small B).  VB_GEMM_NARROW, read at vt_create: -1 = that
+ * automatic choice (default), 0 = never, 1 = wherever a narrow instantiation exists.  A captured graph keeps the tiles of its capture.
+ * The v projection (stored transposed) and head convs 2-4 of 64 columns have one tile form and no bit.  vit_48 and shape-generic models: 0.
+ * NULL model: -1, vt_last_error "null model". */
+#define VT_GEMM_PATCH 1  /* patch embedding */
+#define VT_GEMM_QK 2     /* q | k projection, where the model's attention route launches it as a GEMM (192 / 384 geometry, candidate
+                            elimination, VB_FUSED_QKV=0); 0 under the fused qkv + attention kernel */
+#define VT_GEMM_PROJ 4   /* attention output projection */
+#define VT_GEMM_FC1 8    /* MLP fc1 */
+#define VT_GEMM_FC2 16   /* MLP fc2 */
+#define VT_GEMM_HEAD 32  /* head conv1 of the three towers (and conv2, chosen by its own tile count) */
+int vt_gemm_form(const vt_model* m, int32_t B);
 
 /* The tail of Vit_dist.track (lib/test/tracker/vit_dist.py:107-111,150-156; clip_box,
  * lib/utils/box_ops.py:97-106): scale the windowed box back to image pixels, map it to the frame,

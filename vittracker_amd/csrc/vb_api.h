@@ -52,6 +52,8 @@ int set_candidate_elimination(VbModel* m, int n, const int32_t* loc, const doubl
 // The form the stages run in from the next blocks() on: VT_CE_MASKED (the default) or VT_CE_COMPACT (vb_ce.h); ViT-Base only.
 int set_ce_form(VbModel* m, int form, std::string* err);
 int ce_result(VbModel* m, int B, hipStream_t st, uint8_t* removed_stage, float* scores, std::string* err);
+// Which GEMM kinds of a plain forward of B frames run the narrow 128 x 64 tile: the VT_GEMM_* bits of include/vittrack.h (vt_gemm_form)
+int gemm_form(const VbModel* m, int B);
 // blocks[0..nblocks) on the residual stream (tokens_in: optional replacement, copied in first), then the final norm:
 // the search rows go to the head's input map (and to feat_out as f32 (B,Lx,C), optional); resid_out optional copy
 int blocks(VbModel* m, const float* tokens_in, int B, int nblocks, hipStream_t st, float* feat_out, float* resid_out, std::string* err,

@@ -16,7 +16,12 @@
 //
 // Pipeline (256 x 256 tile): the software-pipelined k-loop below (two LDS stages of one 64-deep k-tile, one DMA piece per
 // group of 8 MFMAs, two barriers per k-tile, counted vmcnt).  The narrow tile (256 x 64, head convs 2-4) keeps a simple
-// two-buffer 64-deep loop.  (Rounds 2-3 also carried a 4-stage, a whole-line two-stage and a phase-interleaved form of the wide
+// two-buffer 64-deep loop.  The 128 x 64 tile is the narrow form of the ViT GEMMs for launches whose 256 x 256 tiles would leave most
+// CUs idle (a few sequences; vitb.hip narrow_pick): eight times the workgroups, a ring of four 24 KiB stages with counted vmcnt.  Every
+// output element keeps its whole sum in one workgroup and in the wide loop's order (k-tiles ascending, k-step 0 then 1, from zero) and
+// goes through the same epilogue arithmetic, and a wave's sub-tile is 64 features wide under either tile, so the LayerNorm statistics are
+// the same slices: the two forms give the same bits (tests/test_gpu_vitb_narrow.py).  EPI_VT has no narrow form: its transposed store
+// moves 128 tokens of a feature per row, which takes TM == 8.  (Rounds 2-3 also carried a 4-stage, a whole-line two-stage and a phase-interleaved form of the wide
 // loop; all measured slower -- NOTES_r1_r3.md -- and were removed in round 5.)
 //
 // XCD-aware tile order: consecutive workgroup ids are dealt round-robin over the 8 XCDs, so id -> (id % 8) * per_xcd +
@@ -67,6 +72,11 @@
 #endif
 
 namespace vbg {
+
+// LDS stages of one 64-deep k-tile.  Tiles of fewer than 256 tokens (the narrow form of the launches that leave most CUs idle under the
+// 256 x 256 tile) run a ring of four with counted vmcnt: three k-tiles in flight in front of the one being multiplied.
+template <int BM, int BN>
+constexpr int stages() { return BM < 256 ? 4 : 2; }
 
 typedef __bf16 bf16;
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
@@ -178,7 +188,9 @@ __global__ __launch_bounds__(NWAVES * 64) void gemm_kernel(const Args a) {
     constexpr int BUF_BYTES = (SX + SW) * 1024;
     constexpr bool WIDE = (BM / 16) % NWAVES == 0 && (BN / 16) % NWAVES == 0;      // the 256 x 256 tile
     constexpr bool SWP = WIDE;
-    constexpr int EP_OFF = 2 * BUF_BYTES;                                           // epilogue staging: 8 waves x 4 KiB behind the stages
+    constexpr int NSTG = stages<BM, BN>();                                          // LDS stages of one k-tile: 2, the narrow tiles' ring 4
+    constexpr bool RING = NSTG > 2;
+    constexpr int EP_OFF = NSTG * BUF_BYTES;                                        // epilogue staging: 8 waves x 4 KiB behind the stages
     extern __shared__ __attribute__((aligned(16))) char smem[];
 
     const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -263,7 +275,7 @@ __global__ __launch_bounds__(NWAVES * 64) void gemm_kernel(const Args a) {
         if constexpr (LNC) {
             if (a.rstd) {
 #pragma unroll
-                for (int h = 0; h < TM * 16 / 64; ++h) {
+                for (int h = 0; h < (TM * 16 + 63) / 64; ++h) {      // (a sub-tile of fewer than 64 tokens: one request, its tail unused)
                     int m = m0 + wm * TM * 16 + h * 64 + lane;
                     m = m < a.M ? m : a.M - 1;
                     __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(a.rstd + m),
@@ -417,13 +429,14 @@ __global__ __launch_bounds__(NWAVES * 64) void gemm_kernel(const Args a) {
             if (a.n_split) { const int t = nw / a.n_split; obase += (size_t)t * a.gOut; ncol = nw - t * a.n_split; }
         }
 #pragma unroll
-        for (int c = 0; c < TM / 2; ++c) {
+        for (int c = 0; c < (TM + 1) / 2; ++c) {       // (an odd TM: the last chunk holds 16 rows)
 #pragma unroll
             for (int jj = 0; jj < 2; ++jj) {
-                const int row = jj * 16 + l15;
+                const int row = jj * 16 + l15, j = 2 * c + jj < TM ? 2 * c + jj : TM - 1;
+                if (2 * c + jj >= TM) continue;
 #pragma unroll
                 for (int i = 0; i < TN; ++i) {
-                    f4 v = LNC ? fma4(acc[i][2 * c + jj], splat4(rs[2 * c + jj]), bs[i]) : acc[i][2 * c + jj] + bs[i];
+                    f4 v = LNC ? fma4(acc[i][j], splat4(rs[j]), bs[i]) : acc[i][j] + bs[i];
                     if constexpr (EPI == EPI_GELU) v = gelu4(v);
                     if constexpr (EPI == EPI_CONV) v = f4{fmaxf(v.x, 0.f), fmaxf(v.y, 0.f), fmaxf(v.z, 0.f), fmaxf(v.w, 0.f)};
                     *reinterpret_cast<bf16x4a*>(ep + row * 128 + (((i * 2 + (q4 >> 3)) ^ (row & 7)) << 4) + (q4 & 4) * 2) = to_bf16x4(v);
@@ -432,6 +445,7 @@ __global__ __launch_bounds__(NWAVES * 64) void gemm_kernel(const Args a) {
             lds_fence();
 #pragma unroll
             for (int t = 0; t < 4; ++t) {
+                if (2 * c + t / 2 >= TM) continue;
                 const int row = 8 * t + (lane >> 3), ch = lane & 7;
                 const uint4 v = *reinterpret_cast<const uint4a*>(ep + row * 128 + ((ch ^ (row & 7)) << 4));
                 const int m = mw + c * 32 + row;
@@ -729,6 +743,52 @@ __global__ __launch_bounds__(NWAVES * 64) void gemm_kernel(const Args a) {
             if (!more) break;
             stage_vec(m0, n0);           // the next tile's bias / rstd; the wait at the top of the loop covers them
         }
+    } else if constexpr (RING) {
+        // ---- The narrow tiles: a ring of four stages of one 64-deep k-tile, ONE barrier per k-tile, counted vmcnt.  In front of k-tile kt
+        // a wave waits until all of its DMA but the NS instructions each of k-tiles kt + 1 and kt + 2 has landed (loads return in order),
+        // the barrier then says the same of every wave and that every wave is done reading k-tile kt - 1, whose stage takes k-tile kt + 3.
+        // Per accumulator the sum runs as in the other two loops: k-tiles ascending, k-step 0 then k-step 1, from zero.
+        static_assert(NSTG == 4, "the tail's waits are written for two k-tiles in flight behind the current one");
+        const int nk = a.K / BK;
+        auto prologue = [&]() {
+#pragma unroll
+            for (int s = 0; s < NSTG - 1; ++s)
+                if (s < nk) stage(s, smem + s * BUF_BYTES);
+        };
+        set_sources(m0, n0);
+        prologue();
+        for (;;) {
+            zero_acc();
+            for (int kt = 0; kt < nk; ++kt) {
+                const int rem = nk - 1 - kt;      // k-tiles behind this one; min(rem, 2) of them have been requested
+                if (rem >= 2) asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(2 * NS) : "memory");
+                else if (rem == 1) asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(NS) : "memory");
+                else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+                __builtin_amdgcn_s_barrier();
+                if (kt + NSTG - 1 < nk) stage(kt + NSTG - 1, smem + ((kt + NSTG - 1) % NSTG) * BUF_BYTES);
+                const char* cur = smem + (kt % NSTG) * BUF_BYTES;
+                const char* xp = cur + (wm * TM * 2) * 1024 + fr;
+                const char* wp = cur + (SX + wn * TN * 2) * 1024 + fr;
+#pragma unroll
+                for (int kk = 0; kk < 2; ++kk) mfma_step(xp + kk * 1024, wp + kk * 1024, 2048);
+            }
+            const int cm0 = m0, cn0 = n0;
+            vb += gridDim.x;
+            const bool more = vb < nwg;
+            if (more) {      // the next tile's first three k-tiles go out ahead of the epilogue, once every wave is done reading the last one
+                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+                __builtin_amdgcn_s_barrier();
+                tile_of(vb, m0, n0);
+                set_sources(m0, n0);
+                prologue();
+            }
+            epilogue(cm0, cn0);
+            if (!more) break;
+            stage_vec(m0, n0);
+            // the epilogue's stores and loads count in vmcnt with the DMA, and stores do not return in order with loads: drain before the
+            // counted waits start again
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        }
     } else {
         const int nk = a.K / BK;
         // ---- two buffers of one 64-deep k-tile; the DMA of the next tile's first k-tile is issued ahead of the epilogue
@@ -767,6 +827,6 @@ __global__ __launch_bounds__(NWAVES * 64) void gemm_kernel(const Args a) {
 }
 
 template <int BM, int BN>
-constexpr int lds_bytes() { return 2 * (BM / 16 * 2 + BN / 16 * 2) * 1024 + NWAVES * 4096; }   // pipeline stages + epilogue staging
+constexpr int lds_bytes() { return stages<BM, BN>() * (BM / 16 * 2 + BN / 16 * 2) * 1024 + NWAVES * 4096; }   // pipeline stages + epilogue staging
 
 }  // namespace vbg

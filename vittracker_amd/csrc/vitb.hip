@@ -33,6 +33,9 @@ constexpr int C_BASE = 768, HEADS_BASE = 12, C_LARGE = 1024, HEADS_LARGE = 16;
 // 144 + 576 = 720.  The model carries its own (VbModel::L, LZ, LX, F, TZ, TX); the token counts below are the attention kernels' template arguments.
 constexpr int L256 = 320, L384 = 720;
 constexpr float LN_EPS = 1e-6f;
+// The automatic tile choice (narrow_pick): narrow where the 256 x 256 tiles of a launch number at most this many per cent of the slice's CUs
+// (the sweep of tools/vitb_latency.py)
+constexpr int NARROW_FILL = 33;
 constexpr int HEAD_CH[5] = {0 /* the model's width: VbModel::head_ch */, 256, 128, 64, 32};
 
 struct Err {
@@ -105,6 +108,10 @@ struct VbModel {
     float u8_centre = 128.f;        // VB_U8_CENTER=0: the uncentred fold (diagnostic: NOTES R7-1 shows it over the token bound)
     Buf<bf16> zop;           // template cache: the templates' operand rows [max_batch * LZ][PATCH_K]
     bool center = true;      // VB_LN_CENTER
+    // VB_GEMM_NARROW (read at vt_create): -1 = per launch, the 128 x 64 tile where the 256 x 256 tiles would fill at most narrow_fill per cent
+    // of the slice's CUs (narrow_pick); 0 = never; 1 = wherever a narrow instantiation exists.  Both tiles give the same bits (vb_gemm.h)
+    int gemm_narrow = -1;
+    int narrow_fill = NARROW_FILL;      // VB_GEMM_NARROW_FILL: the threshold of the automatic choice (tools/vitb_latency.py sweeps it)
     Buf<vbg::f2> stats;
     // candidate elimination by key masking (vb_ce.h; vb::set_candidate_elimination).  ce_loc / ce_keep: per stage its block and its count of
     // kept search tokens (a count equal to the previous one: the stage is a no-op and runs nothing); ce_first: the block of the first stage
@@ -236,6 +243,22 @@ template <typename F>
 void dispatch_width(int C, F&& f) {
     if (C == C_LARGE) f(std::integral_constant<int, C_LARGE>{});
     else f(std::integral_constant<int, C_BASE>{});
+}
+
+// Which tile a GEMM launch runs, from its count of 256 x 256 tiles and the slice's CUs alone: the narrow tile where the wide ones would leave
+// most of the CUs idle.  One rule for launch_tile and vb::gemm_form.
+bool narrow_pick(const VbModel* m, int M, int N, int groups, int cus) {
+    if (m->gemm_narrow >= 0) return m->gemm_narrow != 0;
+    const long long wide = (long long)((M + 255) / 256) * ((N + 255) / 256) * groups;
+    const int budget = cus > 0 ? std::min(cus, num_cus()) : num_cus();
+    return wide * 100 <= (long long)m->narrow_fill * budget;
+}
+
+// A GEMM kind of the ViT path on the tile narrow_pick chooses for this launch
+template <int AMODE, int EPI>
+int launch_tile(const VbModel* m, const vbg::Args& a, int groups, hipStream_t st, const Err& E, int cus) {
+    if (narrow_pick(m, a.M, a.N, groups, cus)) return launch_gemm<128, 64, 8, 1, AMODE, EPI>(a, groups, st, E, cus);
+    return launch_gemm<256, 256, 2, 4, AMODE, EPI>(a, groups, st, E, cus);
 }
 
 template <typename K>
@@ -393,6 +416,8 @@ int create(const vt_config* cfg, VbModel** out, std::string* err) {
     m->zshift = log2_exact(LZ); m->xshift = log2_exact(LX);
     m->fold = env_int("VB_LN_FOLD", 1) != 0;
     m->center = env_int("VB_LN_CENTER", 1) != 0;
+    m->gemm_narrow = env_int("VB_GEMM_NARROW", -1);
+    m->narrow_fill = env_int("VB_GEMM_NARROW_FILL", NARROW_FILL);
     m->fused_qkv = env_int("VB_FUSED_QKV", 1) != 0;
     m->u8_centre = env_int("VB_U8_CENTER", 1) != 0 ? 128.f : 0.f;
     m->attn_stream = env_int("VB_ATTN_STREAM", 0) != 0;
@@ -428,6 +453,13 @@ int create(const vt_config* cfg, VbModel** out, std::string* err) {
         {kernel_ptr(gemm_kernel<256, 256, 2, 4, A_PLAIN, EPI_GELU>), lds_bytes<256, 256>()},
         {kernel_ptr(gemm_kernel<256, 256, 2, 4, A_CONV, EPI_CONV>), lds_bytes<256, 256>()},
         {kernel_ptr(gemm_kernel<256, 64, 8, 1, A_CONV, EPI_CONV>), lds_bytes<256, 64>()},
+        {kernel_ptr(gemm_kernel<128, 64, 8, 1, A_PLAIN, EPI_PATCH>), lds_bytes<128, 64>()},
+        {kernel_ptr(gemm_kernel<128, 64, 8, 1, A_PLAIN, EPI_PATCH_ROWS>), lds_bytes<128, 64>()},
+        {kernel_ptr(gemm_kernel<128, 64, 8, 1, A_PLAIN, EPI_PATCH_ROWS_N>), lds_bytes<128, 64>()},
+        {kernel_ptr(gemm_kernel<128, 64, 8, 1, A_PLAIN, EPI_BF16>), lds_bytes<128, 64>()},
+        {kernel_ptr(gemm_kernel<128, 64, 8, 1, A_PLAIN, EPI_RESID>), lds_bytes<128, 64>()},
+        {kernel_ptr(gemm_kernel<128, 64, 8, 1, A_PLAIN, EPI_GELU>), lds_bytes<128, 64>()},
+        {kernel_ptr(gemm_kernel<128, 64, 8, 1, A_CONV, EPI_CONV>), lds_bytes<128, 64>()},
         {kernel_ptr(vba::attn_kernel<L256, HD>), vba::Geo<L256, HD>::LDS_BYTES},
         {kernel_ptr(vbs::attn_stream_kernel<L256>), vbs::LDS_BYTES},
         {kernel_ptr(vbs::attn_stream_kernel<L384>), vbs::LDS_BYTES},
@@ -653,7 +685,7 @@ int stem(VbModel* m, const float* z, const float* x, int B, hipStream_t st, floa
     a.M = M; a.N = C; a.K = PATCH_K; a.L = L;
     if (m->fold) v.stats_of(a);
     if (m->fold && m->center) { a.cm = m->cpos.p; a.cm_mod = L; }
-    if ((rc = launch_gemm<256, 256, 2, 4, vbg::A_PLAIN, vbg::EPI_PATCH>(a, 1, st, E, v.cus))) return rc;
+    if ((rc = launch_tile<vbg::A_PLAIN, vbg::EPI_PATCH>(m, a, 1, st, E, v.cus))) return rc;
     if (m->fold && (rc = run_finalize(m, v, M, st, E))) return rc;
     if (tokens_out) VB_HIP(hipMemcpyAsync(tokens_out, v.resid, (size_t)M * C * 4, hipMemcpyDeviceToDevice, st));
     return VT_OK;
@@ -705,8 +737,8 @@ int stem_rows(VbModel* m, ZSrc zsrc, const float* z, const float* x, const unsig
     // operand rows -> (frame, token): a shift at 64 / 256 rows per frame, the rows themselves at 144 / 576 (EPI_PATCH_ROWS_N)
     auto rows_gemm = [&](vbg::Args& g, int rows, int shift) {
         g.row_shift = shift < 0 ? rows : shift;
-        return shift < 0 ? launch_gemm<256, 256, 2, 4, vbg::A_PLAIN, vbg::EPI_PATCH_ROWS_N>(g, 1, st, E, v.cus)
-                       : launch_gemm<256, 256, 2, 4, vbg::A_PLAIN, vbg::EPI_PATCH_ROWS>(g, 1, st, E, v.cus);
+        return shift < 0 ? launch_tile<vbg::A_PLAIN, vbg::EPI_PATCH_ROWS_N>(m, g, 1, st, E, v.cus)
+                       : launch_tile<vbg::A_PLAIN, vbg::EPI_PATCH_ROWS>(m, g, 1, st, E, v.cus);
     };
     if (zsrc != Z_NONE) {
         vbg::Args az = a;
@@ -754,10 +786,11 @@ static int run_attention(const VbModel* m, const SliceView& v, const BlockW& b, 
     a.rstd = rstd;
     a.X = v.xn; a.W = b.wqkv.p; a.bias = b.bqkv.p; a.out = v.qk;          // q | k: rows 0 .. 2C of W_qkv
     a.M = M; a.N = 2 * C; a.K = C; a.ldo = 2 * C; a.rb = 4;    // 4 tile rows x 8 columns per XCD: measured 4 % faster than row-major
-    if ((rc = launch_gemm<256, 256, 2, 4, vbg::A_PLAIN, vbg::EPI_BF16>(a, 1, st, E, v.cus))) return rc;
+    if ((rc = launch_tile<vbg::A_PLAIN, vbg::EPI_BF16>(m, a, 1, st, E, v.cus))) return rc;
     vbg::Args w{};
     w.X = v.xn; w.W = b.wqkv.p + (size_t)2 * C * C; w.bias = b.bqkv.p + 2 * C; w.vt = v.vt;   // v: rows 2C .. 3C, stored transposed
     w.M = M; w.N = C; w.K = C; w.L = L; w.rstd = rstd;
+    // (always the 256 x 256 tile: the transposed store moves 128 tokens of a feature per row, TM == 8 -- vb_gemm.h)
     if ((rc = launch_gemm<256, 256, 2, 4, vbg::A_PLAIN, vbg::EPI_VT>(w, 1, st, E, v.cus))) return rc;
     if (keys && m->g384)
         hipLaunchKernelGGL((vbs::attn_stream_masked_kernel<L384>), dim3(B * HEADS * vbs::splits<L384>()), dim3(256), vbs::LDS_BYTES, st, v.qk, v.vt, v.ao, HEADS, keys);
@@ -782,7 +815,7 @@ static int run_attention_rt(const VbModel* m, const SliceView& v, const BlockW& 
     a.rstd = rstd;
     a.X = v.xn; a.W = b.wqkv.p; a.bias = b.bqkv.p; a.out = v.qk;
     a.M = M; a.N = 2 * C; a.K = C; a.ldo = 2 * C; a.rb = 4;
-    if ((rc = launch_gemm<256, 256, 2, 4, vbg::A_PLAIN, vbg::EPI_BF16>(a, 1, st, E, v.cus))) return rc;
+    if ((rc = launch_tile<vbg::A_PLAIN, vbg::EPI_BF16>(m, a, 1, st, E, v.cus))) return rc;
     vbg::Args w{};
     w.X = v.xn; w.W = b.wqkv.p + (size_t)2 * C * C; w.bias = b.bqkv.p + 2 * C; w.vt = v.vt;
     w.M = M; w.N = C; w.K = C; w.L = Lp; w.rstd = rstd;
@@ -813,7 +846,7 @@ int blocks(VbModel* m, const float* tokens_in, int B, int nblocks, hipStream_t s
         vbg::Args p{};
         p.X = X; p.W = W; p.bias = bias; p.resid = v.resid; p.M = M; p.N = C; p.K = K;
         if (feeds_ln) { v.stats_of(p); p.cm = cm; }
-        if (int r = launch_gemm<256, 256, 2, 4, vbg::A_PLAIN, vbg::EPI_RESID>(p, 1, st, E, v.cus)) return r;
+        if (int r = launch_tile<vbg::A_PLAIN, vbg::EPI_RESID>(m, p, 1, st, E, v.cus)) return r;
         return feeds_ln ? run_finalize(m, v, M, st, E) : VT_OK;
     };
     // candidate elimination (vb_ce.h): from the first stage's block on the attention is the streaming kernel, under the key bitmap the
@@ -903,7 +936,7 @@ int blocks(VbModel* m, const float* tokens_in, int B, int nblocks, hipStream_t s
         vbg::Args f1{};
         f1.rstd = rstd;
         f1.X = v.xn; f1.W = b.w1.p; f1.bias = b.b1.p; f1.out = v.hid; f1.M = M; f1.N = HID; f1.K = C; f1.ldo = HID; f1.rb = 4;
-        if ((rc = launch_gemm<256, 256, 2, 4, vbg::A_PLAIN, vbg::EPI_GELU>(f1, 1, st, E, v.cus))) return rc;
+        if ((rc = launch_tile<vbg::A_PLAIN, vbg::EPI_GELU>(m, f1, 1, st, E, v.cus))) return rc;
         if ((rc = resid_gemm(v.hid, b.w2.p, b.b2.p, HID, fold && i + 1 < nblocks, cmean))) return rc;      // the final norm reads the f32 stream itself
     }
     if (cidx) {      // compacted rows: the final norm scatters through the last stage's table, removed tokens' rows are zeros (vit_ce.py:170-181)
@@ -927,6 +960,17 @@ int blocks(VbModel* m, const float* tokens_in, int B, int nblocks, hipStream_t s
     return VT_OK;
 }
 
+int gemm_form(const VbModel* m, int B) {
+    const int M = B * m->L, C = m->C;
+    int form = 0;
+    if (narrow_pick(m, M, C, 1, 0)) form |= VT_GEMM_PATCH | VT_GEMM_PROJ | VT_GEMM_FC2;
+    // the q | k projection is a GEMM of its own only outside the fused qkv + attention kernel (run_attention)
+    if ((!m->fused_qkv || m->g384 || m->ce_first >= 0) && narrow_pick(m, M, 2 * C, 1, 0)) form |= VT_GEMM_QK;
+    if (narrow_pick(m, M, m->HID, 1, 0)) form |= VT_GEMM_FC1;
+    if (narrow_pick(m, B * m->LX, 3 * HEAD_CH[1], 1, 0)) form |= VT_GEMM_HEAD;
+    return form;
+}
+
 int head(VbModel* m, const float* feat_in, int B, hipStream_t st, float* score, float* size, float* offset, std::string* err,
          const Slice* sl) {
     const Err E{err};
@@ -944,7 +988,7 @@ int head(VbModel* m, const float* feat_in, int B, hipStream_t st, float* score, 
         a.X = v.map[0]; a.W = m->wc[0].p; a.bias = m->bc[0].p; a.out = v.map[1];
         a.M = M; a.N = 3 * HEAD_CH[1]; a.K = 9 * C; a.ldo = HEAD_CH[1]; a.C = C; a.F = F; a.out_padded = 1;
         a.n_split = HEAD_CH[1]; a.gOut = Bt * P2 * HEAD_CH[1];
-        if ((rc = launch_gemm<256, 256, 2, 4, vbg::A_CONV, vbg::EPI_CONV>(a, 1, st, E, v.cus))) return rc;
+        if ((rc = launch_tile<vbg::A_CONV, vbg::EPI_CONV>(m, a, 1, st, E, v.cus))) return rc;
     }
     for (int li = 1; li < 4; ++li) {   // conv2..4: one launch per layer, blockIdx.y = tower
         const int cin = HEAD_CH[li], cout = HEAD_CH[li + 1], rows = li == 1 ? 256 : (cout < 64 ? 64 : cout);
@@ -953,7 +997,7 @@ int head(VbModel* m, const float* feat_in, int B, hipStream_t st, float* score, 
         a.M = M; a.N = cout; a.K = 9 * cin; a.ldo = cout; a.C = cin; a.F = F; a.out_padded = li < 3;
         a.gX = Bt * P2 * cin; a.gW = (long long)rows * 9 * cin; a.gBias = cout;
         a.gOut = li < 3 ? Bt * P2 * cout : Bt * LX * cout;
-        if (li == 1 ? (rc = launch_gemm<256, 256, 2, 4, vbg::A_CONV, vbg::EPI_CONV>(a, 3, st, E, v.cus))
+        if (li == 1 ? (rc = launch_tile<vbg::A_CONV, vbg::EPI_CONV>(m, a, 3, st, E, v.cus))
                     : (rc = launch_gemm<256, 64, 8, 1, vbg::A_CONV, vbg::EPI_CONV>(a, 3, st, E, v.cus))) return rc;
     }
     hipLaunchKernelGGL((vbm::conv5_kernel<32>), dim3((M + 255) / 256), dim3(256), 0, st, v.map[4], m->w5.p, m->b5.p, M, LX,

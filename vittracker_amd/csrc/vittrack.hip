@@ -1595,6 +1595,11 @@ int vt_set_open_loop(vt_model* m, int32_t on) {
     return VT_OK;
 }
 
+int vt_gemm_form(const vt_model* m, int32_t B) {
+    if (!m) return (void)fail(VT_ERR_ARG, "null model"), -1;
+    return m->vb ? vb::gemm_form(m->vb, B) : 0;
+}
+
 int vt_crop_form(void) {
     bool bytes = false;
     if (crop_selftest(&bytes)) return -1;

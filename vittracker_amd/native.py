@@ -72,6 +72,7 @@ ABI = {
     "vt_stem_u8": (C.c_int, [_vp, _vp, _i32, _vp, _vp]),
     "vt_patch_u8_supported": (C.c_int, [_vp, _i32]),
     "vt_crop_form": (C.c_int, []),
+    "vt_gemm_form": (C.c_int, [_vp, _i32]),
     "vt_set_candidate_elimination": (C.c_int, [_vp, _i32, C.POINTER(_i32), C.POINTER(C.c_double), _vp]),
     "vt_set_ce_form": (C.c_int, [_vp, _i32]),
     "vt_ce_result": (C.c_int, [_vp, _i32, _vp, _vp, _vp]),
@@ -657,6 +658,9 @@ def ce_keep_counts(len_x: int, keep_ratio):
     return out
 
 
+#: the bits of Model.gemm_form (include/vittrack.h VT_GEMM_*): the GEMM kinds that run on the narrow tile
+GEMM_PATCH, GEMM_QK, GEMM_PROJ, GEMM_FC1, GEMM_FC2, GEMM_HEAD = 1, 2, 4, 8, 16, 32
+
 #: the forms candidate elimination runs in (include/vittrack.h VT_CE_MASKED / VT_CE_COMPACT)
 CE_FORMS = {"masked": 0, "compact": 1}
 
@@ -1093,6 +1097,10 @@ class Model:
     def set_open_loop(self, on: bool = True):
         """vt_set_open_loop: track_step (and graphs captured from now on) leave `states` untouched; the step's box is in `record`."""
         _check(self._L.vt_set_open_loop(self._h, 1 if on else 0), "vt_set_open_loop", self._L)
+
+    def gemm_form(self, B: int) -> int:
+        """vt_gemm_form: the GEMM_* bits of the GEMM kinds a plain forward of B frames runs on the narrow tile (0 on the vit_48 path)."""
+        return int(self._L.vt_gemm_form(self._h, int(B)))
 
     def patch_u8_supported(self, B: int) -> bool:
         return bool(self._L.vt_patch_u8_supported(self._h, int(B)))
