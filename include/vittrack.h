@@ -55,7 +55,11 @@ typedef struct vt_graph vt_graph;
  *         OSTrack-256 (64 + 256 = 320 tokens, 16 x 16 maps) and OSTrack-384 (144 + 576 = 720 tokens, 24 x 24 maps)
  *     channels 1024, heads 16, head_channels 256, stride 16, depth 1..24 (24), the same two (template, search) pairs -- ViT-Large: the same
  *         kernels at the second width.  This exact tuple is the ViT-Large model; any other 1024-wide configuration is a shape-generic one.
- * and rejects everything else with VT_ERR_ARG and a message naming these.  The tuned kernels are specialised on their tile
+ * and rejects everything else with VT_ERR_ARG and a message naming these.  vt_create_vit (below) accepts the patch-16 ViT family by name:
+ *     (channels, heads) = (192, 3) ViT-Tiny, (384, 6) ViT-Small -- depth 1..12 (12), MLP 4 x channels --, (768, 12), (1024, 16) as above;
+ *         head_channels 256, stride 16, (template, search) = (128, 256) or (192, 384).  Under vt_create 192 / 3 and 384 / 6 are shape-generic
+ *         vit_dist models: the entry point, not the widths, names the family.
+ * The tuned kernels are specialised on their tile
  * counts (token tiles per frame, feature chunks, map sides are template parameters -- that is where their register blocking comes
  * from), so widths and crop sizes are NOT run-time parameters of THOSE kernels. */
 typedef struct vt_config {
@@ -105,6 +109,17 @@ const char* vt_version(void);
  * depth up to 24) on the same code with the same routes per geometry; vt_query reports channels = 1024, stage tensors are (B, L, 1024).
  * A depth outside 1..24 there: VT_ERR_ARG, "unsupported ViT-Large configuration". */
 int vt_create(const vt_config* cfg, vt_model** out);
+/* The patch-16 OSTrack ViT family by name (the reference's build_small_ostrack, lib/models/ostrack/ostrack.py:288-342, and its
+ * vit_base / vit_large backbones): (channels, heads) = (192, 3) ViT-Tiny, (384, 6) ViT-Small -- depth 1..12, MLP 4 x channels --,
+ * (768, 12), (1024, 16); head_channels 256, stride 16, (template, search) = (128, 256) or (192, 384).  For the last two tuples it is
+ * vt_create.  The first two are shape-generic vit_dist models under vt_create (a different network: LeViT stem), so the family has its own
+ * entry point; the model it returns is a ViT-Base-path model at that width in every respect (stage tensors (B, L, channels), vt_query
+ * reports the width, vt_load_weights wants the OSTrack ckpt['net'] keys at these shapes, template cache, uint8 patches, vt_track_step*,
+ * graphs, vt_gemm_form / VB_GEMM_NARROW, VB_LN_FOLD, VB_FUSED_QKV).  Kernels: the same GEMMs (an odd number of 64-deep k-tiles -- K = 192,
+ * 1728 -- runs the two-buffer loop; a 64-column slice of a tile past N = 192 / 384 writes nothing), LayerNorm at 64 lanes x float2 / float
+ * x 3, the fused qkv + attention kernel at 6 / 3 k-tiles.  Candidate elimination stays a width-768 feature.  Anything else: VT_ERR_ARG,
+ * "unsupported ViT configuration" naming the four tuples and both geometries. */
+int vt_create_vit(const vt_config* cfg, vt_model** out);
 void vt_destroy(vt_model* m);
 
 /* network.load_state_dict(ckpt['net'], strict=False) (lib/test/tracker/vit_dist.py:25):

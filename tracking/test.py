@@ -6,6 +6,7 @@
     python tracking/test.py vit_dist vit_48_h32_noKD --dataset_name folder:/videos --batch 64 --continuous   # any frame sizes
     python tracking/test.py ostrack vitb_256 --dataset_name synthetic:4x20 --synthetic_weights [--batch 4 [--continuous]]   # ViT-Base OSTrack
     python tracking/test.py ostrack vitl_256 --dataset_name synthetic:4x6 --synthetic_weights [--batch 4]   # ViT-Large OSTrack (also vitl_384)
+    python tracking/test.py ostrack vits_256 --dataset_name synthetic:2x4 --synthetic_weights [--batch 2]   # ViT-Small / ViT-Tiny (vits_384, vitt_256, vitt_384)
 
 Same positional arguments and options as the reference, plus ``--batch B`` (> 0 selects the MI355X-native lock-step
 batched runner; with ``--continuous`` the continuous-batching runner, which keeps B slots busy across frame sizes and

@@ -1,4 +1,4 @@
-// vb_api.h -- internal interface between the C-ABI layer (vittrack.hip) and the ViT-Base / ViT-Large runtime (vitb.hip).
+// vb_api.h -- internal interface between the C-ABI layer (vittrack.hip) and the patch-16 ViT runtime (vitb.hip: ViT-Base / -Large / -Small / -Tiny).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -28,6 +28,9 @@ struct Slice {
 // create: channels 768, heads 12 (ViT-Base) or channels 1024, heads 16 (ViT-Large), head_channels 256, stride 16 at (template, search) =
 // (128, 256) or (192, 384); the model carries its width C, its token counts and map side, every function below works on them.
 int create(const vt_config* cfg, VbModel** out, std::string* err);
+// create_vit (vt_create_vit): the patch-16 family by (channels, heads) = (192, 3) ViT-Tiny, (384, 6) ViT-Small (depth <= 12), or the two tuples of
+// create, which it hands to create.  Anything else: VT_ERR_ARG, "unsupported ViT configuration".
+int create_vit(const vt_config* cfg, VbModel** out, std::string* err);
 void destroy(VbModel* m);
 int load_weights(VbModel* m, const TensorMap& tm, std::string* err);
 // patch_embed(z), patch_embed(x), += pos_embed, cat((z, x))  -> the model's f32 residual stream; tokens_out (optional): a copy

@@ -20,7 +20,8 @@
 // CUs idle (a few sequences; vitb.hip narrow_pick): eight times the workgroups, a ring of four 24 KiB stages with counted vmcnt.  Every
 // output element keeps its whole sum in one workgroup and in the wide loop's order (k-tiles ascending, k-step 0 then 1, from zero) and
 // goes through the same epilogue arithmetic, and a wave's sub-tile is 64 features wide under either tile, so the LayerNorm statistics are
-// the same slices: the two forms give the same bits (tests/test_gpu_vitb_narrow.py).  EPI_VT has no narrow form: its transposed store
+// the same slices: the two forms give the same bits (tests/test_gpu_vitb_narrow.py).  An N that is no multiple of the tile width (192, 384 under
+// the 256-wide tile; W carries zero rows to the tile's end) costs whole wave slices only: a slice past N stores nothing.  EPI_VT has no narrow form: its transposed store
 // moves 128 tokens of a feature per row, which takes TM == 8.  (Rounds 2-3 also carried a 4-stage, a whole-line two-stage and a phase-interleaved form of the wide
 // loop; all measured slower -- NOTES_r1_r3.md -- and were removed in round 5.)
 //
@@ -88,7 +89,9 @@ typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 constexpr int BK = 64;
 constexpr int NWAVES = 8;
 
-enum AMode { A_PLAIN = 0, A_CONV = 1 };
+// A_ANYK (a flag on A_PLAIN): the 256 x 256 tile on the two-buffer loop, which takes any whole number of k-tiles, where the software-pipelined
+// loop wants them in pairs (K = 192, ViT-Tiny).  The same operands, k order and epilogue: the same bits as the other loops.
+enum AMode { A_PLAIN = 0, A_CONV = 1, A_ANYK = 2 };
 enum Epi {
     EPI_PATCH = 0,   // resid[m][n] = acc + bias[n] + pos[m % L][n]                     (f32 out)
     EPI_BF16 = 1,    // out[m][n] = bf16(acc + bias[n])                                  (q (pre-scaled) and k projections)
@@ -187,7 +190,7 @@ __global__ __launch_bounds__(NWAVES * 64) void gemm_kernel(const Args a) {
     constexpr int NSX = SX / NWAVES;
     constexpr int BUF_BYTES = (SX + SW) * 1024;
     constexpr bool WIDE = (BM / 16) % NWAVES == 0 && (BN / 16) % NWAVES == 0;      // the 256 x 256 tile
-    constexpr bool SWP = WIDE;
+    constexpr bool SWP = WIDE && !(AMODE & A_ANYK);
     constexpr int NSTG = stages<BM, BN>();                                          // LDS stages of one k-tile: 2, the narrow tiles' ring 4
     constexpr bool RING = NSTG > 2;
     constexpr int EP_OFF = NSTG * BUF_BYTES;                                        // epilogue staging: 8 waves x 4 KiB behind the stages
@@ -303,6 +306,7 @@ __global__ __launch_bounds__(NWAVES * 64) void gemm_kernel(const Args a) {
         if constexpr (EPI == EPI_VT) {
             // swapped tile: features on lanes.  Chunk = 16 features x 128 tokens (256-byte rows)
             static_assert(EPI != EPI_VT || TM == 8, "128 tokens per row");
+            if (nw >= a.N) return;      // a 64-feature wave slice past N (N = 192, 384 under the 256-wide tile) would write into the next frame
             float bs[TN];
             f4 rs[TM];
 #pragma unroll

@@ -137,6 +137,77 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict_
     }
 }
 
+// The same LayerNorm at a width that is no multiple of 256 (ViT-Small 384, ViT-Tiny 192): C = 64 lanes x NV vectors of VW floats, VW = 2 at
+// a multiple of 128, else 1 (C a multiple of 64).  All 64 lanes are active, so the butterfly sums no padding; a wave still reads and writes
+// whole contiguous runs of 64 VW floats.  Its own kernel: layernorm_kernel<768 / 1024> keep their code.
+template <int VW> struct LnVec;
+template <> struct LnVec<1> { typedef float f; typedef bf16 b; };
+template <> struct LnVec<2> { typedef vbg::f2 f; typedef vbg::bf16x2 b; };
+template <int VW>
+__device__ __forceinline__ float ln_hsum(typename LnVec<VW>::f v) {
+    if constexpr (VW == 2) return v.x + v.y;
+    else return v;
+}
+template <int VW>
+__device__ __forceinline__ typename LnVec<VW>::b ln_to_bf16(typename LnVec<VW>::f v) {
+    if constexpr (VW == 2) return __builtin_convertvector(v, vbg::bf16x2);
+    else return (bf16)v;
+}
+
+template <int C>
+__global__ __launch_bounds__(256) void layernorm_small_kernel(const float* __restrict__ resid, const float* __restrict__ gamma,
+                                                              const float* __restrict__ beta, float eps, int M, int L, int Lz, int F,
+                                                              bf16* __restrict__ xn, bf16* __restrict__ map, float* __restrict__ feat,
+                                                              bf16* __restrict__ xb, float* __restrict__ rstd_out, float* __restrict__ mean_out) {
+    static_assert(C % 64 == 0 && C % 256 != 0, "C = 64 lanes x (float2 | float) x n; multiples of 256 take layernorm_kernel");
+    constexpr int VW = C % 128 == 0 ? 2 : 1, NV = C / (64 * VW);
+    typedef typename LnVec<VW>::f fv;
+    typedef typename LnVec<VW>::b bv;
+    const int lane = threadIdx.x & 63;
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= M) return;
+    const float* p = resid + (size_t)row * C;
+    fv v[NV];
+    float s = 0.f;
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+        v[i] = *reinterpret_cast<const fv*>(p + (i * 64 + lane) * VW);
+        s += ln_hsum<VW>(v[i]);
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
+    const float mean = s * (1.0f / C);
+    float ss = 0.f;
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+        v[i] = v[i] - mean;
+        ss += ln_hsum<VW>(v[i] * v[i]);
+        if (xb) *reinterpret_cast<bv*>(xb + (size_t)row * C + (i * 64 + lane) * VW) = ln_to_bf16<VW>(v[i]);      // centred, as in layernorm_kernel
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) ss += __shfl_xor(ss, o);
+    const float rstd = 1.0f / sqrtf(ss * (1.0f / C) + eps);
+    if (rstd_out) {
+        if (lane == 0) { rstd_out[row] = rstd; if (mean_out) mean_out[row] = mean; }
+        if (!xn && !map && !feat) return;
+    }
+    const int f = row / L, t = row - f * L;
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+        const int c = (i * 64 + lane) * VW;
+        const fv y = v[i] * rstd * *reinterpret_cast<const fv*>(gamma + c) + *reinterpret_cast<const fv*>(beta + c);
+        if (xn) *reinterpret_cast<bv*>(xn + (size_t)row * C + c) = ln_to_bf16<VW>(y);
+        if (t >= Lz) {
+            const int tt = t - Lz;
+            if (map) {
+                const int yy = tt / F, xx = tt - yy * F, P = F + 2;
+                *reinterpret_cast<bv*>(map + ((size_t)(f * P + yy + 1) * P + xx + 1) * C + c) = ln_to_bf16<VW>(y);
+            }
+            if (feat) *reinterpret_cast<fv*>(feat + ((size_t)f * (L - Lz) + tt) * C + c) = y;
+        }
+    }
+}
+
 // Per-row rstd from the (sum, centred sum of squares) pairs the residual-writing GEMM epilogues leave per 64-column wave slice
 // (vb_gemm.h): Chan's pairwise update, exact mean first.  stats: [P][ld] float2, P = C / 64.  One thread per row.
 template <int P>

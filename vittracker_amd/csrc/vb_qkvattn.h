@@ -53,7 +53,7 @@ struct Args {
     int hgroup;           // heads walked together (see the item order in the kernel); divides heads
 };
 
-// The kernel's body at model width DM (768: ViT-Base, 1024: ViT-Large).  DM sets the row pitch of X / W / out, the distance between the q, k
+// The kernel's body at model width DM (768: ViT-Base, 1024: ViT-Large, 384: ViT-Small, 192: ViT-Tiny).  DM sets the row pitch of X / W / out, the distance between the q, k
 // and v sections of W and bias, and the number of k-tiles (DM / 64); the stages and the images hold 64-deep k-tiles of one head and do not
 // depend on it.
 template <int DM>
@@ -109,7 +109,7 @@ __device__ __forceinline__ void qkv_attn_body(const Args& a) {
             for (int j = 0; j < 5; ++j) acc[i][j] = splat4(0.f);
         // this wave's feature tile i: kind i >> 1 (0 q, 1 k, 2 v), tile (i >> 1) 4 + wn 2 + (i & 1) of the head's 12
         constexpr int NK = DM / 64;
-        static_assert(NK % 2 == 0, "k-tiles come in stage pairs");
+        static_assert(NK >= 2, "the prologue requests two k-tiles");      // an odd count (ViT-Tiny: 3) ends in stage 0, below
         const std::integral_constant<int, 0> S0{};
         const std::integral_constant<int, 1> S1{};
         auto SB = [&]() { __builtin_amdgcn_sched_barrier(0); };
@@ -189,10 +189,11 @@ __device__ __forceinline__ void qkv_attn_body(const Args& a) {
             for (int j = 0; j < 5; ++j) XA[j] = ldx(S0, 0, j);
             Wr[0] = ldw(S0, 0, 0);
             Wr[1] = ldw(S0, 0, 1);
-            for (int kt = 0; kt < NK; kt += 2) {
+            for (int kt = 0; kt + 1 < NK; kt += 2) {
                 ktile(kt, S0);
                 ktile(kt + 1, S1);
             }
+            if constexpr (NK % 2 != 0) ktile(NK - 1, S0);      // (a k-tile asks for nothing beyond NK: its kt + 1 / kt + 2 tests)
         }
         asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
         __syncthreads();
@@ -282,7 +283,7 @@ __device__ __forceinline__ void qkv_attn_body(const Args& a) {
 
 __global__ __launch_bounds__(512) void qkv_attn_kernel(const Args a) { qkv_attn_body<768>(a); }
 
-// the same kernel at another width (ViT-Large: DM = 1024, 16 k-tiles, 16 heads)
+// the same kernel at another width (ViT-Large: DM = 1024, 16 k-tiles, 16 heads; ViT-Small: 384, 6, 6; ViT-Tiny: 192, 3, 3)
 template <int DM>
 __global__ __launch_bounds__(512) void qkv_attn_wide_kernel(const Args a) { qkv_attn_body<DM>(a); }
 

@@ -2,9 +2,10 @@
 // weights as [cout][tap][cin], attention scale folded into W_q), workspace, launch sequence.  Kernels: vb_gemm.h, vb_misc.h and the
 // three attention kernels vb_attn.h, vb_qkvattn.h, vb_attn_stream.h (the 384 geometry's), whose shared arithmetic lives in vb_attn.h;
 // vb_ce.h: OSTrack candidate elimination by key masking or compacted (the stages' score / select / gather kernels; vb::blocks routes them).
-// Reached through the same C ABI as the vit_48 path (vt_create with channels = 768, or the ViT-Large tuple at channels = 1024).  The two
-// model points differ in width, head count and hidden width alone (VbModel::C / HEADS / HID); the kernels take them at run time except
-// the three that compile the width in (dispatch_width below).
+// Reached through the same C ABI as the vit_48 path (vt_create with channels = 768, or the ViT-Large tuple at channels = 1024; vt_create_vit for
+// those two and for ViT-Small 384 / 6 and ViT-Tiny 192 / 3).  The model points differ in width, head count and hidden width alone (VbModel::C /
+// HEADS / HID); the kernels take them at run time except the three that compile the width in (dispatch_width below).  What the two small
+// widths need beyond that: launch_wide (an odd number of k-tiles), tile_pad (N no multiple of 256), patch_operand (rows shorter than 768).
 // Layout of this file: Buf owns device memory (a model is freed by deleting it); Hooks holds the experiment switches, read once;
 // SliceView holds what a frame slice addresses, built once per entry; run_attention launches one of the four attention forms.
 #include "vb_api.h"
@@ -29,6 +30,8 @@ namespace {
 constexpr int HD = 64, PATCH_K = 768, HW = 256 /* head width */;
 // the two model points (lib/models/ostrack/vit.py:393-400): width, heads of 64, MLP width = 4 x width
 constexpr int C_BASE = 768, HEADS_BASE = 12, C_LARGE = 1024, HEADS_LARGE = 16;
+// the small patch-16 students (build_small_ostrack, lib/models/ostrack/ostrack.py:288-342; timm's DeiT-Small / DeiT-Tiny): vb::create_vit only
+constexpr int C_SMALL = 384, HEADS_SMALL = 6, C_TINY = 192, HEADS_TINY = 3;
 // The two geometries (template / search crop -> tokens at stride 16): OSTrack-256 = 128 / 256 -> 64 + 256 = 320, OSTrack-384 = 192 / 384 ->
 // 144 + 576 = 720.  The model carries its own (VbModel::L, LZ, LX, F, TZ, TX); the token counts below are the attention kernels' template arguments.
 constexpr int L256 = 320, L384 = 720;
@@ -159,11 +162,15 @@ int upload(Buf<T>& d, const void* h, size_t count, const Err& E) {
     return VT_OK;
 }
 
-int upload_bf16(Buf<bf16>& d, const std::vector<float>& h, const Err& E) {
-    std::vector<uint16_t> t(h.size());
+// pad: zero elements behind the tensor (tile_pad)
+int upload_bf16(Buf<bf16>& d, const std::vector<float>& h, const Err& E, size_t pad = 0) {
+    std::vector<uint16_t> t(h.size() + pad, 0);
     for (size_t i = 0; i < h.size(); ++i) t[i] = f2bf(h[i]);
     return upload(d, t.data(), t.size(), E);
 }
+// The 256-wide tiles fetch whole 256-row weight panels: a weight matrix whose last GEMM has N rows (N = 192, 384: no multiple of 256) carries
+// zero rows up to the end of that GEMM's last column tile.  Nothing computed from them is stored (the epilogues skip wave slices past N).
+size_t tile_pad(int N, int K) { return (size_t)((N + 255) / 256 * 256 - N) * K; }
 int upload_f32(Buf<float>& d, const float* h, size_t n, const Err& E) { return upload(d, h, n, E); }
 
 // a state-dict tensor as it is: looked up, checked and uploaded, one helper per element type (*host: the tensor's host values)
@@ -173,11 +180,11 @@ int load_f32(Buf<float>& d, const vb::TensorMap& tm, const std::string& name, in
     if (host) *host = p;
     return upload_f32(d, p, (size_t)numel, E);
 }
-int load_bf16(Buf<bf16>& d, const vb::TensorMap& tm, const std::string& name, int64_t numel, const Err& E, const float** host = nullptr) {
+int load_bf16(Buf<bf16>& d, const vb::TensorMap& tm, const std::string& name, int64_t numel, const Err& E, const float** host = nullptr, size_t pad = 0) {
     const float* p;
     if (int rc = need(tm, name, numel, &p, E)) return rc;
     if (host) *host = p;
-    return upload_bf16(d, std::vector<float>(p, p + numel), E);
+    return upload_bf16(d, std::vector<float>(p, p + numel), E, pad);
 }
 
 int num_cus() {
@@ -221,7 +228,7 @@ int launch_gemm(const vbg::Args& a, int groups, hipStream_t st, const Err& E, in
     if (a.M < 1 || a.K % vbg::BK != 0 || a.N % 8 != 0)
         return E.fail(VT_ERR_ARG, "gemm shape: K must be a multiple of 64 and N of 8 (got M=" + std::to_string(a.M) + " N=" +
                                       std::to_string(a.N) + " K=" + std::to_string(a.K) + ")");
-    if (BM == 256 && BN == 256 && a.K % (2 * vbg::BK) != 0) return E.fail(VT_ERR_ARG, "gemm shape: the 256 x 256 tile needs K to be a multiple of 128");
+    if (BM == 256 && BN == 256 && !(AMODE & vbg::A_ANYK) && a.K % (2 * vbg::BK) != 0) return E.fail(VT_ERR_ARG, "gemm shape: the 256 x 256 tile needs K to be a multiple of 128");
     const Hooks& H = hooks();
     vbg::Args ad = a;
     ad.dbg = H.dbg;
@@ -238,10 +245,12 @@ int launch_gemm(const vbg::Args& a, int groups, hipStream_t st, const Err& E, in
 }
 
 // The kernels that compile the width in (vbm::layernorm_kernel<C>, vbm::ln_finalize_kernel<C / 64>, the fused qkv + attention kernel): f
-// is called with the model's width as a std::integral_constant.  vb::create admits no third width.
+// is called with the model's width as a std::integral_constant.  vb::create / vb::create_vit admit no fifth width.
 template <typename F>
 void dispatch_width(int C, F&& f) {
     if (C == C_LARGE) f(std::integral_constant<int, C_LARGE>{});
+    else if (C == C_SMALL) f(std::integral_constant<int, C_SMALL>{});
+    else if (C == C_TINY) f(std::integral_constant<int, C_TINY>{});
     else f(std::integral_constant<int, C_BASE>{});
 }
 
@@ -255,10 +264,25 @@ bool narrow_pick(const VbModel* m, int M, int N, int groups, int cus) {
 }
 
 // A GEMM kind of the ViT path on the tile narrow_pick chooses for this launch
+// The wide form of a GEMM kind.  The 256 x 256 tile's software-pipelined loop takes k-tiles in pairs; an odd count (ViT-Tiny: K = 192 of qkv /
+// proj / fc1, K = 9 x 192 of the head's conv1) goes to a tile on the two-buffer loop, which takes any: the same 256 x 256 tile for the
+// token GEMMs (A_ANYK), the head's 256 x 64 tile for conv1.  Same k order from zero, same epilogue, same 64-column wave slices: same bits.
+template <int AMODE, int EPI>
+int launch_wide(const vbg::Args& a, int groups, hipStream_t st, const Err& E, int cus) {
+    if (a.K % (2 * vbg::BK) != 0) {
+        if constexpr (AMODE == vbg::A_CONV) return launch_gemm<256, 64, 8, 1, vbg::A_CONV, vbg::EPI_CONV>(a, groups, st, E, cus);
+        else if constexpr (EPI == vbg::EPI_BF16 || EPI == vbg::EPI_VT || EPI == vbg::EPI_RESID || EPI == vbg::EPI_GELU)
+            return launch_gemm<256, 256, 2, 4, AMODE | vbg::A_ANYK, EPI>(a, groups, st, E, cus);
+    }
+    return launch_gemm<256, 256, 2, 4, AMODE, EPI>(a, groups, st, E, cus);      // (the patch GEMMs: K = 768 at every width)
+}
+
 template <int AMODE, int EPI>
 int launch_tile(const VbModel* m, const vbg::Args& a, int groups, hipStream_t st, const Err& E, int cus) {
     if (narrow_pick(m, a.M, a.N, groups, cus)) return launch_gemm<128, 64, 8, 1, AMODE, EPI>(a, groups, st, E, cus);
-    return launch_gemm<256, 256, 2, 4, AMODE, EPI>(a, groups, st, E, cus);
+    // (N = 384 / 192 stays on the 256-wide tile, a quarter of whose columns are padding there: proj / fc2 on a tile that fits N -- 256 x 128 /
+    // 256 x 64 on the two-buffer loop -- measured SLOWER, 6.94 against 6.42 ms and 3.37 against 3.02 ms per step of 256 frames: NOTES.md)
+    return launch_wide<AMODE, EPI>(a, groups, st, E, cus);
 }
 
 template <typename K>
@@ -269,8 +293,13 @@ int run_layernorm(const VbModel* m, const float* resid, const float* g, const fl
                   const Err& E, bf16* xb = nullptr, float* rstd = nullptr, float* mean = nullptr, int rows = 0) {
     const int M = rows ? rows : B * m->L;
     dispatch_width(m->C, [&](auto W) {
-        hipLaunchKernelGGL((vbm::layernorm_kernel<decltype(W)::value>), dim3((M + 3) / 4), dim3(256), 0, st, resid, g, b, LN_EPS, M, m->L, m->LZ, m->F,
-                           xn, map, feat, xb, rstd, mean);
+        constexpr int CW = decltype(W)::value;
+        if constexpr (CW % 256 == 0)
+            hipLaunchKernelGGL((vbm::layernorm_kernel<CW>), dim3((M + 3) / 4), dim3(256), 0, st, resid, g, b, LN_EPS, M, m->L, m->LZ, m->F, xn, map, feat,
+                               xb, rstd, mean);
+        else      // 384, 192: float2 / float per lane (vb_misc.h)
+            hipLaunchKernelGGL((vbm::layernorm_small_kernel<CW>), dim3((M + 3) / 4), dim3(256), 0, st, resid, g, b, LN_EPS, M, m->L, m->LZ, m->F, xn, map,
+                               feat, xb, rstd, mean);
     });
     VB_HIP(hipGetLastError());
     return VT_OK;
@@ -297,6 +326,14 @@ struct SliceView {
     // a GEMM that writes residual rows also leaves their bf16 copy and LayerNorm statistics (the folded LayerNorms, vb_gemm.h)
     void stats_of(vbg::Args& a) const { a.xb = xn; a.stats = stats; a.ldstats = ldstats; }
 };
+
+// The patch GEMMs' operand rows [rows][PATCH_K] of a slice.  At widths of at least PATCH_K they lie in a workspace of the width's own rows (ao,
+// folded: xn receives the tokens' bf16 copy from the GEMM epilogue; else xn); a narrower model's rows (384, 192) are shorter than an operand
+// row, so there the operand lies in the MLP's hidden rows (HID = 4 C >= PATCH_K), idle until the first fc1.
+bf16* patch_operand(const VbModel* m, const SliceView& v) {
+    static_assert(4 * C_TINY >= PATCH_K, "the hidden rows hold an operand row");
+    return m->C >= PATCH_K ? (m->fold ? v.ao : v.xn) : v.hid;
+}
 
 int run_finalize(const VbModel* m, const SliceView& v, int M, hipStream_t st, const Err& E) {
     dispatch_width(m->C, [&](auto W) {
@@ -359,7 +396,7 @@ int fold_patch_u8(VbModel* m, const Err& E) {
         bsum += bd;
     }
     int rc;
-    if ((rc = upload_bf16(m->wpatch_u8, w, E)) || (rc = upload_f32(m->bpatch_u8, b.data(), b.size(), E))) return rc;
+    if ((rc = upload_bf16(m->wpatch_u8, w, E, tile_pad(C, PATCH_K))) || (rc = upload_f32(m->bpatch_u8, b.data(), b.size(), E))) return rc;
     return upload_centring(m->cpos_u8, m->h_pos, C, bsum, E);
 }
 
@@ -373,6 +410,8 @@ int set_normalization(VbModel* m, const float* mean3, const float* std3, std::st
     std::memcpy(m->norm_std, std3, 12);
     return m->loaded ? fold_patch_u8(m, E) : VT_OK;      // before vt_load_weights: remembered, load_weights folds with it
 }
+
+static int build_model(const vt_config* cfg, VbModel** out, const Err& E);
 
 int create(const vt_config* cfg, VbModel** out, std::string* err) {
     const Err E{err};
@@ -391,6 +430,27 @@ int create(const vt_config* cfg, VbModel** out, std::string* err) {
                                   "(OSTrack-384); got channels=" + std::to_string(cfg->channels) + " heads=" + std::to_string(cfg->heads) +
                                   " head_channels=" + std::to_string(cfg->head_channels) + " stride=" + std::to_string(cfg->stride) +
                                   " template=" + std::to_string(cfg->template_size) + " search=" + std::to_string(cfg->search_size));
+    return build_model(cfg, out, E);
+}
+
+int create_vit(const vt_config* cfg, VbModel** out, std::string* err) {
+    const Err E{err};
+    const bool base = cfg->channels == C_BASE && cfg->heads == HEADS_BASE, large = cfg->channels == C_LARGE && cfg->heads == HEADS_LARGE;
+    if (base || large) return create(cfg, out, err);      // the two tuples vt_create knows: its checks, its messages
+    const bool g256 = cfg->template_size == 128 && cfg->search_size == 256, g384 = cfg->template_size == 192 && cfg->search_size == 384;
+    const bool small = (cfg->channels == C_SMALL && cfg->heads == HEADS_SMALL) || (cfg->channels == C_TINY && cfg->heads == HEADS_TINY);
+    if (!small || cfg->head_channels != HW || cfg->stride != 16 || !(g256 || g384) || cfg->depth < 1 || cfg->depth > 12)
+        return E.fail(VT_ERR_ARG, "unsupported ViT configuration: this build implements (CHANNELS, HEADS) = (192, 3), (384, 6) with 1 <= depth <= 12, "
+                                  "(768, 12), (1024, 16) with 1 <= depth <= 24, HEAD.NUM_CHANNELS=256, STRIDE=16, template 128 / search 256 or "
+                                  "template 192 / search 384; got channels=" + std::to_string(cfg->channels) + " heads=" + std::to_string(cfg->heads) +
+                                  " depth=" + std::to_string(cfg->depth) + " head_channels=" + std::to_string(cfg->head_channels) + " stride=" +
+                                  std::to_string(cfg->stride) + " template=" + std::to_string(cfg->template_size) + " search=" + std::to_string(cfg->search_size));
+    return build_model(cfg, out, E);
+}
+
+// the model of a checked configuration: workspace, switches, kernel attributes
+static int build_model(const vt_config* cfg, VbModel** out, const Err& E) {
+    const bool g384 = cfg->template_size == 192 && cfg->search_size == 384;
     if (cfg->depth < 1 || cfg->depth > 24 || cfg->max_batch < 1) return E.fail(VT_ERR_ARG, "bad depth / max_batch");
     // the EPI_PATCH_ROWS_N epilogue finds a row's frame by a multiply-high that is exact while rows * rows-per-frame < 2^32
     if (g384 && (uint64_t)cfg->max_batch * 576 * 576 >= (1ull << 32)) return E.fail(VT_ERR_ARG, "max_batch too large for the 192 / 384 geometry");
@@ -468,7 +528,13 @@ int create(const vt_config* cfg, VbModel** out, std::string* err) {
         {kernel_ptr(vbs::attn_stream_rt_kernel), vbs::LDS_BYTES},
         {kernel_ptr(vbc::ce_score_all_rt_kernel), 16 * L384 * 4},
         {kernel_ptr(vbq::qkv_attn_kernel), vbq::LDS_BYTES},
-        {kernel_ptr(vbq::qkv_attn_wide_kernel<C_LARGE>), vbq::LDS_BYTES}};
+        {kernel_ptr(vbq::qkv_attn_wide_kernel<C_LARGE>), vbq::LDS_BYTES},
+        {kernel_ptr(vbq::qkv_attn_wide_kernel<C_SMALL>), vbq::LDS_BYTES},
+        {kernel_ptr(vbq::qkv_attn_wide_kernel<C_TINY>), vbq::LDS_BYTES},
+        {kernel_ptr(gemm_kernel<256, 256, 2, 4, A_PLAIN | A_ANYK, EPI_BF16>), lds_bytes<256, 256>()},
+        {kernel_ptr(gemm_kernel<256, 256, 2, 4, A_PLAIN | A_ANYK, EPI_VT>), lds_bytes<256, 256>()},
+        {kernel_ptr(gemm_kernel<256, 256, 2, 4, A_PLAIN | A_ANYK, EPI_RESID>), lds_bytes<256, 256>()},
+        {kernel_ptr(gemm_kernel<256, 256, 2, 4, A_PLAIN | A_ANYK, EPI_GELU>), lds_bytes<256, 256>()}};
     for (const auto& k : dynamic_lds)
         if (e == hipSuccess) e = hipFuncSetAttribute(k.kernel, hipFuncAttributeMaxDynamicSharedMemorySize, k.lds);
     if (e != hipSuccess) {
@@ -574,7 +640,7 @@ int load_weights(VbModel* m, const TensorMap& tm, std::string* err) {
     const std::string bb = "backbone.";
     const int L = m->L, LZ = m->LZ, LX = m->LX, C = m->C, HID = m->HID;
     const float *wp, *bp;
-    if ((rc = load_bf16(m->wpatch, tm, bb + "patch_embed.proj.weight", (int64_t)C * PATCH_K, E, &wp))) return rc;
+    if ((rc = load_bf16(m->wpatch, tm, bb + "patch_embed.proj.weight", (int64_t)C * PATCH_K, E, &wp, tile_pad(C, PATCH_K)))) return rc;
     if ((rc = load_f32(m->bpatch, tm, bb + "patch_embed.proj.bias", C, E, &bp))) return rc;
     m->h_wpatch.assign(wp, wp + (size_t)C * PATCH_K);
     m->h_bpatch.assign(bp, bp + C);
@@ -596,20 +662,20 @@ int load_weights(VbModel* m, const TensorMap& tm, std::string* err) {
         if ((rc = load_f32(b.ln2g, tm, pre + "norm2.weight", C, E, &g2)) || (rc = load_f32(b.ln2b, tm, pre + "norm2.bias", C, E, &be2))) return rc;
         if ((rc = load_f32(b.bproj, tm, pre + "attn.proj.bias", C, E)) || (rc = load_f32(b.b2, tm, pre + "mlp.fc2.bias", C, E))) return rc;
         // a Linear behind a LayerNorm: the norm folded in (VB_LN_FOLD), its first `nscaled` output rows times the attention scale
-        auto folded = [&](const std::string& name, int N, const float* g, const float* be, int nscaled, Buf<bf16>& W, Buf<float>& Bv) {
+        auto folded = [&](const std::string& name, int N, const float* g, const float* be, int nscaled, Buf<bf16>& W, Buf<float>& Bv, size_t pad) {
             const float *pw, *pb;
             if ((rc = need(tm, pre + name + ".weight", (int64_t)N * C, &pw, E)) || (rc = need(tm, pre + name + ".bias", N, &pb, E))) return rc;
             std::vector<float> w(pw, pw + (size_t)N * C), bias(pb, pb + N);
             if (m->fold) fold_layernorm(w, bias, g, be, N, C);
             for (size_t k = 0; k < (size_t)nscaled * C; ++k) w[k] *= scale;
             for (int k = 0; k < nscaled; ++k) bias[k] *= scale;
-            if ((rc = upload_bf16(W, w, E))) return rc;
+            if ((rc = upload_bf16(W, w, E, pad))) return rc;
             return upload_f32(Bv, bias.data(), bias.size(), E);
         };
-        if ((rc = folded("attn.qkv", 3 * C, g1, be1, C, b.wqkv, b.bqkv))) return rc;
-        if ((rc = load_bf16(b.wproj, tm, pre + "attn.proj.weight", (int64_t)C * C, E))) return rc;
-        if ((rc = folded("mlp.fc1", HID, g2, be2, 0, b.w1, b.b1))) return rc;
-        if ((rc = load_bf16(b.w2, tm, pre + "mlp.fc2.weight", (int64_t)HID * C, E))) return rc;
+        if ((rc = folded("attn.qkv", 3 * C, g1, be1, C, b.wqkv, b.bqkv, tile_pad(C, C)))) return rc;      // the v GEMM's N = C rows end the matrix
+        if ((rc = load_bf16(b.wproj, tm, pre + "attn.proj.weight", (int64_t)C * C, E, nullptr, tile_pad(C, C)))) return rc;
+        if ((rc = folded("mlp.fc1", HID, g2, be2, 0, b.w1, b.b1, tile_pad(HID, C)))) return rc;
+        if ((rc = load_bf16(b.w2, tm, pre + "mlp.fc2.weight", (int64_t)HID * C, E, nullptr, tile_pad(C, HID)))) return rc;
     }
     if ((rc = load_f32(m->ng, tm, bb + "norm.weight", C, E)) || (rc = load_f32(m->nb, tm, bb + "norm.bias", C, E))) return rc;
     // ---- head: Conv3x3(+bias) + BatchNorm(eval, eps 1e-5) folded in double (head.py:8-21), weights as [cout][tap][cin]
@@ -677,7 +743,7 @@ int stem(VbModel* m, const float* z, const float* x, int B, hipStream_t st, floa
     if (rc || (rc = check_slice(m, B, sl, E))) return rc;
     const int L = m->L, M = B * L, C = m->C;
     const SliceView v(m, B, sl);
-    bf16* const patches = m->fold ? v.ao : v.xn;     // folded: xn receives the tokens' bf16 copy from the GEMM epilogue
+    bf16* const patches = patch_operand(m, v);
     hipLaunchKernelGGL(vbm::patchify_kernel, dim3(grid256((size_t)M * 96)), dim3(256), 0, st, z, x, patches, B, m->TZ, m->TX);
     VB_HIP(hipGetLastError());
     vbg::Args a{};
@@ -721,7 +787,8 @@ int stem_rows(VbModel* m, ZSrc zsrc, const float* z, const float* x, const unsig
     if (xu8 && (reinterpret_cast<uintptr_t>(xu8) & 15)) return E.fail(VT_ERR_ARG, "the uint8 patch must be 16-byte aligned on the ViT-Base path");
     const int L = m->L, LZ = m->LZ, LX = m->LX, C = m->C;
     const SliceView v(m, B, sl);
-    bf16* const xop = m->fold ? v.ao : v.xn;      // B * LX dense rows inside the slice's B * L (as vb::stem's operand)
+    // B * LX dense rows inside the slice's B * L (as vb::stem's operand); in the hidden rows (narrow models) behind the B * LZ rows of a given template
+    bf16* const xop = patch_operand(m, v) + (m->C >= PATCH_K ? (size_t)0 : (size_t)B * LZ * PATCH_K);
     const bf16* zop = m->zop.p + v.f0 * LZ * PATCH_K;
     if (zsrc == Z_GIVEN) {      // not through the cache: a call with its own template leaves vt_set_template's rows alone
         if ((rc = patchify_dense(z, m->TZ, B, v.hid, st, E))) return rc;
@@ -774,9 +841,12 @@ static int run_attention(const VbModel* m, const SliceView& v, const BlockW& b, 
         // heads walked together: 6 of 12 measured best at width 768 (vb_qkvattn.h); 16 heads of width 1024 take 4, the divisor whose group of
         // weight rows (4 x 384 KiB) is nearest to that one's (6 x 288 KiB)
         static const int hgv = env_int("VB_QA_HGROUP", -1);
+        // (ViT-Small / ViT-Tiny: all 6 / 3 heads of a frame together -- their whole qkv matrix, 864 / 216 KiB, is smaller than one such group)
         const int hg = hgv < 0 ? (C == C_LARGE ? 4 : 6) : hgv;
         qa.hgroup = (hg > 0 && HEADS % hg == 0) ? hg : HEADS;
         if (C == C_LARGE) hipLaunchKernelGGL(vbq::qkv_attn_wide_kernel<C_LARGE>, dim3(persistent_grid(v.cus)), dim3(512), vbq::LDS_BYTES, st, qa);
+        else if (C == C_SMALL) hipLaunchKernelGGL(vbq::qkv_attn_wide_kernel<C_SMALL>, dim3(persistent_grid(v.cus)), dim3(512), vbq::LDS_BYTES, st, qa);
+        else if (C == C_TINY) hipLaunchKernelGGL(vbq::qkv_attn_wide_kernel<C_TINY>, dim3(persistent_grid(v.cus)), dim3(512), vbq::LDS_BYTES, st, qa);
         else hipLaunchKernelGGL(vbq::qkv_attn_kernel, dim3(persistent_grid(v.cus)), dim3(512), vbq::LDS_BYTES, st, qa);
         VB_HIP(hipGetLastError());
         return VT_OK;
@@ -791,7 +861,7 @@ static int run_attention(const VbModel* m, const SliceView& v, const BlockW& b, 
     w.X = v.xn; w.W = b.wqkv.p + (size_t)2 * C * C; w.bias = b.bqkv.p + 2 * C; w.vt = v.vt;   // v: rows 2C .. 3C, stored transposed
     w.M = M; w.N = C; w.K = C; w.L = L; w.rstd = rstd;
     // (always the 256 x 256 tile: the transposed store moves 128 tokens of a feature per row, TM == 8 -- vb_gemm.h)
-    if ((rc = launch_gemm<256, 256, 2, 4, vbg::A_PLAIN, vbg::EPI_VT>(w, 1, st, E, v.cus))) return rc;
+    if ((rc = launch_wide<vbg::A_PLAIN, vbg::EPI_VT>(w, 1, st, E, v.cus))) return rc;
     if (keys && m->g384)
         hipLaunchKernelGGL((vbs::attn_stream_masked_kernel<L384>), dim3(B * HEADS * vbs::splits<L384>()), dim3(256), vbs::LDS_BYTES, st, v.qk, v.vt, v.ao, HEADS, keys);
     else if (keys)
@@ -819,7 +889,7 @@ static int run_attention_rt(const VbModel* m, const SliceView& v, const BlockW& 
     vbg::Args w{};
     w.X = v.xn; w.W = b.wqkv.p + (size_t)2 * C * C; w.bias = b.bqkv.p + 2 * C; w.vt = v.vt;
     w.M = M; w.N = C; w.K = C; w.L = Lp; w.rstd = rstd;
-    if ((rc = launch_gemm<256, 256, 2, 4, vbg::A_PLAIN, vbg::EPI_VT>(w, 1, st, E, v.cus))) return rc;
+    if ((rc = launch_wide<vbg::A_PLAIN, vbg::EPI_VT>(w, 1, st, E, v.cus))) return rc;
     hipLaunchKernelGGL(vbs::attn_stream_rt_kernel, dim3(B * HEADS * vbs::splits_rt(Lp)), dim3(256), vbs::LDS_BYTES, st, v.qk, v.vt, v.ao, HEADS, Lp, nkeys);
     VB_HIP(hipGetLastError());
     return VT_OK;

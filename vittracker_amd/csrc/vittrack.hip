@@ -1199,10 +1199,10 @@ int init_model(vt_model* m, const vt_config* cfg, bool vitb) {
 }
 
 // ViT-Base or ViT-Large model: the shared part of vt_model is the output scratch, the window and the streams
-int create_vitb(const vt_config* cfg, vt_model** out) {
+int create_vitb(const vt_config* cfg, vt_model** out, bool family_vit = false) {
     std::string err;
     VbModel* vbm = nullptr;
-    int rc = vb::create(cfg, &vbm, &err);
+    int rc = family_vit ? vb::create_vit(cfg, &vbm, &err) : vb::create(cfg, &vbm, &err);
     if (rc) return fail(rc, err);
     if ((rc = crop_selftest())) { vb::destroy(vbm); return rc; }      // every model kind can be handed to vt_crop (after the argument checks: they need no device)
     vt_model* m = new vt_model();
@@ -1219,6 +1219,11 @@ extern "C" {
 
 const char* vt_last_error(void) { return g_err.c_str(); }
 const char* vt_version(void) { return "vittrack-hip 0.2 (gfx950, " VT_PRECISION_NAME " contractions)"; }
+
+int vt_create_vit(const vt_config* cfg, vt_model** out) {
+    if (!cfg || !out) return fail(VT_ERR_ARG, "null argument");
+    return create_vitb(cfg, out, true);
+}
 
 int vt_create(const vt_config* cfg, vt_model** out) {
     if (!cfg || !out) return fail(VT_ERR_ARG, "null argument");

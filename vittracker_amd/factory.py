@@ -9,13 +9,16 @@ def network_builder(cfg):
     """The build function of cfg's model family.  The vit_dist YAMLs keep the config default ``TYPE: vit_base_patch16_224`` (the
     reference's vit_dist builder never reads it), so the width decides: 768 channels is the ViT-Base backbone, anything else
     the distilled stem + blocks of that width.  No vit_dist YAML names ``vit_large_patch16_224``: that TYPE alone selects the ViT-Large
-    backbone (its width comes from the TYPE, as in the reference's build_ostrack)."""
+    backbone (its width comes from the TYPE, as in the reference's build_ostrack); likewise ``vit_small_patch16_224`` / ``vit_tiny_patch16_224``
+    (384 / 6 and 192 / 3).  A vit_dist YAML of 384 or 192 channels keeps the default TYPE and stays a distilled model."""
     from .model import build_ostrack_dist
     from .model_vitb import build_ostrack
     bb = cfg.MODEL.BACKBONE
     if int(bb.CHANNELS) == 768 and str(bb.TYPE).startswith("vit_base_patch16_224"):
         return build_ostrack
     if str(bb.TYPE).startswith("vit_large_patch16_224"):
+        return build_ostrack
+    if str(bb.TYPE) in ("vit_small_patch16_224", "vit_tiny_patch16_224"):      # timm's names: the TYPE alone selects them, as for ViT-Large
         return build_ostrack
     return build_ostrack_dist
 

@@ -40,6 +40,8 @@ class CenterHead:
 
 
 class OstrackDist:
+    family = None      # native.Model(family=...): vt_create's own choice (model_vitb.OSTrack asks for the patch-16 ViT by name)
+
     def __init__(self, cfg, depth=3, mode="eval", max_batch=1):
         if mode != "eval":
             raise NotImplementedError("only the inference graph (mode='eval') is implemented; the distillation "
@@ -120,7 +122,7 @@ class OstrackDist:
                 raise native.VtError("call .cuda() first: vittracker_amd has no CPU execution path")
             g = self.geom
             self._nat = native.Model(g["template_size"], g["search_size"], g["channels"], g["heads"], self.depth,
-                                     g["head_channels"], g["stride"], self.max_batch)
+                                     g["head_channels"], g["stride"], self.max_batch, family=self.family)
             self._nat.load_state_dict(self._state)
         return self._nat
 

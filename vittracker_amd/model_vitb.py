@@ -1,7 +1,8 @@
-"""Model-level drop-in for the plain-ViT OSTrack path (ViT-Base, BASELINE config 4, and ViT-Large): ``build_ostrack(cfg, training=False) -> OSTrack``
+"""Model-level drop-in for the plain-ViT OSTrack path (ViT-Base, BASELINE config 4, ViT-Large, ViT-Small, ViT-Tiny): ``build_ostrack(cfg, training=False) -> OSTrack``
 with the surface the reference's callers use (``lib/models/ostrack/ostrack.py:22-151,164-286``):
 
-    net = build_ostrack(cfg, training=False)            # MODEL.BACKBONE.TYPE = vit_base_patch16_224[_ce] | vit_large_patch16_224, HEAD = CENTER / 256
+    net = build_ostrack(cfg, training=False)            # MODEL.BACKBONE.TYPE = vit_base_patch16_224[_ce] | vit_{large,small,tiny}_patch16_224, HEAD = CENTER / 256
+    net = build_small_ostrack(cfg, training=False)      # the reference's depth-3 students: TYPE vit_base_patch16_224_ce, CHANNELS / HEADS = 192 / 3, 384 / 6, 768 / 12
     net.load_state_dict(ckpt['net'], strict=False)      # keys backbone.* / box_head.*
     net = net.cuda(); net.eval()
     out = net.forward(template=z, search=x)             # {'pred_boxes','score_map','size_map','offset_map'}
@@ -16,7 +17,7 @@ DESIGN.md 11.4): by key masking (``ce_form="masked"``, the default: no token mov
 the kept tokens are gathered into shorter frames behind every stage, as the reference does).  Either way the kept tokens take the
 reference's values and removed tokens come back as zeros.  ``ce_form=None`` reads the environment variable ``VB_CE_FORM``.  The template rows of
 the score come from ``CE_TEMPLATE_RANGE`` as ``lib/utils/ce_utils.py:15-49`` picks them (``ALL``, ``CTR_POINT``, ``CTR_REC``), one
-selection per model.  Not implemented (NotImplementedError): ViT-Large CE, ``CE_TEMPLATE_RANGE: GT_BOX``, a ``ce_keep_rate`` argument
+selection per model.  Not implemented (NotImplementedError): candidate elimination at any width but 768 (ViT-Large, ViT-Small and ViT-Tiny CE), ``CE_TEMPLATE_RANGE: GT_BOX``, a ``ce_keep_rate`` argument
 of ``forward``, a ``_ce`` TYPE without ``CE_LOC``, and the prompt / draw variants (``MODEL.PROCESS.*``)."""
 from __future__ import annotations
 
@@ -30,6 +31,12 @@ from .model import CenterHead, OstrackDist
 #: what MODEL.BACKBONE.TYPE fixes for the large backbone (lib/models/ostrack/vit.py:393-400: embed_dim, num_heads, depth).  As in the
 #: reference the TYPE decides: CHANNELS / HEADS of the YAML are not read for it.
 VIT_LARGE = {"channels": 1024, "heads": 16, "depth": 24}
+#: the small students under timm's names (DeiT-Small / DeiT-Tiny; the reference ships no such TYPE): again the TYPE decides
+VIT_SMALL = {"channels": 384, "heads": 6, "depth": 12}
+VIT_TINY = {"channels": 192, "heads": 3, "depth": 12}
+TYPE_FIXES = {"vit_large_patch16_224": VIT_LARGE, "vit_small_patch16_224": VIT_SMALL, "vit_tiny_patch16_224": VIT_TINY}
+#: (CHANNELS, HEADS) build_small_ostrack accepts (lib/models/ostrack/ostrack.py:301-308 passes them on as they are; these are the widths with kernels)
+SMALL_WIDTHS = ((192, 3), (384, 6), (768, 12))
 
 #: generate_mask_cond (lib/utils/ce_utils.py:22-49): the slice of template map rows AND columns that is set, per template map side of the two geometries (8: 128 px, 12: 192 px)
 CE_RANGE_SLICES = {"CTR_POINT": {8: (3, 4), 12: (5, 6)}, "CTR_REC": {8: (3, 5), 12: (5, 7)}}
@@ -55,16 +62,36 @@ def ce_template_rows(template_range: str, feat_sz_z: int):
 
 
 class OSTrack(OstrackDist):
-    def __init__(self, cfg, depth=None, max_batch=1, ce_form=None):
+    family = "vit"      # vt_create_vit: 384 / 6 and 192 / 3 are LeViT-stem vit_dist models under vt_create
+
+    def __init__(self, cfg, depth=None, max_batch=1, ce_form=None, small=False):
+        """small: build_small_ostrack's model -- TYPE vit_base_patch16_224_ce at depth 3 with the YAML's CHANNELS / HEADS, CE_LOC may be empty."""
         g = geometry(cfg)
         if g["head_type"] != "CENTER":
             raise ValueError("HEAD TYPE %s is not supported." % g["head_type"])
         bb_type = str(cfg.MODEL.BACKBONE.TYPE)
         self.ce_loc, self.ce_keep_ratio, self.ce_rows = [], [], None
         self.ce_form = native.ce_form_name(ce_form)      # "masked" | "compact"; read by a candidate-elimination backbone only
-        if bb_type == "vit_large_patch16_224":
-            g["channels"], g["heads"] = VIT_LARGE["channels"], VIT_LARGE["heads"]
-            depth = VIT_LARGE["depth"] if depth is None else depth
+        if small:
+            if bb_type != "vit_base_patch16_224_ce":
+                raise NotImplementedError(f"build_small_ostrack: backbone {cfg.MODEL.BACKBONE.TYPE!r}: only vit_base_patch16_224_ce (depth 3, CHANNELS / HEADS "
+                                          "from the YAML) is implemented")
+            if (g["channels"], g["heads"]) not in SMALL_WIDTHS:
+                raise NotImplementedError(f"build_small_ostrack: (CHANNELS, HEADS) = ({g['channels']}, {g['heads']}): implemented are "
+                                          + ", ".join(str(w) for w in SMALL_WIDTHS))
+            depth = 3 if depth is None else depth
+            self.ce_loc = [int(v) for v in cfg.MODEL.BACKBONE.CE_LOC]
+            if self.ce_loc:      # (an empty CE_LOC: the plain depth-3 model, CE_KEEP_RATIO is not read)
+                self.ce_keep_ratio = [float(v) for v in cfg.MODEL.BACKBONE.CE_KEEP_RATIO]
+                if g["channels"] != 768:
+                    raise NotImplementedError("candidate elimination is implemented for width 768 only")
+                if len(self.ce_loc) != len(self.ce_keep_ratio):
+                    raise ValueError(f"CE_LOC {self.ce_loc} and CE_KEEP_RATIO {self.ce_keep_ratio} must have the same length")
+                self.ce_rows = ce_template_rows(cfg.MODEL.BACKBONE.CE_TEMPLATE_RANGE, g["template_size"] // g["stride"])
+        elif bb_type in TYPE_FIXES:
+            fixed = TYPE_FIXES[bb_type]
+            g["channels"], g["heads"] = fixed["channels"], fixed["heads"]
+            depth = fixed["depth"] if depth is None else depth
         elif bb_type == "vit_base_patch16_224":
             depth = 12 if depth is None else depth
         elif bb_type == "vit_base_patch16_224_ce":
@@ -78,8 +105,8 @@ class OSTrack(OstrackDist):
                 raise ValueError(f"CE_LOC {self.ce_loc} and CE_KEEP_RATIO {self.ce_keep_ratio} must have the same length")
             self.ce_rows = ce_template_rows(cfg.MODEL.BACKBONE.CE_TEMPLATE_RANGE, g["template_size"] // g["stride"])
         else:
-            raise NotImplementedError(f"backbone {cfg.MODEL.BACKBONE.TYPE!r}: only vit_base_patch16_224, vit_base_patch16_224_ce and "
-                                      "vit_large_patch16_224 are implemented")
+            raise NotImplementedError(f"backbone {cfg.MODEL.BACKBONE.TYPE!r}: only vit_base_patch16_224, vit_base_patch16_224_ce, "
+                                      "vit_large_patch16_224, vit_small_patch16_224 and vit_tiny_patch16_224 are implemented")
         if str(cfg.MODEL.BACKBONE.CAT_MODE) != "direct":
             raise NotImplementedError("only CAT_MODE 'direct' (template tokens first) is implemented")
         self.geom, self.depth, self.mode, self.head_type, self.max_batch = g, depth, "eval", "CENTER", max_batch
@@ -152,3 +179,13 @@ def build_ostrack(cfg, training=False, max_batch=1, ce_form=None):
     if training:
         raise NotImplementedError("inference graph only")
     return OSTrack(cfg, max_batch=max_batch, ce_form=ce_form)
+
+
+def build_small_ostrack(cfg, training=False, max_batch=1, ce_form=None):
+    """The reference's build_small_ostrack (lib/models/ostrack/ostrack.py:288-342; its tracking/profile_model*.py and onnxexport.py build exactly
+    this): TYPE vit_base_patch16_224_ce at depth 3, width / heads from MODEL.BACKBONE.CHANNELS / HEADS -- (192, 3), (384, 6) or (768, 12).  An
+    empty CE_LOC is the plain depth-3 model; a non-empty one runs at width 768 through build_ostrack's candidate-elimination machinery and
+    raises NotImplementedError at the small widths."""
+    if training:
+        raise NotImplementedError("inference graph only")
+    return OSTrack(cfg, max_batch=max_batch, ce_form=ce_form, small=True)

@@ -45,6 +45,7 @@ ABI = {
     "vt_last_error": (C.c_char_p, []),
     "vt_version": (C.c_char_p, []),
     "vt_create": (C.c_int, [C.POINTER(VtConfig), C.POINTER(_vp)]),
+    "vt_create_vit": (C.c_int, [C.POINTER(VtConfig), C.POINTER(_vp)]),
     "vt_destroy": (None, [_vp]),
     "vt_load_weights": (C.c_int, [_vp, C.POINTER(VtTensor), _i32]),
     "vt_set_window": (C.c_int, [_vp, _vp]),
@@ -749,15 +750,21 @@ class Model:
     ce_form = "masked"      # the form set_candidate_elimination chose
 
     def __init__(self, template_size, search_size, channels=48, heads=1, depth=3, head_channels=32, stride=16,
-                 max_batch=1, precision="f32"):
+                 max_batch=1, precision="f32", family=None):
         """precision: 'f32' (exact fp32 contractions, the parity path) or 'f16' (vit_48 contractions on f16 MFMA,
         BASELINE config 5).  The ViT-Base path (channels=768, heads=12) and the ViT-Large one (channels=1024, heads=16, head_channels=256
-        at 128 / 256 or 192 / 384) always contract in bf16."""
-        self.precision = precision
+        at 128 / 256 or 192 / 384) always contract in bf16.
+        family: None -- vt_create chooses the family from the widths (768 / 12 and the ViT-Large tuple: the patch-16 ViT; everything else,
+        384 / 6 and 192 / 3 included, the LeViT-stem vit_dist model); "vit" -- vt_create_vit: the patch-16 OSTrack ViT at (channels, heads) =
+        (192, 3) ViT-Tiny, (384, 6) ViT-Small, (768, 12), (1024, 16), anything else refused."""
+        if family not in (None, "vit"):
+            raise ValueError(f"family={family!r}: None (vt_create's choice) or 'vit'")
+        self.precision, self.family = precision, family
         self._L = lib(precision)
         self.cfg = VtConfig(template_size, search_size, channels, heads, depth, head_channels, stride, max_batch)
         h = C.c_void_p()
-        _check(self._L.vt_create(C.byref(self.cfg), C.byref(h)), "vt_create", self._L)
+        create = "vt_create_vit" if family == "vit" else "vt_create"
+        _check(getattr(self._L, create)(C.byref(self.cfg), C.byref(h)), create, self._L)
         self._h = h
         q = [C.c_int32() for _ in range(4)]
         _check(self._L.vt_query(self._h, *[C.byref(v) for v in q]), "vt_query", self._L)

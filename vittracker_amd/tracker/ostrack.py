@@ -1,5 +1,5 @@
 """Tracker plugin: ``OSTrack`` -- the ViT-Base / ViT-Large OSTrack tracker with the reference's ``initialize() / track()`` contract
-(``lib/test/tracker/ostrack.py:23-189`` for the ``vit_base_patch16_224`` / ``vit_base_patch16_224_ce`` / ``vit_large_patch16_224`` backbones), on the
+(``lib/test/tracker/ostrack.py:23-189`` for the ``vit_base_patch16_224`` / ``vit_base_patch16_224_ce`` / ``vit_large_patch16_224`` backbones and the small students ``vit_small_patch16_224`` / ``vit_tiny_patch16_224``), on the
 MI355X-native library.
 
 The frame step of the two reference trackers is the same statement -- ``sample_target``, ``Preprocessor.process``, the network,
@@ -26,7 +26,7 @@ class OSTrack(Vit_dist):
         from ..model_vitb import build_ostrack
         if network_builder(params.cfg) is not build_ostrack:
             raise ValueError("the ostrack tracker runs the ViT-Base OSTrack model (MODEL.BACKBONE.TYPE vit_base_patch16_224, CHANNELS 768) or the "
-                             "ViT-Large one (TYPE vit_large_patch16_224); "
+                             "ViT-Large / -Small / -Tiny ones (TYPE vit_large_patch16_224, vit_small_patch16_224, vit_tiny_patch16_224); "
                              "this cfg names another one (tracker vit_dist runs the distilled models)")
         super().__init__(params, dataset_name)
 
