@@ -3,7 +3,8 @@ behind every stage the kept tokens are gathered into shorter frames and everythi
 public results as the masked form (tests/test_gpu_vitb_ce.py, whose helpers, tolerances and constructions are reused here).
 
   1  test_stage1_is_the_masked_forms   the first removing stage scores and selects before anything moves: ce_result bit-identical between the
-                                       forms for one stage, and stage 1's scores and removed set under the published three stages; 320 and 720.
+                                       forms for one stage, under CTR_POINT (the plain loop) and ALL (the MFMA form); 320 and 720.
+     test_stage1_under_the_published_three_stages   stage 1's scores and removed set under the published three stages; 320 and 720.
   2  test_compacted_attention          test_masked_attention's construction in the compact form, the bf16 oracle chunked over the COMPACTED
                                        key order; keep ratios chosen for the tails of the run-time kernel (ce_compact_cases.ATTN_RATIOS).
      test_pad_and_read_past_rows_are_never_used   NaN / stale rows beyond the live ones: the kept rows do not change by a bit.
@@ -36,14 +37,15 @@ def _result(m, B):
 
 
 # ------------------------------------------------------------------------------------------ 1: stage 1 is the masked form's
+@pytest.mark.parametrize("trange", ["CTR_POINT", "ALL"])      # the plain score loop and the MFMA form: one launch choice under both forms
 @pytest.mark.parametrize("L", [320, 720])
-def test_stage1_is_the_masked_forms(L):
+def test_stage1_is_the_masked_forms(L, trange):
     import torch
     r = cb.score_refs("plain", L)
     x = torch.from_numpy(r["X"]).cuda()
     got = {}
     for form in ("masked", "compact"):
-        m = cc.model(L, 1, r["sd"], cb.SCORE_B, [0], [cb.KEEP_RATIO], cb.range_rows("CTR_POINT", L), form=form)
+        m = cc.model(L, 1, r["sd"], cb.SCORE_B, [0], [cb.KEEP_RATIO], cb.range_rows(trange, L), form=form)
         try:
             assert m.ce_form == form
             m.blocks(x, nblocks=1)
@@ -52,7 +54,13 @@ def test_stage1_is_the_masked_forms(L):
             m.close()
     assert np.array_equal(got["masked"][0], got["compact"][0]) and np.array_equal(got["masked"][1], got["compact"][1])
     assert ((got["compact"][0] == 0).sum(1) == r["count"]).all()
-    # the published three stages (depth 4: blocks 0, 1, 2): stage 1's scores and its removed set
+
+
+@pytest.mark.parametrize("L", [320, 720])
+def test_stage1_under_the_published_three_stages(L):
+    """The published three stages (depth 4: blocks 0, 1, 2): stage 1's scores and its removed set are the masked form's."""
+    import torch
+    got = {}
     sd, X = bb.regime("plain", L, seed=cb.SEEDS[("plain", L)], B=2, depth=4)
     x = torch.from_numpy(X).cuda()
     for form in ("masked", "compact"):

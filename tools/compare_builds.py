@@ -9,15 +9,23 @@
 VARIANTS in tests/test_gpu_variants.py, VT_TRACK_U8=0, VT_GRAPH_CHAINS=2 and 3, and the crop forms tests/test_gpu_patch_u8.py forces
 (crop_bytes, crop_fast_off, crop_band_off, crop_band4, crop_band2, crop_band4_unaligned), and the ViT-Base attention routes the default never
 takes: vb_unfused (attn_kernel<320, 64>), vb_stream (attn_stream_kernel<320>), vb_nofold.  Configs: g128, g256, generic (112, 224), f16 (the f16
-build at G128, needs --f16), vitb, vitb384 (192 / 384, depth 12).  Batches 1, 5, 7, 96, 256 (vitb 1, 96; vitb384 1, 5).  Entries: forward, forward on the cached template, forward_u8,
+build at G128, needs --f16), vitb, vitb384 (192 / 384, depth 12), vitbce, vitbce384 (candidate elimination, below).  Batches 1, 5, 7, 96, 256
+(vitb 1, 96; vitb384 1, 5; vitbce, vitbce384 1, 5).  Entries: forward, forward on the cached template, forward_u8,
 capture + replay, track_step, track_step_frames, track_step_images (NV12, and I420 under BT.709: the other body of the band image kernel)
 -- four steps each for the tracker entries, so the state
 feeds back.  A child prints sha256 over the bytes of all six outputs (+ states and record) per case, or the library's error code where it
-refuses the case: both libraries must refuse with the same code.  Children run one after the other."""
+refuses the case: both libraries must refuse with the same code.  Children run one after the other.
+
+vitbce / vitbce384: a depth-4 ViT-Base model with CE_LOC [0, 1, 2] and keep ratios 0.7 at either geometry, in the masked and the compact
+form, under CE_TEMPLATE_RANGE CTR_POINT (the plain score loop), ALL (the MFMA score) and ALL with VB_CE_SCORE_PLAIN=1 (the plain loop at 64 /
+144 rows); entries forward and capture + replay.  The hash covers the six outputs and both arrays of ce_result as bytes, NaN scores included."""
 import argparse, json, os, subprocess, sys
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 KEYS = ("score_map", "size_map", "offset_map", "pred_boxes", "hann_boxes", "conf")
-VITB_BATCHES = {"vitb": (1, 96), "vitb384": (1, 5)}      # the ViT-Base configs and the batches of --batches each of them runs
+VITB_BATCHES = {"vitb": (1, 96), "vitb384": (1, 5), "vitbce": (1, 5), "vitbce384": (1, 5)}      # the ViT-Base configs and the batches of --batches each of them runs
+CE_GEOMS = {"vitbce": (128, 256), "vitbce384": (192, 384)}      # the candidate-elimination configs
+CE_LOC, CE_RATIO, CE_DEPTH = [0, 1, 2], [0.7, 0.7, 0.7], 4
+CE_RANGES = (("CTR_POINT", "0"), ("ALL", "0"), ("ALL", "1"))      # (CE_TEMPLATE_RANGE, VB_CE_SCORE_PLAIN: read when the model is created)
 
 VITB_CHILD = r"""
 import sys, json, hashlib
@@ -66,7 +74,49 @@ def child(configs, batches):
             code = re.search(r"\((-?\d+)\)", str(e))
             res[name] = "refused " + (code.group(1) if code else str(e)[:60])
 
+    def ce_cases(cfg):
+        from vittracker_amd.model_vitb import ce_template_rows
+        tz, tx = CE_GEOMS[cfg]
+        sd = synth.synth_vitb_state_dict(26, depth=CE_DEPTH, len_z=(tz // 16) ** 2, len_x=(tx // 16) ** 2)
+        for B in (b for b in batches if b in VITB_BATCHES[cfg]):
+            z, x = synth.synth_inputs(40 + B, B, tz, tx)
+            zd, xd = torch.from_numpy(z).cuda(), torch.from_numpy(x).cuda()
+            for form in ("masked", "compact"):
+                for trange, plain in CE_RANGES:
+                    def make():
+                        os.environ["VB_CE_SCORE_PLAIN"] = plain
+                        m = native.Model(tz, tx, channels=768, heads=12, depth=CE_DEPTH, head_channels=256, max_batch=B)
+                        m.load_state_dict(sd)
+                        m.set_candidate_elimination(CE_LOC, CE_RATIO, ce_template_rows(trange, tz // 16), form=form)
+                        return m
+                    tag = f"{cfg}/{form}/{trange}{'+plain' if plain == '1' else ''}/B{B}/"
+
+                    def forward():
+                        m = make()
+                        try:
+                            return digest(m.forward(zd, xd), *m.ce_result(B))
+                        finally:
+                            m.close()
+
+                    def captured():
+                        m = make()
+                        try:
+                            g, out = m.capture(zd, xd)
+                            g.launch()
+                            g.launch()
+                            h = digest(out, *m.ce_result(B))
+                            del g
+                            return h
+                        finally:
+                            m.close()
+                    case(tag + "forward", forward)
+                    case(tag + "capture", captured)
+        os.environ.pop("VB_CE_SCORE_PLAIN", None)
+
     for cfg in configs:
+        if cfg in CE_GEOMS:
+            ce_cases(cfg)
+            continue
         tz, tx = {"g128": (64, 128), "g256": (128, 256), "generic": (112, 224), "f16": (64, 128), "vitb": (128, 256), "vitb384": (192, 384)}[cfg]
         if cfg in VITB_BATCHES:
             sd = synth.synth_vitb_state_dict(26, len_z=(tz // 16) ** 2, len_x=(tx // 16) ** 2)
@@ -175,7 +225,7 @@ def main():
     ap.add_argument("--matrix", action="store_true")
     ap.add_argument("--f16", default="")
     ap.add_argument("--envs", default="")
-    ap.add_argument("--configs", default="g128,g256,generic,f16,vitb,vitb384")
+    ap.add_argument("--configs", default="g128,g256,generic,f16,vitb,vitb384,vitbce,vitbce384")
     ap.add_argument("--batches", default="1,5,7,96,256")
     ap.add_argument("--out", default="")
     a = ap.parse_args()

@@ -40,27 +40,18 @@ constexpr int MAX_LX = 576;        // search tokens of the larger geometry (ce_s
 
 __device__ __forceinline__ bool key_present(const uint32_t* fb, int key) { return !fb || ((fb[key >> 5] >> (key & 31)) & 1u); }
 
-// grid = B * heads, 256 threads.  qk: [frame][L][2 C] bf16 (q pre-scaled | k); bits: [frame][ceil(L / 32)] or nullptr (every key present);
-// rows: the nrows selected template rows; part: [frame][heads][L - Lz] f32, the sum over the rows of the softmax weights of the search keys.
+// The plain score of one (frame, head), under ce_score_kernel and ce_score_rt_kernel.  qf / kf: the head's q / k columns of the frame's first
+// row, rows of 2 C; Lp: rows per frame; present(s): whether this lane's key lane + 64 s exists and is present (evaluated where it is used:
+// the callers differ in what they precompute); red: [4][Lp] floats of LDS, the four waves' partial sums; out: [n], search keys Lz .. Lz + n.
 // A wave takes rows w, w + 4, ...; a lane the keys lane, lane + 64, ... of every row.
-template <int L>
-__global__ __launch_bounds__(256) void ce_score_kernel(const bf16* __restrict__ qk, const uint32_t* __restrict__ bits,
-                                                       const int32_t* __restrict__ rows, int nrows, float* __restrict__ part, int heads, int Lz) {
-    constexpr int HD = 64, KPL = (L + 63) / 64, W = (L + 31) / 32;
-    __shared__ float red[4][L];
+template <int KPL, typename Present>
+__device__ __forceinline__ void score_rows(const bf16* qf, const bf16* kf, int C, int Lp, const int32_t* __restrict__ rows, int nrows, Present present,
+                                           float* red, int Lz, int n, float* __restrict__ out) {
+    constexpr int HD = 64;
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    const int f = blockIdx.x / heads, h = blockIdx.x - f * heads, C = heads * HD;
-    const bf16* qf = qk + (size_t)f * L * 2 * C + h * HD;
-    const bf16* kf = qf + C;
-    const uint32_t* fb = bits ? bits + (size_t)f * W : nullptr;
-    bool ok[KPL];
     float acc[KPL];
 #pragma unroll
-    for (int s = 0; s < KPL; ++s) {
-        const int key = lane + 64 * s;
-        ok[s] = key < L && key_present(fb, key);
-        acc[s] = 0.f;
-    }
+    for (int s = 0; s < KPL; ++s) acc[s] = 0.f;
     for (int r = w; r < nrows; r += 4) {
         const bf16* qr = qf + (size_t)rows[r] * 2 * C;
         float qv[HD];
@@ -74,7 +65,7 @@ __global__ __launch_bounds__(256) void ce_score_kernel(const bf16* __restrict__ 
 #pragma unroll
         for (int s = 0; s < KPL; ++s) {
             sc[s] = -INFINITY;
-            if (ok[s]) {
+            if (present(s)) {
                 const bf16* kr = kf + (size_t)(lane + 64 * s) * 2 * C;
                 float a = 0.f;
 #pragma unroll
@@ -103,38 +94,50 @@ __global__ __launch_bounds__(256) void ce_score_kernel(const bf16* __restrict__ 
     }
 #pragma unroll
     for (int s = 0; s < KPL; ++s)
-        if (lane + 64 * s < L) red[w][lane + 64 * s] = acc[s];
+        if (lane + 64 * s < Lp) red[w * Lp + lane + 64 * s] = acc[s];
     __syncthreads();
-    const int Lx = L - Lz;
-    float* out = part + ((size_t)f * heads + h) * Lx;
-    for (int j = threadIdx.x; j < Lx; j += 256) out[j] = ((red[0][Lz + j] + red[1][Lz + j]) + red[2][Lz + j]) + red[3][Lz + j];
+    for (int j = threadIdx.x; j < n; j += 256) out[j] = ((red[Lz + j] + red[Lp + Lz + j]) + red[2 * Lp + Lz + j]) + red[3 * Lp + Lz + j];
 }
 
-// ce_score_kernel's result for CE_TEMPLATE_RANGE ALL (every template row: Lz / 16 whole query tiles) on the 16x16x32 bf16 MFMA.  The plain
-// loop above costs 3.3 x / 3.7 x the block's own attention there (64 / 144 rows: DESIGN.md 11.4); this form reads K once per query TILE.
-// grid = B * heads, 256 threads; qk, bits, part as above.  A wave takes query tiles w, w + 4, ..  S = Q K^T per 16-key tile: the q rows are the
-// A operand and the k rows the B operand, both fetched from global memory with vba::load_q's addressing (row = lane & 15, k = 8 (lane >> 4)
-// + {0..7}: the layout of either operand), so a lane holds S[query 16 qt + 4 (lane >> 4) + j][key 16 t + (lane & 15)], j = 0..3 -- a
-// query's softmax runs along the lanes, the sum over queries along j and the four lane groups.  Two passes over the keys per query tile,
-// nothing of size L in registers (the per-key accumulators live in LDS): pass 1 the online maximum and sum of each lane's column of keys, then
-// combined over the 16 key lanes by butterfly; pass 2 the logits again, exp2 against the row maximum with the log2 e factor, times 1 / sum,
-// added into the lane's accumulator of that key.  The 16 partial sums of a key (4 waves x 4 lane groups) meet in LDS in a fixed order.
+// grid = B * heads, 256 threads.  qk: [frame][L][2 C] bf16 (q pre-scaled | k); bits: [frame][ceil(L / 32)] or nullptr (every key present);
+// rows: the nrows selected template rows; part: [frame][heads][L - Lz] f32, the sum over the rows of the softmax weights of the search keys.
 template <int L>
-__global__ __launch_bounds__(256) void ce_score_all_kernel(const bf16* __restrict__ qk, const uint32_t* __restrict__ bits, float* __restrict__ part,
-                                                           int heads, int Lz) {
-    constexpr int HD = 64, KS = HD / 32, NT = L / 16, W = (L + 31) / 32;
-    static_assert(L % 16 == 0, "whole key tiles");
-    constexpr int UNR = NT % 5 == 0 ? 5 : 1;      // key tiles in flight per loop trip (20 and 45 tiles: 5); more and L = 720 spills
-    __shared__ float red[16][L];
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+__global__ __launch_bounds__(256) void ce_score_kernel(const bf16* __restrict__ qk, const uint32_t* __restrict__ bits,
+                                                       const int32_t* __restrict__ rows, int nrows, float* __restrict__ part, int heads, int Lz) {
+    constexpr int HD = 64, KPL = (L + 63) / 64, W = (L + 31) / 32;
+    __shared__ float red[4][L];
+    const int lane = threadIdx.x & 63;
     const int f = blockIdx.x / heads, h = blockIdx.x - f * heads, C = heads * HD;
     const bf16* qf = qk + (size_t)f * L * 2 * C + h * HD;
-    const bf16* kf = qf + C;
     const uint32_t* fb = bits ? bits + (size_t)f * W : nullptr;
+    bool ok[KPL];
+#pragma unroll
+    for (int s = 0; s < KPL; ++s) {
+        const int key = lane + 64 * s;
+        ok[s] = key < L && key_present(fb, key);
+    }
+    score_rows<KPL>(qf, qf + C, C, L, rows, nrows, [&](int s) { return ok[s]; }, &red[0][0], Lz, L - Lz, part + ((size_t)f * heads + h) * (L - Lz));
+}
+
+// ce_score_kernel's result for CE_TEMPLATE_RANGE ALL (every template row: Lz / 16 whole query tiles) on the 16x16x32 bf16 MFMA, of one
+// (frame, head), under ce_score_all_kernel and ce_score_all_rt_kernel.  The plain loop above costs 3.3 x / 3.7 x the block's own attention
+// there (64 / 144 rows: DESIGN.md 11.4); this form reads K once per query TILE.  qf, kf, Lp, Lz, n, out as score_rows, Lp / 16 whole key
+// tiles; gone(t): 0 where this lane's key 16 t + (lane & 15) is present, else -inf; red: [16][Lp] floats of LDS; UNR: key
+// tiles in flight per loop trip.  A wave takes query tiles w, w + 4, ..  S = Q K^T per 16-key tile: the q rows are the A operand and the k
+// rows the B operand, both fetched from global memory with vba::load_q's addressing (row = lane & 15, k = 8 (lane >> 4) + {0..7}: the layout
+// of either operand), so a lane holds S[query 16 qt + 4 (lane >> 4) + j][key 16 t + (lane & 15)], j = 0..3 -- a query's softmax runs along
+// the lanes, the sum over queries along j and the four lane groups.  Two passes over the keys per query tile, nothing of size L in registers
+// (the per-key accumulators live in LDS): pass 1 the online maximum and sum of each lane's column of keys, then combined over the 16 key
+// lanes by butterfly; pass 2 the logits again, exp2 against the row maximum with the log2 e factor, times 1 / sum, added into the lane's
+// accumulator of that key.  The 16 partial sums of a key (4 waves x 4 lane groups) meet in LDS in a fixed order.
+template <int UNR, typename Gone>
+__device__ __forceinline__ void score_all_tiles(const bf16* qf, const bf16* kf, int C, int Lp, Gone gone, float* red, int Lz, int n, float* __restrict__ out) {
+    constexpr int HD = 64, KS = HD / 32;
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, NT = Lp / 16;
     const int l15 = lane & 15, g = lane >> 4;
     // this lane's accumulator of key 16 t + l15 is red[4 w + g][16 t + l15]: its own slot, so the key loops need no unrolling (with the
     // accumulators in registers the compiler unrolls 45 tiles, hoists their loads and spills at L = 720)
-    float* const acc = red[w * 4 + g] + l15;
+    float* const acc = red + (size_t)(w * 4 + g) * Lp + l15;
     for (int t = 0; t < NT; ++t) acc[16 * t] = 0.f;
     // one key tile's logits of this lane's four queries; an absent key's column is -inf
     auto logits = [&](const bf16x8 (&qa)[KS], int t) {
@@ -143,11 +146,9 @@ __global__ __launch_bounds__(256) void ce_score_all_kernel(const bf16* __restric
         f4 S = splat4(0.f);
 #pragma unroll
         for (int ks = 0; ks < KS; ++ks) S = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qa[ks], kb[ks], S, 0, 0, 0);
-        // the MFMAs run for every lane, whatever the bitmap says: with `present ? S : -inf` the compiler put them inside the branch on the
-        // lane's bit, and an MFMA under a partial EXEC mask returned wrong logits for every fifth tile.  A 16-key tile lies inside one word
-        const uint32_t word = fb ? fb[t >> 1] : 0xffffffffu;
-        const float gone = ((word >> ((16 * t + l15) & 31)) & 1u) ? 0.f : -INFINITY;
-        return S + splat4(gone);
+        // the MFMAs run for every lane, whatever gone() says, and -inf is ADDED: with `present ? S : -inf` the compiler put them inside the
+        // branch on the lane's bit, and an MFMA under a partial EXEC mask returned wrong logits for every fifth tile
+        return S + splat4(gone(t));
     };
     for (int qt = w; qt < Lz / 16; qt += 4) {
         bf16x8 qa[KS];
@@ -192,14 +193,49 @@ __global__ __launch_bounds__(256) void ce_score_all_kernel(const bf16* __restric
         }
     }
     __syncthreads();
-    const int Lx = L - Lz;
-    float* out = part + ((size_t)f * heads + h) * Lx;
-    for (int j = threadIdx.x; j < Lx; j += 256) {
+    for (int j = threadIdx.x; j < n; j += 256) {
         float s = 0.f;
 #pragma unroll
-        for (int i = 0; i < 16; ++i) s += red[i][Lz + j];
+        for (int i = 0; i < 16; ++i) s += red[(size_t)i * Lp + Lz + j];
         out[j] = s;
     }
+}
+
+// grid = B * heads, 256 threads; qk, bits, part as ce_score_kernel.
+template <int L>
+__global__ __launch_bounds__(256) void ce_score_all_kernel(const bf16* __restrict__ qk, const uint32_t* __restrict__ bits, float* __restrict__ part,
+                                                           int heads, int Lz) {
+    constexpr int HD = 64, NT = L / 16, W = (L + 31) / 32;
+    static_assert(L % 16 == 0, "whole key tiles");
+    constexpr int UNR = NT % 5 == 0 ? 5 : 1;      // key tiles in flight per loop trip (20 and 45 tiles: 5); more and L = 720 spills
+    __shared__ float red[16][L];
+    const int l15 = threadIdx.x & 15;
+    const int f = blockIdx.x / heads, h = blockIdx.x - f * heads, C = heads * HD;
+    const bf16* qf = qk + (size_t)f * L * 2 * C + h * HD;
+    const uint32_t* fb = bits ? bits + (size_t)f * W : nullptr;
+    auto gone = [&](int t) {      // a 16-key tile lies inside one word
+        const uint32_t word = fb ? fb[t >> 1] : 0xffffffffu;
+        return ((word >> ((16 * t + l15) & 31)) & 1u) ? 0.f : -INFINITY;
+    };
+    score_all_tiles<UNR>(qf, qf + C, C, L, gone, &red[0][0], Lz, L - Lz, part + ((size_t)f * heads + h) * (L - Lz));
+}
+
+// What the two select kernels share.  head_sum: candidate j's partial sums of frame f, [frame][heads][n], added in head order.  rank_of: how
+// many of the n candidates that counts(i) admits stand before candidate j -- a higher score, or an equal one at a lower index.
+__device__ __forceinline__ float head_sum(const float* __restrict__ part, int f, int heads, int n, int j) {
+    float v = 0.f;
+    for (int h = 0; h < heads; ++h) v += part[((size_t)f * heads + h) * n + j];
+    return v;
+}
+template <typename Counts>
+__device__ __forceinline__ int rank_of(const float* s, int n, int j, Counts counts) {
+    const float sj = s[j];
+    int rank = 0;
+    for (int i = 0; i < n; ++i) {
+        const float si = s[i];
+        rank += (counts(i) && (si > sj || (si == sj && i < j))) ? 1 : 0;
+    }
+    return rank;
 }
 
 // grid = B, 256 threads.  part as ce_score_kernel left it; scale = 1 / (heads * nrows); prev: the bitmap this stage's attention ran under
@@ -213,8 +249,7 @@ __global__ __launch_bounds__(256) void ce_select_kernel(const float* __restrict_
     const int f = blockIdx.x, Lx = L - Lz, W = (L + 31) / 32;
     const uint32_t* fb = prev ? prev + (size_t)f * W : nullptr;
     for (int j = threadIdx.x; j < Lx; j += 256) {
-        float v = 0.f;
-        for (int h = 0; h < heads; ++h) v += part[((size_t)f * heads + h) * Lx + j];
+        float v = head_sum(part, f, heads, Lx, j);
         const bool p = key_present(fb, Lz + j);
         v = p ? v * scale : __builtin_nanf("");
         s[j] = v;
@@ -225,13 +260,7 @@ __global__ __launch_bounds__(256) void ce_select_kernel(const float* __restrict_
     for (int j = threadIdx.x; j < Lx; j += 256) {
         bool k = false;
         if (pres[j]) {
-            const float sj = s[j];
-            int rank = 0;
-            for (int i = 0; i < Lx; ++i) {
-                const float si = s[i];
-                rank += (pres[i] && (si > sj || (si == sj && i < j))) ? 1 : 0;
-            }
-            k = rank < keep;
+            k = rank_of(s, Lx, j, [&](int i) { return pres[i] != 0; }) < keep;
             if (!k) removed[(size_t)f * Lx + j] = (uint8_t)stage;
             else if (!prev) removed[(size_t)f * Lx + j] = 0;
         }
@@ -280,132 +309,24 @@ __global__ __launch_bounds__(256) void ce_score_rt_kernel(const bf16* __restrict
                                                           float* __restrict__ part, int heads, int Lz) {
     constexpr int HD = 64;
     extern __shared__ float red_rt[];      // [4][Lp]
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const int lane = threadIdx.x & 63;
     const int f = blockIdx.x / heads, h = blockIdx.x - f * heads, C = heads * HD;
     const bf16* qf = qk + (size_t)f * Lp * 2 * C + h * HD;
-    const bf16* kf = qf + C;
-    float acc[KPL];
-#pragma unroll
-    for (int s = 0; s < KPL; ++s) acc[s] = 0.f;
-    for (int r = w; r < nrows; r += 4) {
-        const bf16* qr = qf + (size_t)rows[r] * 2 * C;
-        float qv[HD];
-#pragma unroll
-        for (int d = 0; d < HD; d += 8) {
-            const bf16x8 t = *reinterpret_cast<const bf16x8*>(qr + d);
-#pragma unroll
-            for (int j = 0; j < 8; ++j) qv[d + j] = (float)t[j];
-        }
-        float sc[KPL], mx = -INFINITY;
-#pragma unroll
-        for (int s = 0; s < KPL; ++s) {
-            sc[s] = -INFINITY;
-            if (lane + 64 * s < nkeys) {
-                const bf16* kr = kf + (size_t)(lane + 64 * s) * 2 * C;
-                float a = 0.f;
-#pragma unroll
-                for (int d = 0; d < HD; d += 8) {
-                    const bf16x8 t = *reinterpret_cast<const bf16x8*>(kr + d);
-#pragma unroll
-                    for (int j = 0; j < 8; ++j) a = fmaf(qv[d + j], (float)t[j], a);
-                }
-                sc[s] = a;
-            }
-            mx = fmaxf(mx, sc[s]);
-        }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o));
-        float sum = 0.f;
-#pragma unroll
-        for (int s = 0; s < KPL; ++s) {
-            sc[s] = __builtin_amdgcn_exp2f((sc[s] - mx) * vba::LOG2E);
-            sum += sc[s];
-        }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o);
-        const float inv = 1.0f / sum;
-#pragma unroll
-        for (int s = 0; s < KPL; ++s) acc[s] = fmaf(sc[s], inv, acc[s]);
-    }
-#pragma unroll
-    for (int s = 0; s < KPL; ++s)
-        if (lane + 64 * s < Lp) red_rt[w * Lp + lane + 64 * s] = acc[s];
-    __syncthreads();
     const int n = nkeys - Lz;
-    float* out = part + ((size_t)f * heads + h) * n;
-    for (int j = threadIdx.x; j < n; j += 256)
-        out[j] = ((red_rt[Lz + j] + red_rt[Lp + Lz + j]) + red_rt[2 * Lp + Lz + j]) + red_rt[3 * Lp + Lz + j];
+    score_rows<KPL>(qf, qf + C, C, Lp, rows, nrows, [&](int s) { return lane + 64 * s < nkeys; }, red_rt, Lz, n, part + ((size_t)f * heads + h) * n);
 }
 
 // ce_score_all_kernel at a run-time frame length (every template row, on the MFMA).  grid = B * heads, 256 threads, 16 * Lp floats of dynamic
-// LDS.  The pad keys lie in the last key tile; their column gets -inf by the additive form, with the MFMAs outside any branch as above.
+// LDS.  The pad keys lie in the last key tile.
 __global__ __launch_bounds__(256) void ce_score_all_rt_kernel(const bf16* __restrict__ qk, int Lp, int nkeys, float* __restrict__ part, int heads, int Lz) {
-    constexpr int HD = 64, KS = HD / 32;
+    constexpr int HD = 64;
     extern __shared__ float red_rt[];      // [16][Lp]
-    const int NT = Lp / 16;
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const int l15 = threadIdx.x & 15;
     const int f = blockIdx.x / heads, h = blockIdx.x - f * heads, C = heads * HD;
     const bf16* qf = qk + (size_t)f * Lp * 2 * C + h * HD;
-    const bf16* kf = qf + C;
-    const int l15 = lane & 15, g = lane >> 4;
-    float* const acc = red_rt + (size_t)(w * 4 + g) * Lp + l15;
-    for (int t = 0; t < NT; ++t) acc[16 * t] = 0.f;
-    auto logits = [&](const bf16x8 (&qa)[KS], int t) {
-        bf16x8 kb[KS];
-        vba::load_q(kb, kf, t, l15, g, C);
-        f4 S = splat4(0.f);
-#pragma unroll
-        for (int ks = 0; ks < KS; ++ks) S = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qa[ks], kb[ks], S, 0, 0, 0);
-        const float gone = 16 * t + l15 < nkeys ? 0.f : -INFINITY;
-        return S + splat4(gone);
-    };
-    for (int qt = w; qt < Lz / 16; qt += 4) {
-        bf16x8 qa[KS];
-        vba::load_q(qa, qf, qt, l15, g, C);
-        float m[4], l[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) { m[j] = -1e30f; l[j] = 0.f; }
-        for (int t = 0; t < NT; ++t) {
-            const f4 S = logits(qa, t);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const float mn = fmaxf(m[j], S[j]);
-                l[j] = l[j] * __builtin_amdgcn_exp2f((m[j] - mn) * vba::LOG2E) + __builtin_amdgcn_exp2f((S[j] - mn) * vba::LOG2E);
-                m[j] = mn;
-            }
-        }
-#pragma unroll
-        for (int o = 1; o < 16; o <<= 1)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const float mo = __shfl_xor(m[j], o), lo = __shfl_xor(l[j], o), mn = fmaxf(m[j], mo);
-                {      // one normaliser for all 16 lanes, as in ce_score_all_kernel
-#pragma clang fp contract(off)
-                    const float mine = l[j] * __builtin_amdgcn_exp2f((m[j] - mn) * vba::LOG2E), theirs = lo * __builtin_amdgcn_exp2f((mo - mn) * vba::LOG2E);
-                    l[j] = mine + theirs;
-                }
-                m[j] = mn;
-            }
-        float inv[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) inv[j] = 1.0f / l[j];
-        for (int t = 0; t < NT; ++t) {
-            const f4 S = logits(qa, t);
-            float p[4];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) p[j] = __builtin_amdgcn_exp2f((S[j] - m[j]) * vba::LOG2E) * inv[j];
-            acc[16 * t] += (p[0] + p[1]) + (p[2] + p[3]);
-        }
-    }
-    __syncthreads();
     const int n = nkeys - Lz;
-    float* out = part + ((size_t)f * heads + h) * n;
-    for (int j = threadIdx.x; j < n; j += 256) {
-        float s = 0.f;
-#pragma unroll
-        for (int i = 0; i < 16; ++i) s += red_rt[(size_t)i * Lp + Lz + j];
-        out[j] = s;
-    }
+    score_all_tiles<1>(qf, qf + C, C, Lp, [&](int t) { return 16 * t + l15 < nkeys ? 0.f : -INFINITY; }, red_rt, Lz, n,
+                       part + ((size_t)f * heads + h) * n);
 }
 
 // Select on the current candidates.  grid = B, 256 threads.  part: [frame][heads][ncand], candidate i of a frame being global search token
@@ -426,19 +347,12 @@ __global__ __launch_bounds__(256) void ce_select_compact_kernel(const float* __r
         inv[(size_t)f * Lx + j] = -1;
     }
     for (int j = threadIdx.x; j < ncand; j += 256) {
-        float v = 0.f;
-        for (int h = 0; h < heads; ++h) v += part[((size_t)f * heads + h) * ncand + j];
-        s[j] = v * scale;
+        s[j] = head_sum(part, f, heads, ncand, j) * scale;
     }
     __syncthreads();      // also orders the NaN / -1 fill before the writes below (the same block, global memory)
     for (int j = threadIdx.x; j < ncand; j += 256) {
         const float sj = s[j];
-        int rank = 0;
-        for (int i = 0; i < ncand; ++i) {
-            const float si = s[i];
-            rank += (si > sj || (si == sj && i < j)) ? 1 : 0;
-        }
-        const bool k = rank < keep;
+        const bool k = rank_of(s, ncand, j, [](int) { return true; }) < keep;
         const int gidx = pf ? pf[j] : j;
         scores[(size_t)f * Lx + gidx] = sj;
         if (!k) removed[(size_t)f * Lx + gidx] = (uint8_t)stage;

@@ -254,6 +254,14 @@ void dispatch_width(int C, F&& f) {
     else f(std::integral_constant<int, C_BASE>{});
 }
 
+// The kernels that compile the frame length in (the streaming attention and the candidate-elimination scores on full frames): f is called
+// with the model's tokens per frame, L256 or L384, as a std::integral_constant.
+template <typename F>
+void dispatch_geo(const VbModel* m, F&& f) {
+    if (m->g384) f(std::integral_constant<int, L384>{});
+    else f(std::integral_constant<int, L256>{});
+}
+
 // Which tile a GEMM launch runs, from its count of 256 x 256 tiles and the slice's CUs alone: the narrow tile where the wide ones would leave
 // most of the CUs idle.  One rule for launch_tile and vb::gemm_form.
 bool narrow_pick(const VbModel* m, int M, int N, int groups, int cus) {
@@ -413,6 +421,13 @@ int set_normalization(VbModel* m, const float* mean3, const float* std3, std::st
 
 static int build_model(const vt_config* cfg, VbModel** out, const Err& E);
 
+// the "got ..." tail of create's / create_vit's refusals (the ViT-Base message names no depth)
+static std::string got_config(const vt_config* cfg, bool depth) {
+    return "got channels=" + std::to_string(cfg->channels) + " heads=" + std::to_string(cfg->heads) +
+           (depth ? " depth=" + std::to_string(cfg->depth) : std::string()) + " head_channels=" + std::to_string(cfg->head_channels) +
+           " stride=" + std::to_string(cfg->stride) + " template=" + std::to_string(cfg->template_size) + " search=" + std::to_string(cfg->search_size);
+}
+
 int create(const vt_config* cfg, VbModel** out, std::string* err) {
     const Err E{err};
     const bool g256 = cfg->template_size == 128 && cfg->search_size == 256, g384 = cfg->template_size == 192 && cfg->search_size == 384;
@@ -420,16 +435,11 @@ int create(const vt_config* cfg, VbModel** out, std::string* err) {
     if (large) {       // vt_create sends only the exact ViT-Large tuple here; the depth is what is left to refuse
         if (cfg->heads != HEADS_LARGE || cfg->head_channels != HW || cfg->stride != 16 || !(g256 || g384) || cfg->depth < 1 || cfg->depth > 24)
             return E.fail(VT_ERR_ARG, "unsupported ViT-Large configuration: this build implements CHANNELS=1024, HEADS=16, HEAD.NUM_CHANNELS=256, "
-                                      "STRIDE=16, 1 <= depth <= 24, template 128 / search 256 or template 192 / search 384; got channels=" +
-                                      std::to_string(cfg->channels) + " heads=" + std::to_string(cfg->heads) + " depth=" + std::to_string(cfg->depth) +
-                                      " head_channels=" + std::to_string(cfg->head_channels) + " stride=" + std::to_string(cfg->stride) +
-                                      " template=" + std::to_string(cfg->template_size) + " search=" + std::to_string(cfg->search_size));
+                                      "STRIDE=16, 1 <= depth <= 24, template 128 / search 256 or template 192 / search 384; " + got_config(cfg, true));
     } else if (cfg->channels != C_BASE || cfg->heads != HEADS_BASE || cfg->head_channels != HW || cfg->stride != 16 || !(g256 || g384))
         return E.fail(VT_ERR_ARG, "unsupported ViT-Base configuration: this build implements CHANNELS=768, HEADS=12, "
                                   "HEAD.NUM_CHANNELS=256, STRIDE=16, template 128 / search 256 (OSTrack-256) or template 192 / search 384 "
-                                  "(OSTrack-384); got channels=" + std::to_string(cfg->channels) + " heads=" + std::to_string(cfg->heads) +
-                                  " head_channels=" + std::to_string(cfg->head_channels) + " stride=" + std::to_string(cfg->stride) +
-                                  " template=" + std::to_string(cfg->template_size) + " search=" + std::to_string(cfg->search_size));
+                                  "(OSTrack-384); " + got_config(cfg, false));
     return build_model(cfg, out, E);
 }
 
@@ -442,9 +452,7 @@ int create_vit(const vt_config* cfg, VbModel** out, std::string* err) {
     if (!small || cfg->head_channels != HW || cfg->stride != 16 || !(g256 || g384) || cfg->depth < 1 || cfg->depth > 12)
         return E.fail(VT_ERR_ARG, "unsupported ViT configuration: this build implements (CHANNELS, HEADS) = (192, 3), (384, 6) with 1 <= depth <= 12, "
                                   "(768, 12), (1024, 16) with 1 <= depth <= 24, HEAD.NUM_CHANNELS=256, STRIDE=16, template 128 / search 256 or "
-                                  "template 192 / search 384; got channels=" + std::to_string(cfg->channels) + " heads=" + std::to_string(cfg->heads) +
-                                  " depth=" + std::to_string(cfg->depth) + " head_channels=" + std::to_string(cfg->head_channels) + " stride=" +
-                                  std::to_string(cfg->stride) + " template=" + std::to_string(cfg->template_size) + " search=" + std::to_string(cfg->search_size));
+                                  "template 192 / search 384; " + got_config(cfg, true));
     return build_model(cfg, out, E);
 }
 
@@ -830,9 +838,11 @@ int stem_rows(VbModel* m, ZSrc zsrc, const float* z, const float* x, const unsig
 //   otherwise qk GEMM + v GEMM (V^T) and    vbs::attn_stream_kernel<720> (the 384 geometry), vbs::attn_stream_kernel<320> (VB_ATTN_STREAM) or
 //                                           vba::attn_kernel<320, 64>
 // ce: a block from the first candidate-elimination stage on -- always qk GEMM + v GEMM + the streaming kernel at either geometry (the stage's
-// score reads the q | k rows the qk GEMM leaves in v.qk); keys: the slice's key bitmap (vb_ce.h), nullptr = every key (the first stage's block)
+// score reads the q | k rows the qk GEMM leaves in v.qk); keys: the slice's key bitmap (vb_ce.h), nullptr = every key (the first stage's block).
+// Lp > 0: behind a compacting stage (the compact form) -- the GEMMs on the slice's B * Lp dense rows, then vbs::attn_stream_rt_kernel with the
+// frames' nkeys live rows as keys, at either geometry
 static int run_attention(const VbModel* m, const SliceView& v, const BlockW& b, const float* rstd, int B, hipStream_t st, const Err& E,
-                         bool ce = false, const uint32_t* keys = nullptr) {
+                         bool ce = false, const uint32_t* keys = nullptr, int Lp = 0, int nkeys = 0) {
     int rc;
     const int C = m->C, HEADS = m->HEADS;
     if (m->fused_qkv && !m->g384 && !ce) {
@@ -844,14 +854,15 @@ static int run_attention(const VbModel* m, const SliceView& v, const BlockW& b, 
         // (ViT-Small / ViT-Tiny: all 6 / 3 heads of a frame together -- their whole qkv matrix, 864 / 216 KiB, is smaller than one such group)
         const int hg = hgv < 0 ? (C == C_LARGE ? 4 : 6) : hgv;
         qa.hgroup = (hg > 0 && HEADS % hg == 0) ? hg : HEADS;
-        if (C == C_LARGE) hipLaunchKernelGGL(vbq::qkv_attn_wide_kernel<C_LARGE>, dim3(persistent_grid(v.cus)), dim3(512), vbq::LDS_BYTES, st, qa);
-        else if (C == C_SMALL) hipLaunchKernelGGL(vbq::qkv_attn_wide_kernel<C_SMALL>, dim3(persistent_grid(v.cus)), dim3(512), vbq::LDS_BYTES, st, qa);
-        else if (C == C_TINY) hipLaunchKernelGGL(vbq::qkv_attn_wide_kernel<C_TINY>, dim3(persistent_grid(v.cus)), dim3(512), vbq::LDS_BYTES, st, qa);
-        else hipLaunchKernelGGL(vbq::qkv_attn_kernel, dim3(persistent_grid(v.cus)), dim3(512), vbq::LDS_BYTES, st, qa);
+        dispatch_width(C, [&](auto W) {      // width 768: the non-template kernel
+            constexpr int CW = decltype(W)::value;
+            if constexpr (CW == C_BASE) hipLaunchKernelGGL(vbq::qkv_attn_kernel, dim3(persistent_grid(v.cus)), dim3(512), vbq::LDS_BYTES, st, qa);
+            else hipLaunchKernelGGL(vbq::qkv_attn_wide_kernel<CW>, dim3(persistent_grid(v.cus)), dim3(512), vbq::LDS_BYTES, st, qa);
+        });
         VB_HIP(hipGetLastError());
         return VT_OK;
     }
-    const int L = m->L, M = B * L;
+    const int L = Lp ? Lp : m->L, M = B * L;      // rows of a frame, of the slice
     vbg::Args a{};
     a.rstd = rstd;
     a.X = v.xn; a.W = b.wqkv.p; a.bias = b.bqkv.p; a.out = v.qk;          // q | k: rows 0 .. 2C of W_qkv
@@ -862,38 +873,139 @@ static int run_attention(const VbModel* m, const SliceView& v, const BlockW& b, 
     w.M = M; w.N = C; w.K = C; w.L = L; w.rstd = rstd;
     // (always the 256 x 256 tile: the transposed store moves 128 tokens of a feature per row, TM == 8 -- vb_gemm.h)
     if ((rc = launch_wide<vbg::A_PLAIN, vbg::EPI_VT>(w, 1, st, E, v.cus))) return rc;
-    if (keys && m->g384)
-        hipLaunchKernelGGL((vbs::attn_stream_masked_kernel<L384>), dim3(B * HEADS * vbs::splits<L384>()), dim3(256), vbs::LDS_BYTES, st, v.qk, v.vt, v.ao, HEADS, keys);
-    else if (keys)
-        hipLaunchKernelGGL((vbs::attn_stream_masked_kernel<L256>), dim3(B * HEADS * vbs::splits<L256>()), dim3(256), vbs::LDS_BYTES, st, v.qk, v.vt, v.ao, HEADS, keys);
-    else if (m->g384)
-        hipLaunchKernelGGL((vbs::attn_stream_kernel<L384>), dim3(B * HEADS * vbs::splits<L384>()), dim3(256), vbs::LDS_BYTES, st, v.qk, v.vt, v.ao, HEADS);
-    else if (m->attn_stream || ce)
-        hipLaunchKernelGGL((vbs::attn_stream_kernel<L256>), dim3(B * HEADS * vbs::splits<L256>()), dim3(256), vbs::LDS_BYTES, st, v.qk, v.vt, v.ao, HEADS);
+    if (Lp)
+        hipLaunchKernelGGL(vbs::attn_stream_rt_kernel, dim3(B * HEADS * vbs::splits_rt(Lp)), dim3(256), vbs::LDS_BYTES, st, v.qk, v.vt, v.ao, HEADS, Lp, nkeys);
+    else if (keys || m->g384 || m->attn_stream || ce)
+        dispatch_geo(m, [&](auto G) {
+            constexpr int LG = decltype(G)::value;
+            const dim3 grid(B * HEADS * vbs::splits<LG>());
+            if (keys) hipLaunchKernelGGL((vbs::attn_stream_masked_kernel<LG>), grid, dim3(256), vbs::LDS_BYTES, st, v.qk, v.vt, v.ao, HEADS, keys);
+            else hipLaunchKernelGGL((vbs::attn_stream_kernel<LG>), grid, dim3(256), vbs::LDS_BYTES, st, v.qk, v.vt, v.ao, HEADS);
+        });
     else
         hipLaunchKernelGGL((vba::attn_kernel<L256, HD>), dim3(B * HEADS), dim3(256), (vba::Geo<L256, HD>::LDS_BYTES), st, v.qk, v.vt, v.ao, HEADS);
     VB_HIP(hipGetLastError());
     return VT_OK;
 }
 
-// A block's attention behind a compacting stage (the compact form of candidate elimination): qk GEMM + v GEMM on the slice's B * Lp dense
-// rows, then vbs::attn_stream_rt_kernel with the frames' nkeys live rows as keys, at either geometry
-static int run_attention_rt(const VbModel* m, const SliceView& v, const BlockW& b, const float* rstd, int B, int Lp, int nkeys, hipStream_t st, const Err& E) {
-    int rc;
-    const int C = m->C, HEADS = m->HEADS, M = B * Lp;
-    vbg::Args a{};
-    a.rstd = rstd;
-    a.X = v.xn; a.W = b.wqkv.p; a.bias = b.bqkv.p; a.out = v.qk;
-    a.M = M; a.N = 2 * C; a.K = C; a.ldo = 2 * C; a.rb = 4;
-    if ((rc = launch_tile<vbg::A_PLAIN, vbg::EPI_BF16>(m, a, 1, st, E, v.cus))) return rc;
-    vbg::Args w{};
-    w.X = v.xn; w.W = b.wqkv.p + (size_t)2 * C * C; w.bias = b.bqkv.p + 2 * C; w.vt = v.vt;
-    w.M = M; w.N = C; w.K = C; w.L = Lp; w.rstd = rstd;
-    if ((rc = launch_wide<vbg::A_PLAIN, vbg::EPI_VT>(w, 1, st, E, v.cus))) return rc;
-    hipLaunchKernelGGL(vbs::attn_stream_rt_kernel, dim3(B * HEADS * vbs::splits_rt(Lp)), dim3(256), vbs::LDS_BYTES, st, v.qk, v.vt, v.ao, HEADS, Lp, nkeys);
-    VB_HIP(hipGetLastError());
-    return VT_OK;
-}
+// Candidate elimination (vb_ce.h) along one vb::blocks call on a slice: from the first stage's block on the attention is the streaming
+// kernel, under the key bitmap the stages so far have left for the slice's frames (masked form) or on the rows the last stage gathered
+// (compact form); a stage runs behind its block's attention: score, then select.  A plain model: `on` is false and nothing below changes.
+namespace {
+struct CeWalk {
+    const VbModel* const m;
+    const SliceView& v;
+    const int B;
+    const bool on, compact;
+    const uint32_t* keys = nullptr;         // masked form: the bitmap the last stage left; nullptr: every key present
+    const int32_t* cidx = nullptr;          // compact form: the current index table; nullptr: nothing compacted yet
+    int stage = 0, kept;                    // the next stage; the search tokens still there
+    int Lc, nkeys, M;                       // rows and live rows of a frame at the current stage; the slice's residual rows, B * Lc
+    const bf16* proj_x = nullptr;           // where this block's proj GEMM reads the attention rows and their centring means: v.ao and the
+    const float* proj_cm = nullptr;         // caller's, or where the stage's gather left them
+    CeWalk(const VbModel* m, const SliceView& v, int B)
+        : m(m), v(v), B(B), on(m->ce_first >= 0), compact(on && m->ce_form == VT_CE_COMPACT), kept(m->LX), Lc(m->L), nkeys(m->L), M(B * m->L) {}
+
+    // The score of the q | k rows the block's attention left in v.qk, into part.  Every template row (CE_TEMPLATE_RANGE ALL) takes whole query
+    // tiles on the MFMA, a selection of rows (or VB_CE_SCORE_PLAIN) the plain loop.  Full frames run the <L> kernels under the key bitmap
+    // `bits` (nullptr: every key); compacted frames (rt) of Lc rows, the first nkeys of them live, the run-time kernels.
+    int launch_score(float* part, const uint32_t* bits, bool rt, hipStream_t st, const Err& E) const {
+        const int H = m->HEADS, LZ = m->LZ, nrows = m->ce_nrows;
+        const int32_t* rows = m->ce_rows.p;
+        const dim3 grid(B * H);
+        const bool all = nrows == LZ && !m->ce_plain;
+        if (!rt)
+            dispatch_geo(m, [&](auto G) {
+                constexpr int L = decltype(G)::value;
+                if (all) hipLaunchKernelGGL(vbc::ce_score_all_kernel<L>, grid, dim3(256), 0, st, v.qk, bits, part, H, LZ);
+                else hipLaunchKernelGGL(vbc::ce_score_kernel<L>, grid, dim3(256), 0, st, v.qk, bits, rows, nrows, part, H, LZ);
+            });
+        else if (all) hipLaunchKernelGGL(vbc::ce_score_all_rt_kernel, grid, dim3(256), 16 * Lc * 4, st, v.qk, Lc, nkeys, part, H, LZ);
+        else if (Lc <= 320) hipLaunchKernelGGL(vbc::ce_score_rt_kernel<5>, grid, dim3(256), 4 * Lc * 4, st, v.qk, Lc, nkeys, rows, nrows, part, H, LZ);
+        else hipLaunchKernelGGL(vbc::ce_score_rt_kernel<12>, grid, dim3(256), 4 * Lc * 4, st, v.qk, Lc, nkeys, rows, nrows, part, H, LZ);
+        VB_HIP(hipGetLastError());
+        return VT_OK;
+    }
+
+    // Behind the attention of block i: the stage that sits there, if one does and it removes something (a stage that keeps every token it
+    // meets is a no-op, as attn_blocks.py:40-41 returns early).  cmean: the rows' centring means while nothing has moved them.
+    int after_attention(int i, const float* cmean, hipStream_t st, const Err& E) {
+        proj_x = v.ao; proj_cm = cmean;
+        if (!on || stage >= (int)m->ce_loc.size() || m->ce_loc[stage] != i) return VT_OK;
+        const int k = stage++, keep = m->ce_keep[k];
+        if (keep >= kept) return VT_OK;
+        const size_t LX = (size_t)m->LX;
+        float* part = m->ce_part.p + v.f0 * m->HEADS * LX;
+        uint8_t* removed = m->ce_removed.p + v.f0 * LX;
+        float* scores = m->ce_scores.p + ((size_t)k * m->maxB + v.f0) * LX;
+        const float scale = 1.0f / (float)(m->HEADS * m->ce_nrows);
+        if (int rc = launch_score(part, keys, cidx != nullptr, st, E)) return rc;
+        if (int rc = compact ? compact_stage(k, part, removed, scores, scale, st, E) : masked_stage(k, part, removed, scores, scale, st, E)) return rc;
+        kept = keep;
+        return VT_OK;
+    }
+
+    int masked_stage(int k, const float* part, uint8_t* removed, float* scores, float scale, hipStream_t st, const Err& E) {
+        uint32_t* next = m->ce_bits.p + ((size_t)k * m->maxB + v.f0) * m->ce_words();
+        hipLaunchKernelGGL(vbc::ce_select_kernel, dim3(B), dim3(256), 0, st, part, keys, next, removed, scores, m->HEADS, scale, k + 1, m->ce_keep[k], m->L, m->LZ);
+        VB_HIP(hipGetLastError());
+        keys = next;
+        return VT_OK;
+    }
+
+    // The compact form: the same score on the current rows (the first removing stage on the full frame, with the <L> kernels; later ones on
+    // the compacted rows at their run-time length), select on the current candidates, then the gather of the kept rows of ao / resid (and the
+    // rows' centring means) to the next stride.  The gather goes through the MLP's hidden workspace, idle between fc2 and the next fc1: frames
+    // are gathered in parallel and a frame's destination overlaps earlier frames' sources.  The residual rows are copied back; the proj
+    // GEMM, which follows, reads the attention rows and the means where the gather left them (proj_x / proj_cm).
+    int compact_stage(int k, const float* part, uint8_t* removed, float* scores, float scale, hipStream_t st, const Err& E) {
+        const int keep = m->ce_keep[k], C = m->C, Ln = m->ce_lp(k);
+        const size_t LX = (size_t)m->LX, rows = (size_t)B * Ln;
+        int32_t* next = m->ce_index.p + m->ce_index_off[k] + v.f0 * keep;
+        int32_t* src = m->ce_src.p + v.f0 * LX;
+        hipLaunchKernelGGL(vbc::ce_select_compact_kernel, dim3(B), dim3(256), 0, st, part, cidx, next, src, m->ce_inv.p + v.f0 * LX, removed, scores, m->HEADS,
+                           scale, k + 1, kept, keep, m->LX);
+        VB_HIP(hipGetLastError());
+        bf16* gao = v.hid;
+        float* gres = reinterpret_cast<float*>(v.hid + rows * C);
+        float* gmean = gres + rows * C;
+        hipLaunchKernelGGL(vbc::ce_gather_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, v.ao, v.resid, v.rmean, src, gao, gres, gmean, B, Lc, Ln,
+                           m->LZ, keep, m->LX, C);
+        VB_HIP(hipGetLastError());
+        VB_HIP(hipMemcpyAsync(v.resid, gres, rows * C * 4, hipMemcpyDeviceToDevice, st));
+        Lc = Ln; nkeys = m->LZ + keep; M = B * Ln; cidx = next;
+        proj_x = gao;
+        if (proj_cm) proj_cm = gmean;
+        return VT_OK;
+    }
+
+    // Behind the last block: the final norm, whose rows of removed tokens are zeros (vit_ce.py:170-181).  Compacted rows scatter through the
+    // last stage's table; dense rows take the plain norm and then the zeros under the last bitmap.
+    int tail(hipStream_t st, const Err& E, float* feat_out, float* resid_out) const {
+        const int C = m->C;
+        const size_t LX = (size_t)m->LX;
+        if (cidx) {
+            const int32_t* inv = m->ce_inv.p + v.f0 * LX;
+            if (resid_out) {
+                hipLaunchKernelGGL(vbc::ce_scatter_rows_kernel, dim3((B * m->L + 3) / 4), dim3(256), 0, st, v.resid, inv, resid_out, B, Lc, m->L, m->LZ, C);
+                VB_HIP(hipGetLastError());
+            }
+            hipLaunchKernelGGL(vbc::ce_final_norm_kernel<C_BASE>, dim3((B * m->LX + 3) / 4), dim3(256), 0, st, v.resid, m->ng.p, m->nb.p, LN_EPS, inv, B, Lc,
+                               m->LZ, m->LX, m->F, v.map[0], feat_out);
+            VB_HIP(hipGetLastError());
+            return VT_OK;
+        }
+        if (resid_out) VB_HIP(hipMemcpyAsync(resid_out, v.resid, (size_t)M * C * 4, hipMemcpyDeviceToDevice, st));
+        if (int rc = run_layernorm(m, v.resid, m->ng.p, m->nb.p, B, st, nullptr, v.map[0], feat_out, E)) return rc;
+        if (keys) {
+            hipLaunchKernelGGL(vbc::ce_zero_rows_kernel, dim3(grid256((size_t)B * LX * (C / 4))), dim3(256), 0, st, keys, v.map[0], feat_out, B, m->L, m->LZ, m->F, C);
+            VB_HIP(hipGetLastError());
+        } else if (m->ce_set)      // no stage ran in [0, nblocks) (or every stage is a no-op): nothing is removed
+            VB_HIP(hipMemsetAsync(m->ce_removed.p + v.f0 * LX, 0, (size_t)B * LX, st));
+        return VT_OK;
+    }
+};
+}  // namespace
 
 int blocks(VbModel* m, const float* tokens_in, int B, int nblocks, hipStream_t st, float* feat_out, float* resid_out, std::string* err,
            const Slice* sl) {
@@ -901,11 +1013,11 @@ int blocks(VbModel* m, const float* tokens_in, int B, int nblocks, hipStream_t s
     int rc = check(m, B, E);
     if (rc || (rc = check_slice(m, B, sl, E))) return rc;
     const int C = m->C, HID = m->HID;
-    int M = B * m->L;      // the slice's residual rows: B frames of L, behind a compacting stage B frames of Lc
     const SliceView v(m, B, sl);
+    CeWalk ce(m, v, B);      // ce.M: the slice's residual rows, B frames of L; behind a compacting stage, B frames of ce.Lc
     if (nblocks < 0 || nblocks > m->depth) nblocks = m->depth;
     if (tokens_in && tokens_in != v.resid)
-        VB_HIP(hipMemcpyAsync(v.resid, tokens_in, (size_t)M * C * 4, hipMemcpyDeviceToDevice, st));
+        VB_HIP(hipMemcpyAsync(v.resid, tokens_in, (size_t)ce.M * C * 4, hipMemcpyDeviceToDevice, st));
     const bool fold = m->fold;
     float* const rstd = fold ? v.rstd : nullptr;
     // folded LayerNorms: a residual stream from outside has no bf16 copy / rstd yet (vb::stem leaves both behind its GEMM)
@@ -914,120 +1026,25 @@ int blocks(VbModel* m, const float* tokens_in, int B, int nblocks, hipStream_t s
     // a GEMM onto the residual stream; feeds_ln: a folded LayerNorm reads what it leaves (bf16 copy centred on cmean + statistics, then finalize)
     auto resid_gemm = [&](const bf16* X, const bf16* W, const float* bias, int K, bool feeds_ln, const float* cm) {
         vbg::Args p{};
-        p.X = X; p.W = W; p.bias = bias; p.resid = v.resid; p.M = M; p.N = C; p.K = K;
+        p.X = X; p.W = W; p.bias = bias; p.resid = v.resid; p.M = ce.M; p.N = C; p.K = K;
         if (feeds_ln) { v.stats_of(p); p.cm = cm; }
         if (int r = launch_tile<vbg::A_PLAIN, vbg::EPI_RESID>(m, p, 1, st, E, v.cus)) return r;
-        return feeds_ln ? run_finalize(m, v, M, st, E) : VT_OK;
-    };
-    // candidate elimination (vb_ce.h): from the first stage's block on the attention is the streaming kernel, under the key bitmap the
-    // stages so far have left for this slice's frames; a stage runs behind its block's attention: score, then select
-    const bool ce = m->ce_first >= 0;
-    const size_t ceW = (size_t)m->ce_words(), LX = (size_t)m->LX;
-    const uint32_t* keys = nullptr;
-    int stage = 0, kept = m->LX;
-    auto ce_stage = [&](int k) {
-        uint32_t* next = m->ce_bits.p + ((size_t)k * m->maxB + v.f0) * ceW;
-        float* part = m->ce_part.p + v.f0 * m->HEADS * LX;
-        if (m->ce_nrows == m->LZ && !m->ce_plain) {      // every template row (CE_TEMPLATE_RANGE ALL): whole query tiles on the MFMA
-            if (m->g384) hipLaunchKernelGGL(vbc::ce_score_all_kernel<L384>, dim3(B * m->HEADS), dim3(256), 0, st, v.qk, keys, part, m->HEADS, m->LZ);
-            else hipLaunchKernelGGL(vbc::ce_score_all_kernel<L256>, dim3(B * m->HEADS), dim3(256), 0, st, v.qk, keys, part, m->HEADS, m->LZ);
-        } else if (m->g384)
-            hipLaunchKernelGGL(vbc::ce_score_kernel<L384>, dim3(B * m->HEADS), dim3(256), 0, st, v.qk, keys, m->ce_rows.p, m->ce_nrows, part, m->HEADS, m->LZ);
-        else
-            hipLaunchKernelGGL(vbc::ce_score_kernel<L256>, dim3(B * m->HEADS), dim3(256), 0, st, v.qk, keys, m->ce_rows.p, m->ce_nrows, part, m->HEADS, m->LZ);
-        hipLaunchKernelGGL(vbc::ce_select_kernel, dim3(B), dim3(256), 0, st, part, keys, next, m->ce_removed.p + v.f0 * LX,
-                           m->ce_scores.p + ((size_t)k * m->maxB + v.f0) * LX, m->HEADS, 1.0f / (float)(m->HEADS * m->ce_nrows), k + 1, m->ce_keep[k],
-                           m->L, m->LZ);
-        keys = next;
-    };
-    // The compact form: the same score on the current rows (the first removing stage on the full frame, with the <L> kernels; later ones on
-    // the compacted rows at their run-time length), select on the current candidates, then the gather of the kept rows of ao / resid (and the
-    // rows' centring means) to the next stride.  The gather goes through the MLP's hidden workspace, idle between fc2 and the next fc1: frames
-    // are gathered in parallel and a frame's destination overlaps earlier frames' sources.  The residual rows are copied back; the proj
-    // GEMM, which follows, reads the attention rows and the means where the gather left them (proj_x / proj_cm).
-    const bool compact = ce && m->ce_form == VT_CE_COMPACT;
-    int Lc = m->L, nkeys = m->L;            // rows and live rows of a frame at the current stage
-    const int32_t* cidx = nullptr;          // the current index table; nullptr: nothing compacted yet
-    const bf16* proj_x = v.ao;
-    const float* proj_cm = cmean;
-    auto ce_stage_compact = [&](int k) -> int {
-        const int ncand = kept, keep = m->ce_keep[k], H = m->HEADS, LZ = m->LZ;
-        float* part = m->ce_part.p + v.f0 * H * LX;
-        const bool all = m->ce_nrows == LZ && !m->ce_plain;
-        if (!cidx) {
-            if (all && m->g384) hipLaunchKernelGGL(vbc::ce_score_all_kernel<L384>, dim3(B * H), dim3(256), 0, st, v.qk, nullptr, part, H, LZ);
-            else if (all) hipLaunchKernelGGL(vbc::ce_score_all_kernel<L256>, dim3(B * H), dim3(256), 0, st, v.qk, nullptr, part, H, LZ);
-            else if (m->g384) hipLaunchKernelGGL(vbc::ce_score_kernel<L384>, dim3(B * H), dim3(256), 0, st, v.qk, nullptr, m->ce_rows.p, m->ce_nrows, part, H, LZ);
-            else hipLaunchKernelGGL(vbc::ce_score_kernel<L256>, dim3(B * H), dim3(256), 0, st, v.qk, nullptr, m->ce_rows.p, m->ce_nrows, part, H, LZ);
-        } else if (all)
-            hipLaunchKernelGGL(vbc::ce_score_all_rt_kernel, dim3(B * H), dim3(256), 16 * Lc * 4, st, v.qk, Lc, nkeys, part, H, LZ);
-        else if (Lc <= 320)
-            hipLaunchKernelGGL(vbc::ce_score_rt_kernel<5>, dim3(B * H), dim3(256), 4 * Lc * 4, st, v.qk, Lc, nkeys, m->ce_rows.p, m->ce_nrows, part, H, LZ);
-        else
-            hipLaunchKernelGGL(vbc::ce_score_rt_kernel<12>, dim3(B * H), dim3(256), 4 * Lc * 4, st, v.qk, Lc, nkeys, m->ce_rows.p, m->ce_nrows, part, H, LZ);
-        VB_HIP(hipGetLastError());
-        int32_t* next = m->ce_index.p + m->ce_index_off[k] + v.f0 * keep;
-        int32_t* src = m->ce_src.p + v.f0 * LX;
-        hipLaunchKernelGGL(vbc::ce_select_compact_kernel, dim3(B), dim3(256), 0, st, part, cidx, next, src, m->ce_inv.p + v.f0 * LX, m->ce_removed.p + v.f0 * LX,
-                           m->ce_scores.p + ((size_t)k * m->maxB + v.f0) * LX, H, 1.0f / (float)(H * m->ce_nrows), k + 1, ncand, keep, m->LX);
-        VB_HIP(hipGetLastError());
-        const int Ln = m->ce_lp(k);
-        const size_t rows = (size_t)B * Ln;
-        bf16* gao = v.hid;
-        float* gres = reinterpret_cast<float*>(v.hid + rows * C);
-        float* gmean = gres + rows * C;
-        hipLaunchKernelGGL(vbc::ce_gather_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, v.ao, v.resid, v.rmean, src, gao, gres, gmean, B, Lc, Ln,
-                           LZ, keep, m->LX, C);
-        VB_HIP(hipGetLastError());
-        VB_HIP(hipMemcpyAsync(v.resid, gres, rows * C * 4, hipMemcpyDeviceToDevice, st));
-        Lc = Ln; nkeys = LZ + keep; M = B * Ln; cidx = next;
-        proj_x = gao;
-        if (cmean) proj_cm = gmean;
-        return VT_OK;
+        return feeds_ln ? run_finalize(m, v, ce.M, st, E) : VT_OK;
     };
     for (int i = 0; i < nblocks; ++i) {
         const BlockW& b = m->blk[i];
-        if (!fold && (rc = run_layernorm(m, v.resid, b.ln1g.p, b.ln1b.p, B, st, v.xn, nullptr, nullptr, E, nullptr, nullptr, nullptr, M))) return rc;
-        if (cidx) rc = run_attention_rt(m, v, b, rstd, B, Lc, nkeys, st, E);
-        else rc = run_attention(m, v, b, rstd, B, st, E, ce && i >= m->ce_first, keys);
-        if (rc) return rc;
-        proj_x = v.ao; proj_cm = cmean;
-        if (ce && stage < (int)m->ce_loc.size() && m->ce_loc[stage] == i) {
-            if (m->ce_keep[stage] < kept) {      // a stage that keeps every token it meets is a no-op, as attn_blocks.py:40-41 returns early
-                if (compact) { if ((rc = ce_stage_compact(stage))) return rc; }
-                else ce_stage(stage);
-                VB_HIP(hipGetLastError());
-                kept = m->ce_keep[stage];
-            }
-            ++stage;
-        }
-        if ((rc = resid_gemm(proj_x, b.wproj.p, b.bproj.p, C, fold, proj_cm))) return rc;
-        if (!fold && (rc = run_layernorm(m, v.resid, b.ln2g.p, b.ln2b.p, B, st, v.xn, nullptr, nullptr, E, nullptr, nullptr, nullptr, M))) return rc;
+        if (!fold && (rc = run_layernorm(m, v.resid, b.ln1g.p, b.ln1b.p, B, st, v.xn, nullptr, nullptr, E, nullptr, nullptr, nullptr, ce.M))) return rc;
+        if ((rc = run_attention(m, v, b, rstd, B, st, E, ce.on && i >= m->ce_first, ce.keys, ce.cidx ? ce.Lc : 0, ce.nkeys))) return rc;
+        if ((rc = ce.after_attention(i, cmean, st, E))) return rc;      // a candidate-elimination stage, where one sits behind this block
+        if ((rc = resid_gemm(ce.proj_x, b.wproj.p, b.bproj.p, C, fold, ce.proj_cm))) return rc;
+        if (!fold && (rc = run_layernorm(m, v.resid, b.ln2g.p, b.ln2b.p, B, st, v.xn, nullptr, nullptr, E, nullptr, nullptr, nullptr, ce.M))) return rc;
         vbg::Args f1{};
         f1.rstd = rstd;
-        f1.X = v.xn; f1.W = b.w1.p; f1.bias = b.b1.p; f1.out = v.hid; f1.M = M; f1.N = HID; f1.K = C; f1.ldo = HID; f1.rb = 4;
+        f1.X = v.xn; f1.W = b.w1.p; f1.bias = b.b1.p; f1.out = v.hid; f1.M = ce.M; f1.N = HID; f1.K = C; f1.ldo = HID; f1.rb = 4;
         if ((rc = launch_tile<vbg::A_PLAIN, vbg::EPI_GELU>(m, f1, 1, st, E, v.cus))) return rc;
         if ((rc = resid_gemm(v.hid, b.w2.p, b.b2.p, HID, fold && i + 1 < nblocks, cmean))) return rc;      // the final norm reads the f32 stream itself
     }
-    if (cidx) {      // compacted rows: the final norm scatters through the last stage's table, removed tokens' rows are zeros (vit_ce.py:170-181)
-        const int32_t* inv = m->ce_inv.p + v.f0 * LX;
-        if (resid_out) {
-            hipLaunchKernelGGL(vbc::ce_scatter_rows_kernel, dim3((B * m->L + 3) / 4), dim3(256), 0, st, v.resid, inv, resid_out, B, Lc, m->L, m->LZ, C);
-            VB_HIP(hipGetLastError());
-        }
-        hipLaunchKernelGGL(vbc::ce_final_norm_kernel<C_BASE>, dim3((B * m->LX + 3) / 4), dim3(256), 0, st, v.resid, m->ng.p, m->nb.p, LN_EPS, inv, B, Lc, m->LZ,
-                           m->LX, m->F, v.map[0], feat_out);
-        VB_HIP(hipGetLastError());
-        return VT_OK;
-    }
-    if (resid_out) VB_HIP(hipMemcpyAsync(resid_out, v.resid, (size_t)M * C * 4, hipMemcpyDeviceToDevice, st));
-    if ((rc = run_layernorm(m, v.resid, m->ng.p, m->nb.p, B, st, nullptr, v.map[0], feat_out, E))) return rc;
-    if (keys) {      // the removed tokens' rows of the final norm are zeros (vit_ce.py:170-181)
-        hipLaunchKernelGGL(vbc::ce_zero_rows_kernel, dim3(grid256((size_t)B * LX * (C / 4))), dim3(256), 0, st, keys, v.map[0], feat_out, B, m->L, m->LZ, m->F, C);
-        VB_HIP(hipGetLastError());
-    } else if (m->ce_set)      // no stage ran in [0, nblocks) (or every stage is a no-op): nothing is removed
-        VB_HIP(hipMemsetAsync(m->ce_removed.p + v.f0 * LX, 0, (size_t)B * LX, st));
-    return VT_OK;
+    return ce.tail(st, E, feat_out, resid_out);
 }
 
 int gemm_form(const VbModel* m, int B) {
