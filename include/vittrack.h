@@ -352,10 +352,20 @@ int vt_track_step_frames(vt_model* m, const vt_frame* frames_dev, double* states
  *   P010       NV12 in little-endian 16-bit samples: plane0 H rows of 2 W bytes, plane1 H/2 rows of 2 W bytes ((U, V) pairs).  The
  *              8-bit sample is the HIGH byte of each word, so a P016 surface is read the same way.  H and W even.
  *   GRAY8      plane0: H rows of W bytes; rgb = (Y, Y, Y), no conversion.
- * The format word: bits 0-7 the layout (the VT_PIX_* values; 6 and 7 are never assigned), bits 8-11 the matrix (0 = BT.601, 1 =
+ *   RGBP/BGRP  planar RGB, three planes of H rows of W bytes: plane0 is the R plane (BGRP: the B plane) at pitch0; plane1 is the G plane
+ *              at pitch1 (0 = W); the third plane (B; BGRP: R) begins pitch1 * H bytes after plane1 -- the I420 rule for a trailing
+ *              plane.  rgb = (R[y][x], G[y][x], B[y][x]), no conversion.  A contiguous (3, H, W) uint8 tensor at p (torchvision's
+ *              read_image / decode_jpeg, every CHW dataloader) is plane0 = p, plane1 = p + H W, pitches 0.  H and W may be odd.
+ *   I444       planar 4:4:4 (ffmpeg's yuv444p): plane0 H rows of W luma bytes; plane1 the U plane, H rows of W bytes at pitch1 (0 = W);
+ *              the V plane begins pitch1 * H bytes after plane1.  Every pixel has its own chroma: U, V at (x, y).  H and W may be odd.
+ *   I422       planar 4:2:2 (yuv422p): as I444 with chroma planes of H rows of W/2 bytes (pitch1 0 = W/2): U, V at (x >> 1, y).  W even,
+ *              H may be odd.
+ *     The four planar layouts are read as single bytes: plane0 and plane1 need NO alignment (p + H W of an odd-sized CHW frame is not
+ *     4-byte aligned).  plane1's extent covers both trailing planes: pitch1 (2 H - 1) + its row bytes, inside a 32-bit offset.
+ * The format word: bits 0-7 the layout (the VT_PIX_* values; 6, 7, 14 and 15 are never assigned), bits 8-11 the matrix (0 = BT.601, 1 =
  * BT.709), bits 12-15 the range (0 = limited, 1 = full), bits 16-31 zero -- format = VT_PIX_P010 | VT_PIX_BT709 | VT_PIX_FULL.  Every
  * value that was legal before the colour fields existed means what it meant (NV12 = BT.601 limited).  Matrix and range belong to the
- * YUV layouts (NV12 / NV21, I420 / YV12, YUYV / UYVY, P010); on the RGB family and GRAY8 they must be 0.
+ * YUV layouts (NV12 / NV21, I420 / YV12, YUYV / UYVY, P010, I444 / I422); on the RGB family (RGBP / BGRP included) and GRAY8 they must be 0.
  * Colour, every YUV layout: chroma is never interpolated (a 2 x 2 block of 4:2:0, a pair of 4:2:2, shares its U, V); int32, >> arithmetic:
  *       yy = max(Y - 16, 0) * cy   (limited range)      yy = Y * cy   (full range)
  *       R = clamp((yy + cvr (V - 128)                   + (1 << 19)) >> 20, 0, 255)
@@ -371,7 +381,8 @@ int vt_track_step_frames(vt_model* m, const vt_frame* frames_dev, double* states
  *     Checked on the CPU over all 2^24 (Y, U, V): the value before the shift stays below 5.8e8 (inside int32), and before clamping
  *     each channel differs from the fp64 formula by at most 0.5000 / 0.5002 / 0.5000 (601 full / 709 limited / 709 full; OpenCV's
  *     601-limited literals: up to 0.69).  tests/test_frame_formats_yuv.py repeats the check.
- *   Not supported: chroma interpolation and chroma siting, BT.2020 / PQ / HLG, 4:4:4 layouts, big-endian samples.
+ *   Not supported: chroma interpolation and chroma siting, BT.2020 / PQ / HLG, big-endian samples, the V-first twins of the planar
+ *   layouts (YV16 / YV24), two-plane 4:2:2 / 4:4:4 (NV16 / NV24), 16-bit planar layouts.
  *   pitch0 / pitch1: bytes between rows of plane0 / plane1, >= the row's bytes (0 = the row's bytes).  A plane is [plane, plane +
  *   pitch (rows - 1) + row bytes); nothing outside it is read.  plane1 / pitch1 are unused by the one-plane formats.
  * Planes: device memory or device-mapped pinned host memory.  The table (B,) lives there too and is read when the kernels run: a
@@ -379,8 +390,8 @@ int vt_track_step_frames(vt_model* m, const vt_frame* frames_dev, double* states
  * A descriptor is unusable -- treated as a too-small box: NaN resize factor, zero (uint8) or NaN (fp32) patch, nothing read through
  * it, the other sequences unaffected -- when its format word is not one described above (an unassigned layout, a matrix or range
  * beyond 1, a bit in 16-31, matrix or range bits on an RGB layout or GRAY8) or `reserved` is not 0, a plane it needs is null or not
- * 4-byte aligned, a pitch is below the row's bytes, H or W is < 1, W is odd for a 4:2:2 layout, H or W is odd for a 4:2:0 layout, or a
- * plane does not fit a 32-bit offset. */
+ * 4-byte aligned (the four planar layouts: null only), a pitch is below the row's bytes, H or W is < 1, W is odd for a 4:2:2 layout (I422
+ * included), H or W is odd for a 4:2:0 layout, or a plane does not fit a 32-bit offset. */
 enum { VT_PIX_RGB = 0, VT_PIX_BGR = 1, VT_PIX_RGBA = 2, VT_PIX_BGRA = 3, VT_PIX_NV12 = 4, VT_PIX_NV21 = 5 };
 /* the layouts added to bits 0-7 (6 and 7 are never assigned) ... */
 #define VT_PIX_I420 8
@@ -389,6 +400,11 @@ enum { VT_PIX_RGB = 0, VT_PIX_BGR = 1, VT_PIX_RGBA = 2, VT_PIX_BGRA = 3, VT_PIX_
 #define VT_PIX_UYVY 11
 #define VT_PIX_P010 12
 #define VT_PIX_GRAY8 13
+/* ... the planar layouts (14 and 15 are never assigned) ... */
+#define VT_PIX_RGBP 16
+#define VT_PIX_BGRP 17
+#define VT_PIX_I444 18
+#define VT_PIX_I422 19
 /* ... and the colour tags of a YUV layout, or-ed into the format word: matrix in bits 8-11, range in bits 12-15 */
 #define VT_PIX_BT601 0x0000
 #define VT_PIX_BT709 0x0100

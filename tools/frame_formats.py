@@ -2,7 +2,7 @@
 """Pixel formats on the device: what reading NV12 / NV21, BGR and RGBA / BGRA directly costs against RGB, and what the
 other layouts and colour rows (P010, I420, YUYV / UYVY, GRAY8; BT.709, full range) cost against NV12 BT.601.
 
-    python tools/frame_formats.py [--batch 256] [--rounds 5] [--reps 20] [--distinct 32] [--sections crop,step,small,convert,new,parent]
+    python tools/frame_formats.py [--batch 256] [--rounds 5] [--reps 20] [--distinct 32] [--sections crop,step,small,convert,new,parent,planar]
                                   [--parent-lib OTHER.so]
 
 Fixed seeds, 1920 x 1080 frames (`--distinct` different frames, cycled over the sequences) with 30-120 px boxes:
@@ -21,6 +21,12 @@ Fixed seeds, 1920 x 1080 frames (`--distinct` different frames, cycled over the 
                           (T = 128 / 256) and G128 / G256 steps at B = 256, this build and the parent's loaded side by side in ONE
                           process and timed in the same interleaved rounds: per form the median and the [min, max] over the rounds;
                           inside_parent_range = this build's median lies inside the parent's own round-to-round range
+  planar                  (section "planar") B = 256 on ONE (B, 3, H, W) uint8 tensor, every sequence its own frame: crop_us[T][form] = the
+                          uint8 table crop of RGBP / BGRP (native.images_from_chw), I444 and I422 (the same planes read as Y, U, V) next to
+                          I420 (the byte-fetch family they share) and the RGB frame route on the permuted copy; step_us[G][form] = the
+                          open-loop G128 / G256 step on those tables; permute_step_us[G] = what a caller does without the layout --
+                          hwc.copy_(chw.permute(0, 2, 3, 1)) inside the captured, timed graph, then vt_track_step_frames -- against the
+                          step on the CHW frames (ratio = permute + step over CHW step)
 Method: every form is a captured graph (`--reps` launches for a crop, one step for a step; outputs preallocated, no host work
 inside); the forms are timed in `--rounds` interleaved rounds (the order rotates every round), each a host-timed region of replays
 with one synchronisation, and the best round of each form is reported.  The shader clock is probed (vt_probe_clock, a dense MFMA
@@ -234,6 +240,66 @@ def _parent_ab(a, B, n, g, states):
     return res
 
 
+def _planar(a, B, g, states):
+    """Section planar: one (B, 3, H, W) batch as RGBP / BGRP / I444 / I422 tables, I420 and the permuted RGB copy beside it."""
+    import torch
+    from vittracker_amd import native
+    from vittracker_amd.native import FrameTable, Image, ImageTable
+    chw = torch.randint(0, 256, (B, 3, H, W), dtype=torch.uint8, device="cuda", generator=g)
+    hwc = chw.permute(0, 2, 3, 1).contiguous()
+    i420 = [torch.randint(0, 256, (3 * H // 2, W), dtype=torch.uint8, device="cuda", generator=g) for _ in range(B)]
+    forms = {"rgbp": native.images_from_chw(chw), "bgrp": native.images_from_chw(chw, "bgr"),
+             "i444": [Image.i444(f[0], f[1], f[2]) for f in chw],
+             "i422": [Image.i422(f[0], f[1, :, :W // 2], f[2, :, :W // 2]) for f in chw],      # chroma rows at pitch W, planes W H apart
+             "i420": [Image.i420_buffer(f) for f in i420]}
+    tabs = {k: ImageTable.of(v) for k, v in forms.items()}
+    ft = FrameTable(B, "cuda")
+    for b in range(B):
+        ft.set_tensor(b, hwc[b])
+    ft.upload()
+    res = {"crop_us": {}, "step_us": {}, "permute_step_us": {}, "batch_bytes": int(chw.numel())}
+    m = _model(128, B)
+    for T in (128, 256):
+        graphs, outs = {}, []
+        for name, t in [("rgb_frames", ft)] + list(tabs.items()):
+            o = torch.empty(B, T, T, 3, dtype=torch.uint8, device="cuda")
+            rf = torch.empty(B, dtype=torch.float64, device="cuda")
+            outs.append((o, rf))
+            call = m.crop_u8_frames if name == "rgb_frames" else m.crop_u8_images
+
+            def fn(cs, call=call, t=t, o=o, rf=rf):
+                for _ in range(a.reps):
+                    call(t, states, 4.0, T, out=o, resize_factor=rf, stream=cs)
+            graphs[name] = _capture(fn)
+        rounds = _interleaved(graphs, a.reps, a.rounds, a.replays, all_rounds=True)
+        row = {k: _stats(v) for k, v in rounds.items()}
+        row["ratio_vs_rgb_frames"] = {k: round(min(v) / min(rounds["rgb_frames"]), 3) for k, v in rounds.items()}
+        row["ratio_vs_i420"] = {k: round(min(v) / min(rounds["i420"]), 3) for k, v in rounds.items()}
+        row["rgbp_equals_rgb_frames"] = bool(torch.equal(outs[0][0], outs[1][0]))
+        res["crop_us"][str(T)] = row
+    del m, graphs
+    for S in (128, 256):
+        m = _model(S, B)
+        step_forms = {"rgb_frames": (m.track_step_frames, ft)}
+        step_forms.update({k: (m.track_step_images, tabs[k]) for k in ("rgbp", "i444", "i422")})
+        graphs, (x, rf, out, rec) = _step_graphs(m, S, B, states, step_forms)
+
+        def permute_then_step(cs):      # today's caller: the whole batch transposed, then the RGB step on it
+            hwc.copy_(chw.permute(0, 2, 3, 1))
+            m.track_step_frames(ft, states, 4.0, MEAN, STD, x, rf, out, record=rec, stream=cs)
+        graphs["permute_then_step"] = _capture(permute_then_step)
+        graphs["permute_alone"] = _capture(lambda cs: hwc.copy_(chw.permute(0, 2, 3, 1)))
+        rounds = _interleaved(graphs, 1, a.rounds, a.replays * 5, all_rounds=True)
+        row = {k: _stats(v) for k, v in rounds.items() if not k.startswith("permute")}
+        row["ratio_vs_rgb_frames"] = {k: round(min(v) / min(rounds["rgb_frames"]), 3) for k, v in rounds.items() if not k.startswith("permute")}
+        res["step_us"][f"G{S}"] = row
+        res["permute_step_us"][f"G{S}"] = {"permute_then_step": _stats(rounds["permute_then_step"]), "permute_alone": _stats(rounds["permute_alone"]),
+                                           "chw_step": _stats(rounds["rgbp"]),
+                                           "ratio": round(min(rounds["permute_then_step"]) / min(rounds["rgbp"]), 2)}
+        del m, graphs
+    return res
+
+
 def _nv12_to_rgb(y, uv):
     """The whole frames (n, H, W) / (n, H/2, W/2, 2) -> (n, H, W, 3) uint8 with unfused int32 torch ops: BT.601 limited range,
     OpenCV's fixed point."""
@@ -288,7 +354,7 @@ def main():
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--replays", type=int, default=10)
     ap.add_argument("--distinct", type=int, default=32)
-    ap.add_argument("--sections", default="crop,step,small,convert", help="of crop, step, small, convert, new, parent")
+    ap.add_argument("--sections", default="crop,step,small,convert", help="of crop, step, small, convert, new, parent, planar")
     ap.add_argument("--parent-lib", default=None, help="the parent commit's libvittrack_hip.so (section parent)")
     a = ap.parse_args()
     sections = set(a.sections.split(","))
@@ -306,6 +372,8 @@ def main():
         if not a.parent_lib:
             raise SystemExit("section parent needs --parent-lib")
         res["parent_ab"] = _parent_ab(a, B, n, g, states)
+    if "planar" in sections:
+        res["planar"] = _planar(a, B, g, states)
     frames = {f: _planes(f, n, g) for f in (FORMATS if sections & {"crop", "step", "small", "convert"} else ("rgb", "nv12"))}
     if "new" in sections:
         # (0) the added layouts and colour rows against NV12 BT.601 and the RGB frame route

@@ -295,11 +295,11 @@ class BatchedVitTracker:
         if isinstance(frames, torch.Tensor) and frames.is_cuda:
             t = frames
             if t.dtype != torch.uint8 or t.dim() != 4 or t.shape[3] != 3 or t.shape[0] != self.B or not t.is_contiguous():
-                raise ValueError(f"frames must be a contiguous (B={self.B}, H, W, 3) uint8 tensor")
+                raise ValueError(f"frames must be a contiguous (B={self.B}, H, W, 3) uint8 tensor (a (B, 3, H, W) batch: pass native.images_from_chw(frames))")
         else:
             a = np.ascontiguousarray(np.stack(frames) if not isinstance(frames, np.ndarray) else frames)
             if a.dtype != np.uint8 or a.ndim != 4 or a.shape[3] != 3 or a.shape[0] != self.B:
-                raise ValueError(f"frames must be (B={self.B}, H, W, 3) uint8")
+                raise ValueError(f"frames must be (B={self.B}, H, W, 3) uint8 (a (B, 3, H, W) batch: pass native.images_from_chw(frames))")
             zero_copy = a.nbytes <= self.ZERO_COPY_MAX_BYTES
             if self.frames is None or tuple(self.frames[0].shape) != a.shape or self.frames[0].is_cuda == zero_copy:
                 torch.cuda.current_stream().synchronize()      # nothing may still read the old buffers
@@ -343,7 +343,8 @@ class BatchedVitTracker:
 
     def initialize(self, frames, init_boxes):
         """frames: (B,H,W,3) uint8 (numpy, list of arrays or CUDA tensor) -- or a list of B frames of different sizes, any of which
-        may be a native.Image (any layout of include/vittrack.h: NV12 / NV21, P010, I420, YUYV, GRAY8, BGR, RGBA / BGRA, RGB);
+        may be a native.Image (any layout of include/vittrack.h: NV12 / NV21, P010, I420, YUYV, GRAY8, BGR, RGBA / BGRA, RGB, planar RGB /
+        I444 / I422 -- native.images_from_chw(batch) for a (B, 3, H, W) tensor);
         init_boxes: (B,4) [x,y,w,h]."""
         import torch
         kind, fr = self._route(frames)

@@ -171,10 +171,11 @@ __device__ __forceinline__ u4v frame_column_entry(const ColumnTap& t) {
     return u4v{3u * (unsigned)t.xb, (unsigned)(t.vc0 ? t.ax0 : 0) | ((unsigned)(t.vc1 ? t.ax1 : 0) << 16), (unsigned)(t.vc1 ? 24 * (t.xx1 - t.xb) : 0), 0u};
 }
 // vt_image layouts: plane-0 byte offset of the left tap (bpp bytes a pixel, yadd: see yuv_layout), weights, steps (bit 0 = the right
-// tap is the next pixel, bit 1 = its chroma pair is the next pair), chroma byte offset (cmul bytes a pair)
-__device__ __forceinline__ u4v image_column_entry(const ColumnTap& t, unsigned bpp, unsigned yadd, unsigned cmul) {
-    const unsigned step = t.vc1 && t.xx1 != t.xb ? 1u : 0u, cstep = t.vc1 && (t.xx1 >> 1) != (t.xb >> 1) ? 2u : 0u;
-    return u4v{bpp * (unsigned)t.xb + yadd, (unsigned)(t.vc0 ? t.ax0 : 0) | ((unsigned)(t.vc1 ? t.ax1 : 0) << 16), step | cstep, cmul * (unsigned)(t.xb >> 1)};
+// tap is the next pixel, bit 1 = its chroma pair is the next pair), chroma byte offset (cmul bytes a pair; cxs: a pair is 1 << cxs
+// pixels wide -- 1, or 0 where every pixel has its own chroma)
+__device__ __forceinline__ u4v image_column_entry(const ColumnTap& t, unsigned bpp, unsigned yadd, unsigned cmul, unsigned cxs = 1u) {
+    const unsigned step = t.vc1 && t.xx1 != t.xb ? 1u : 0u, cstep = t.vc1 && (t.xx1 >> cxs) != (t.xb >> cxs) ? 2u : 0u;
+    return u4v{bpp * (unsigned)t.xb + yadd, (unsigned)(t.vc0 ? t.ax0 : 0) | ((unsigned)(t.vc1 ? t.ax1 : 0) << 16), step | cstep, cmul * ((unsigned)t.xb >> cxs)};
 }
 
 // Output row oy: its two source rows (a row outside the valid range reads row 0), their 11-bit weights and validity
@@ -734,10 +735,11 @@ __global__ __launch_bounds__(256) void crop_band_kernel(const unsigned char* __r
 // those bodies fetch a 3-byte pixel pair as one window, and the existing instantiations stay as they compile today.
 struct ImageView {
     const unsigned char* p0;       // plane 0: the packed pixels, or the luma plane
-    const unsigned char* p1;       // plane 1: NV12 / NV21 / P010 chroma pairs, or the first chroma plane of I420 / YV12
+    const unsigned char* p1;       // plane 1: NV12 / NV21 / P010 chroma pairs, or the first chroma plane of I420 / YV12 / I444 / I422, or the G plane
     unsigned pitch0, pitch1;       // bytes between rows
     unsigned nrec0, nrec1;         // each plane's extent, the bound of its buffer descriptor (loads beyond it return zero, fetch nothing)
-    unsigned p2;                   // I420 / YV12: byte offset of the second chroma plane from p1 (pitch1 H / 2); inside nrec1
+    unsigned p2;                   // I420 / YV12: byte offset of the second chroma plane from p1 (pitch1 H / 2); inside nrec1.  The planar
+                                   // layouts (RGBP / BGRP, I444 / I422): of the third plane (pitch1 H)
     int H, W, fmt, col;            // fmt: the layout (bits 0-7 of vt_image.format); col: matrix | range << 1 (0 = BT.601 limited)
     bool ok;                       // false: an unusable descriptor, poisoned like a too-small box
 };
@@ -751,27 +753,31 @@ __device__ __forceinline__ ImageView image_view(const vt_image* images, int b) {
     const int fmt = (int)(word & 0xffu), mat = (int)((word >> 8) & 0xfu), rng = (int)((word >> 12) & 0xfu);
     const bool nv = fmt == VT_PIX_NV12 || fmt == VT_PIX_NV21, p010 = fmt == VT_PIX_P010;
     const bool pl = fmt == VT_PIX_I420 || fmt == VT_PIX_YV12, pk2 = fmt == VT_PIX_YUYV || fmt == VT_PIX_UYVY;
-    const bool sub420 = nv || p010 || pl, yuv = sub420 || pk2;
-    const long long bpp = (fmt == VT_PIX_RGBA || fmt == VT_PIX_BGRA) ? 4 : ((p010 || pk2) ? 2 : ((nv || pl || fmt == VT_PIX_GRAY8) ? 1 : 3));
-    bool ok = ((fmt >= VT_PIX_RGB && fmt <= VT_PIX_NV21) || (fmt >= VT_PIX_I420 && fmt <= VT_PIX_GRAY8)) && (word >> 16) == 0u && mat <= 1 &&
+    // the planar layouts: three full-height planes of single bytes (I422: chroma planes of W / 2 bytes a row), read as single bytes,
+    // hence no alignment rule (plane 1 of a contiguous (3, H, W) tensor of odd H W is at an odd address)
+    const bool prgb = fmt == VT_PIX_RGBP || fmt == VT_PIX_BGRP, p422 = fmt == VT_PIX_I422, pln = prgb || fmt == VT_PIX_I444 || p422;
+    const bool sub420 = nv || p010 || pl, yuv = sub420 || pk2 || (pln && !prgb);
+    const long long bpp = (fmt == VT_PIX_RGBA || fmt == VT_PIX_BGRA) ? 4 : ((p010 || pk2) ? 2 : ((nv || pl || pln || fmt == VT_PIX_GRAY8) ? 1 : 3));
+    const unsigned long long amask = pln ? 0ull : 3ull;
+    bool ok = ((fmt >= VT_PIX_RGB && fmt <= VT_PIX_NV21) || (fmt >= VT_PIX_I420 && fmt <= VT_PIX_GRAY8) || pln) && (word >> 16) == 0u && mat <= 1 &&
               rng <= 1 && (yuv || (mat | rng) == 0) && d->reserved == 0 && H >= 1 && W >= 1 && H <= 0x10000000 && W <= 0x10000000 &&
-              (!sub420 || ((H | W) & 1) == 0) && (!pk2 || (W & 1) == 0);
+              (!sub420 || ((H | W) & 1) == 0) && (!(pk2 || p422) || (W & 1) == 0);
     const long long row0 = bpp * W, pitch0 = d->pitch0 == 0 ? row0 : d->pitch0;
-    ok = ok && pitch0 >= row0 && pitch0 <= 0xfffffff0ll && p0 != nullptr && (reinterpret_cast<unsigned long long>(p0) & 3ull) == 0;
+    ok = ok && pitch0 >= row0 && pitch0 <= 0xfffffff0ll && p0 != nullptr && (reinterpret_cast<unsigned long long>(p0) & amask) == 0;
     const unsigned long long ext0 = ok ? (unsigned long long)pitch0 * (unsigned long long)(H - 1) + (unsigned long long)row0 : 0ull;
     ok = ok && ext0 <= 0xfffffff0ull;
     long long pitch1 = 0;
     unsigned long long ext1 = 0, p2 = 0;
-    if (sub420) {
+    if (sub420 || pln) {
         // chroma: H / 2 rows of W bytes (NV12 / NV21) or 2 W bytes (P010); I420 / YV12: two planes of H / 2 rows of W / 2 bytes back
-        // to back at one pitch, i.e. H rows, and the extent covers both
-        const long long row1 = p010 ? 2ll * W : (pl ? W / 2 : (long long)W);
-        const long long rows1 = pl ? H : H / 2;
+        // to back at one pitch, i.e. H rows, and the extent covers both; the planar layouts: two planes of H rows back to back, 2 H rows
+        const long long row1 = p010 ? 2ll * W : ((pl || p422) ? W / 2 : (long long)W);
+        const long long rows1 = pln ? 2ll * H : (pl ? H : H / 2);
         pitch1 = d->pitch1 == 0 ? row1 : d->pitch1;
-        ok = ok && pitch1 >= row1 && pitch1 <= 0xfffffff0ll && p1 != nullptr && (reinterpret_cast<unsigned long long>(p1) & 3ull) == 0;
+        ok = ok && pitch1 >= row1 && pitch1 <= 0xfffffff0ll && p1 != nullptr && (reinterpret_cast<unsigned long long>(p1) & amask) == 0;
         ext1 = ok ? (unsigned long long)pitch1 * (unsigned long long)(rows1 - 1) + (unsigned long long)row1 : 0ull;
         ok = ok && ext1 <= 0xfffffff0ull;
-        p2 = (ok && pl) ? (unsigned long long)pitch1 * (unsigned long long)(H / 2) : 0ull;
+        p2 = (ok && (pl || pln)) ? (unsigned long long)pitch1 * (unsigned long long)(pln ? H : H / 2) : 0ull;
     }
     return ImageView{p0, p1, ok ? (unsigned)pitch0 : 0u, ok ? (unsigned)pitch1 : 0u, ok ? (unsigned)ext0 : 0u, ok ? (unsigned)ext1 : 0u,
                      (unsigned)p2, ok ? H : 1, ok ? W : 1, fmt, ok ? (mat | (rng << 1)) : 0, ok};
@@ -846,22 +852,35 @@ __device__ __forceinline__ unsigned yuv_rgb(unsigned y8, const ChromaTerms& c, c
     return ch(yy + c.r) | (ch(yy + c.g) << 8) | (ch(yy + c.b) << 16);
 }
 // Where the three samples of pixel (x, y) of a YUV layout lie, as uniform multipliers: luma at byte y pitch0 + x ymul + yadd of plane 0;
-// U and V at bytes (y >> cys) cpitch + (x >> 1) cmul + uoff / voff of plane 1 (or, c0: of plane 0 -- the packed 4:2:2 layouts).
+// U and V at bytes (y >> cys) cpitch + (x >> cxs) cmul + uoff / voff of plane 1 (or, c0: of plane 0 -- the packed 4:2:2 layouts).
 // P010: the sample is the high byte of each little-endian 16-bit word, hence the odd offsets.
-struct YuvLayout { unsigned ymul, yadd, cys, cpitch, cmul, uoff, voff; bool c0; };
+// I444: every pixel its own chroma (cxs = 0), the V plane pitch1 H bytes behind the U plane.  Planar RGB is addressed exactly so -- plane
+// 0 where I444 keeps luma, the two trailing planes where it keeps U and V -- and differs in what the three bytes mean (is_planar_rgb).
+struct YuvLayout { unsigned ymul, yadd, cys, cpitch, cmul, uoff, voff, cxs; bool c0; };
 __device__ __forceinline__ YuvLayout yuv_layout(const ImageView& iv) {
     switch (iv.fmt) {
-        case VT_PIX_NV21: return YuvLayout{1u, 0u, 1u, iv.pitch1, 2u, 1u, 0u, false};
-        case VT_PIX_I420: return YuvLayout{1u, 0u, 1u, iv.pitch1, 1u, 0u, iv.p2, false};
-        case VT_PIX_YV12: return YuvLayout{1u, 0u, 1u, iv.pitch1, 1u, iv.p2, 0u, false};
-        case VT_PIX_YUYV: return YuvLayout{2u, 0u, 0u, iv.pitch0, 4u, 1u, 3u, true};
-        case VT_PIX_UYVY: return YuvLayout{2u, 1u, 0u, iv.pitch0, 4u, 0u, 2u, true};
-        case VT_PIX_P010: return YuvLayout{2u, 1u, 1u, iv.pitch1, 4u, 1u, 3u, false};
-        case VT_PIX_GRAY8: return YuvLayout{1u, 0u, 0u, 0u, 0u, 0u, 0u, true};      // luma only
-        default: return YuvLayout{1u, 0u, 1u, iv.pitch1, 2u, 0u, 1u, false};         // NV12
+        case VT_PIX_NV21: return YuvLayout{1u, 0u, 1u, iv.pitch1, 2u, 1u, 0u, 1u, false};
+        case VT_PIX_I420: return YuvLayout{1u, 0u, 1u, iv.pitch1, 1u, 0u, iv.p2, 1u, false};
+        case VT_PIX_YV12: return YuvLayout{1u, 0u, 1u, iv.pitch1, 1u, iv.p2, 0u, 1u, false};
+        case VT_PIX_YUYV: return YuvLayout{2u, 0u, 0u, iv.pitch0, 4u, 1u, 3u, 1u, true};
+        case VT_PIX_UYVY: return YuvLayout{2u, 1u, 0u, iv.pitch0, 4u, 0u, 2u, 1u, true};
+        case VT_PIX_P010: return YuvLayout{2u, 1u, 1u, iv.pitch1, 4u, 1u, 3u, 1u, false};
+        case VT_PIX_GRAY8: return YuvLayout{1u, 0u, 0u, 0u, 0u, 0u, 0u, 1u, true};      // luma only
+        case VT_PIX_I422: return YuvLayout{1u, 0u, 0u, iv.pitch1, 1u, 0u, iv.p2, 1u, false};
+        case VT_PIX_RGBP:
+        case VT_PIX_BGRP:
+        case VT_PIX_I444: return YuvLayout{1u, 0u, 0u, iv.pitch1, 1u, 0u, iv.p2, 0u, false};
+        default: return YuvLayout{1u, 0u, 1u, iv.pitch1, 2u, 0u, 1u, 1u, false};         // NV12
     }
 }
-__device__ __forceinline__ bool is_yuv_layout(int fmt) { return fmt == VT_PIX_NV12 || fmt == VT_PIX_NV21 || (fmt >= VT_PIX_I420 && fmt <= VT_PIX_P010); }
+// Planar RGB (RGBP / BGRP): the bytes at yuv_layout's luma / U / V places are the channels themselves -- plane 0, G, the third plane
+__device__ __forceinline__ bool is_planar_rgb(int fmt) { return fmt == VT_PIX_RGBP || fmt == VT_PIX_BGRP; }
+__device__ __forceinline__ unsigned planar_rgb(unsigned a, unsigned g, unsigned c, bool bgr) {      // R | G << 8 | B << 16
+    return bgr ? (c | (g << 8) | (a << 16)) : (a | (g << 8) | (c << 16));
+}
+__device__ __forceinline__ bool is_yuv_layout(int fmt) {
+    return fmt == VT_PIX_NV12 || fmt == VT_PIX_NV21 || (fmt >= VT_PIX_I420 && fmt <= VT_PIX_P010) || fmt == VT_PIX_I444 || fmt == VT_PIX_I422;
+}
 // The tracker's tail clips against each sequence's own frame size (TrackTail::frames): the crop of vt_track_step_images writes the
 // sizes of its descriptors into a vt_frame-shaped table as it reads them (sizes may be null: vt_crop_images)
 __device__ __forceinline__ void image_sizes_out(vt_frame* sizes, const vt_image* images, int b) {
@@ -904,17 +923,19 @@ __global__ __launch_bounds__(256) void crop_image_kernel(const vt_image* __restr
     auto byte0 = [&](unsigned o) { return (unsigned)__builtin_amdgcn_raw_buffer_load_b8(rs0, (int)o, 0, 0) & 0xffu; };
     const int fmt = iv.fmt;
     const bool swap = fmt == VT_PIX_BGR || fmt == VT_PIX_BGRA;
-    const bool yuvf = is_yuv_layout(fmt);
+    const bool yuvf = is_yuv_layout(fmt), prgb = is_planar_rgb(fmt);
     const YuvLayout yl = yuv_layout(iv);
     const YuvCoef kc = yuv_coef(iv.col);
     const bool c1 = !yl.c0 && iv.p1 != nullptr;      // where the chroma samples are: plane 1, or plane 0 (packed 4:2:2)
     const auto rsc = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned char*>(c1 ? iv.p1 : iv.p0), 0, (int)(c1 ? iv.nrec1 : iv.nrec0), 0x00020000);
     auto pixel = [&](int x, int y) -> unsigned {      // rgb(d) at (x, y), inside the image
-        if (yuvf) {      // every sample a single byte: see yuv_layout
-            const unsigned co = ((unsigned)y >> yl.cys) * yl.cpitch + (unsigned)(x >> 1) * yl.cmul;
+        if (yuvf || prgb) {      // every sample a single byte: see yuv_layout
+            const unsigned co = ((unsigned)y >> yl.cys) * yl.cpitch + ((unsigned)x >> yl.cxs) * yl.cmul;
             const unsigned u = (unsigned)__builtin_amdgcn_raw_buffer_load_b8(rsc, (int)(co + yl.uoff), 0, 0) & 0xffu;
             const unsigned v = (unsigned)__builtin_amdgcn_raw_buffer_load_b8(rsc, (int)(co + yl.voff), 0, 0) & 0xffu;
-            return yuv_rgb(byte0((unsigned)y * iv.pitch0 + (unsigned)x * yl.ymul + yl.yadd), chroma_terms(u, v, kc), kc);
+            const unsigned a = byte0((unsigned)y * iv.pitch0 + (unsigned)x * yl.ymul + yl.yadd);
+            if (prgb) return planar_rgb(a, u, v, fmt == VT_PIX_BGRP);
+            return yuv_rgb(a, chroma_terms(u, v, kc), kc);
         }
         if (fmt == VT_PIX_GRAY8) return byte0((unsigned)y * iv.pitch0 + (unsigned)x) * 0x010101u;
         const unsigned o = (unsigned)y * iv.pitch0 + (unsigned)x * ((fmt == VT_PIX_RGBA || fmt == VT_PIX_BGRA) ? 4u : 3u);
@@ -975,7 +996,8 @@ __global__ __launch_bounds__(256) void crop_image_kernel(const vt_image* __restr
 //   - NV12 / NV21, the three other colour rows: crop_band_image_kernel's aligned 8-byte luma and chroma windows and its GUARD rule; the
 //     five coefficients and the luma floor come from SGPRs (yuv_coef) instead of literals
 //   - P010: aligned windows of its own (8 bytes of luma, 12 of chroma), one item at a time; derivation at the lambda
-//   - I420 / YV12, YUYV / UYVY, GRAY8: every sample of a tap as a single byte at the offsets yuv_layout gives, one item at a time
+//   - I420 / YV12, YUYV / UYVY, GRAY8, and the planar layouts (I444 / I422, RGBP / BGRP): every sample of a tap as a single byte at the
+//     offsets yuv_layout gives, one item at a time
 // LDS: the tables below are this body's own, next to the kernel's (a workgroup allocates both sets: 2 x 7.4 KB at most, T = 256 in the
 // fp32 form; four workgroups a CU stay far inside the CU's LDS) -- the kernel's code was to stay as it compiles, its arrays included.
 // (`four` and `swap` below are false for every word that reaches a family here: an RGB layout with colour bits is poisoned first.)
@@ -1007,14 +1029,14 @@ __device__ __forceinline__ void crop_band_image_ext(const vt_image* __restrict__
     }
     const int fmt = iv.fmt;
     const bool nv = fmt == VT_PIX_NV12 || fmt == VT_PIX_NV21, four = fmt == VT_PIX_RGBA || fmt == VT_PIX_BGRA;
-    const bool newf = fmt >= VT_PIX_I420;      // I420 / YV12, YUYV / UYVY, P010, GRAY8: their column and row entries follow yuv_layout
+    const bool newf = fmt >= VT_PIX_I420;      // I420 / YV12, YUYV / UYVY, P010, GRAY8, the planar layouts: their column and row entries follow yuv_layout
     const YuvLayout yl = yuv_layout(iv);
     const YuvCoef kc = yuv_coef(iv.col);
     const unsigned bpp = (nv || newf) ? yl.ymul : (four ? 4u : 3u);
     const CropWindow g = crop_window(states, b, crop_sz, T, iv.H, iv.W);
     if (blockIdx.x == 0 && tid == 0) resize_factor[b] = (double)T / (double)crop_sz;
     fill_band_tables<T, NROWS>(xtab, ytab, ctab, row0, g, iv.pitch0, newf ? yl.cys : 1u, newf ? yl.cpitch : iv.pitch1,
-                               [&](const ColumnTap& t) { return image_column_entry(t, bpp, newf ? yl.yadd : 0u, newf ? yl.cmul : 2u); });
+                               [&](const ColumnTap& t) { return image_column_entry(t, bpp, newf ? yl.yadd : 0u, newf ? yl.cmul : 2u, newf ? yl.cxs : 1u); });
     __syncthreads();
     const auto rs0 = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned char*>(iv.p0), 0, (int)iv.nrec0, 0x00020000);
     const bool c1 = nv || (newf && !yl.c0);      // chroma in plane 1; else (packed 4:2:2) in plane 0
@@ -1191,18 +1213,25 @@ __device__ __forceinline__ void crop_band_image_ext(const vt_image* __restrict__
             __builtin_amdgcn_sched_barrier(0);
         }
     };
-    // I420 / YV12, YUYV / UYVY, GRAY8: the band's tables, every sample of a tap fetched as a single byte through the bounded descriptors
-    // (yuv_layout says where: the two chroma planes of I420 are plane 1 at offsets 0 and p2, packed 4:2:2 keeps its chroma in plane 0).
+    // I420 / YV12, YUYV / UYVY, GRAY8, I444 / I422, RGBP / BGRP: the band's tables, every sample of a tap fetched as a single byte through
+    // the bounded descriptors (yuv_layout says where: the two chroma planes of I420 / I444 / I422 are plane 1 at offsets 0 and p2, packed
+    // 4:2:2 keeps its chroma in plane 0; planar RGB lies as I444 does and skips the conversion).
     // Every offset lies inside its plane by construction (x + step <= W - 1, rows <= H - 2): no guard form.
-    auto bytewise = [&]() {
-        const bool gray = fmt == VT_PIX_GRAY8;
+    // PRGB: planar RGB, an instantiation of its own, so that the loop of the layouts that were here first compiles as it did.
+    auto bytewise = [&](auto prgb_c) {
+        constexpr bool PRGB = decltype(prgb_c)::value;
+        const bool gray = fmt == VT_PIX_GRAY8, pbgr = fmt == VT_PIX_BGRP;
         const unsigned ystep = yl.ymul, cstepb = yl.cmul;
         auto lum = [&](unsigned o) { return (unsigned)__builtin_amdgcn_raw_buffer_load_b8(rs0, (int)o, 0, 0) & 0xffu; };
         auto chr = [&](unsigned o) { return (unsigned)__builtin_amdgcn_raw_buffer_load_b8(rs1, (int)o, 0, 0) & 0xffu; };
         auto tap = [&](unsigned yo, unsigned co) -> unsigned {
-            if (gray) return lum(yo) * 0x010101u;
-            const unsigned u = chr(co + yl.uoff), v = chr(co + yl.voff);
-            return yuv_rgb(lum(yo), chroma_terms(u, v, kc), kc);
+            if constexpr (PRGB) {
+                return planar_rgb(lum(yo), chr(co + yl.uoff), chr(co + yl.voff), pbgr);
+            } else {
+                if (gray) return lum(yo) * 0x010101u;
+                const unsigned u = chr(co + yl.uoff), v = chr(co + yl.voff);
+                return yuv_rgb(lum(yo), chroma_terms(u, v, kc), kc);
+            }
         };
 #pragma unroll
         for (int j = 0; j < IPT; ++j) {
@@ -1234,8 +1263,10 @@ __device__ __forceinline__ void crop_band_image_ext(const vt_image* __restrict__
             if (guard) yuv(std::true_type{});
             else yuv(std::false_type{});
         }
+    } else if (is_planar_rgb(fmt)) {
+        bytewise(std::true_type{});
     } else {
-        bytewise();
+        bytewise(std::false_type{});
     }
 }
 

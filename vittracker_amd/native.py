@@ -292,11 +292,16 @@ assert IMAGE_DTYPE.itemsize == 48
 PIX_I420, PIX_YV12, PIX_YUYV, PIX_UYVY, PIX_P010, PIX_GRAY8 = range(8, 14)
 PIX_LAYOUT_NAMES = dict(enumerate(PIX_NAMES))
 PIX_LAYOUT_NAMES.update({PIX_I420: "i420", PIX_YV12: "yv12", PIX_YUYV: "yuyv", PIX_UYVY: "uyvy", PIX_P010: "p010", PIX_GRAY8: "gray8"})
+#: ... the planar layouts (14 and 15 are never assigned): three full-height planes of single bytes, no alignment rule ...
+PIX_RGBP, PIX_BGRP, PIX_I444, PIX_I422 = range(16, 20)
+PIX_LAYOUT_NAMES.update({PIX_RGBP: "rgbp", PIX_BGRP: "bgrp", PIX_I444: "i444", PIX_I422: "i422"})
 #: ... its bits 8-11 (the matrix of a YUV layout) and 12-15 (its range); bits 16-31 must be 0
 PIX_MATRICES = ("bt601", "bt709")
 PIX_RANGES = ("limited", "full")
 _YUV420 = (PIX_NV12, PIX_NV21, PIX_I420, PIX_YV12, PIX_P010)
 _YUV422 = (PIX_YUYV, PIX_UYVY)
+_PLANAR = (PIX_RGBP, PIX_BGRP, PIX_I444, PIX_I422)
+_PLANAR_YUV = (PIX_I444, PIX_I422)
 
 
 def pix_format(layout: int, matrix: str = "bt601", range: str = "limited") -> int:      # noqa: A002  (the keyword the constructors take)
@@ -331,23 +336,29 @@ def _row_bytes(fmt: int, W: int):
         return 2 * W, 0
     if lay == PIX_GRAY8:
         return W, 0
+    if lay in _PLANAR:
+        return W, (W // 2 if lay == PIX_I422 else W)
     return (4 if lay in (PIX_RGBA, PIX_BGRA) else 3) * W, 0
 
 
 def _plane1_rows(fmt: int, H: int) -> int:
-    """Rows of plane 1: H / 2, or H for I420 / YV12 (its two chroma planes of H / 2 rows lie back to back at one pitch)."""
-    return H if (fmt & 0xff) in (PIX_I420, PIX_YV12) else H // 2
+    """Rows of plane 1: H / 2, or H for I420 / YV12 (its two chroma planes of H / 2 rows lie back to back at one pitch), or 2 H for
+    the planar layouts (two planes of H rows back to back)."""
+    lay = fmt & 0xff
+    return 2 * H if lay in _PLANAR else (H if lay in (PIX_I420, PIX_YV12) else H // 2)
 
 
 class Image:
     """One frame in a pixel format the tracker reads directly (vt_image, include/vittrack.h): RGB, BGR, RGBA, BGRA, GRAY8, NV12, NV21,
-    P010 / P016, I420, YV12, YUYV (YUY2) or UYVY.
+    P010 / P016, I420, YV12, YUYV (YUY2), UYVY, planar RGB / BGR (CHW tensors), I444 or I422.
     Planes are numpy arrays (host: BatchedVitTracker packs them into its pinned arena) or uint8 tensors on the GPU (read in place).
     Rows may be strided (a pitch wider than the row), pixels may not.  Build one with the constructors: Image.rgb(a), .bgr(a),
     .rgba(a), .bgra(a) for (H, W, 3 | 4) arrays, .gray(a) for (H, W), .nv12(y, uv) / .nv21(y, vu) for an (H, W) luma plane and an
     (H/2, W/2, 2) chroma plane (H, W even), .p010(y, uv) for the same shapes in 16-bit samples, .i420(y, u, v) / .yv12(y, v, u) /
     .i420_buffer(buf) for planar 4:2:0, .yuyv(a) / .uyvy(a) for (H, W, 2) packed 4:2:2.  Every YUV constructor takes
-    matrix="bt601" | "bt709" and range="limited" | "full" (default: BT.601 limited)."""
+    matrix="bt601" | "bt709" and range="limited" | "full" (default: BT.601 limited).  Planar frames: .chw(t) for a (3, H, W) array or
+    tensor (images_from_chw(batch) for a (B, 3, H, W) one), .rgb_planar(r, g, b) / .bgr_planar(b, g, r), .i444(y, u, v) / .i422(y, u, v)
+    for three planes that lie back to back; they are read as single bytes and need no alignment."""
 
     __slots__ = ("format", "planes", "H", "W", "pitches")
 
@@ -543,6 +554,86 @@ class Image:
         """UYVY: each 4 bytes U Y0 V Y1."""
         return cls._packed422(pix_format(PIX_UYVY, matrix, range), a)
 
+    @staticmethod
+    def _address(a) -> int:
+        return int(a.data_ptr()) if hasattr(a, "data_ptr") else int(a.__array_interface__["data"][0])
+
+    @classmethod
+    def _planar3(cls, fmt, p0, p1, p2):
+        """Three full-height planes of single bytes (RGBP / BGRP, I444, I422: chroma planes of W / 2 columns).  The descriptor has two
+        plane pointers and two pitches: the trailing planes must share one row pitch and the third must begin pitch1 * H bytes after
+        the second.  Planes that lie otherwise raise; nothing is copied here."""
+        lay = fmt & 0xff
+        name = pix_name(fmt)
+        s0, t0, g0 = cls._strides(p0)
+        if len(s0) != 2 or s0[0] < 1 or s0[1] < 1 or (lay == PIX_I422 and s0[1] % 2):
+            raise VtError(f"the first plane of an {name} image must be (H, W){' with W even' if lay == PIX_I422 else ''}, got {tuple(s0)}")
+        H, W = int(s0[0]), int(s0[1])
+        if (W > 1 and t0[1] != 1) or (H > 1 and t0[0] < W):
+            raise VtError(f"{name} plane 0 strides {tuple(t0)}: pixels must be contiguous bytes, rows at least W apart")
+        cw = W // 2 if lay == PIX_I422 else W
+        pitch1 = None
+        for c in (p1, p2):
+            sc, tc, gc = cls._strides(c)
+            if tuple(sc) != (H, cw):
+                raise VtError(f"the trailing planes of an {name} image must be {(H, cw)}, got {tuple(sc)}")
+            if gc != g0:
+                raise VtError(f"the planes of an {name} image must all be on the GPU or all on the host")
+            if (cw > 1 and tc[1] != 1) or (H > 1 and tc[0] < cw):
+                raise VtError(f"{name} plane strides {tuple(tc)}: pixels must be contiguous bytes, rows at least {cw} apart")
+            q = tc[0] if H > 1 else None
+            if pitch1 is not None and q is not None and q != pitch1:
+                raise VtError(f"the two trailing planes of an {name} image must have one row pitch, got {pitch1} and {q}")
+            pitch1 = q if q is not None else pitch1
+        gap = cls._address(p2) - cls._address(p1)
+        if pitch1 is None:      # one row: the pitch is what lies between the two planes
+            pitch1 = gap
+        if gap != pitch1 * H or pitch1 < cw:
+            raise VtError(f"the trailing planes of an {name} image are not back to back: the third must begin pitch1 * H = "
+                          f"{pitch1 * H} bytes after the second, it begins {gap} bytes after it (the descriptor has one pointer and "
+                          f"one pitch for both); put them into one buffer, e.g. a (3, H, W) array for Image.chw")
+        return cls(fmt, (p0, p1, p2), H, W, (t0[0] if H > 1 else W, pitch1))
+
+    @classmethod
+    def rgb_planar(cls, r, g, b):
+        """Planar RGB: three (H, W) planes.  G and B must share one row pitch with B beginning pitch * H bytes after G (the planes of a
+        (3, H, W) array lie so); R may be anywhere."""
+        return cls._planar3(PIX_RGBP, r, g, b)
+
+    @classmethod
+    def bgr_planar(cls, b, g, r):
+        """Planar BGR: as rgb_planar with the B plane first."""
+        return cls._planar3(PIX_BGRP, b, g, r)
+
+    @classmethod
+    def i444(cls, y, u, v, matrix="bt601", range="limited"):      # noqa: A002
+        """Planar 4:4:4 (ffmpeg's yuv444p; screen capture): luma, U and V, (H, W) each; V begins pitch1 * H bytes after U."""
+        return cls._planar3(pix_format(PIX_I444, matrix, range), y, u, v)
+
+    @classmethod
+    def i422(cls, y, u, v, matrix="bt601", range="limited"):      # noqa: A002
+        """Planar 4:2:2 (yuv422p): luma (H, W), U and V (H, W/2) each, W even; V begins pitch1 * H bytes after U."""
+        return cls._planar3(pix_format(PIX_I422, matrix, range), y, u, v)
+
+    @classmethod
+    def chw(cls, t, order="rgb"):
+        """A (3, H, W) uint8 frame as torchvision.io.read_image / decode_jpeg and CHW dataloaders hand it out -- a numpy array, a CPU
+        tensor or a CUDA tensor (read in place) --, with no copy.  The last dimension must be dense; row pitch and plane spacing come
+        from the strides (a contiguous frame, a frame of a contiguous (B, 3, H, W) batch, rows padded to a pitch with planes pitch * H
+        apart).  A view whose strides are those of a permuted (H, W, 3) array is taken as the packed frame it is.  order: "rgb" or
+        "bgr", the meaning of the three planes."""
+        if order not in ("rgb", "bgr"):
+            raise VtError(f"order must be 'rgb' or 'bgr', got {order!r}")
+        shape, st, _ = cls._strides(t)
+        if len(shape) != 3 or shape[0] != 3 or shape[1] < 1 or shape[2] < 1:
+            raise VtError(f"a CHW image must be (3, H, W), got {tuple(shape)}")
+        if st[0] == 1 and st[2] == 3:      # a permuted HWC array: packed pixels
+            hwc = t.permute(1, 2, 0) if hasattr(t, "permute") else t.transpose(1, 2, 0)
+            return cls._packed(PIX_RGB if order == "rgb" else PIX_BGR, hwc, 3)
+        if shape[2] > 1 and st[2] != 1:
+            raise VtError(f"CHW strides {tuple(st)}: the last dimension must be dense (or the view a permuted (H, W, 3) array)")
+        return cls._planar3(PIX_RGBP if order == "rgb" else PIX_BGRP, t[0], t[1], t[2])
+
     @property
     def is_cuda(self) -> bool:
         import torch
@@ -554,12 +645,14 @@ class Image:
         return (self.H, self.W, 3)
 
     def plane_rows(self):
-        """Per plane of the descriptor: (rows, row bytes).  I420 / YV12: plane 1 is both chroma planes back to back, H rows of W / 2."""
+        """Per plane of the descriptor: (rows, row bytes).  I420 / YV12: plane 1 is both chroma planes back to back, H rows of W / 2;
+        the planar layouts: both trailing planes, 2 H rows."""
         r0, r1 = _row_bytes(self.format, self.W)
         return [(self.H, r0)] + ([(_plane1_rows(self.format, self.H), r1)] if r1 else [])
 
     def host_planes(self):
-        """The host planes as plane_rows() counts them: three separate I420 / YV12 planes give luma and the two chroma planes stacked."""
+        """The host planes as plane_rows() counts them: three separate planes (I420 / YV12, the planar layouts) give plane 0 and the two
+        trailing planes stacked."""
         pl = [p.numpy() if hasattr(p, "numpy") else np.asarray(p) for p in self.planes]
         if len(pl) == 3:
             return [pl[0], np.concatenate([pl[1], pl[2]], axis=0)]
@@ -572,6 +665,15 @@ class Image:
             pitches = self.pitches
         return (int(ptrs[0]), int(ptrs[1]) if len(ptrs) > 1 else 0, int(pitches[0]), int(pitches[1]) if len(pitches) > 1 else 0,
                 self.H, self.W, self.format, 0)
+
+
+def images_from_chw(batch, order="rgb"):
+    """A (B, 3, H, W) uint8 batch (numpy array, CPU or CUDA tensor) as a list of B Images that share its memory: Image.chw of every
+    frame, no copy.  What BatchedVitTracker.initialize / track take in place of batch.permute(0, 2, 3, 1).contiguous()."""
+    shape = tuple(getattr(batch, "shape", ()))
+    if len(shape) != 4 or shape[1] != 3:
+        raise VtError(f"a CHW batch must be (B, 3, H, W), got {shape}")
+    return [Image.chw(batch[b], order) for b in range(shape[0])]
 
 
 def pack_image_offsets(images, start: int = 0, align: int = ARENA_ALIGN):
@@ -599,7 +701,7 @@ class ImageTable(_DescriptorTable):
             raise VtError(f"unknown pixel format {fmt}")
         if high or mat >= len(PIX_MATRICES) or rng >= len(PIX_RANGES):
             raise VtError(f"unknown pixel format {fmt:#x}: matrix {mat}, range {rng}, bits 16-31 {high:#x}")
-        if (mat or rng) and lay not in _YUV420 + _YUV422:
+        if (mat or rng) and lay not in _YUV420 + _YUV422 + _PLANAR_YUV:
             raise VtError(f"a {pix_name(fmt)} image takes no matrix or range bits, got format {fmt:#x}")
         if int(reserved) != 0:
             raise VtError("vt_image.reserved must be 0")
@@ -607,7 +709,7 @@ class ImageTable(_DescriptorTable):
             raise VtError(f"image of {H}x{W} pixels: H and W must be >= 1")
         if lay in _YUV420 and (H % 2 or W % 2):
             raise VtError(f"an {pix_name(fmt)} image must have even H and W, got {H}x{W}")
-        if lay in _YUV422 and W % 2:
+        if lay in _YUV422 + (PIX_I422,) and W % 2:
             raise VtError(f"a {pix_name(fmt)} image must have even W, got {H}x{W}")
         r0, r1 = _row_bytes(fmt, W)
         planes = [(ptr0, pitch0, H, r0, nbytes0)] + ([(ptr1, pitch1, _plane1_rows(fmt, H), r1, nbytes1)] if r1 else [])
@@ -616,7 +718,7 @@ class ImageTable(_DescriptorTable):
             pitch = pitch or rb
             if pitch < rb:
                 raise VtError(f"plane {k}: row pitch {pitch} is shorter than a row ({rb} bytes)")
-            if not ptr or int(ptr) % 4:
+            if not ptr or (int(ptr) % 4 and lay not in _PLANAR):      # the planar layouts are read as single bytes: any address
                 raise VtError(f"plane {k}: address {int(ptr or 0):#x} is null or not 4-byte aligned")
             need = pitch * (rows - 1) + rb
             if pitch > 0xfffffff0 or need > 0xfffffff0:

@@ -103,7 +103,8 @@ class Vit_dist(BaseTracker):
         self._rec_host = torch.empty(5).pin_memory()
 
     def initialize(self, image, info: dict):
-        """image: an (H, W, 3) RGB array, or a native.Image (NV12 / NV21, BGR, RGBA / BGRA) that the device crop reads directly."""
+        """image: an (H, W, 3) RGB array, or a native.Image (any layout of include/vittrack.h -- NV12 / NV21, BGR, RGBA / BGRA, ...;
+        Image.chw(t) for a (3, H, W) frame) that the device crop reads directly."""
         if isinstance(image, Image) and self._bt is None:
             raise VtError("an Image frame needs the device pipeline (params.host_crop is set)")
         if self._bt is not None:
