@@ -19,7 +19,8 @@ same tolerances as the plain ones, with no allowance for the offset.
 Maps and boxes: max abs 1.3e-2 (score / size, range [0, 1]) and 3.0e-2 (offset) over the four fixtures, boxes 3.9e-3 / 4.9e-3 (a box's
 w / h ARE size-map values); held at 2.2e-2 / 4.4e-2 on maps and 9e-3 on boxes = the head's four bf16 convolutions on features that carry
 TOL_REL(12) (every fixture's argmax margin is >= 0.03, so no argmax flip is excusable).  north_star's 1e-3 applies to the fp32 vit_48
-path, not to this bf16 one."""
+path, not to this bf16 one.  The sharp statement about the head alone is tests/test_gpu_bf16_head_budget.py: its error against the fp64
+truth within a small multiple of a bf16 oracle's, per map, frame and channel, at every width, both map sizes and both tile forms."""
 import os
 
 import numpy as np
