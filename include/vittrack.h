@@ -362,10 +362,11 @@ int vt_track_step_frames(vt_model* m, const vt_frame* frames_dev, double* states
  *              H may be odd.
  *     The four planar layouts are read as single bytes: plane0 and plane1 need NO alignment (p + H W of an odd-sized CHW frame is not
  *     4-byte aligned).  plane1's extent covers both trailing planes: pitch1 (2 H - 1) + its row bytes, inside a 32-bit offset.
- * The format word: bits 0-7 the layout (the VT_PIX_* values; 6, 7, 14 and 15 are never assigned), bits 8-11 the matrix (0 = BT.601, 1 =
+ * The format word: bits 0-7 the layout (the VT_PIX_* values; 6, 7, 14, 15, 20, 27-31, 35, 39, 43 and 47 up are never assigned), bits 8-11 the matrix (0 = BT.601, 1 =
  * BT.709), bits 12-15 the range (0 = limited, 1 = full), bits 16-31 zero -- format = VT_PIX_P010 | VT_PIX_BT709 | VT_PIX_FULL.  Every
  * value that was legal before the colour fields existed means what it meant (NV12 = BT.601 limited).  Matrix and range belong to the
- * YUV layouts (NV12 / NV21, I420 / YV12, YUYV / UYVY, P010, I444 / I422); on the RGB family (RGBP / BGRP included) and GRAY8 they must be 0.
+ * YUV layouts (NV12 / NV21, I420 / YV12, YUYV / UYVY, P010, I444 / I422, YV16 / YV24, NV16 / NV24, P210 / P410, I010 ... I416); on the RGB
+ * family (RGBP / BGRP included), GRAY8 and GRAY10 / GRAY12 / GRAY16 they must be 0.
  * Colour, every YUV layout: chroma is never interpolated (a 2 x 2 block of 4:2:0, a pair of 4:2:2, shares its U, V); int32, >> arithmetic:
  *       yy = max(Y - 16, 0) * cy   (limited range)      yy = Y * cy   (full range)
  *       R = clamp((yy + cvr (V - 128)                   + (1 << 19)) >> 20, 0, 255)
@@ -381,8 +382,25 @@ int vt_track_step_frames(vt_model* m, const vt_frame* frames_dev, double* states
  *     Checked on the CPU over all 2^24 (Y, U, V): the value before the shift stays below 5.8e8 (inside int32), and before clamping
  *     each channel differs from the fp64 formula by at most 0.5000 / 0.5002 / 0.5000 (601 full / 709 limited / 709 full; OpenCV's
  *     601-limited literals: up to 0.69).  tests/test_frame_formats_yuv.py repeats the check.
- *   Not supported: chroma interpolation and chroma siting, BT.2020 / PQ / HLG, big-endian samples, the V-first twins of the planar
- *   layouts (YV16 / YV24), two-plane 4:2:2 / 4:4:4 (NV16 / NV24), 16-bit planar layouts.
+ *   YV16/YV24  I422 / I444 with the V plane first: plane1 is the V plane, the U plane begins pitch1 * H bytes after it.
+ *   NV16       two-plane 4:2:2 (capture cards): plane0 H rows of W luma bytes; plane1 H rows of W/2 (U, V) byte pairs (pitch1 0 = W): U, V
+ *              at pair x >> 1 of row y.  W even, H may be odd.
+ *   NV24       two-plane 4:4:4: plane1 H rows of W (U, V) pairs, 2 W bytes (pitch1 0 = 2 W): U, V at (x, y).  H and W may be odd.
+ *   P210/P410  NV16 / NV24 in little-endian 16-bit words, MSB-aligned (hardware decoders): plane0 H rows of 2 W bytes, plane1 H rows of
+ *              2 W (P210) / 4 W (P410) bytes.  The 8-bit sample is the HIGH byte of each word, P010's rule: a P216 / P416 surface is read
+ *              the same way.  P210: W even.
+ *   16-bit planar layouts, LSB-aligned little-endian words (ffmpeg's yuv420p10le ... yuv444p16le, gray10le ... gray16le): the code is
+ *              32 | sub << 2 | dep -- sub 0 / 1 / 2 / 3 = 4:2:0 / 4:2:2 / 4:4:4 / luma only, dep 0 / 1 / 2 = 10 / 12 / 16 bits:
+ *              I010 / I012 / I016 = 32 / 33 / 34, I210 / I212 / I216 = 36 / 37 / 38, I410 / I412 / I416 = 40 / 41 / 42, GRAY10 / GRAY12 /
+ *              GRAY16 = 44 / 45 / 46.  Planes are those of I420, I422, I444 and GRAY8 with row bytes doubled: plane0 H rows of 2 W bytes;
+ *              plane1 the U plane, rows of W (4:2:0, 4:2:2) or 2 W (4:4:4) bytes; the V plane begins pitch1 * (chroma rows: H/2 for
+ *              4:2:0, else H) bytes after plane1, and plane1's extent covers both.  Parity as the 8-bit layouts: H and W even for 4:2:0,
+ *              W even for 4:2:2.
+ *     The 8-bit sample of every 16-bit layout is s8 = min(v >> (depth - 8), 255): the top eight bits of the depth, truncated as P010's
+ *     are; a word above the depth's range saturates.  Everything after s8 -- the colour rows, no chroma interpolation -- is as above.
+ *     Alignment: the byte layouts (YV16 / YV24, NV16 / NV24), the high-byte ones (P210 / P410) and the 16-bit depth are read as single
+ *     bytes and need none; the 10- and 12-bit layouts are fetched as 16-bit words: plane0, plane1 and both pitches must be even.
+ *   Not supported: chroma interpolation and chroma siting, BT.2020 / PQ / HLG, big-endian samples.
  *   pitch0 / pitch1: bytes between rows of plane0 / plane1, >= the row's bytes (0 = the row's bytes).  A plane is [plane, plane +
  *   pitch (rows - 1) + row bytes); nothing outside it is read.  plane1 / pitch1 are unused by the one-plane formats.
  * Planes: device memory or device-mapped pinned host memory.  The table (B,) lives there too and is read when the kernels run: a
@@ -390,8 +408,9 @@ int vt_track_step_frames(vt_model* m, const vt_frame* frames_dev, double* states
  * A descriptor is unusable -- treated as a too-small box: NaN resize factor, zero (uint8) or NaN (fp32) patch, nothing read through
  * it, the other sequences unaffected -- when its format word is not one described above (an unassigned layout, a matrix or range
  * beyond 1, a bit in 16-31, matrix or range bits on an RGB layout or GRAY8) or `reserved` is not 0, a plane it needs is null or not
- * 4-byte aligned (the four planar layouts: null only), a pitch is below the row's bytes, H or W is < 1, W is odd for a 4:2:2 layout (I422
- * included), H or W is odd for a 4:2:0 layout, or a plane does not fit a 32-bit offset. */
+ * 4-byte aligned (the four planar layouts and codes 21-46: null only; the 10- and 12-bit layouts: null, an odd address or an odd pitch), a
+ * pitch is below the row's bytes (doubled for 16-bit samples), H or W is < 1, W is odd for a 4:2:2 layout (I422, YV16, NV16, P210 and
+ * I210 / I212 / I216 included), H or W is odd for a 4:2:0 layout (I010 / I012 / I016 included), or a plane does not fit a 32-bit offset. */
 enum { VT_PIX_RGB = 0, VT_PIX_BGR = 1, VT_PIX_RGBA = 2, VT_PIX_BGRA = 3, VT_PIX_NV12 = 4, VT_PIX_NV21 = 5 };
 /* the layouts added to bits 0-7 (6 and 7 are never assigned) ... */
 #define VT_PIX_I420 8
@@ -405,6 +424,29 @@ enum { VT_PIX_RGB = 0, VT_PIX_BGR = 1, VT_PIX_RGBA = 2, VT_PIX_BGRA = 3, VT_PIX_
 #define VT_PIX_BGRP 17
 #define VT_PIX_I444 18
 #define VT_PIX_I422 19
+/* ... the V-first planar and the two-plane layouts of 4:2:2 and 4:4:4 in bytes, the two-plane ones in MSB-aligned 16-bit words (20 and
+ * 27-31 are never assigned) ... */
+#define VT_PIX_YV16 21
+#define VT_PIX_YV24 22
+#define VT_PIX_NV16 23
+#define VT_PIX_NV24 24
+#define VT_PIX_P210 25
+#define VT_PIX_P410 26
+/* ... the planar layouts in LSB-aligned little-endian 16-bit words, 32 | sub << 2 | dep: sub 0 / 1 / 2 / 3 = 4:2:0 / 4:2:2 / 4:4:4 /
+ * luma only, dep 0 / 1 / 2 = 10 / 12 / 16 bits (dep 3, i.e. 35, 39, 43 and 47, and everything above 47 are never assigned) ... */
+#define VT_PIX_WIDE(sub, dep) (32 | (sub) << 2 | (dep))
+#define VT_PIX_I010 32
+#define VT_PIX_I012 33
+#define VT_PIX_I016 34
+#define VT_PIX_I210 36
+#define VT_PIX_I212 37
+#define VT_PIX_I216 38
+#define VT_PIX_I410 40
+#define VT_PIX_I412 41
+#define VT_PIX_I416 42
+#define VT_PIX_GRAY10 44
+#define VT_PIX_GRAY12 45
+#define VT_PIX_GRAY16 46
 /* ... and the colour tags of a YUV layout, or-ed into the format word: matrix in bits 8-11, range in bits 12-15 */
 #define VT_PIX_BT601 0x0000
 #define VT_PIX_BT709 0x0100

@@ -2,7 +2,7 @@
 """Pixel formats on the device: what reading NV12 / NV21, BGR and RGBA / BGRA directly costs against RGB, and what the
 other layouts and colour rows (P010, I420, YUYV / UYVY, GRAY8; BT.709, full range) cost against NV12 BT.601.
 
-    python tools/frame_formats.py [--batch 256] [--rounds 5] [--reps 20] [--distinct 32] [--sections crop,step,small,convert,new,parent,planar]
+    python tools/frame_formats.py [--batch 256] [--rounds 5] [--reps 20] [--distinct 32] [--sections crop,step,small,convert,new,parent,planar,wide]
                                   [--parent-lib OTHER.so]
 
 Fixed seeds, 1920 x 1080 frames (`--distinct` different frames, cycled over the sequences) with 30-120 px boxes:
@@ -27,6 +27,12 @@ Fixed seeds, 1920 x 1080 frames (`--distinct` different frames, cycled over the 
                           open-loop G128 / G256 step on those tables; permute_step_us[G] = what a caller does without the layout --
                           hwc.copy_(chw.permute(0, 2, 3, 1)) inside the captured, timed graph, then vt_track_step_frames -- against the
                           step on the CHW frames (ratio = permute + step over CHW step)
+  wide                    (section "wide") B = 256: crop_us[T][form] = the uint8 table crop of I010, I210, I410 (the 16-bit fetch family), P210,
+                          NV16 and GRAY16 (byte fetch) next to I420 (byte fetch), P010 (aligned windows) and the RGB frame route in the same
+                          interleaved rounds, ratio_vs_i420 / ratio_vs_rgb_frames; step_us[G][form] = the open-loop G128 / G256 step on
+                          those tables; convert_step_us[G] = what a caller does without the layout -- the whole I010 frames shifted down
+                          to bytes ((t >> 2).to(uint8), two torch kernels) inside the captured, timed graph, then the step on the I420
+                          frames -- against the step on the I010 frames (ratio = convert + step over I010 step)
 Method: every form is a captured graph (`--reps` launches for a crop, one step for a step; outputs preallocated, no host work
 inside); the forms are timed in `--rounds` interleaved rounds (the order rotates every round), each a host-timed region of replays
 with one synchronisation, and the best round of each form is reported.  The shader clock is probed (vt_probe_clock, a dense MFMA
@@ -300,6 +306,88 @@ def _planar(a, B, g, states):
     return res
 
 
+def _wide(a, B, n, g, states):
+    """Section wide: the 16-bit and two-plane layouts beside I420, P010 and the RGB frame route; the I010 step against shifting whole
+    frames down to I420 first."""
+    import torch
+    from vittracker_amd.native import FrameTable, Image, ImageTable
+    mk = lambda *s: torch.randint(0, 256, s, dtype=torch.uint8, device="cuda", generator=g)      # noqa: E731
+    # every sequence its own I010 frame, in one (B, 3H/2, W) buffer of 16-bit words laid out as an I420 buffer is; its 8-bit twin
+    w16 = torch.randint(0, 1024, (B, 3 * H // 2, W), dtype=torch.int16, device="cuda", generator=g)
+    tmp16, b8 = torch.empty_like(w16), torch.empty(B, 3 * H // 2, W, dtype=torch.uint8, device="cuda")
+
+    def convert():
+        torch.bitwise_right_shift(w16, 2, out=tmp16)      # (t >> 2).to(torch.uint8) without an allocation
+        b8.copy_(tmp16)
+    convert()
+
+    def i010(f):
+        c = f[H:].reshape(H, W // 2)
+        return Image.i010(f[:H], c[:H // 2], c[H // 2:])
+    keep = {k: [mk(*sh) for _ in range(n)] for k, sh in (("y16", (H, 2 * W)), ("y8", (H, W)), ("c210", (2 * H, W)), ("c410", (2 * H, 2 * W)),
+                                                        ("p210", (H, W // 2, 4)), ("nv16", (H, W // 2, 2)), ("p010", (H // 2, W // 2, 4)),
+                                                        ("rgb", (H, W, 3)))}
+    k = lambda name, b: keep[name][b % n]      # noqa: E731
+    forms = {"i420": [Image.i420_buffer(f) for f in b8],
+             "p010": [Image.p010(k("y16", b), k("p010", b)) for b in range(B)],
+             "i010": [i010(f) for f in w16],
+             "i210": [Image.yuv16(k("y16", b), k("c210", b)[:H], k("c210", b)[H:], depth=10, sub="422") for b in range(B)],
+             "i410": [Image.yuv16(k("y16", b), k("c410", b)[:H], k("c410", b)[H:], depth=10, sub="444") for b in range(B)],
+             "p210": [Image.p210(k("y16", b), k("p210", b)) for b in range(B)],
+             "nv16": [Image.nv16(k("y8", b), k("nv16", b)) for b in range(B)],
+             "gray16": [Image.gray16(k("y16", b), depth=16) for b in range(B)]}
+    tabs = {name: ImageTable.of(v) for name, v in forms.items()}
+    ft = FrameTable(B, "cuda")
+    for b in range(B):
+        ft.set_tensor(b, k("rgb", b))
+    ft.upload()
+    res = {"crop_us": {}, "step_us": {}, "convert_step_us": {},
+           "family": {"i420": "byte fetch", "p010": "P010 aligned windows", "i010": "16-bit fetch", "i210": "16-bit fetch", "i410": "16-bit fetch",
+                      "p210": "byte fetch (high bytes)", "nv16": "byte fetch", "gray16": "byte fetch (high bytes, luma only)"}}
+    m = _model(128, B)
+    for T in (128, 256):
+        graphs, outs = {}, []
+        for name, t in [("rgb_frames", ft)] + list(tabs.items()):
+            o = torch.empty(B, T, T, 3, dtype=torch.uint8, device="cuda")
+            rf = torch.empty(B, dtype=torch.float64, device="cuda")
+            outs.append((o, rf))
+            call = m.crop_u8_frames if name == "rgb_frames" else m.crop_u8_images
+
+            def fn(cs, call=call, t=t, o=o, rf=rf):
+                for _ in range(a.reps):
+                    call(t, states, 4.0, T, out=o, resize_factor=rf, stream=cs)
+            graphs[name] = _capture(fn)
+        rounds = _interleaved(graphs, a.reps, a.rounds, a.replays, all_rounds=True)
+        row = {name: _stats(v) for name, v in rounds.items()}
+        row["ratio_vs_rgb_frames"] = {name: round(min(v) / min(rounds["rgb_frames"]), 3) for name, v in rounds.items()}
+        row["ratio_vs_i420"] = {name: round(min(v) / min(rounds["i420"]), 3) for name, v in rounds.items()}
+        names = ["rgb_frames"] + list(tabs)
+        row["i010_equals_i420_of_its_top_bits"] = bool(torch.equal(outs[names.index("i010")][0], outs[names.index("i420")][0]))
+        res["crop_us"][str(T)] = row
+    del m, graphs
+    for S in (128, 256):
+        m = _model(S, B)
+        step_forms = {"rgb_frames": (m.track_step_frames, ft)}
+        step_forms.update({name: (m.track_step_images, t) for name, t in tabs.items()})
+        graphs, (x, rf, out, rec) = _step_graphs(m, S, B, states, step_forms)
+
+        def convert_then_step(cs):      # today's caller: the whole frames shifted down to bytes, then the I420 step on them
+            convert()
+            m.track_step_images(tabs["i420"], states, 4.0, MEAN, STD, x, rf, out, record=rec, stream=cs)
+        graphs["convert_then_step"] = _capture(convert_then_step)
+        graphs["convert_alone"] = _capture(lambda cs: convert())
+        rounds = _interleaved(graphs, 1, a.rounds, a.replays * 5, all_rounds=True)
+        row = {name: _stats(v) for name, v in rounds.items() if not name.startswith("convert")}
+        row["ratio_vs_rgb_frames"] = {name: round(min(v) / min(rounds["rgb_frames"]), 3) for name, v in rounds.items() if not name.startswith("convert")}
+        row["ratio_vs_i420"] = {name: round(min(v) / min(rounds["i420"]), 3) for name, v in rounds.items() if not name.startswith("convert")}
+        res["step_us"][f"G{S}"] = row
+        res["convert_step_us"][f"G{S}"] = {"convert_then_step": _stats(rounds["convert_then_step"]), "convert_alone": _stats(rounds["convert_alone"]),
+                                           "i010_step": _stats(rounds["i010"]), "i420_step": _stats(rounds["i420"]),
+                                           "ratio": round(min(rounds["convert_then_step"]) / min(rounds["i010"]), 2)}
+        del m, graphs
+    return res
+
+
 def _nv12_to_rgb(y, uv):
     """The whole frames (n, H, W) / (n, H/2, W/2, 2) -> (n, H, W, 3) uint8 with unfused int32 torch ops: BT.601 limited range,
     OpenCV's fixed point."""
@@ -354,7 +442,7 @@ def main():
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--replays", type=int, default=10)
     ap.add_argument("--distinct", type=int, default=32)
-    ap.add_argument("--sections", default="crop,step,small,convert", help="of crop, step, small, convert, new, parent, planar")
+    ap.add_argument("--sections", default="crop,step,small,convert", help="of crop, step, small, convert, new, parent, planar, wide")
     ap.add_argument("--parent-lib", default=None, help="the parent commit's libvittrack_hip.so (section parent)")
     a = ap.parse_args()
     sections = set(a.sections.split(","))
@@ -374,6 +462,8 @@ def main():
         res["parent_ab"] = _parent_ab(a, B, n, g, states)
     if "planar" in sections:
         res["planar"] = _planar(a, B, g, states)
+    if "wide" in sections:
+        res["wide"] = _wide(a, B, n, g, states)
     frames = {f: _planes(f, n, g) for f in (FORMATS if sections & {"crop", "step", "small", "convert"} else ("rgb", "nv12"))}
     if "new" in sections:
         # (0) the added layouts and colour rows against NV12 BT.601 and the RGB frame route

@@ -733,6 +733,12 @@ __global__ __launch_bounds__(256) void crop_band_kernel(const unsigned char* __r
 // denotes an RGB image rgb(d); the kernels below crop it with exactly the arithmetic of the kernels above -- only the fetch of a tap
 // pixel differs: it is converted to an RGB dword (R | G << 8 | B << 16) first.  New kernels, not new frame sources of the bodies above:
 // those bodies fetch a 3-byte pixel pair as one window, and the existing instantiations stay as they compile today.
+// The planar 16-bit layouts: 32 | sub << 2 | dep, codes 32-46 with dep != 3 (include/vittrack.h)
+__device__ __forceinline__ bool is_wide16(int fmt) { return fmt >= VT_PIX_I010 && fmt <= VT_PIX_GRAY16 && (fmt & 3) != 3; }
+// ... and of those the LSB-aligned 10- and 12-bit ones, whose 8-bit sample is min(word >> (depth - 8), 255): the shift, 2 or 4; 0 for
+// every layout whose samples are single bytes (the 16-bit ones of dep 2 included: the high byte)
+__device__ __forceinline__ unsigned wide_shift(int fmt) { return is_wide16(fmt) && (fmt & 3) != 2 ? 2u + 2u * (unsigned)(fmt & 3) : 0u; }
+
 struct ImageView {
     const unsigned char* p0;       // plane 0: the packed pixels, or the luma plane
     const unsigned char* p1;       // plane 1: NV12 / NV21 / P010 chroma pairs, or the first chroma plane of I420 / YV12 / I444 / I422, or the G plane
@@ -756,28 +762,45 @@ __device__ __forceinline__ ImageView image_view(const vt_image* images, int b) {
     // the planar layouts: three full-height planes of single bytes (I422: chroma planes of W / 2 bytes a row), read as single bytes,
     // hence no alignment rule (plane 1 of a contiguous (3, H, W) tensor of odd H W is at an odd address)
     const bool prgb = fmt == VT_PIX_RGBP || fmt == VT_PIX_BGRP, p422 = fmt == VT_PIX_I422, pln = prgb || fmt == VT_PIX_I444 || p422;
-    const bool sub420 = nv || p010 || pl, yuv = sub420 || pk2 || (pln && !prgb);
-    const long long bpp = (fmt == VT_PIX_RGBA || fmt == VT_PIX_BGRA) ? 4 : ((p010 || pk2) ? 2 : ((nv || pl || pln || fmt == VT_PIX_GRAY8) ? 1 : 3));
-    const unsigned long long amask = pln ? 0ull : 3ull;
-    bool ok = ((fmt >= VT_PIX_RGB && fmt <= VT_PIX_NV21) || (fmt >= VT_PIX_I420 && fmt <= VT_PIX_GRAY8) || pln) && (word >> 16) == 0u && mat <= 1 &&
+    // the wide family (codes 21-26, 32-46).  v3: three planes of single bytes, V first; sp: two planes, plane 1 of (U, V) pairs at full
+    // height, in bytes (NV16 / NV24) or 16-bit words (P210 / P410); w16: planar 16-bit words, 32 | sub << 2 | dep (is_wide16), sub 0 /
+    // 1 / 2 / 3 = 4:2:0 / 4:2:2 / 4:4:4 / luma only, dep 0 / 1 / 2 = 10 / 12 / 16 bits (3: unassigned).  c422 / c444: the chroma
+    // columns of every wide layout.  lsb: the 10- and 12-bit words are fetched as aligned 16-bit loads -- even addresses, even pitches;
+    // every other wide layout is read as single bytes at any address
+    const bool v3 = fmt == VT_PIX_YV16 || fmt == VT_PIX_YV24, sp = fmt >= VT_PIX_NV16 && fmt <= VT_PIX_P410, sp16 = fmt >= VT_PIX_P210 && sp;
+    const bool w16 = is_wide16(fmt);
+    const int wsub = w16 ? (fmt >> 2) & 3 : -1;
+    const bool lsb = wide_shift(fmt) != 0u;
+    const bool c422 = fmt == VT_PIX_YV16 || fmt == VT_PIX_NV16 || fmt == VT_PIX_P210 || wsub == 1;
+    const bool c444 = fmt == VT_PIX_YV24 || fmt == VT_PIX_NV24 || fmt == VT_PIX_P410 || wsub == 2;
+    const bool wide = v3 || sp || w16;
+    const bool sub420 = nv || p010 || pl || wsub == 0, yuv = sub420 || pk2 || (pln && !prgb) || (wide && wsub != 3);
+    const long long bpp = (fmt == VT_PIX_RGBA || fmt == VT_PIX_BGRA) ? 4 : ((p010 || pk2 || sp16 || w16) ? 2 : ((nv || pl || pln || wide || fmt == VT_PIX_GRAY8) ? 1 : 3));
+    const unsigned long long amask = (pln || wide) ? (lsb ? 1ull : 0ull) : 3ull;
+    bool ok = ((fmt >= VT_PIX_RGB && fmt <= VT_PIX_NV21) || (fmt >= VT_PIX_I420 && fmt <= VT_PIX_GRAY8) || pln || wide) && (word >> 16) == 0u && mat <= 1 &&
               rng <= 1 && (yuv || (mat | rng) == 0) && d->reserved == 0 && H >= 1 && W >= 1 && H <= 0x10000000 && W <= 0x10000000 &&
-              (!sub420 || ((H | W) & 1) == 0) && (!(pk2 || p422) || (W & 1) == 0);
+              (!sub420 || ((H | W) & 1) == 0) && (!(pk2 || p422 || c422) || (W & 1) == 0);
     const long long row0 = bpp * W, pitch0 = d->pitch0 == 0 ? row0 : d->pitch0;
-    ok = ok && pitch0 >= row0 && pitch0 <= 0xfffffff0ll && p0 != nullptr && (reinterpret_cast<unsigned long long>(p0) & amask) == 0;
+    ok = ok && pitch0 >= row0 && pitch0 <= 0xfffffff0ll && p0 != nullptr && (reinterpret_cast<unsigned long long>(p0) & amask) == 0 && !(lsb && (pitch0 & 1));
     const unsigned long long ext0 = ok ? (unsigned long long)pitch0 * (unsigned long long)(H - 1) + (unsigned long long)row0 : 0ull;
     ok = ok && ext0 <= 0xfffffff0ull;
     long long pitch1 = 0;
     unsigned long long ext1 = 0, p2 = 0;
-    if (sub420 || pln) {
+    if (sub420 || pln || (wide && wsub != 3)) {
         // chroma: H / 2 rows of W bytes (NV12 / NV21) or 2 W bytes (P010); I420 / YV12: two planes of H / 2 rows of W / 2 bytes back
-        // to back at one pitch, i.e. H rows, and the extent covers both; the planar layouts: two planes of H rows back to back, 2 H rows
-        const long long row1 = p010 ? 2ll * W : ((pl || p422) ? W / 2 : (long long)W);
-        const long long rows1 = pln ? 2ll * H : (pl ? H : H / 2);
+        // to back at one pitch, i.e. H rows, and the extent covers both; the planar layouts: two planes of H rows back to back, 2 H rows.
+        // The wide family: W / 2 (4:2:0, 4:2:2) or W (4:4:4) chroma samples a row per plane, twice that in a plane of pairs, bytes
+        // doubled in 16-bit words; three-plane layouts as I420 (4:2:0) or the planar layouts, planes of pairs H rows
+        const long long cw = (c444 ? (long long)W : W / 2) * (sp ? 2ll : 1ll) * ((sp16 || w16) ? 2ll : 1ll);
+        const long long row1 = wide ? cw : (p010 ? 2ll * W : ((pl || p422) ? W / 2 : (long long)W));
+        const bool three = pl || pln || v3 || w16;      // a trailing chroma plane: pitch1 x chroma rows behind plane 1
+        const long long crows = sub420 ? H / 2 : H;
+        const long long rows1 = three ? 2 * crows : crows;
         pitch1 = d->pitch1 == 0 ? row1 : d->pitch1;
-        ok = ok && pitch1 >= row1 && pitch1 <= 0xfffffff0ll && p1 != nullptr && (reinterpret_cast<unsigned long long>(p1) & amask) == 0;
+        ok = ok && pitch1 >= row1 && pitch1 <= 0xfffffff0ll && p1 != nullptr && (reinterpret_cast<unsigned long long>(p1) & amask) == 0 && !(lsb && (pitch1 & 1));
         ext1 = ok ? (unsigned long long)pitch1 * (unsigned long long)(rows1 - 1) + (unsigned long long)row1 : 0ull;
         ok = ok && ext1 <= 0xfffffff0ull;
-        p2 = (ok && (pl || pln)) ? (unsigned long long)pitch1 * (unsigned long long)(pln ? H : H / 2) : 0ull;
+        p2 = (ok && three) ? (unsigned long long)pitch1 * (unsigned long long)crows : 0ull;
     }
     return ImageView{p0, p1, ok ? (unsigned)pitch0 : 0u, ok ? (unsigned)pitch1 : 0u, ok ? (unsigned)ext0 : 0u, ok ? (unsigned)ext1 : 0u,
                      (unsigned)p2, ok ? H : 1, ok ? W : 1, fmt, ok ? (mat | (rng << 1)) : 0, ok};
@@ -856,9 +879,24 @@ __device__ __forceinline__ unsigned yuv_rgb(unsigned y8, const ChromaTerms& c, c
 // P010: the sample is the high byte of each little-endian 16-bit word, hence the odd offsets.
 // I444: every pixel its own chroma (cxs = 0), the V plane pitch1 H bytes behind the U plane.  Planar RGB is addressed exactly so -- plane
 // 0 where I444 keeps luma, the two trailing planes where it keeps U and V -- and differs in what the three bytes mean (is_planar_rgb).
+// The wide family.  YV16 / YV24: I422 / I444 with U and V exchanged.  NV16 / NV24: NV12's pairs at full height (cys = 0), NV24 a pair
+// a pixel.  P210 / P410: those in 16-bit words, the high byte of each as P010.  Planar 16-bit (is_wide16): I420 / I422 / I444 / GRAY8
+// in 16-bit words -- dep 2: the high bytes (odd offsets), fetched as bytes; dep 0 / 1: the offsets are those of the aligned words
+// themselves, fetched by the 16-bit family of the two image kernels (wide_shift).
 struct YuvLayout { unsigned ymul, yadd, cys, cpitch, cmul, uoff, voff, cxs; bool c0; };
 __device__ __forceinline__ YuvLayout yuv_layout(const ImageView& iv) {
+    if (is_wide16(iv.fmt)) {
+        const unsigned sub = ((unsigned)iv.fmt >> 2) & 3u, hb = ((unsigned)iv.fmt & 3u) == 2u ? 1u : 0u;
+        if (sub == 3u) return YuvLayout{2u, hb, 0u, 0u, 0u, 0u, 0u, 1u, true};      // luma only
+        return YuvLayout{2u, hb, sub == 0u ? 1u : 0u, iv.pitch1, 2u, hb, iv.p2 + hb, sub == 2u ? 0u : 1u, false};
+    }
     switch (iv.fmt) {
+        case VT_PIX_YV16: return YuvLayout{1u, 0u, 0u, iv.pitch1, 1u, iv.p2, 0u, 1u, false};
+        case VT_PIX_YV24: return YuvLayout{1u, 0u, 0u, iv.pitch1, 1u, iv.p2, 0u, 0u, false};
+        case VT_PIX_NV16: return YuvLayout{1u, 0u, 0u, iv.pitch1, 2u, 0u, 1u, 1u, false};
+        case VT_PIX_NV24: return YuvLayout{1u, 0u, 0u, iv.pitch1, 2u, 0u, 1u, 0u, false};
+        case VT_PIX_P210: return YuvLayout{2u, 1u, 0u, iv.pitch1, 4u, 1u, 3u, 1u, false};
+        case VT_PIX_P410: return YuvLayout{2u, 1u, 0u, iv.pitch1, 4u, 1u, 3u, 0u, false};
         case VT_PIX_NV21: return YuvLayout{1u, 0u, 1u, iv.pitch1, 2u, 1u, 0u, 1u, false};
         case VT_PIX_I420: return YuvLayout{1u, 0u, 1u, iv.pitch1, 1u, 0u, iv.p2, 1u, false};
         case VT_PIX_YV12: return YuvLayout{1u, 0u, 1u, iv.pitch1, 1u, iv.p2, 0u, 1u, false};
@@ -879,8 +917,11 @@ __device__ __forceinline__ unsigned planar_rgb(unsigned a, unsigned g, unsigned 
     return bgr ? (c | (g << 8) | (a << 16)) : (a | (g << 8) | (c << 16));
 }
 __device__ __forceinline__ bool is_yuv_layout(int fmt) {
-    return fmt == VT_PIX_NV12 || fmt == VT_PIX_NV21 || (fmt >= VT_PIX_I420 && fmt <= VT_PIX_P010) || fmt == VT_PIX_I444 || fmt == VT_PIX_I422;
+    return fmt == VT_PIX_NV12 || fmt == VT_PIX_NV21 || (fmt >= VT_PIX_I420 && fmt <= VT_PIX_P010) || fmt == VT_PIX_I444 || fmt == VT_PIX_I422 ||
+           (fmt >= VT_PIX_YV16 && fmt <= VT_PIX_P410) || (fmt >= VT_PIX_I010 && fmt < VT_PIX_GRAY10);
 }
+// luma only: rgb = (Y, Y, Y), Y the 8-bit sample at yuv_layout's luma place
+__device__ __forceinline__ bool is_gray_layout(int fmt) { return fmt == VT_PIX_GRAY8 || fmt >= VT_PIX_GRAY10; }
 // The tracker's tail clips against each sequence's own frame size (TrackTail::frames): the crop of vt_track_step_images writes the
 // sizes of its descriptors into a vt_frame-shaped table as it reads them (sizes may be null: vt_crop_images)
 __device__ __forceinline__ void image_sizes_out(vt_frame* sizes, const vt_image* images, int b) {
@@ -928,7 +969,19 @@ __global__ __launch_bounds__(256) void crop_image_kernel(const vt_image* __restr
     const YuvCoef kc = yuv_coef(iv.col);
     const bool c1 = !yl.c0 && iv.p1 != nullptr;      // where the chroma samples are: plane 1, or plane 0 (packed 4:2:2)
     const auto rsc = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned char*>(c1 ? iv.p1 : iv.p0), 0, (int)(c1 ? iv.nrec1 : iv.nrec0), 0x00020000);
+    // The 10- and 12-bit planar layouts: one 16-bit load a sample, s8 = min(word >> wsh, 255).  Bound: planes and pitches are even
+    // (image_view), so a word's offset pitch y + 2 x is even and at most extent - 2, the extent pitch (rows - 1) + 2 (samples a row)
+    // being even: no load starts at the extent's last byte, and none crosses it.
+    const unsigned wsh = wide_shift(fmt);
+    auto word0 = [&](unsigned o) { const unsigned w = ((unsigned)__builtin_amdgcn_raw_buffer_load_b16(rs0, (int)o, 0, 0) & 0xffffu) >> wsh; return w < 255u ? w : 255u; };
+    auto wordc = [&](unsigned o) { const unsigned w = ((unsigned)__builtin_amdgcn_raw_buffer_load_b16(rsc, (int)o, 0, 0) & 0xffffu) >> wsh; return w < 255u ? w : 255u; };
     auto pixel = [&](int x, int y) -> unsigned {      // rgb(d) at (x, y), inside the image
+        if (wsh != 0u) {         // uniform: the 16-bit fetch family
+            const unsigned a = word0((unsigned)y * iv.pitch0 + (unsigned)x * 2u);
+            if (!yuvf) return a * 0x010101u;      // GRAY10 / GRAY12
+            const unsigned co = ((unsigned)y >> yl.cys) * yl.cpitch + ((unsigned)x >> yl.cxs) * 2u;
+            return yuv_rgb(a, chroma_terms(wordc(co), wordc(co + yl.voff), kc), kc);
+        }
         if (yuvf || prgb) {      // every sample a single byte: see yuv_layout
             const unsigned co = ((unsigned)y >> yl.cys) * yl.cpitch + ((unsigned)x >> yl.cxs) * yl.cmul;
             const unsigned u = (unsigned)__builtin_amdgcn_raw_buffer_load_b8(rsc, (int)(co + yl.uoff), 0, 0) & 0xffu;
@@ -937,6 +990,7 @@ __global__ __launch_bounds__(256) void crop_image_kernel(const vt_image* __restr
             if (prgb) return planar_rgb(a, u, v, fmt == VT_PIX_BGRP);
             return yuv_rgb(a, chroma_terms(u, v, kc), kc);
         }
+        if (fmt == VT_PIX_GRAY16) return byte0((unsigned)y * iv.pitch0 + (unsigned)x * 2u + 1u) * 0x010101u;      // the high byte
         if (fmt == VT_PIX_GRAY8) return byte0((unsigned)y * iv.pitch0 + (unsigned)x) * 0x010101u;
         const unsigned o = (unsigned)y * iv.pitch0 + (unsigned)x * ((fmt == VT_PIX_RGBA || fmt == VT_PIX_BGRA) ? 4u : 3u);
         const unsigned a = byte0(o), gr = byte0(o + 1u), c = byte0(o + 2u);
@@ -1218,12 +1272,28 @@ __device__ __forceinline__ void crop_band_image_ext(const vt_image* __restrict__
     // 4:2:2 keeps its chroma in plane 0; planar RGB lies as I444 does and skips the conversion).
     // Every offset lies inside its plane by construction (x + step <= W - 1, rows <= H - 2): no guard form.
     // PRGB: planar RGB, an instantiation of its own, so that the loop of the layouts that were here first compiles as it did.
-    auto bytewise = [&](auto prgb_c) {
-        constexpr bool PRGB = decltype(prgb_c)::value;
-        const bool gray = fmt == VT_PIX_GRAY8, pbgr = fmt == VT_PIX_BGRP;
+    // The wide family's byte layouts (YV16 / YV24, NV16 / NV24, P210 / P410, the 16-bit planar ones through their high bytes) are rows
+    // of yuv_layout and run this loop as it is.
+    // WIDE: the 10- and 12-bit planar layouts and GRAY10 / GRAY12, an instantiation of its own: every sample ONE 16-bit load through the
+    // same bounded descriptors, s8 = min(word >> wsh, 255) with wsh = depth - 8 uniform, then this loop -- as many loads as the byte
+    // family issues.  Bound: image_view admits these layouts at even plane addresses and even pitches only, the column entries are
+    // 2 x (yadd = 0) and 2 (x >> cxs), the trailing plane begins at the even p2: every word's offset is even, and the extent
+    // pitch (rows - 1) + 2 (samples a row) is even too, so the last word starts at extent - 2 -- no load starts at the extent's last
+    // byte or crosses it.
+    auto bytewise = [&](auto prgb_c, auto wide_c) {
+        constexpr bool PRGB = decltype(prgb_c)::value, WIDE = decltype(wide_c)::value;
+        const bool gray = is_gray_layout(fmt), pbgr = fmt == VT_PIX_BGRP;
         const unsigned ystep = yl.ymul, cstepb = yl.cmul;
-        auto lum = [&](unsigned o) { return (unsigned)__builtin_amdgcn_raw_buffer_load_b8(rs0, (int)o, 0, 0) & 0xffu; };
-        auto chr = [&](unsigned o) { return (unsigned)__builtin_amdgcn_raw_buffer_load_b8(rs1, (int)o, 0, 0) & 0xffu; };
+        const unsigned wsh = wide_shift(fmt);
+        auto s8 = [&](unsigned w) { w = (w & 0xffffu) >> wsh; return w < 255u ? w : 255u; };
+        auto lum = [&](unsigned o) {
+            if constexpr (WIDE) return s8((unsigned)__builtin_amdgcn_raw_buffer_load_b16(rs0, (int)o, 0, 0));
+            else return (unsigned)__builtin_amdgcn_raw_buffer_load_b8(rs0, (int)o, 0, 0) & 0xffu;
+        };
+        auto chr = [&](unsigned o) {
+            if constexpr (WIDE) return s8((unsigned)__builtin_amdgcn_raw_buffer_load_b16(rs1, (int)o, 0, 0));
+            else return (unsigned)__builtin_amdgcn_raw_buffer_load_b8(rs1, (int)o, 0, 0) & 0xffu;
+        };
         auto tap = [&](unsigned yo, unsigned co) -> unsigned {
             if constexpr (PRGB) {
                 return planar_rgb(lum(yo), chr(co + yl.uoff), chr(co + yl.voff), pbgr);
@@ -1264,9 +1334,11 @@ __device__ __forceinline__ void crop_band_image_ext(const vt_image* __restrict__
             else yuv(std::false_type{});
         }
     } else if (is_planar_rgb(fmt)) {
-        bytewise(std::true_type{});
+        bytewise(std::true_type{}, std::false_type{});
+    } else if (wide_shift(fmt) != 0u) {
+        bytewise(std::false_type{}, std::true_type{});
     } else {
-        bytewise(std::false_type{});
+        bytewise(std::false_type{}, std::false_type{});
     }
 }
 

@@ -295,13 +295,43 @@ PIX_LAYOUT_NAMES.update({PIX_I420: "i420", PIX_YV12: "yv12", PIX_YUYV: "yuyv", P
 #: ... the planar layouts (14 and 15 are never assigned): three full-height planes of single bytes, no alignment rule ...
 PIX_RGBP, PIX_BGRP, PIX_I444, PIX_I422 = range(16, 20)
 PIX_LAYOUT_NAMES.update({PIX_RGBP: "rgbp", PIX_BGRP: "bgrp", PIX_I444: "i444", PIX_I422: "i422"})
+#: ... the V-first planar and the two-plane 4:2:2 / 4:4:4 layouts in bytes, the two-plane ones in MSB-aligned 16-bit words (20 and 27-31
+#: are never assigned) ...
+PIX_YV16, PIX_YV24, PIX_NV16, PIX_NV24, PIX_P210, PIX_P410 = range(21, 27)
+PIX_LAYOUT_NAMES.update({PIX_YV16: "yv16", PIX_YV24: "yv24", PIX_NV16: "nv16", PIX_NV24: "nv24", PIX_P210: "p210", PIX_P410: "p410"})
+#: ... the planar layouts in LSB-aligned little-endian 16-bit words, 32 | sub << 2 | dep: sub 0 / 1 / 2 / 3 = 4:2:0 / 4:2:2 / 4:4:4 / luma
+#: only, dep 0 / 1 / 2 = 10 / 12 / 16 bits (dep 3 and everything above 46 are never assigned) ...
+WIDE_SUBS = ("420", "422", "444", "gray")
+WIDE_DEPTHS = (10, 12, 16)
+
+
+def pix_wide(sub: str, depth: int) -> int:
+    """The layout code of a planar 16-bit layout: sub "420" | "422" | "444" | "gray", depth 10 | 12 | 16."""
+    if sub not in WIDE_SUBS or depth not in WIDE_DEPTHS:
+        raise VtError(f"a 16-bit planar layout is sub in {WIDE_SUBS} and depth in {WIDE_DEPTHS}, got {sub!r}, {depth!r}")
+    return 32 | WIDE_SUBS.index(sub) << 2 | WIDE_DEPTHS.index(depth)
+
+
+PIX_I010, PIX_I012, PIX_I016 = (pix_wide("420", d) for d in WIDE_DEPTHS)
+PIX_I210, PIX_I212, PIX_I216 = (pix_wide("422", d) for d in WIDE_DEPTHS)
+PIX_I410, PIX_I412, PIX_I416 = (pix_wide("444", d) for d in WIDE_DEPTHS)
+PIX_GRAY10, PIX_GRAY12, PIX_GRAY16 = (pix_wide("gray", d) for d in WIDE_DEPTHS)
+_WIDE16 = tuple(pix_wide(s, d) for s in WIDE_SUBS for d in WIDE_DEPTHS)
+PIX_LAYOUT_NAMES.update({pix_wide(s, d): {"420": "i0", "422": "i2", "444": "i4", "gray": "gray"}[s] + str(d) for s in WIDE_SUBS for d in WIDE_DEPTHS})
 #: ... its bits 8-11 (the matrix of a YUV layout) and 12-15 (its range); bits 16-31 must be 0
 PIX_MATRICES = ("bt601", "bt709")
 PIX_RANGES = ("limited", "full")
-_YUV420 = (PIX_NV12, PIX_NV21, PIX_I420, PIX_YV12, PIX_P010)
+_YUV420 = (PIX_NV12, PIX_NV21, PIX_I420, PIX_YV12, PIX_P010, PIX_I010, PIX_I012, PIX_I016)
 _YUV422 = (PIX_YUYV, PIX_UYVY)
 _PLANAR = (PIX_RGBP, PIX_BGRP, PIX_I444, PIX_I422)
 _PLANAR_YUV = (PIX_I444, PIX_I422)
+_WIDE422 = (PIX_YV16, PIX_NV16, PIX_P210, PIX_I210, PIX_I212, PIX_I216)
+_WIDE444 = (PIX_YV24, PIX_NV24, PIX_P410, PIX_I410, PIX_I412, PIX_I416)
+_WIDE_GRAY = (PIX_GRAY10, PIX_GRAY12, PIX_GRAY16)
+_WIDE = (PIX_YV16, PIX_YV24, PIX_NV16, PIX_NV24, PIX_P210, PIX_P410) + _WIDE16
+_WIDE_PAIRS = (PIX_NV16, PIX_NV24, PIX_P210, PIX_P410)                            # plane 1 holds (U, V) pairs, H rows
+_WIDE_WORDS = (PIX_P210, PIX_P410) + _WIDE16                                      # two bytes a sample
+_WIDE_LSB = tuple(c for c in _WIDE16 if c & 3 != 2)                               # fetched as aligned 16-bit loads: even addresses and pitches
 
 
 def pix_format(layout: int, matrix: str = "bt601", range: str = "limited") -> int:      # noqa: A002  (the keyword the constructors take)
@@ -326,6 +356,11 @@ def pix_name(fmt: int) -> str:
 def _row_bytes(fmt: int, W: int):
     """Bytes of one row of plane 0 and of plane 1 (0: no plane 1)."""
     lay = fmt & 0xff
+    if lay in _WIDE:      # chroma samples a row: W (4:4:4) or W / 2; twice as many in a plane of pairs; bytes doubled in 16-bit words
+        b = 2 if lay in _WIDE_WORDS else 1
+        if lay in _WIDE_GRAY:
+            return b * W, 0
+        return b * W, b * (W if lay in _WIDE444 else W // 2) * (2 if lay in _WIDE_PAIRS else 1)
     if lay in (PIX_NV12, PIX_NV21):
         return W, W
     if lay == PIX_P010:
@@ -345,7 +380,14 @@ def _plane1_rows(fmt: int, H: int) -> int:
     """Rows of plane 1: H / 2, or H for I420 / YV12 (its two chroma planes of H / 2 rows lie back to back at one pitch), or 2 H for
     the planar layouts (two planes of H rows back to back)."""
     lay = fmt & 0xff
+    if lay in _WIDE:      # planes of pairs: H rows; three-plane layouts: both chroma planes, of H / 2 rows (4:2:0) or H rows each
+        return H if lay in _WIDE_PAIRS else (H if lay in _YUV420 else 2 * H)
     return 2 * H if lay in _PLANAR else (H if lay in (PIX_I420, PIX_YV12) else H // 2)
+
+
+def _chroma_rows(fmt: int, H: int) -> int:
+    """Rows of ONE chroma plane (the trailing plane begins pitch1 times this many bytes after plane 1)."""
+    return H // 2 if fmt & 0xff in _YUV420 else H
 
 
 class Image:
@@ -358,7 +400,10 @@ class Image:
     .i420_buffer(buf) for planar 4:2:0, .yuyv(a) / .uyvy(a) for (H, W, 2) packed 4:2:2.  Every YUV constructor takes
     matrix="bt601" | "bt709" and range="limited" | "full" (default: BT.601 limited).  Planar frames: .chw(t) for a (3, H, W) array or
     tensor (images_from_chw(batch) for a (B, 3, H, W) one), .rgb_planar(r, g, b) / .bgr_planar(b, g, r), .i444(y, u, v) / .i422(y, u, v)
-    for three planes that lie back to back; they are read as single bytes and need no alignment."""
+    for three planes that lie back to back; they are read as single bytes and need no alignment.  The wide layouts: .yv16(y, v, u) /
+    .yv24(y, v, u), .nv16(y, uv) / .nv24(y, uv) with (H, W/2, 2) / (H, W, 2) pairs, .p210(y, uv) / .p410(y, uv) for those in MSB-aligned
+    16-bit samples, .yuv16(y, u, v, depth=10 | 12 | 16, sub="420" | "422" | "444") for ffmpeg's yuv4xxpNNle (.i010: yuv420p10le) and
+    .gray16(a, depth=) for grayNNle; 16-bit planes are uint16 / int16 arrays or tensors, or their uint8 views."""
 
     __slots__ = ("format", "planes", "H", "W", "pitches")
 
@@ -453,22 +498,22 @@ class Image:
         return cls._yuv(pix_format(PIX_NV21, matrix, range), y, vu)
 
     @staticmethod
-    def _bytes16(a, what):
+    def _bytes16(a, what, name="P010"):
         """A 16-bit plane as bytes (last axis doubled): uint16 / int16 numpy arrays and tensors, or their uint8 views as they are."""
         import torch
         if isinstance(a, np.ndarray):
             if a.dtype == np.uint8:
                 return a
             if a.dtype.kind not in "ui" or a.dtype.itemsize != 2 or a.dtype.byteorder == ">":
-                raise VtError(f"P010 {what} must be little-endian 16-bit samples or their uint8 view, got {a.dtype}")
+                raise VtError(f"{name} {what} must be little-endian 16-bit samples or their uint8 view, got {a.dtype}")
             if a.ndim == 0 or a.strides[-1] != 2:
-                raise VtError(f"P010 {what} strides {a.strides}: samples must be contiguous")
+                raise VtError(f"{name} {what} strides {a.strides}: samples must be contiguous")
             return a.view(np.uint8)      # the last axis doubled; rows keep their stride
         if isinstance(a, torch.Tensor):
             if a.dtype == torch.uint8:
                 return a
             if a.dtype not in (torch.int16, torch.uint16) or (a.dim() and a.shape[-1] > 1 and a.stride(-1) != 1):
-                raise VtError(f"P010 {what} must be contiguous 16-bit samples or their uint8 view, got {a.dtype}")
+                raise VtError(f"{name} {what} must be contiguous 16-bit samples or their uint8 view, got {a.dtype}")
             return a.view(torch.uint8)
         raise VtError(f"image planes must be numpy arrays or GPU tensors, got {type(a).__name__}")
 
@@ -559,40 +604,135 @@ class Image:
         return int(a.data_ptr()) if hasattr(a, "data_ptr") else int(a.__array_interface__["data"][0])
 
     @classmethod
-    def _planar3(cls, fmt, p0, p1, p2):
-        """Three full-height planes of single bytes (RGBP / BGRP, I444, I422: chroma planes of W / 2 columns).  The descriptor has two
-        plane pointers and two pitches: the trailing planes must share one row pitch and the third must begin pitch1 * H bytes after
-        the second.  Planes that lie otherwise raise; nothing is copied here."""
+    def _planar3(cls, fmt, p0, p1, p2, spp=1):
+        """Three planes of single bytes (RGBP / BGRP, I444, I422 / YV16: chroma planes of W / 2 columns) or, spp = 2, of 16-bit samples
+        given as bytes (the planar 16-bit layouts; 4:2:0: chroma planes of H / 2 rows).  The descriptor has two plane pointers and two
+        pitches: the trailing planes must share one row pitch and the third must begin pitch1 * (its rows) bytes after the second.
+        Planes that lie otherwise raise; nothing is copied here."""
         lay = fmt & 0xff
         name = pix_name(fmt)
+        half = lay in (PIX_I422,) + _WIDE422 + _YUV420      # chroma planes of W / 2 columns
         s0, t0, g0 = cls._strides(p0)
-        if len(s0) != 2 or s0[0] < 1 or s0[1] < 1 or (lay == PIX_I422 and s0[1] % 2):
-            raise VtError(f"the first plane of an {name} image must be (H, W){' with W even' if lay == PIX_I422 else ''}, got {tuple(s0)}")
+        if len(s0) == 2 and s0[1] % spp == 0:
+            s0 = (s0[0], s0[1] // spp)
+        if len(s0) != 2 or s0[0] < 1 or s0[1] < 1 or (half and s0[1] % 2) or (lay in _YUV420 and s0[0] % 2):
+            raise VtError(f"the first plane of an {name} image must be (H, W){' with W even' if half else ''}"
+                          f"{' and H even' if lay in _YUV420 else ''}, got {tuple(s0)}")
         H, W = int(s0[0]), int(s0[1])
-        if (W > 1 and t0[1] != 1) or (H > 1 and t0[0] < W):
-            raise VtError(f"{name} plane 0 strides {tuple(t0)}: pixels must be contiguous bytes, rows at least W apart")
-        cw = W // 2 if lay == PIX_I422 else W
+        if (W * spp > 1 and t0[1] != 1) or (H > 1 and t0[0] < W * spp):
+            raise VtError(f"{name} plane 0 strides {tuple(t0)}: pixels must be contiguous bytes, rows at least {'2 ' if spp == 2 else ''}W apart")
+        cw, ch = (W // 2 if half else W) * spp, _chroma_rows(fmt, H)
         pitch1 = None
         for c in (p1, p2):
             sc, tc, gc = cls._strides(c)
-            if tuple(sc) != (H, cw):
-                raise VtError(f"the trailing planes of an {name} image must be {(H, cw)}, got {tuple(sc)}")
+            if tuple(sc) != (ch, cw):
+                raise VtError(f"the trailing planes of an {name} image must be {(ch, cw // spp)}, got "
+                              f"{(sc[0], sc[1] // spp) if len(sc) == 2 else tuple(sc)}")
             if gc != g0:
                 raise VtError(f"the planes of an {name} image must all be on the GPU or all on the host")
-            if (cw > 1 and tc[1] != 1) or (H > 1 and tc[0] < cw):
+            if (cw > 1 and tc[1] != 1) or (ch > 1 and tc[0] < cw):
                 raise VtError(f"{name} plane strides {tuple(tc)}: pixels must be contiguous bytes, rows at least {cw} apart")
-            q = tc[0] if H > 1 else None
+            q = tc[0] if ch > 1 else None
             if pitch1 is not None and q is not None and q != pitch1:
                 raise VtError(f"the two trailing planes of an {name} image must have one row pitch, got {pitch1} and {q}")
             pitch1 = q if q is not None else pitch1
         gap = cls._address(p2) - cls._address(p1)
         if pitch1 is None:      # one row: the pitch is what lies between the two planes
             pitch1 = gap
-        if gap != pitch1 * H or pitch1 < cw:
-            raise VtError(f"the trailing planes of an {name} image are not back to back: the third must begin pitch1 * H = "
-                          f"{pitch1 * H} bytes after the second, it begins {gap} bytes after it (the descriptor has one pointer and "
+        if gap != pitch1 * ch or pitch1 < cw:
+            raise VtError(f"the trailing planes of an {name} image are not back to back: the third must begin pitch1 * {'H/2' if ch != H else 'H'} = "
+                          f"{pitch1 * ch} bytes after the second, it begins {gap} bytes after it (the descriptor has one pointer and "
                           f"one pitch for both); put them into one buffer, e.g. a (3, H, W) array for Image.chw")
-        return cls(fmt, (p0, p1, p2), H, W, (t0[0] if H > 1 else W, pitch1))
+        return cls(fmt, (p0, p1, p2), H, W, (t0[0] if H > 1 else W * spp, pitch1))
+
+    @classmethod
+    def _pairs(cls, fmt, y, c, spp=1):
+        """Two planes at full height: luma (H, W) and (U, V) pairs (H, W/2, 2) (4:2:2) or (H, W, 2) (4:4:4), in bytes or, spp = 2, in
+        16-bit samples given as bytes."""
+        lay = fmt & 0xff
+        name = pix_name(fmt)
+        half = lay in _WIDE422
+        sy, ty, gy = cls._strides(y)
+        sc, tc, gc = cls._strides(c)
+        if len(sy) == 2 and sy[1] % spp == 0:
+            sy = (sy[0], sy[1] // spp)
+        if len(sy) != 2 or sy[0] < 1 or sy[1] < 1 or (half and sy[1] % 2):
+            raise VtError(f"an {name} luma plane must be (H, W){' with W even' if half else ''}, got {tuple(sy)}")
+        H, W = int(sy[0]), int(sy[1])
+        cw = W // 2 if half else W
+        if tuple(sc) != (H, cw, 2 * spp):
+            raise VtError(f"an {name} chroma plane must be {(H, cw, 2)}, got {(sc[0], sc[1], sc[2] // spp) if len(sc) == 3 else tuple(sc)}")
+        if gy != gc:
+            raise VtError(f"the two planes of an {name} image must both be on the GPU or both on the host")
+        if (W * spp > 1 and ty[1] != 1) or (H > 1 and ty[0] < W * spp):
+            raise VtError(f"{name} luma strides {tuple(ty)}: pixels must be contiguous bytes, rows at least {'2 ' if spp == 2 else ''}W apart")
+        if tc[2] != 1 or (cw > 1 and tc[1] != 2 * spp) or (H > 1 and tc[0] < 2 * spp * cw):
+            raise VtError(f"{name} chroma strides {tuple(tc)}: pairs must be contiguous bytes, rows at least {2 * spp * cw} bytes apart")
+        return cls(fmt, (y, c), H, W, (ty[0] if H > 1 else W * spp, tc[0] if H > 1 else 2 * spp * cw))
+
+    @classmethod
+    def yv16(cls, y, v, u, matrix="bt601", range="limited"):      # noqa: A002
+        """YV16: I422 with the V plane first; U begins pitch1 * H bytes after V."""
+        return cls._planar3(pix_format(PIX_YV16, matrix, range), y, v, u)
+
+    @classmethod
+    def yv24(cls, y, v, u, matrix="bt601", range="limited"):      # noqa: A002
+        """YV24: I444 with the V plane first."""
+        return cls._planar3(pix_format(PIX_YV24, matrix, range), y, v, u)
+
+    @classmethod
+    def nv16(cls, y, uv, matrix="bt601", range="limited"):      # noqa: A002
+        """Two-plane 4:2:2 as capture cards produce it: luma (H, W) and (U, V) pairs (H, W/2, 2); W even."""
+        return cls._pairs(pix_format(PIX_NV16, matrix, range), y, uv)
+
+    @classmethod
+    def nv24(cls, y, uv, matrix="bt601", range="limited"):      # noqa: A002
+        """Two-plane 4:4:4: luma (H, W) and (U, V) pairs (H, W, 2)."""
+        return cls._pairs(pix_format(PIX_NV24, matrix, range), y, uv)
+
+    @classmethod
+    def p210(cls, y, uv, matrix="bt601", range="limited"):      # noqa: A002
+        """A hardware decoder's P210 surface (a P216 one is read the same way): NV16 in little-endian 16-bit samples, as uint16 /
+        int16 arrays or tensors (H, W) and (H, W/2, 2), or their uint8 views.  The 8-bit sample is the high byte of each word."""
+        return cls._pairs(pix_format(PIX_P210, matrix, range), cls._bytes16(y, "luma", "P210"), cls._bytes16(uv, "chroma", "P210"), spp=2)
+
+    @classmethod
+    def p410(cls, y, uv, matrix="bt601", range="limited"):      # noqa: A002
+        """P410 / P416: NV24 in little-endian 16-bit samples, (H, W) and (H, W, 2); the high byte of each word."""
+        return cls._pairs(pix_format(PIX_P410, matrix, range), cls._bytes16(y, "luma", "P410"), cls._bytes16(uv, "chroma", "P410"), spp=2)
+
+    @classmethod
+    def yuv16(cls, y, u, v, depth=10, sub="420", matrix="bt601", range="limited"):      # noqa: A002
+        """Planar YUV in LSB-aligned little-endian 16-bit samples (ffmpeg's yuv420p10le ... yuv444p16le): depth 10 | 12 | 16, sub "420"
+        | "422" | "444"; luma (H, W), U and V (H/2, W/2), (H, W/2) or (H, W) as uint16 / int16 arrays or tensors, or their uint8 views
+        (last axis doubled).  The 8-bit sample is min(word >> (depth - 8), 255).  V must begin pitch1 * (chroma rows) bytes after U;
+        10- and 12-bit planes must lie at even addresses and even pitches (they are fetched as 16-bit words)."""
+        if sub not in WIDE_SUBS[:3]:
+            raise VtError(f"sub must be one of {WIDE_SUBS[:3]}, got {sub!r}")
+        lay = pix_wide(sub, depth)
+        name = pix_name(lay)
+        return cls._planar3(pix_format(lay, matrix, range), cls._bytes16(y, "luma", name), cls._bytes16(u, "chroma", name),
+                            cls._bytes16(v, "chroma", name), spp=2)
+
+    @classmethod
+    def i010(cls, y, u, v, matrix="bt601", range="limited"):      # noqa: A002
+        """yuv420p10le, what software HEVC Main10 / AV1 10-bit decoders produce: Image.yuv16(y, u, v, depth=10, sub="420")."""
+        return cls.yuv16(y, u, v, 10, "420", matrix, range)
+
+    @classmethod
+    def gray16(cls, a, depth=16):
+        """A grey frame in LSB-aligned little-endian 16-bit samples (gray10le / gray12le / gray16le; thermal and scientific cameras),
+        (H, W) uint16 / int16 or its uint8 view (H, 2 W): rgb = (s, s, s) with s = min(word >> (depth - 8), 255)."""
+        lay = pix_wide("gray", depth)
+        name = pix_name(lay)
+        ab = cls._bytes16(a, "plane", name)
+        shape, st, _ = cls._strides(ab)
+        if len(shape) != 2 or shape[0] < 1 or shape[1] < 2 or shape[1] % 2:
+            raise VtError(f"a {name} image must be (H, W) 16-bit samples, got {tuple(getattr(a, 'shape', ()))}")
+        H, W = int(shape[0]), int(shape[1]) // 2
+        if st[1] != 1 or (H > 1 and st[0] < 2 * W):
+            raise VtError(f"{name} strides {tuple(st)}: samples must be contiguous, rows at least 2 W bytes apart")
+        return cls(lay, (ab,), H, W, (st[0] if H > 1 else 2 * W,))
 
     @classmethod
     def rgb_planar(cls, r, g, b):
@@ -701,7 +841,7 @@ class ImageTable(_DescriptorTable):
             raise VtError(f"unknown pixel format {fmt}")
         if high or mat >= len(PIX_MATRICES) or rng >= len(PIX_RANGES):
             raise VtError(f"unknown pixel format {fmt:#x}: matrix {mat}, range {rng}, bits 16-31 {high:#x}")
-        if (mat or rng) and lay not in _YUV420 + _YUV422 + _PLANAR_YUV:
+        if (mat or rng) and (lay not in _YUV420 + _YUV422 + _PLANAR_YUV + _WIDE or lay in _WIDE_GRAY):
             raise VtError(f"a {pix_name(fmt)} image takes no matrix or range bits, got format {fmt:#x}")
         if int(reserved) != 0:
             raise VtError("vt_image.reserved must be 0")
@@ -709,7 +849,7 @@ class ImageTable(_DescriptorTable):
             raise VtError(f"image of {H}x{W} pixels: H and W must be >= 1")
         if lay in _YUV420 and (H % 2 or W % 2):
             raise VtError(f"an {pix_name(fmt)} image must have even H and W, got {H}x{W}")
-        if lay in _YUV422 + (PIX_I422,) and W % 2:
+        if lay in _YUV422 + (PIX_I422,) + _WIDE422 and W % 2:
             raise VtError(f"a {pix_name(fmt)} image must have even W, got {H}x{W}")
         r0, r1 = _row_bytes(fmt, W)
         planes = [(ptr0, pitch0, H, r0, nbytes0)] + ([(ptr1, pitch1, _plane1_rows(fmt, H), r1, nbytes1)] if r1 else [])
@@ -718,8 +858,11 @@ class ImageTable(_DescriptorTable):
             pitch = pitch or rb
             if pitch < rb:
                 raise VtError(f"plane {k}: row pitch {pitch} is shorter than a row ({rb} bytes)")
-            if not ptr or (int(ptr) % 4 and lay not in _PLANAR):      # the planar layouts are read as single bytes: any address
+            if not ptr or (int(ptr) % 4 and lay not in _PLANAR + _WIDE):      # the planar and wide layouts are read as single bytes: any address
                 raise VtError(f"plane {k}: address {int(ptr or 0):#x} is null or not 4-byte aligned")
+            if lay in _WIDE_LSB and (int(ptr) % 2 or pitch % 2):      # ... but for 10- and 12-bit words, fetched as aligned 16-bit loads
+                raise VtError(f"plane {k}: address {int(ptr):#x} or row pitch {pitch} is odd; the 16-bit samples of a {pix_name(fmt)} image "
+                              f"must be 2-byte aligned")
             need = pitch * (rows - 1) + rb
             if pitch > 0xfffffff0 or need > 0xfffffff0:
                 raise VtError(f"plane {k}: {need} bytes are beyond the 32-bit offsets of the crop kernels")
