@@ -195,17 +195,15 @@ class BatchedVitTracker:
         it = iter(offs)
         for i, im in enumerate(ims):
             if im.is_cuda:
-                d = im.descriptor()
+                d, room = im.descriptor(), (None, None)
             else:
                 po = next(it)
                 rows = im.plane_rows()
                 for a, o, (n, rb) in zip(im.host_planes(), po, rows):
                     ar.np[o:o + n * rb].reshape(n, rb)[...] = np.asarray(a).reshape(n, rb)
                 d = im.descriptor([base + o for o in po], [rb for _, rb in rows])
-                ImageTable.check(d[6], d[0], d[1], d[4], d[5], d[2], d[3], 0, nbytes0=ar.cap - po[0],
-                                 nbytes1=ar.cap - po[1] if len(po) > 1 else None)
-            if im.is_cuda:
-                ImageTable.check(d[6], d[0], d[1], d[4], d[5], d[2], d[3])
+                room = (ar.cap - po[0], ar.cap - po[1] if len(po) > 1 else None)
+            ImageTable.check_descriptor(d, *room)
             tab[i] = d
         return ar.flush(end)[:tb]
 

@@ -13,16 +13,20 @@ import weakref
 
 import numpy as np
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
+# the pixel formats of the image route live in pixfmt.py (no ctypes, no library); every public name of theirs is re-exported here
+from .pixfmt import (ARENA_ALIGN, IMAGE_DTYPE, LAYOUTS, PIX_BGR, PIX_BGRA, PIX_BGRP, PIX_GRAY8, PIX_GRAY10, PIX_GRAY12,  # noqa: F401
+                     PIX_GRAY16, PIX_I010, PIX_I012, PIX_I016, PIX_I210, PIX_I212, PIX_I216, PIX_I410, PIX_I412, PIX_I416, PIX_I420,
+                     PIX_I422, PIX_I444, PIX_LAYOUT_NAMES, PIX_MATRICES, PIX_NAMES, PIX_NV12, PIX_NV16, PIX_NV21, PIX_NV24, PIX_P010,
+                     PIX_P210, PIX_P410, PIX_RANGES, PIX_RGB, PIX_RGBA, PIX_RGBP, PIX_UYVY, PIX_YUYV, PIX_YV12, PIX_YV16, PIX_YV24,
+                     WIDE_DEPTHS, WIDE_SUBS, Image, Layout, VtError, check_image, images_from_chw, pack_image_offsets, pack_planes,
+                     pix_fields, pix_format, pix_name, pix_wide)
+
+_HERE =os.path.dirname(os.path.abspath(__file__))
 #: VITTRACK_LIB=<path> selects another build of the fp32 library (A/B tools: tools/ab_stages.py, tools/block_stamps.py)
 LIB_PATH = os.environ.get("VITTRACK_LIB") or os.path.join(_HERE, "csrc", "libvittrack_hip.so")
 #: the same sources built with every vit_48 contraction on f16 MFMA (BASELINE config 5; make -C csrc all)
 LIB_PATH_F16 = os.path.join(_HERE, "csrc", "libvittrack_hip_f16.so")
 PRECISIONS = ("f32", "f16")
-
-
-class VtError(RuntimeError):
-    pass
 
 
 class VtConfig(C.Structure):
@@ -148,22 +152,6 @@ def _stream(stream):
 #: struct vt_frame (include/vittrack.h): {const uint8_t* data; int32_t H, W; int64_t pitch;}, 24 bytes
 FRAME_DTYPE = np.dtype([("data", "<u8"), ("H", "<i4"), ("W", "<i4"), ("pitch", "<i8")])
 assert FRAME_DTYPE.itemsize == 24
-#: frames packed into one arena start at multiples of this many bytes (vt_frame wants 4; 256 keeps every frame on its own cache lines)
-ARENA_ALIGN = 256
-
-
-def pack_planes(sizes, start: int = 0, align: int = ARENA_ALIGN):
-    """Byte offsets of items packed one after the other from `start`, every plane of every item at a multiple of `align`.  sizes: per
-    item the byte counts of its planes.  Returns ([per item: [plane offsets]], end)."""
-    out, o = [], int(start)
-    for planes in sizes:
-        offs = []
-        for n in planes:
-            o = -(-o // align) * align
-            offs.append(o)
-            o += int(n)
-        out.append(offs)
-    return out, o
 
 
 def pack_offsets(shapes, start: int = 0, align: int = ARENA_ALIGN):
@@ -278,550 +266,6 @@ class FrameTable(_DescriptorTable):
         return [(int(h), int(w)) for h, w in zip(self.host["H"], self.host["W"])]
 
 
-# ---- pixel formats (vt_crop_images & co.) -----------------------------------------------------------------------------------
-#: vt_image.format (include/vittrack.h)
-PIX_RGB, PIX_BGR, PIX_RGBA, PIX_BGRA, PIX_NV12, PIX_NV21 = range(6)
-PIX_NAMES = ("rgb", "bgr", "rgba", "bgra", "nv12", "nv21")
-#: struct vt_image (include/vittrack.h): {const uint8_t *plane0, *plane1; int64_t pitch0, pitch1; int32_t H, W, format, reserved;}
-IMAGE_DTYPE = np.dtype([("plane0", "<u8"), ("plane1", "<u8"), ("pitch0", "<i8"), ("pitch1", "<i8"), ("H", "<i4"), ("W", "<i4"),
-                        ("format", "<i4"), ("reserved", "<i4")])
-assert IMAGE_DTYPE.itemsize == 48
-
-
-#: the layouts added to bits 0-7 of vt_image.format (6 and 7 are never assigned) ...
-PIX_I420, PIX_YV12, PIX_YUYV, PIX_UYVY, PIX_P010, PIX_GRAY8 = range(8, 14)
-PIX_LAYOUT_NAMES = dict(enumerate(PIX_NAMES))
-PIX_LAYOUT_NAMES.update({PIX_I420: "i420", PIX_YV12: "yv12", PIX_YUYV: "yuyv", PIX_UYVY: "uyvy", PIX_P010: "p010", PIX_GRAY8: "gray8"})
-#: ... the planar layouts (14 and 15 are never assigned): three full-height planes of single bytes, no alignment rule ...
-PIX_RGBP, PIX_BGRP, PIX_I444, PIX_I422 = range(16, 20)
-PIX_LAYOUT_NAMES.update({PIX_RGBP: "rgbp", PIX_BGRP: "bgrp", PIX_I444: "i444", PIX_I422: "i422"})
-#: ... the V-first planar and the two-plane 4:2:2 / 4:4:4 layouts in bytes, the two-plane ones in MSB-aligned 16-bit words (20 and 27-31
-#: are never assigned) ...
-PIX_YV16, PIX_YV24, PIX_NV16, PIX_NV24, PIX_P210, PIX_P410 = range(21, 27)
-PIX_LAYOUT_NAMES.update({PIX_YV16: "yv16", PIX_YV24: "yv24", PIX_NV16: "nv16", PIX_NV24: "nv24", PIX_P210: "p210", PIX_P410: "p410"})
-#: ... the planar layouts in LSB-aligned little-endian 16-bit words, 32 | sub << 2 | dep: sub 0 / 1 / 2 / 3 = 4:2:0 / 4:2:2 / 4:4:4 / luma
-#: only, dep 0 / 1 / 2 = 10 / 12 / 16 bits (dep 3 and everything above 46 are never assigned) ...
-WIDE_SUBS = ("420", "422", "444", "gray")
-WIDE_DEPTHS = (10, 12, 16)
-
-
-def pix_wide(sub: str, depth: int) -> int:
-    """The layout code of a planar 16-bit layout: sub "420" | "422" | "444" | "gray", depth 10 | 12 | 16."""
-    if sub not in WIDE_SUBS or depth not in WIDE_DEPTHS:
-        raise VtError(f"a 16-bit planar layout is sub in {WIDE_SUBS} and depth in {WIDE_DEPTHS}, got {sub!r}, {depth!r}")
-    return 32 | WIDE_SUBS.index(sub) << 2 | WIDE_DEPTHS.index(depth)
-
-
-PIX_I010, PIX_I012, PIX_I016 = (pix_wide("420", d) for d in WIDE_DEPTHS)
-PIX_I210, PIX_I212, PIX_I216 = (pix_wide("422", d) for d in WIDE_DEPTHS)
-PIX_I410, PIX_I412, PIX_I416 = (pix_wide("444", d) for d in WIDE_DEPTHS)
-PIX_GRAY10, PIX_GRAY12, PIX_GRAY16 = (pix_wide("gray", d) for d in WIDE_DEPTHS)
-_WIDE16 = tuple(pix_wide(s, d) for s in WIDE_SUBS for d in WIDE_DEPTHS)
-PIX_LAYOUT_NAMES.update({pix_wide(s, d): {"420": "i0", "422": "i2", "444": "i4", "gray": "gray"}[s] + str(d) for s in WIDE_SUBS for d in WIDE_DEPTHS})
-#: ... its bits 8-11 (the matrix of a YUV layout) and 12-15 (its range); bits 16-31 must be 0
-PIX_MATRICES = ("bt601", "bt709")
-PIX_RANGES = ("limited", "full")
-_YUV420 = (PIX_NV12, PIX_NV21, PIX_I420, PIX_YV12, PIX_P010, PIX_I010, PIX_I012, PIX_I016)
-_YUV422 = (PIX_YUYV, PIX_UYVY)
-_PLANAR = (PIX_RGBP, PIX_BGRP, PIX_I444, PIX_I422)
-_PLANAR_YUV = (PIX_I444, PIX_I422)
-_WIDE422 = (PIX_YV16, PIX_NV16, PIX_P210, PIX_I210, PIX_I212, PIX_I216)
-_WIDE444 = (PIX_YV24, PIX_NV24, PIX_P410, PIX_I410, PIX_I412, PIX_I416)
-_WIDE_GRAY = (PIX_GRAY10, PIX_GRAY12, PIX_GRAY16)
-_WIDE = (PIX_YV16, PIX_YV24, PIX_NV16, PIX_NV24, PIX_P210, PIX_P410) + _WIDE16
-_WIDE_PAIRS = (PIX_NV16, PIX_NV24, PIX_P210, PIX_P410)                            # plane 1 holds (U, V) pairs, H rows
-_WIDE_WORDS = (PIX_P210, PIX_P410) + _WIDE16                                      # two bytes a sample
-_WIDE_LSB = tuple(c for c in _WIDE16 if c & 3 != 2)                               # fetched as aligned 16-bit loads: even addresses and pitches
-
-
-def pix_format(layout: int, matrix: str = "bt601", range: str = "limited") -> int:      # noqa: A002  (the keyword the constructors take)
-    """The vt_image.format word of a layout and its colour tags."""
-    if matrix not in PIX_MATRICES:
-        raise VtError(f"matrix must be one of {PIX_MATRICES}, got {matrix!r}")
-    if range not in PIX_RANGES:
-        raise VtError(f"range must be one of {PIX_RANGES}, got {range!r}")
-    return int(layout) | (PIX_MATRICES.index(matrix) << 8) | (PIX_RANGES.index(range) << 12)
-
-
-def pix_fields(fmt: int):
-    """(layout, matrix bits, range bits, bits 16-31) of a format word."""
-    fmt = int(fmt) & 0xffffffff
-    return fmt & 0xff, (fmt >> 8) & 0xf, (fmt >> 12) & 0xf, fmt >> 16
-
-
-def pix_name(fmt: int) -> str:
-    return PIX_LAYOUT_NAMES.get(int(fmt) & 0xff, f"format {int(fmt)}").upper()
-
-
-def _row_bytes(fmt: int, W: int):
-    """Bytes of one row of plane 0 and of plane 1 (0: no plane 1)."""
-    lay = fmt & 0xff
-    if lay in _WIDE:      # chroma samples a row: W (4:4:4) or W / 2; twice as many in a plane of pairs; bytes doubled in 16-bit words
-        b = 2 if lay in _WIDE_WORDS else 1
-        if lay in _WIDE_GRAY:
-            return b * W, 0
-        return b * W, b * (W if lay in _WIDE444 else W // 2) * (2 if lay in _WIDE_PAIRS else 1)
-    if lay in (PIX_NV12, PIX_NV21):
-        return W, W
-    if lay == PIX_P010:
-        return 2 * W, 2 * W
-    if lay in (PIX_I420, PIX_YV12):
-        return W, W // 2
-    if lay in _YUV422:
-        return 2 * W, 0
-    if lay == PIX_GRAY8:
-        return W, 0
-    if lay in _PLANAR:
-        return W, (W // 2 if lay == PIX_I422 else W)
-    return (4 if lay in (PIX_RGBA, PIX_BGRA) else 3) * W, 0
-
-
-def _plane1_rows(fmt: int, H: int) -> int:
-    """Rows of plane 1: H / 2, or H for I420 / YV12 (its two chroma planes of H / 2 rows lie back to back at one pitch), or 2 H for
-    the planar layouts (two planes of H rows back to back)."""
-    lay = fmt & 0xff
-    if lay in _WIDE:      # planes of pairs: H rows; three-plane layouts: both chroma planes, of H / 2 rows (4:2:0) or H rows each
-        return H if lay in _WIDE_PAIRS else (H if lay in _YUV420 else 2 * H)
-    return 2 * H if lay in _PLANAR else (H if lay in (PIX_I420, PIX_YV12) else H // 2)
-
-
-def _chroma_rows(fmt: int, H: int) -> int:
-    """Rows of ONE chroma plane (the trailing plane begins pitch1 times this many bytes after plane 1)."""
-    return H // 2 if fmt & 0xff in _YUV420 else H
-
-
-class Image:
-    """One frame in a pixel format the tracker reads directly (vt_image, include/vittrack.h): RGB, BGR, RGBA, BGRA, GRAY8, NV12, NV21,
-    P010 / P016, I420, YV12, YUYV (YUY2), UYVY, planar RGB / BGR (CHW tensors), I444 or I422.
-    Planes are numpy arrays (host: BatchedVitTracker packs them into its pinned arena) or uint8 tensors on the GPU (read in place).
-    Rows may be strided (a pitch wider than the row), pixels may not.  Build one with the constructors: Image.rgb(a), .bgr(a),
-    .rgba(a), .bgra(a) for (H, W, 3 | 4) arrays, .gray(a) for (H, W), .nv12(y, uv) / .nv21(y, vu) for an (H, W) luma plane and an
-    (H/2, W/2, 2) chroma plane (H, W even), .p010(y, uv) for the same shapes in 16-bit samples, .i420(y, u, v) / .yv12(y, v, u) /
-    .i420_buffer(buf) for planar 4:2:0, .yuyv(a) / .uyvy(a) for (H, W, 2) packed 4:2:2.  Every YUV constructor takes
-    matrix="bt601" | "bt709" and range="limited" | "full" (default: BT.601 limited).  Planar frames: .chw(t) for a (3, H, W) array or
-    tensor (images_from_chw(batch) for a (B, 3, H, W) one), .rgb_planar(r, g, b) / .bgr_planar(b, g, r), .i444(y, u, v) / .i422(y, u, v)
-    for three planes that lie back to back; they are read as single bytes and need no alignment.  The wide layouts: .yv16(y, v, u) /
-    .yv24(y, v, u), .nv16(y, uv) / .nv24(y, uv) with (H, W/2, 2) / (H, W, 2) pairs, .p210(y, uv) / .p410(y, uv) for those in MSB-aligned
-    16-bit samples, .yuv16(y, u, v, depth=10 | 12 | 16, sub="420" | "422" | "444") for ffmpeg's yuv4xxpNNle (.i010: yuv420p10le) and
-    .gray16(a, depth=) for grayNNle; 16-bit planes are uint16 / int16 arrays or tensors, or their uint8 views."""
-
-    __slots__ = ("format", "planes", "H", "W", "pitches")
-
-    def __init__(self, fmt: int, planes, H: int, W: int, pitches):
-        self.format, self.planes, self.H, self.W, self.pitches = int(fmt), tuple(planes), int(H), int(W), tuple(int(p) for p in pitches)
-
-    @staticmethod
-    def _strides(a):
-        """(shape, byte strides, on the GPU) of a uint8 numpy array or tensor; anything else raises."""
-        import torch
-        if isinstance(a, torch.Tensor):
-            if a.dtype != torch.uint8:
-                raise VtError(f"image planes must be uint8, got {a.dtype}")
-            if not (a.is_cuda or a.device.type == "cpu"):
-                raise VtError(f"image planes must be numpy arrays or GPU tensors, got a tensor on {a.device}")
-            return tuple(a.shape), tuple(int(v) for v in a.stride()), a.is_cuda
-        if isinstance(a, np.ndarray):
-            if a.dtype != np.uint8:
-                raise VtError(f"image planes must be uint8, got {a.dtype}")
-            return a.shape, a.strides, False
-        raise VtError(f"image planes must be numpy arrays or GPU tensors, got {type(a).__name__}")
-
-    @classmethod
-    def _packed(cls, fmt, a, C_):
-        shape, st, _ = cls._strides(a)
-        name = pix_name(fmt)
-        if len(shape) != 3 or shape[2] != C_ or shape[0] < 1 or shape[1] < 1:
-            raise VtError(f"a {name} image must be (H, W, {C_}), got {tuple(shape)}")
-        H, W = int(shape[0]), int(shape[1])
-        if st[2] != 1 or (W > 1 and st[1] != C_) or (H > 1 and st[0] < C_ * W):
-            raise VtError(f"{name} strides {tuple(st)}: pixels must be {C_} contiguous bytes, rows at least {C_} W apart")
-        return cls(fmt, (a,), H, W, (st[0] if H > 1 else C_ * W,))
-
-    @classmethod
-    def rgb(cls, a):
-        return cls._packed(PIX_RGB, a, 3)
-
-    @classmethod
-    def bgr(cls, a):
-        """A BGR frame as OpenCV hands it out (cv.imread, cv.VideoCapture)."""
-        return cls._packed(PIX_BGR, a, 3)
-
-    @classmethod
-    def rgba(cls, a):
-        return cls._packed(PIX_RGBA, a, 4)
-
-    @classmethod
-    def bgra(cls, a):
-        return cls._packed(PIX_BGRA, a, 4)
-
-    @classmethod
-    def gray(cls, a):
-        """An 8-bit grey frame (thermal / IR cameras), (H, W): rgb = (Y, Y, Y), no conversion."""
-        shape, st, _ = cls._strides(a)
-        if len(shape) != 2 or shape[0] < 1 or shape[1] < 1:
-            raise VtError(f"a GRAY8 image must be (H, W), got {tuple(shape)}")
-        H, W = int(shape[0]), int(shape[1])
-        if (W > 1 and st[1] != 1) or (H > 1 and st[0] < W):
-            raise VtError(f"GRAY8 strides {tuple(st)}: pixels must be contiguous bytes, rows at least W apart")
-        return cls(PIX_GRAY8, (a,), H, W, (st[0] if H > 1 else W,))
-
-    @classmethod
-    def _yuv(cls, fmt, y, c, spp=1):
-        """Two-plane 4:2:0: luma (H, W * spp) bytes and chroma pairs (H/2, W/2, 2 * spp) bytes; spp: bytes per sample."""
-        sy, ty, gy = cls._strides(y)
-        sc, tc, gc = cls._strides(c)
-        name = pix_name(fmt)
-        if len(sy) != 2 or sy[1] % spp:
-            raise VtError(f"an {name} luma plane must be (H, W) with H and W even, got {tuple(sy)}")
-        sy = (sy[0], sy[1] // spp)
-        if sy[0] < 2 or sy[1] < 2 or sy[0] % 2 or sy[1] % 2:
-            raise VtError(f"an {name} luma plane must be (H, W) with H and W even, got {tuple(sy)}")
-        H, W = int(sy[0]), int(sy[1])
-        if tuple(sc) != (H // 2, W // 2, 2 * spp):
-            raise VtError(f"an {name} chroma plane must be (H/2, W/2, 2) = {(H // 2, W // 2, 2)}, got {(sc[0], sc[1], sc[2] // spp) if len(sc) == 3 else tuple(sc)}")
-        if gy != gc:
-            raise VtError(f"the two planes of an {name} image must both be on the GPU or both on the host")
-        if ty[1] != 1 or ty[0] < W * spp:
-            raise VtError(f"{name} luma strides {tuple(ty)}: pixels must be contiguous bytes, rows at least {'2 ' if spp == 2 else ''}W apart")
-        if tc[2] != 1 or (W > 2 and tc[1] != 2 * spp) or (H > 2 and tc[0] < W * spp):
-            raise VtError(f"{name} chroma strides {tuple(tc)}: pairs must be contiguous bytes, rows at least {'2 ' if spp == 2 else ''}W apart")
-        return cls(fmt, (y, c), H, W, (ty[0], tc[0] if H > 2 else W * spp))
-
-    @classmethod
-    def nv12(cls, y, uv, matrix="bt601", range="limited"):      # noqa: A002
-        """A decoder's NV12 surface: luma (H, W) and interleaved (U, V) pairs (H/2, W/2, 2)."""
-        return cls._yuv(pix_format(PIX_NV12, matrix, range), y, uv)
-
-    @classmethod
-    def nv21(cls, y, vu, matrix="bt601", range="limited"):      # noqa: A002
-        """NV21: as NV12 with (V, U) pairs."""
-        return cls._yuv(pix_format(PIX_NV21, matrix, range), y, vu)
-
-    @staticmethod
-    def _bytes16(a, what, name="P010"):
-        """A 16-bit plane as bytes (last axis doubled): uint16 / int16 numpy arrays and tensors, or their uint8 views as they are."""
-        import torch
-        if isinstance(a, np.ndarray):
-            if a.dtype == np.uint8:
-                return a
-            if a.dtype.kind not in "ui" or a.dtype.itemsize != 2 or a.dtype.byteorder == ">":
-                raise VtError(f"{name} {what} must be little-endian 16-bit samples or their uint8 view, got {a.dtype}")
-            if a.ndim == 0 or a.strides[-1] != 2:
-                raise VtError(f"{name} {what} strides {a.strides}: samples must be contiguous")
-            return a.view(np.uint8)      # the last axis doubled; rows keep their stride
-        if isinstance(a, torch.Tensor):
-            if a.dtype == torch.uint8:
-                return a
-            if a.dtype not in (torch.int16, torch.uint16) or (a.dim() and a.shape[-1] > 1 and a.stride(-1) != 1):
-                raise VtError(f"{name} {what} must be contiguous 16-bit samples or their uint8 view, got {a.dtype}")
-            return a.view(torch.uint8)
-        raise VtError(f"image planes must be numpy arrays or GPU tensors, got {type(a).__name__}")
-
-    @classmethod
-    def p010(cls, y, uv, matrix="bt601", range="limited"):      # noqa: A002
-        """A 10-bit decoder's P010 surface (a P016 one is read the same way): NV12's layout in little-endian 16-bit samples -- luma
-        (H, W) and (U, V) pairs (H/2, W/2, 2) as uint16 / int16 arrays or tensors, or their uint8 views (H, 2 W) and (H/2, W/2, 4).
-        The 8-bit sample is the high byte of each word."""
-        yb, cb = cls._bytes16(y, "luma"), cls._bytes16(uv, "chroma")
-        return cls._yuv(pix_format(PIX_P010, matrix, range), yb, cb, spp=2)
-
-    @classmethod
-    def _planar(cls, fmt, y, c1, c2):
-        sy, ty, gy = cls._strides(y)
-        name = pix_name(fmt)
-        if len(sy) != 2 or sy[0] < 2 or sy[1] < 2 or sy[0] % 2 or sy[1] % 2:
-            raise VtError(f"an {name} luma plane must be (H, W) with H and W even, got {tuple(sy)}")
-        H, W = int(sy[0]), int(sy[1])
-        if ty[1] != 1 or ty[0] < W:
-            raise VtError(f"{name} luma strides {tuple(ty)}: pixels must be contiguous bytes, rows at least W apart")
-        pitch1 = None
-        for c in (c1, c2):
-            sc, tc, gc = cls._strides(c)
-            if tuple(sc) != (H // 2, W // 2):
-                raise VtError(f"an {name} chroma plane must be (H/2, W/2) = {(H // 2, W // 2)}, got {tuple(sc)}")
-            if gc != gy:
-                raise VtError(f"the planes of an {name} image must all be on the GPU or all on the host")
-            if (W > 2 and tc[1] != 1) or (H > 2 and tc[0] < W // 2):
-                raise VtError(f"{name} chroma strides {tuple(tc)}: pixels must be contiguous bytes, rows at least W/2 apart")
-            q = tc[0] if H > 2 else None
-            if pitch1 is not None and q is not None and q != pitch1:
-                raise VtError(f"the two chroma planes of an {name} image must have one row pitch, got {pitch1} and {q}")
-            pitch1 = q if q is not None else pitch1
-        pitch1 = pitch1 if pitch1 is not None else W // 2
-        if gy and int(c2.data_ptr()) != int(c1.data_ptr()) + pitch1 * (H // 2):
-            # the descriptor has one plane-1 pointer: the second chroma plane is found pitch1 * H/2 bytes after the first
-            raise VtError(f"the chroma planes of a device {name} image are not contiguous: the second must begin pitch1 * H/2 = "
-                          f"{pitch1 * (H // 2)} bytes after the first (one buffer, as Image.i420_buffer takes); copy them into one")
-        return cls(fmt, (y, c1, c2), H, W, (ty[0], pitch1))
-
-    @classmethod
-    def i420(cls, y, u, v, matrix="bt601", range="limited"):      # noqa: A002
-        """Planar 4:2:0 as software decoders produce it (ffmpeg's yuv420p): luma (H, W), U and V (H/2, W/2) each.  On the GPU the V
-        plane must begin pitch1 * H/2 bytes after the U plane; host planes are packed that way into the arena."""
-        return cls._planar(pix_format(PIX_I420, matrix, range), y, u, v)
-
-    @classmethod
-    def yv12(cls, y, v, u, matrix="bt601", range="limited"):      # noqa: A002
-        """YV12: I420 with the V plane first."""
-        return cls._planar(pix_format(PIX_YV12, matrix, range), y, v, u)
-
-    @classmethod
-    def i420_buffer(cls, buf, matrix="bt601", range="limited"):      # noqa: A002
-        """One contiguous I420 buffer as OpenCV (COLOR_YUV2RGB_I420) and av_image_copy_to_buffer lay it out: a (3H/2, W) array of tight
-        rows -- H rows of luma, then the U plane, then the V plane (H/2 rows of W/2 bytes each)."""
-        shape, st, _ = cls._strides(buf)
-        if len(shape) != 2 or shape[0] < 3 or shape[0] % 3 or shape[1] < 2 or shape[1] % 2:
-            raise VtError(f"an I420 buffer must be (3H/2, W) with H and W even, got {tuple(shape)}")
-        H, W = 2 * int(shape[0]) // 3, int(shape[1])
-        if st[1] != 1 or st[0] != W:
-            raise VtError(f"I420 buffer strides {tuple(st)}: rows must be tight (W bytes apart), the chroma planes follow the luma plane")
-        c = buf[H:].reshape(H, W // 2)      # both chroma planes, H / 2 rows each: a view
-        return cls(pix_format(PIX_I420, matrix, range), (buf[:H], c), H, W, (W, W // 2))
-
-    @classmethod
-    def _packed422(cls, fmt, a):
-        shape, st, _ = cls._strides(a)
-        name = pix_name(fmt)
-        if len(shape) != 3 or shape[2] != 2 or shape[0] < 1 or shape[1] < 2 or shape[1] % 2:
-            raise VtError(f"a {name} image must be (H, W, 2) with W even, got {tuple(shape)}")
-        H, W = int(shape[0]), int(shape[1])
-        if st[2] != 1 or st[1] != 2 or (H > 1 and st[0] < 2 * W):
-            raise VtError(f"{name} strides {tuple(st)}: pixels must be 2 contiguous bytes, rows at least 2 W apart")
-        return cls(fmt, (a,), H, W, (st[0] if H > 1 else 2 * W,))
-
-    @classmethod
-    def yuyv(cls, a, matrix="bt601", range="limited"):      # noqa: A002
-        """Packed 4:2:2 as capture cards and webcams produce it (YUY2): (H, W, 2), each 4 bytes Y0 U Y1 V."""
-        return cls._packed422(pix_format(PIX_YUYV, matrix, range), a)
-
-    @classmethod
-    def uyvy(cls, a, matrix="bt601", range="limited"):      # noqa: A002
-        """UYVY: each 4 bytes U Y0 V Y1."""
-        return cls._packed422(pix_format(PIX_UYVY, matrix, range), a)
-
-    @staticmethod
-    def _address(a) -> int:
-        return int(a.data_ptr()) if hasattr(a, "data_ptr") else int(a.__array_interface__["data"][0])
-
-    @classmethod
-    def _planar3(cls, fmt, p0, p1, p2, spp=1):
-        """Three planes of single bytes (RGBP / BGRP, I444, I422 / YV16: chroma planes of W / 2 columns) or, spp = 2, of 16-bit samples
-        given as bytes (the planar 16-bit layouts; 4:2:0: chroma planes of H / 2 rows).  The descriptor has two plane pointers and two
-        pitches: the trailing planes must share one row pitch and the third must begin pitch1 * (its rows) bytes after the second.
-        Planes that lie otherwise raise; nothing is copied here."""
-        lay = fmt & 0xff
-        name = pix_name(fmt)
-        half = lay in (PIX_I422,) + _WIDE422 + _YUV420      # chroma planes of W / 2 columns
-        s0, t0, g0 = cls._strides(p0)
-        if len(s0) == 2 and s0[1] % spp == 0:
-            s0 = (s0[0], s0[1] // spp)
-        if len(s0) != 2 or s0[0] < 1 or s0[1] < 1 or (half and s0[1] % 2) or (lay in _YUV420 and s0[0] % 2):
-            raise VtError(f"the first plane of an {name} image must be (H, W){' with W even' if half else ''}"
-                          f"{' and H even' if lay in _YUV420 else ''}, got {tuple(s0)}")
-        H, W = int(s0[0]), int(s0[1])
-        if (W * spp > 1 and t0[1] != 1) or (H > 1 and t0[0] < W * spp):
-            raise VtError(f"{name} plane 0 strides {tuple(t0)}: pixels must be contiguous bytes, rows at least {'2 ' if spp == 2 else ''}W apart")
-        cw, ch = (W // 2 if half else W) * spp, _chroma_rows(fmt, H)
-        pitch1 = None
-        for c in (p1, p2):
-            sc, tc, gc = cls._strides(c)
-            if tuple(sc) != (ch, cw):
-                raise VtError(f"the trailing planes of an {name} image must be {(ch, cw // spp)}, got "
-                              f"{(sc[0], sc[1] // spp) if len(sc) == 2 else tuple(sc)}")
-            if gc != g0:
-                raise VtError(f"the planes of an {name} image must all be on the GPU or all on the host")
-            if (cw > 1 and tc[1] != 1) or (ch > 1 and tc[0] < cw):
-                raise VtError(f"{name} plane strides {tuple(tc)}: pixels must be contiguous bytes, rows at least {cw} apart")
-            q = tc[0] if ch > 1 else None
-            if pitch1 is not None and q is not None and q != pitch1:
-                raise VtError(f"the two trailing planes of an {name} image must have one row pitch, got {pitch1} and {q}")
-            pitch1 = q if q is not None else pitch1
-        gap = cls._address(p2) - cls._address(p1)
-        if pitch1 is None:      # one row: the pitch is what lies between the two planes
-            pitch1 = gap
-        if gap != pitch1 * ch or pitch1 < cw:
-            raise VtError(f"the trailing planes of an {name} image are not back to back: the third must begin pitch1 * {'H/2' if ch != H else 'H'} = "
-                          f"{pitch1 * ch} bytes after the second, it begins {gap} bytes after it (the descriptor has one pointer and "
-                          f"one pitch for both); put them into one buffer, e.g. a (3, H, W) array for Image.chw")
-        return cls(fmt, (p0, p1, p2), H, W, (t0[0] if H > 1 else W * spp, pitch1))
-
-    @classmethod
-    def _pairs(cls, fmt, y, c, spp=1):
-        """Two planes at full height: luma (H, W) and (U, V) pairs (H, W/2, 2) (4:2:2) or (H, W, 2) (4:4:4), in bytes or, spp = 2, in
-        16-bit samples given as bytes."""
-        lay = fmt & 0xff
-        name = pix_name(fmt)
-        half = lay in _WIDE422
-        sy, ty, gy = cls._strides(y)
-        sc, tc, gc = cls._strides(c)
-        if len(sy) == 2 and sy[1] % spp == 0:
-            sy = (sy[0], sy[1] // spp)
-        if len(sy) != 2 or sy[0] < 1 or sy[1] < 1 or (half and sy[1] % 2):
-            raise VtError(f"an {name} luma plane must be (H, W){' with W even' if half else ''}, got {tuple(sy)}")
-        H, W = int(sy[0]), int(sy[1])
-        cw = W // 2 if half else W
-        if tuple(sc) != (H, cw, 2 * spp):
-            raise VtError(f"an {name} chroma plane must be {(H, cw, 2)}, got {(sc[0], sc[1], sc[2] // spp) if len(sc) == 3 else tuple(sc)}")
-        if gy != gc:
-            raise VtError(f"the two planes of an {name} image must both be on the GPU or both on the host")
-        if (W * spp > 1 and ty[1] != 1) or (H > 1 and ty[0] < W * spp):
-            raise VtError(f"{name} luma strides {tuple(ty)}: pixels must be contiguous bytes, rows at least {'2 ' if spp == 2 else ''}W apart")
-        if tc[2] != 1 or (cw > 1 and tc[1] != 2 * spp) or (H > 1 and tc[0] < 2 * spp * cw):
-            raise VtError(f"{name} chroma strides {tuple(tc)}: pairs must be contiguous bytes, rows at least {2 * spp * cw} bytes apart")
-        return cls(fmt, (y, c), H, W, (ty[0] if H > 1 else W * spp, tc[0] if H > 1 else 2 * spp * cw))
-
-    @classmethod
-    def yv16(cls, y, v, u, matrix="bt601", range="limited"):      # noqa: A002
-        """YV16: I422 with the V plane first; U begins pitch1 * H bytes after V."""
-        return cls._planar3(pix_format(PIX_YV16, matrix, range), y, v, u)
-
-    @classmethod
-    def yv24(cls, y, v, u, matrix="bt601", range="limited"):      # noqa: A002
-        """YV24: I444 with the V plane first."""
-        return cls._planar3(pix_format(PIX_YV24, matrix, range), y, v, u)
-
-    @classmethod
-    def nv16(cls, y, uv, matrix="bt601", range="limited"):      # noqa: A002
-        """Two-plane 4:2:2 as capture cards produce it: luma (H, W) and (U, V) pairs (H, W/2, 2); W even."""
-        return cls._pairs(pix_format(PIX_NV16, matrix, range), y, uv)
-
-    @classmethod
-    def nv24(cls, y, uv, matrix="bt601", range="limited"):      # noqa: A002
-        """Two-plane 4:4:4: luma (H, W) and (U, V) pairs (H, W, 2)."""
-        return cls._pairs(pix_format(PIX_NV24, matrix, range), y, uv)
-
-    @classmethod
-    def p210(cls, y, uv, matrix="bt601", range="limited"):      # noqa: A002
-        """A hardware decoder's P210 surface (a P216 one is read the same way): NV16 in little-endian 16-bit samples, as uint16 /
-        int16 arrays or tensors (H, W) and (H, W/2, 2), or their uint8 views.  The 8-bit sample is the high byte of each word."""
-        return cls._pairs(pix_format(PIX_P210, matrix, range), cls._bytes16(y, "luma", "P210"), cls._bytes16(uv, "chroma", "P210"), spp=2)
-
-    @classmethod
-    def p410(cls, y, uv, matrix="bt601", range="limited"):      # noqa: A002
-        """P410 / P416: NV24 in little-endian 16-bit samples, (H, W) and (H, W, 2); the high byte of each word."""
-        return cls._pairs(pix_format(PIX_P410, matrix, range), cls._bytes16(y, "luma", "P410"), cls._bytes16(uv, "chroma", "P410"), spp=2)
-
-    @classmethod
-    def yuv16(cls, y, u, v, depth=10, sub="420", matrix="bt601", range="limited"):      # noqa: A002
-        """Planar YUV in LSB-aligned little-endian 16-bit samples (ffmpeg's yuv420p10le ... yuv444p16le): depth 10 | 12 | 16, sub "420"
-        | "422" | "444"; luma (H, W), U and V (H/2, W/2), (H, W/2) or (H, W) as uint16 / int16 arrays or tensors, or their uint8 views
-        (last axis doubled).  The 8-bit sample is min(word >> (depth - 8), 255).  V must begin pitch1 * (chroma rows) bytes after U;
-        10- and 12-bit planes must lie at even addresses and even pitches (they are fetched as 16-bit words)."""
-        if sub not in WIDE_SUBS[:3]:
-            raise VtError(f"sub must be one of {WIDE_SUBS[:3]}, got {sub!r}")
-        lay = pix_wide(sub, depth)
-        name = pix_name(lay)
-        return cls._planar3(pix_format(lay, matrix, range), cls._bytes16(y, "luma", name), cls._bytes16(u, "chroma", name),
-                            cls._bytes16(v, "chroma", name), spp=2)
-
-    @classmethod
-    def i010(cls, y, u, v, matrix="bt601", range="limited"):      # noqa: A002
-        """yuv420p10le, what software HEVC Main10 / AV1 10-bit decoders produce: Image.yuv16(y, u, v, depth=10, sub="420")."""
-        return cls.yuv16(y, u, v, 10, "420", matrix, range)
-
-    @classmethod
-    def gray16(cls, a, depth=16):
-        """A grey frame in LSB-aligned little-endian 16-bit samples (gray10le / gray12le / gray16le; thermal and scientific cameras),
-        (H, W) uint16 / int16 or its uint8 view (H, 2 W): rgb = (s, s, s) with s = min(word >> (depth - 8), 255)."""
-        lay = pix_wide("gray", depth)
-        name = pix_name(lay)
-        ab = cls._bytes16(a, "plane", name)
-        shape, st, _ = cls._strides(ab)
-        if len(shape) != 2 or shape[0] < 1 or shape[1] < 2 or shape[1] % 2:
-            raise VtError(f"a {name} image must be (H, W) 16-bit samples, got {tuple(getattr(a, 'shape', ()))}")
-        H, W = int(shape[0]), int(shape[1]) // 2
-        if st[1] != 1 or (H > 1 and st[0] < 2 * W):
-            raise VtError(f"{name} strides {tuple(st)}: samples must be contiguous, rows at least 2 W bytes apart")
-        return cls(lay, (ab,), H, W, (st[0] if H > 1 else 2 * W,))
-
-    @classmethod
-    def rgb_planar(cls, r, g, b):
-        """Planar RGB: three (H, W) planes.  G and B must share one row pitch with B beginning pitch * H bytes after G (the planes of a
-        (3, H, W) array lie so); R may be anywhere."""
-        return cls._planar3(PIX_RGBP, r, g, b)
-
-    @classmethod
-    def bgr_planar(cls, b, g, r):
-        """Planar BGR: as rgb_planar with the B plane first."""
-        return cls._planar3(PIX_BGRP, b, g, r)
-
-    @classmethod
-    def i444(cls, y, u, v, matrix="bt601", range="limited"):      # noqa: A002
-        """Planar 4:4:4 (ffmpeg's yuv444p; screen capture): luma, U and V, (H, W) each; V begins pitch1 * H bytes after U."""
-        return cls._planar3(pix_format(PIX_I444, matrix, range), y, u, v)
-
-    @classmethod
-    def i422(cls, y, u, v, matrix="bt601", range="limited"):      # noqa: A002
-        """Planar 4:2:2 (yuv422p): luma (H, W), U and V (H, W/2) each, W even; V begins pitch1 * H bytes after U."""
-        return cls._planar3(pix_format(PIX_I422, matrix, range), y, u, v)
-
-    @classmethod
-    def chw(cls, t, order="rgb"):
-        """A (3, H, W) uint8 frame as torchvision.io.read_image / decode_jpeg and CHW dataloaders hand it out -- a numpy array, a CPU
-        tensor or a CUDA tensor (read in place) --, with no copy.  The last dimension must be dense; row pitch and plane spacing come
-        from the strides (a contiguous frame, a frame of a contiguous (B, 3, H, W) batch, rows padded to a pitch with planes pitch * H
-        apart).  A view whose strides are those of a permuted (H, W, 3) array is taken as the packed frame it is.  order: "rgb" or
-        "bgr", the meaning of the three planes."""
-        if order not in ("rgb", "bgr"):
-            raise VtError(f"order must be 'rgb' or 'bgr', got {order!r}")
-        shape, st, _ = cls._strides(t)
-        if len(shape) != 3 or shape[0] != 3 or shape[1] < 1 or shape[2] < 1:
-            raise VtError(f"a CHW image must be (3, H, W), got {tuple(shape)}")
-        if st[0] == 1 and st[2] == 3:      # a permuted HWC array: packed pixels
-            hwc = t.permute(1, 2, 0) if hasattr(t, "permute") else t.transpose(1, 2, 0)
-            return cls._packed(PIX_RGB if order == "rgb" else PIX_BGR, hwc, 3)
-        if shape[2] > 1 and st[2] != 1:
-            raise VtError(f"CHW strides {tuple(st)}: the last dimension must be dense (or the view a permuted (H, W, 3) array)")
-        return cls._planar3(PIX_RGBP if order == "rgb" else PIX_BGRP, t[0], t[1], t[2])
-
-    @property
-    def is_cuda(self) -> bool:
-        import torch
-        return isinstance(self.planes[0], torch.Tensor) and self.planes[0].is_cuda
-
-    @property
-    def shape(self):
-        """(H, W, 3): the shape of the RGB image it denotes."""
-        return (self.H, self.W, 3)
-
-    def plane_rows(self):
-        """Per plane of the descriptor: (rows, row bytes).  I420 / YV12: plane 1 is both chroma planes back to back, H rows of W / 2;
-        the planar layouts: both trailing planes, 2 H rows."""
-        r0, r1 = _row_bytes(self.format, self.W)
-        return [(self.H, r0)] + ([(_plane1_rows(self.format, self.H), r1)] if r1 else [])
-
-    def host_planes(self):
-        """The host planes as plane_rows() counts them: three separate planes (I420 / YV12, the planar layouts) give plane 0 and the two
-        trailing planes stacked."""
-        pl = [p.numpy() if hasattr(p, "numpy") else np.asarray(p) for p in self.planes]
-        if len(pl) == 3:
-            return [pl[0], np.concatenate([pl[1], pl[2]], axis=0)]
-        return pl
-
-    def descriptor(self, ptrs=None, pitches=None):
-        """The vt_image tuple of this image: at its planes' own addresses (device images), or at `ptrs` with `pitches`."""
-        if ptrs is None:
-            ptrs = [int(p.data_ptr()) for p in self.planes]
-            pitches = self.pitches
-        return (int(ptrs[0]), int(ptrs[1]) if len(ptrs) > 1 else 0, int(pitches[0]), int(pitches[1]) if len(pitches) > 1 else 0,
-                self.H, self.W, self.format, 0)
-
-
-def images_from_chw(batch, order="rgb"):
-    """A (B, 3, H, W) uint8 batch (numpy array, CPU or CUDA tensor) as a list of B Images that share its memory: Image.chw of every
-    frame, no copy.  What BatchedVitTracker.initialize / track take in place of batch.permute(0, 2, 3, 1).contiguous()."""
-    shape = tuple(getattr(batch, "shape", ()))
-    if len(shape) != 4 or shape[1] != 3:
-        raise VtError(f"a CHW batch must be (B, 3, H, W), got {shape}")
-    return [Image.chw(batch[b], order) for b in range(shape[0])]
-
-
-def pack_image_offsets(images, start: int = 0, align: int = ARENA_ALIGN):
-    """Byte offsets of the planes of host Images packed one after the other from `start` at tight pitches, every plane at a
-    multiple of `align`.  Returns ([per image: [plane offsets]], end)."""
-    return pack_planes([[rows * rb for rows, rb in im.plane_rows()] for im in images], start, align)
-
-
 class ImageTable(_DescriptorTable):
     """The (B,) vt_image descriptor table of vt_crop_images / vt_track_step_images (include/vittrack.h): one frame per sequence in
     its own pixel format, size and plane pitches."""
@@ -830,52 +274,21 @@ class ImageTable(_DescriptorTable):
     ITEM = IMAGE_DTYPE.itemsize
     KIND, WHAT = "images", "image table must be an ImageTable"
 
+    #: check(fmt, ptr0, ptr1, H, W, pitch0=0, pitch1=0, reserved=0, nbytes0=None, nbytes1=None) -> the pitches used: the device's rules
+    #: for an unusable descriptor, on the host, from the layout's row
+    check = staticmethod(check_image)
+
     @staticmethod
-    def check(fmt: int, ptr0: int, ptr1: int, H: int, W: int, pitch0: int = 0, pitch1: int = 0, reserved: int = 0,
-              nbytes0: int | None = None, nbytes1: int | None = None):
-        """The device's rules for an unusable descriptor, on the host: raises VtError where the kernels would poison the sequence.
-        Returns the pitches actually used (0 -> the row's bytes).  nbytes0 / nbytes1: bytes available from each plane (buffers)."""
-        fmt, H, W, pitch0, pitch1 = int(fmt), int(H), int(W), int(pitch0), int(pitch1)
-        lay, mat, rng, high = pix_fields(fmt)
-        if lay not in PIX_LAYOUT_NAMES:
-            raise VtError(f"unknown pixel format {fmt}")
-        if high or mat >= len(PIX_MATRICES) or rng >= len(PIX_RANGES):
-            raise VtError(f"unknown pixel format {fmt:#x}: matrix {mat}, range {rng}, bits 16-31 {high:#x}")
-        if (mat or rng) and (lay not in _YUV420 + _YUV422 + _PLANAR_YUV + _WIDE or lay in _WIDE_GRAY):
-            raise VtError(f"a {pix_name(fmt)} image takes no matrix or range bits, got format {fmt:#x}")
-        if int(reserved) != 0:
-            raise VtError("vt_image.reserved must be 0")
-        if H < 1 or W < 1 or H > 0x10000000 or W > 0x10000000:
-            raise VtError(f"image of {H}x{W} pixels: H and W must be >= 1")
-        if lay in _YUV420 and (H % 2 or W % 2):
-            raise VtError(f"an {pix_name(fmt)} image must have even H and W, got {H}x{W}")
-        if lay in _YUV422 + (PIX_I422,) + _WIDE422 and W % 2:
-            raise VtError(f"a {pix_name(fmt)} image must have even W, got {H}x{W}")
-        r0, r1 = _row_bytes(fmt, W)
-        planes = [(ptr0, pitch0, H, r0, nbytes0)] + ([(ptr1, pitch1, _plane1_rows(fmt, H), r1, nbytes1)] if r1 else [])
-        used = []
-        for k, (ptr, pitch, rows, rb, nb) in enumerate(planes):
-            pitch = pitch or rb
-            if pitch < rb:
-                raise VtError(f"plane {k}: row pitch {pitch} is shorter than a row ({rb} bytes)")
-            if not ptr or (int(ptr) % 4 and lay not in _PLANAR + _WIDE):      # the planar and wide layouts are read as single bytes: any address
-                raise VtError(f"plane {k}: address {int(ptr or 0):#x} is null or not 4-byte aligned")
-            if lay in _WIDE_LSB and (int(ptr) % 2 or pitch % 2):      # ... but for 10- and 12-bit words, fetched as aligned 16-bit loads
-                raise VtError(f"plane {k}: address {int(ptr):#x} or row pitch {pitch} is odd; the 16-bit samples of a {pix_name(fmt)} image "
-                              f"must be 2-byte aligned")
-            need = pitch * (rows - 1) + rb
-            if pitch > 0xfffffff0 or need > 0xfffffff0:
-                raise VtError(f"plane {k}: {need} bytes are beyond the 32-bit offsets of the crop kernels")
-            if nb is not None and need > int(nb):
-                raise VtError(f"plane {k}: needs {need} bytes, its buffer has {int(nb)}")
-            used.append(pitch)
-        return used[0], (used[1] if len(used) > 1 else int(pitch1))
+    def check_descriptor(desc, nbytes0: int | None = None, nbytes1: int | None = None):
+        """check() of a vt_image tuple (plane0, plane1, pitch0, pitch1, H, W, format, reserved)."""
+        p0, p1, q0, q1, H, W, fmt, res = desc
+        return check_image(fmt, p0, p1, H, W, q0, q1, res, nbytes0, nbytes1)
 
     def set(self, i: int, desc, keep=None, check: bool = True):
         """Entry i from a vt_image tuple (plane0, plane1, pitch0, pitch1, H, W, format, reserved); check=False writes it as it is."""
-        p0, p1, q0, q1, H, W, fmt, res = (int(v) for v in desc)
+        p0, p1, q0, q1, H, W, fmt, res = desc = tuple(int(v) for v in desc)
         if check:
-            q0, q1 = self.check(fmt, p0, p1, H, W, q0, q1, res)
+            q0, q1 = self.check_descriptor(desc)
         self._write(i, (p0, p1, q0, q1, H, W, fmt, res), keep)
 
     def set_image(self, i: int, image: Image):
