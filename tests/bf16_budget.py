@@ -20,6 +20,9 @@ Truth and oracle (``run``).  Truth: the block in fp64 from the fp32 tokens.  Ora
   * the attention output, the GELU output and the proj / fc2 weights rounded to bf16; the residual stream rounded to f32.
 Not mirrored: f32 accumulation order inside an MFMA chain, v_exp_f32 / v_rcp_f32 / the fitted GELU (all around 1e-7 relative, far
 below bf16's 2^-9), LayerNorm statistics in f32.  Where that matters the measured factor shows it (FACTORS below).
+For tests/bf16_mlp_budget.py (the MLP chain's budget) ``run`` also takes a per-stage ``hook``, ``fresh`` (every bf16 copy centred on the row's
+own mean) and the mode "unfolded" (VB_LN_FOLD=0: the LayerNorm in full, its output to bf16, W to bf16 without fold or centring); none of them
+changes what it returns without them.
 
 Regimes (``regime``): functions of (name, L, seed) returning the state dict and the fp32 tokens.  Base: synth_vitb_state_dict(seed),
 tokens RandomState(1).standard_normal; a zero-mean unit token direction u and a unit direction d_h per head.  The ramp and hot-key
@@ -221,22 +224,29 @@ def fold(W, b, g, be, nscaled=0):
     return bf16(Wf), bf_.astype(np.float64)
 
 
-def _linear_ln(sd, p, ln, lin, x, mode, centre, nscaled=0):
-    """LayerNorm `ln` + Linear `lin` of block prefix p on rows x: fp64 as the reference writes it, or folded on bf16 operands."""
+def _linear_ln(sd, p, ln, lin, x, mode, centre, nscaled=0, rstd=None):
+    """LayerNorm `ln` + Linear `lin` of block prefix p on rows x: fp64 as the reference writes it, folded on bf16 operands ('bf16'), or
+    -- mode 'unfolded', VB_LN_FOLD=0 -- the LayerNorm applied in full, its output rounded to bf16, W rounded to bf16 without fold or
+    centring.  rstd: stands in for the rows' own 1 / sqrt(var + eps) in the folded form (tests/bf16_mlp_budget.py emulates defects of
+    the statistics with it)."""
     W, b, g, be = _w(sd, p + lin + ".weight"), _w(sd, p + lin + ".bias"), _w(sd, p + ln + ".weight"), _w(sd, p + ln + ".bias")
-    mean, xc, rstd = _stats(x)
+    mean, xc, rstd_x = _stats(x)
     if mode == "truth":
-        y = (xc * rstd[..., None] * g + be) @ W.T + b
+        y = (xc * rstd_x[..., None] * g + be) @ W.T + b
+        y[..., :nscaled] *= 0.125
+        return y
+    if mode == "unfolded":
+        y = bf16(xc * rstd_x[..., None] * g + be) @ bf16(W).T + b
         y[..., :nscaled] *= 0.125
         return y
     Wf, bf_ = fold(W, b, g, be, nscaled)
     xb = bf16(x - (mean if centre is None else centre)[..., None])
-    return (xb @ Wf.T) * rstd[..., None] + bf_
+    return (xb @ Wf.T) * (rstd_x if rstd is None else rstd)[..., None] + bf_
 
 
-def qkv(sd, x, i=0, mode="truth", centre=None, w=W768):
-    """q (scaled by 1/8), k, v of block i as (B, heads, L, 64) float64; bf16 values in mode 'bf16'."""
-    y = _linear_ln(sd, f"backbone.blocks.{i}.", "norm1", "attn.qkv", np.asarray(x, np.float64), mode, centre, nscaled=w.C)
+def qkv(sd, x, i=0, mode="truth", centre=None, w=W768, rstd=None):
+    """q (scaled by 1/8), k, v of block i as (B, heads, L, 64) float64; bf16 values in mode 'bf16' / 'unfolded'."""
+    y = _linear_ln(sd, f"backbone.blocks.{i}.", "norm1", "attn.qkv", np.asarray(x, np.float64), mode, centre, nscaled=w.C, rstd=rstd)
     if mode != "truth":
         y = bf16(y)
     B, L = y.shape[:2]
@@ -305,26 +315,40 @@ def attention(q, k, v, mode="truth", chunk=None, defect=None, group=0):
     return out
 
 
-def run(sd, X, nblocks=1, mode="truth", chunk=None, w=W768):
-    """[residual after block 1 .. nblocks] (f32 values in mode 'bf16') and block 0's attention output, from fp32 tokens X."""
+def run(sd, X, nblocks=1, mode="truth", chunk=None, w=W768, hook=None, fresh=False):
+    """[residual after block 1 .. nblocks] (f32 values in mode 'bf16' / 'unfolded') and block 0's attention output, from fp32 tokens X.
+    hook(i, stage, value): called per block i at the stages "ao" (attention output), "x1" (residual after proj), "u" (fc1 pre-activation),
+    "h" (hidden activations, after the GELU and its rounding) and "x" (residual after fc2); what it returns, unless None, replaces the
+    value.  In the folded oracle it is also asked for "rstd1" / "rstd2" with the rows norm1 / norm2 see: an array returned stands in for
+    their rstd.  fresh: the oracle centres every bf16 copy on the row's OWN mean, where the device uses the mean from before the last
+    update (tests/bf16_mlp_budget.py measures the difference)."""
+    def tap(i, stage, v):
+        r = None if hook is None else hook(i, stage, v)
+        return v if r is None else r
+
+    def ask(i, stage, v):
+        return None if hook is None or mode != "bf16" else hook(i, stage, v)
+
     x = np.asarray(X, np.float64)
     res, ao0, centre = [], None, None
+    gelu = lambda u: 0.5 * u * (1.0 + _erf(u / np.sqrt(2.0)))
     for i in range(nblocks):
         p = f"backbone.blocks.{i}."
-        ao = attention(*qkv(sd, x, i, mode, centre, w=w), mode=mode, chunk=chunk)
+        ao = attention(*qkv(sd, x, i, mode, centre, w=w, rstd=ask(i, "rstd1", x)), mode=mode, chunk=chunk)
+        ao = tap(i, "ao", ao)
         ao0 = ao if i == 0 else ao0
         if mode == "truth":
-            x1 = x + ao @ _w(sd, p + "attn.proj.weight").T + _w(sd, p + "attn.proj.bias")
-            h = _linear_ln(sd, p, "norm2", "mlp.fc1", x1, mode, None)
-            h = 0.5 * h * (1.0 + _erf(h / np.sqrt(2.0)))
-            x = x1 + h @ _w(sd, p + "mlp.fc2.weight").T + _w(sd, p + "mlp.fc2.bias")
+            x1 = tap(i, "x1", x + ao @ _w(sd, p + "attn.proj.weight").T + _w(sd, p + "attn.proj.bias"))
+            h = tap(i, "h", gelu(tap(i, "u", _linear_ln(sd, p, "norm2", "mlp.fc1", x1, mode, None))))
+            x = tap(i, "x", x1 + h @ _w(sd, p + "mlp.fc2.weight").T + _w(sd, p + "mlp.fc2.bias"))
         else:
             c0 = x.mean(-1) if centre is None else centre                 # what the proj GEMM centres its bf16 copy on
-            x1 = f32(x + ao @ bf16(_w(sd, p + "attn.proj.weight")).T + _w(sd, p + "attn.proj.bias"))
-            h = _linear_ln(sd, p, "norm2", "mlp.fc1", x1, mode, c0)
-            h = bf16(0.5 * h * (1.0 + _erf(h / np.sqrt(2.0))))
-            x = f32(x1 + h @ bf16(_w(sd, p + "mlp.fc2.weight")).T + _w(sd, p + "mlp.fc2.bias"))
-            centre = x1.mean(-1)                                          # ... and the fc2 GEMM: the mean ln_finalize found after proj
+            x1 = tap(i, "x1", f32(x + ao @ bf16(_w(sd, p + "attn.proj.weight")).T + _w(sd, p + "attn.proj.bias")))
+            c0 = x1.mean(-1) if fresh else c0
+            h = tap(i, "u", _linear_ln(sd, p, "norm2", "mlp.fc1", x1, mode, c0, rstd=ask(i, "rstd2", x1)))
+            h = tap(i, "h", bf16(gelu(h)))
+            x = tap(i, "x", f32(x1 + h @ bf16(_w(sd, p + "mlp.fc2.weight")).T + _w(sd, p + "mlp.fc2.bias")))
+            centre = x.mean(-1) if fresh else x1.mean(-1)                 # ... and the fc2 GEMM: the mean ln_finalize found after proj
         res.append(x)
     return res, ao0
 
