@@ -89,7 +89,52 @@ __device__ __forceinline__ f4 join3(u32x2 h, u32x2 m, u32x2 l) {
 __device__ __forceinline__ f4 mma(u32x4 a, u32x4 b, f4 acc) {
     return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), acc, 0, 0, 0);
 }
-// one 16-deep chunk on its own (an odd last chunk of K): the legacy K = 16 instruction takes the lane's quad as a 64-bit operand and
+// One 16-deep chunk on its own (an odd last chunk of K), FOLDED: the two 16-deep halves of a K = 32 instruction need not be the same
+// piece pair, so the chunk's six terms are THREE K = 32 instructions, two terms each, instead of six K = 16 ones that each cost the
+// pipe a K = 32 slot (below) -- a K = 48 tile is 9 slots, not 12, P.V (K = 80) 15, not 18.  With w the stored side (weights, K, V^T:
+// 8-byte pieces in LDS) and x the side computed in the wave, a lane's operands are 16-byte quads of two 8-byte pieces each:
+//     step 0:  [wh | wl] . [xl | xh] = wh xl + wl xh        step 1:  [wh | wm] . [xm | xh] = wh xm + wm xh
+//     step 2:  [wh | wm] . [xh | xm] = wh xh + wm xm        (small terms first, as mma_small / mma_large)
+// The x side's three quads are built once per contraction stage (3-12 output tiles).  The w side's two quads come straight from
+// LDS, per output tile: wh is READ TWICE (ld_odd_w), so that each quad can be one merged read into four adjacent registers with no
+// v_mov; both quads hold their pieces in ASCENDING address order, the order a merged read delivers them in.  What hipcc makes of this
+// (instruction and register counts, and why overlapping windows of one register row [wm | wh | wl] were not used) is in NOTES, "an odd K chunk's six bf16 terms as three K = 32 MFMAs".
+// The same six products as before are summed, two of them inside one instruction: results differ from the six-instruction form in the
+// last bits (tests/test_bf3_fold_arithmetic.py).  All of a tile's instructions are now one kind, so the three join chunk pair 0's
+// accumulator chain: no second accumulator, no add (one chain issues a 16 x 16 x 32 MFMA every 16 cycles, as several do).
+struct odd_w { u32x4 hm, hl; };            // [wh | wm], [wh | wl]
+struct odd_x { u32x4 lh, hm, mh; };        // [xl | xh], [xh | xm], [xm | xh]
+__device__ __forceinline__ u32x4 cat2(u32x2 a, u32x2 b) { return u32x4{a.x, a.y, b.x, b.y}; }
+// from pieces in registers ([0] = h, [1] = m, [2] = l)
+__device__ __forceinline__ odd_w make_odd_w(const u32x2 (&w)[3]) { return odd_w{cat2(w[0], w[1]), cat2(w[0], w[2])}; }
+__device__ __forceinline__ odd_x make_odd_x(const u32x2 (&x)[3]) { return odd_x{cat2(x[2], x[0]), cat2(x[0], x[1]), cat2(x[1], x[0])}; }
+// the w side from LDS: piece pc of the lane at p[idx + pc * stride] (8-byte units).  p2 must EQUAL p and be a register the compiler
+// cannot see through (otherwise the two reads of wh are merged and a v_mov makes the second quad)
+__device__ __forceinline__ odd_w ld_odd_w(lds_cptr<u32x2> p, lds_cptr<u32x2> p2, int idx, int stride = 64) {
+    odd_w r;
+    r.hm = cat2(p2[idx], p2[idx + stride]);
+    r.hl = cat2(p[idx], p[idx + 2 * stride]);
+    return r;
+}
+// step STEP of the folded odd chunk; SWAP: the x side is the A operand (rows = tokens)
+template <int STEP, bool SWAP = false>
+__device__ __forceinline__ f4 mma_odd(const odd_w& w, const odd_x& x, f4 acc) {
+    static_assert(STEP >= 0 && STEP < 3, "three steps");
+    const u32x4 ww = STEP == 0 ? w.hl : w.hm;
+    const u32x4 xw = STEP == 0 ? x.lh : STEP == 1 ? x.mh : x.hm;
+    return SWAP ? mma(xw, ww, acc) : mma(ww, xw, acc);
+}
+// all three, from the three 8-byte pieces of each side
+template <bool SWAP = false>
+__device__ __forceinline__ f4 mma_odd3(const u32x2 (&w)[3], const u32x2 (&x)[3], f4 acc) {
+    const odd_w wr = make_odd_w(w);
+    const odd_x xr = make_odd_x(x);
+    acc = mma_odd<0, SWAP>(wr, xr, acc);
+    acc = mma_odd<1, SWAP>(wr, xr, acc);
+    return mma_odd<2, SWAP>(wr, xr, acc);
+}
+// The unfolded form, kept for the 20-tile (G256) kernels, which sit at the register cap (vt_blocks.h FOLD): the legacy K = 16
+// instruction takes the lane's quad as a 64-bit operand and
 // costs the matrix pipe what a K = 32 instruction costs (tools/src/probe_bf3.hip), i.e. what the same chunk paired with zeros would --
 // without the zero registers: no v_mov to widen an operand, two registers less per operand (round 4).
 // RULE: an accumulator chain uses ONE of the two instructions.  A K = 16 MFMA whose SrcC is the result of a K = 32 MFMA issued just

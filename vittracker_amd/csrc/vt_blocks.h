@@ -266,6 +266,12 @@ __global__ __launch_bounds__(NW * 64, (NW == 5 && !WLDS) ? 3 : 1) void blocks_ke
     static_assert(NW * TPW >= NT, "tiles must be covered");
     // BF3L: the LDS-staged form (G128 balanced frame form: qkv + MLP); BF3G: weights from L2 as in every !WLDS form (G256: MLP only)
     constexpr bool BF3L = BF3 && WLDS, BF3G = BF3 && !WLDS;
+    // FOLD: an odd K chunk's six terms as three K = 32 instructions (vt_bf3.h mma_odd) -- the staged G128 form.  The 20-tile forms keep
+    // the K = 16 instruction: they sit at the 256-register cap, and folded the two forms without A3 spilled (36 / 32 B of scratch).
+    // W2 / X2: a tile's chunk-2 operands of the stored side (one set per output tile) and of the side computed in the wave (per stage)
+    constexpr bool FOLD = BF3L;
+    using W2 = std::conditional_t<FOLD, vt3::odd_w, vt3::u32x2[3]>;
+    using X2 = std::conditional_t<FOLD, vt3::odd_x, vt3::u32x2[3]>;
     static_assert(!BF3L || (BAL && 2 * NT * NC >= W3_FC2_TILES - WBUF_TILES), "BF3 with staging: written for the balanced frame form; fc2's third output tile is staged in the K / V area");
     static_assert(!BAL || (WLDS && TPW == 1 && NW == 2 * (NT - 1)), "balanced variant: NT-1 owners + NT-1 guests");
     static_assert(!A3 || BF3, "A3: written for the three-piece forms");
@@ -354,10 +360,10 @@ __global__ __launch_bounds__(NW * 64, (NW == 5 && !WLDS) ? 3 : 1) void blocks_ke
             for (int c = 0; c < NC; ++c) x[i][c] = ld4(src + 16 * c);
         }
     }
-    // BAL: every guest's copy of the guest tile's residual stream.  A wave is an owner (x[0]) or a guest (x4), never both: the forms
-    // on the fp32 / f16 pipes say so by sharing the registers (10 VGPRs; the three-piece forms, tuned at the register cap, keep theirs)
+    // BAL: every guest's copy of the guest tile's residual stream.  A wave is an owner (x[0]) or a guest (x4), never both: the two
+    // share the registers (10-12 VGPRs; the three-piece forms too since their chunk-2 operands are the folded form's wider quads)
     f4 x4s[NC];
-    f4 (&x4)[NC] = (BAL && !BF3) ? x[0] : x4s;
+    f4 (&x4)[NC] = BAL ? x[0] : x4s;
     if constexpr (BAL) {
         if (w >= NOWN) {
             const float* src = tokens + ((size_t)b * L + 16 * GT + tok) * C + 4 * q;
@@ -419,12 +425,40 @@ __global__ __launch_bounds__(NW * 64, (NW == 5 && !WLDS) ? 3 : 1) void blocks_ke
         const auto Wa3h = BF3L ? lds_lane_base<u32x2>(Wa, 192u * 16u + 8u * lane3) : nullptr;          // chunk-2 pieces, 8 B per lane
         const auto Wb3 = BF3L ? lds_lane_base<u32x4>(Wb, 16u * lane3) : nullptr;
         const auto Wk3 = BF3L ? lds_lane_base<u32x4>(Kimg, 16u * lane3) : nullptr;
-        auto w1_load3 = [&](int t, u32x4 (&a0)[3], u32x2 (&a2)[3]) {       // fc1 pieces of output tile t: chunk pair 0, chunk 2
+        // FOLD: a second, equal copy of a chunk-2 base in a register of its own -- the h piece is read once through each (vt_bf3.h
+        // ld_odd_w).  A twin is made where a contraction stage starts (one v_mov) and lives for that stage only: the kernel sits at
+        // the register cap, and as values of the whole block the twins spilled.
+        auto again = [](auto p) {
+            unsigned a = (unsigned)(uintptr_t)p;
+            asm volatile("" : "+v"(a));
+            return (decltype(p))(uintptr_t)a;
+        };
+        auto twin = [&](auto& p2, auto p) {
+            if constexpr (FOLD) p2 = again(p);
+        };
+        auto Wa3h2 = Wa3h;
+        // a tile's chunk-2 pieces at p[idx + pc * 64]
+        auto ld_w2 = [&](W2& a2, lds_cptr<u32x2> p, lds_cptr<u32x2> p2, int idx) {
+            if constexpr (FOLD) a2 = vt3::ld_odd_w(p, p2, idx);
+            else {
 #pragma unroll
-            for (int pc = 0; pc < 3; ++pc) {
-                a0[pc] = Wa3[t * W3_FC1_OT16 + pc * 64];
-                a2[pc] = Wa3h[t * W3_FC1_OT16 * 2 + pc * 64];
+                for (int pc = 0; pc < 3; ++pc) a2[pc] = p[idx + pc * 64];
             }
+        };
+        // the wave's own chunk-2 pieces as tile48's operand: FOLD builds the three quads, once per stage
+        auto xrow = [&](const u32x2 (&hc)[3]) -> decltype(auto) {
+            if constexpr (FOLD) return vt3::make_odd_x(hc);
+            else return (hc);
+        };
+        // a tile's chunk-2 pieces, read once, as tile48's operand: FOLD builds the two quads where the tile uses them (two v_mov)
+        auto wrow = [&](const u32x2 (&a2)[3]) -> decltype(auto) {
+            if constexpr (FOLD) return vt3::make_odd_w(a2);
+            else return (a2);
+        };
+        auto w1_load3 = [&](int t, u32x4 (&a0)[3], W2& a2) {       // fc1 pieces of output tile t: chunk pair 0, chunk 2
+#pragma unroll
+            for (int pc = 0; pc < 3; ++pc) a0[pc] = Wa3[t * W3_FC1_OT16 + pc * 64];
+            ld_w2(a2, Wa3h, Wa3h2, t * W3_FC1_OT16 * 2);
         };
         auto w2_load3 = [&](int p, u32x4 (&a)[NC][3]) {                     // fc2 pieces of chunk pair p, all three output tiles
 #pragma unroll
@@ -441,38 +475,56 @@ __global__ __launch_bounds__(NW * 64, (NW == 5 && !WLDS) ? 3 : 1) void blocks_ke
 #pragma unroll
             for (int pc = 0; pc < 3; ++pc) hb[pc] = u32x4{a[pc].x, a[pc].y, b2[pc].x, b2[pc].y};
         };
-        // one 16 x 16 output tile of a K = 48 layer: 12 MFMAs as two chains (chunk pair 0 onto `init`; chunk 2, on the K = 16
-        // instruction, onto zero), added.  SWAP: the activation pieces are the A operand (rows = tokens): v, so that V^T comes out.
-        auto tile48 = [&](auto swap, const u32x4 (&a0)[3], const u32x2 (&a2)[3], const u32x4 (&hb)[3], const u32x2 (&hc)[3], f4 init) {
+        // one 16 x 16 output tile of a K = 48 layer: 9 MFMAs as ONE chain onto `init` -- chunk pair 0's six terms and chunk 2's six
+        // folded into three instructions (vt_bf3.h mma_odd: step 0 in front of the small terms, step 1 in front of the two middle
+        // ones, step 2 in front of h h).  SWAP: the activation pieces are the A operand (rows = tokens): v, so that V^T comes out.
+        // !FOLD: 12 MFMAs as two chains (chunk 2 on the K = 16 instruction, onto zero), added.
+        auto tile48 = [&](auto swap, const u32x4 (&a0)[3], const W2& a2, const u32x4 (&hb)[3], const X2& hc, f4 init) {
             constexpr bool SWAP = decltype(swap)::value;
             constexpr int TW[6] = {2, 0, 1, 1, 0, 0}, TX[6] = {0, 2, 1, 0, 1, 0};
-            f4 accA = init, accB = splat4(0.f);
+            if constexpr (FOLD) {
+                f4 acc = init;
 #pragma unroll
-            for (int e = 0; e < 6; ++e) {
-                accB = SWAP ? vt3::mma16(hc[TX[e]], a2[TW[e]], accB) : vt3::mma16(a2[TW[e]], hc[TX[e]], accB);
-                accA = SWAP ? vt3::mma(hb[TX[e]], a0[TW[e]], accA) : vt3::mma(a0[TW[e]], hb[TX[e]], accA);
+                for (int e = 0; e < 6; ++e) {
+                    acc = SWAP ? vt3::mma(hb[TX[e]], a0[TW[e]], acc) : vt3::mma(a0[TW[e]], hb[TX[e]], acc);
+                    if (e == 1) acc = vt3::mma_odd<0, SWAP>(a2, hc, acc);
+                    if (e == 3) acc = vt3::mma_odd<1, SWAP>(a2, hc, acc);
+                    if (e == 5) acc = vt3::mma_odd<2, SWAP>(a2, hc, acc);
+                }
+                return acc;
+            } else {
+                f4 accA = init, accB = splat4(0.f);
+#pragma unroll
+                for (int e = 0; e < 6; ++e) {
+                    accB = SWAP ? vt3::mma16(hc[TX[e]], a2[TW[e]], accB) : vt3::mma16(a2[TW[e]], hc[TX[e]], accB);
+                    accA = SWAP ? vt3::mma(hb[TX[e]], a0[TW[e]], accA) : vt3::mma(a0[TW[e]], hb[TX[e]], accA);
+                }
+                return accA + accB;
             }
-            return accA + accB;
         };
         // ---- A3: K / V^T / q / proj as three-piece operands (layouts: header comment)
-        const auto Kp3 = A3 ? lds_lane_base<u32x4>(Kimg, 16u * lane3) : nullptr;                                   // key tile J, pair-0 piece pc: [J * KP_T16 + pc * 64]
+        // (VP3, the staged form at the register cap: ONE base register per lane stride for the whole K / V^T area -- Wk3's and Kp3h)
+        const auto Kp3 = VP3 ? Wk3 : A3 ? lds_lane_base<u32x4>(Kimg, 16u * lane3) : nullptr;                       // key tile J, pair-0 piece pc: [J * KP_T16 + pc * 64]
         const auto Kp3h = A3 ? lds_lane_base<u32x2>(Kimg, 192u * 16u + 8u * lane3) : nullptr;                      // chunk-2 piece: [J * KP_T16 * 2 + pc * 64]
-        const auto Vp3 = A3 ? lds_lane_base<u32x4>(Kimg + NT * KP_T16, 16u * lane3) : nullptr;                     // feature tile t, pair p: [t * VP_T16 + (p * 3 + pc) * 64]
-        const auto Vp3h = A3 ? lds_lane_base<u32x2>(Kimg + NT * KP_T16, VP_PAIRS * 3 * 64 * 16u + 8u * lane3) : nullptr;   // odd last chunk: [t * VP_T16 * 2 + pc * 64]
-        auto k_load3 = [&](int J, u32x4 (&a0)[3], u32x2 (&a2)[3]) {
+        const auto Vp3 = VP3 ? Kp3 + NT * KP_T16 : A3 ? lds_lane_base<u32x4>(Kimg + NT * KP_T16, 16u * lane3) : nullptr;   // feature tile t, pair p: [t * VP_T16 + (p * 3 + pc) * 64]
+        const auto Vp3h = VP3 ? Kp3h + (NT * KP_T16 + VP_PAIRS * 3 * 64 - 192) * 2                                  // odd last chunk: [t * VP_T16 * 2 + pc * 64]
+                              : A3 ? lds_lane_base<u32x2>(Kimg + NT * KP_T16, VP_PAIRS * 3 * 64 * 16u + 8u * lane3) : nullptr;
+        auto Kp3h2 = Kp3h;
+        auto k_load3 = [&](int J, u32x4 (&a0)[3], W2& a2) {
 #pragma unroll
-            for (int pc = 0; pc < 3; ++pc) {
-                a0[pc] = Kp3[J * KP_T16 + pc * 64];
-                a2[pc] = Kp3h[J * KP_T16 * 2 + pc * 64];
-            }
+            for (int pc = 0; pc < 3; ++pc) a0[pc] = Kp3[J * KP_T16 + pc * 64];
+            ld_w2(a2, Kp3h, Kp3h2, J * KP_T16 * 2);
         };
-        auto wp_load3 = [&](int t, u32x4 (&a0)[3], u32x2 (&a2)[3]) {       // proj pieces of output tile t (fc1's layout): buffer B, or straight from L2 (BF3G)
+        lds_cptr<u32x2> Wp3h = nullptr, Wp3h2 = nullptr;        // proj's chunk-2 pieces (buffer B) and the twin, per stage as well
+        auto proj_bases = [&]() {
+            Wp3h = lds_lane_base<u32x2>(Wb, 192u * 16u + 8u * lane3);
+            twin(Wp3h2, Wp3h);
+        };
+        auto wp_load3 = [&](int t, u32x4 (&a0)[3], W2& a2) {       // proj pieces of output tile t (fc1's layout): buffer B, or straight from L2 (BF3G)
             if constexpr (BF3L) {
 #pragma unroll
-                for (int pc = 0; pc < 3; ++pc) {
-                    a0[pc] = Wb3[t * W3_FC1_OT16 + pc * 64];
-                    a2[pc] = reinterpret_cast<const u32x2*>(Wb)[(t * W3_FC1_OT16 + 192) * 2 + pc * 64 + lane3];
-                }
+                for (int pc = 0; pc < 3; ++pc) a0[pc] = Wb3[t * W3_FC1_OT16 + pc * 64];
+                ld_w2(a2, Wp3h, Wp3h2, t * W3_FC1_OT16 * 2);
             } else {
                 const u32x4* const Gp = reinterpret_cast<const u32x4*>(P3) + (W3_FC1_TILES + W3_FC2_TILES + W3_QKV_TILES) * 64;
 #pragma unroll
@@ -566,10 +618,12 @@ __global__ __launch_bounds__(NW * 64, (NW == 5 && !WLDS) ? 3 : 1) void blocks_ke
                     u32x4 hb[3];
                     u32x2 hc[3];
                     split_h3(h, hb, hc);
+                    const auto& hx = xrow(hc);
+                    twin(Wa3h2, Wa3h);
                     // qkv pieces of output tile t: from the staging buffer (BF3L) or straight from L2 (BF3G), the next tile's in flight
                     const u32x4* const Gq = reinterpret_cast<const u32x4*>(P3) + (W3_FC1_TILES + W3_FC2_TILES) * 64;
                     const u32x2* const Gqh = reinterpret_cast<const u32x2*>(Gq);
-                    auto wq_load3 = [&](int t, u32x4 (&a0)[3], u32x2 (&a2)[3]) {
+                    auto wq_load3 = [&](int t, u32x4 (&a0)[3], W2& a2) {
                         if constexpr (BF3L) w1_load3(t, a0, a2);
                         else {
 #pragma unroll
@@ -580,13 +634,12 @@ __global__ __launch_bounds__(NW * 64, (NW == 5 && !WLDS) ? 3 : 1) void blocks_ke
                         }
                     };
                     u32x4 a0[2][3];
-                    u32x2 a2[2][3];
+                    W2 a2[2];
                     // a tile's accumulator initialiser (its bias) is requested WITH its weight pieces, one tile ahead: requested beside
                     // the next tile's pieces it was the youngest LDS read in flight, so the wait in front of the tile's first MFMA was
                     // lgkmcnt(0) -- for the prefetch just issued: one exposed LDS round trip per tile (round 4)
                     auto bias_q = [&](int t) { return t < 2 * NC ? ld4(S + S_BQKV + 16 * t + 4 * q) : splat4(S[S_BQKV + 2 * C + 16 * (t % NC) + tok]); };
                     f4 bias[2];
-                    f4 kr[NC];           // A3: k of this token tile, published as pieces once all three feature chunks are there
                     wq_load3(0, a0[0], a2[0]);
                     bias[0] = bias_q(0);
 #pragma unroll
@@ -598,15 +651,14 @@ __global__ __launch_bounds__(NW * 64, (NW == 5 && !WLDS) ? 3 : 1) void blocks_ke
                         const int ot = t % NC;
                         f4 r;
                         __builtin_amdgcn_sched_barrier(0);
-                        if (t < 2 * NC) r = tile48(std::false_type{}, a0[t & 1], a2[t & 1], hb, hc, bias[t & 1]);
-                        else r = tile48(std::true_type{}, a0[t & 1], a2[t & 1], hb, hc, bias[t & 1]);
+                        if (t < 2 * NC) r = tile48(std::false_type{}, a0[t & 1], a2[t & 1], hb, hx, bias[t & 1]);
+                        else r = tile48(std::true_type{}, a0[t & 1], a2[t & 1], hb, hx, bias[t & 1]);
                         if (t < NC) qr[i][ot] = r;
                         else if constexpr (A3) {
                             if (t < 2 * NC) {
-                                if constexpr (VP3) {
-                                    kr[ot] = r;
-                                    if (ot == NC - 1) store_k3(Kimg + T * KP_T16, kr);
-                                } else store_k3c(Kimg + T * KP_T16, ot, r);      // the 20-tile form has no registers for kr
+                                // published a feature chunk at a time: neither form has the 12 registers to collect the three (the staged
+                                // form since its chunk-2 operands are the folded form's quads: this loop is the template-cache form's peak)
+                                store_k3c(Kimg + T * KP_T16, ot, r);
                             } else if constexpr (VP3) store_v3(T, ot, r);
                             else if constexpr (VP2L) store_v2l(T, ot, r);
                             else Vo[(ot * NT + T) * 64 + lane] = to_opnd(r);
@@ -681,24 +733,32 @@ __global__ __launch_bounds__(NW * 64, (NW == 5 && !WLDS) ? 3 : 1) void blocks_ke
                     u32x4 hb[3];
                     u32x2 hc[3];
                     split_h3(h, hb, hc);
+                    const auto& hx = xrow(hc);
+                    // all three tiles' pieces in one burst, chunk 2's READ ONCE (6 registers a tile) and made the folded form's two quads where a
+                    // tile uses them (two v_mov): with 8 registers a tile this burst was the template-cache form's register peak
                     u32x4 a0[NC][3];
                     u32x2 a2[NC][3];
 #pragma unroll
-                    for (int j = 0; j < NC; ++j) w1_load3(NC * g + j, a0[j], a2[j]);
+                    for (int j = 0; j < NC; ++j)
+#pragma unroll
+                        for (int pc = 0; pc < 3; ++pc) {
+                            a0[j][pc] = Wa3[(NC * g + j) * W3_FC1_OT16 + pc * 64];
+                            a2[j][pc] = Wa3h[(NC * g + j) * W3_FC1_OT16 * 2 + pc * 64];
+                        }
                     if (g < 2) {
                         f4 bias[NC];
 #pragma unroll
                         for (int j = 0; j < NC; ++j) bias[j] = ld4(S + S_BQKV + 16 * (g * NC + j) + 4 * q);
                         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-                        for (int j = 0; j < NC; ++j) r[j] = tile48(std::false_type{}, a0[j], a2[j], hb, hc, bias[j]);
+                        for (int j = 0; j < NC; ++j) r[j] = tile48(std::false_type{}, a0[j], wrow(a2[j]), hb, hx, bias[j]);
                     } else {
                         f4 bias[NC];
 #pragma unroll
                         for (int j = 0; j < NC; ++j) bias[j] = splat4(S[S_BQKV + 2 * C + 16 * j + tok]);
                         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-                        for (int j = 0; j < NC; ++j) r[j] = tile48(std::true_type{}, a0[j], a2[j], hb, hc, bias[j]);
+                        for (int j = 0; j < NC; ++j) r[j] = tile48(std::true_type{}, a0[j], wrow(a2[j]), hb, hx, bias[j]);
                     }
                     if (zg_tile && zcache_mode == 1) {
                         f4* const zc = zc_guest();
@@ -789,6 +849,8 @@ __global__ __launch_bounds__(NW * 64, (NW == 5 && !WLDS) ? 3 : 1) void blocks_ke
                 u32x4 qb[3];
                 u32x2 qc[3];
                 split_h3(qr[i], qb, qc);
+                const auto& qx = xrow(qc);
+                twin(Kp3h2, Kp3h);
                 f4 s[NT];
                 float m0 = -3.0e38f, m1 = -3.0e38f;
                 {
@@ -796,14 +858,14 @@ __global__ __launch_bounds__(NW * 64, (NW == 5 && !WLDS) ? 3 : 1) void blocks_ke
                     // three tiles' residual streams and q, reads a tile's pieces where it uses them (its SIMD partner covers the wait)
                     constexpr int NB = VP3 ? 2 : 1;
                     u32x4 a0[NB][3];
-                    u32x2 a2[NB][3];
+                    W2 a2[NB];
                     if (NB == 2) k_load3(0, a0[0], a2[0]);
 #pragma unroll
                     for (int J = 0; J < NT; ++J) {       // S^T tiles: rows = keys (A = K pieces), cols = queries (B = q pieces)
                         if (NB == 2 && J + 1 < NT) k_load3(J + 1, a0[(J + 1) % NB], a2[(J + 1) % NB]);
                         if (NB == 1) k_load3(J, a0[0], a2[0]);
                         __builtin_amdgcn_sched_barrier(0);
-                        s[J] = tile48(std::false_type{}, a0[J % NB], a2[J % NB], qb, qc, splat4(0.f));
+                        s[J] = tile48(std::false_type{}, a0[J % NB], a2[J % NB], qb, qx, splat4(0.f));
                         m0 = fmaxf(fmaxf(m0, s[J].x), s[J].y);
                         m1 = fmaxf(fmaxf(m1, s[J].z), s[J].w);
                     }
@@ -817,7 +879,7 @@ __global__ __launch_bounds__(NW * 64, (NW == 5 && !WLDS) ? 3 : 1) void blocks_ke
                 // it uses them, one register set)
                 constexpr int NWB = VP3 ? 2 : 1;
                 u32x4 wa0[NWB][3];
-                u32x2 wa2[NWB][3];
+                W2 wa2[NWB];
                 if constexpr (VP3) {
                     u32x4 pb[VP_PAIRS > 0 ? VP_PAIRS : 1][3];      // P^T as pieces: key-chunk pairs ...
                     u32x2 po[3], plo[3];                            // ... the odd last chunk; a pair's first chunk
@@ -851,10 +913,10 @@ __global__ __launch_bounds__(NW * 64, (NW == 5 && !WLDS) ? 3 : 1) void blocks_ke
                     const f2 dd = d0 + d1;
                     const float rden = __builtin_amdgcn_rcpf(quad_sum(dd.x + dd.y));     // v_rcp_f32: 1 ulp
                     fstamp();
-                    f4 oA[NC], oB[NC];
+                    f4 oA[NC];
 #pragma unroll
-                    for (int t = 0; t < NC; ++t) oA[t] = oB[t] = splat4(0.f);
-                    u32x2 vh[NC][3];
+                    for (int t = 0; t < NC; ++t) oA[t] = splat4(0.f);
+                    u32x2 vh[NC][3];       // read once, 18 registers under the pairs' 36 + 24 (the template-cache form's peak); quads made where used
                     if (NT & 1) {
 #pragma unroll
                         for (int t = 0; t < NC; ++t)
@@ -871,16 +933,20 @@ __global__ __launch_bounds__(NW * 64, (NW == 5 && !WLDS) ? 3 : 1) void blocks_ke
                         __builtin_amdgcn_sched_barrier(0);
                         if (pp + 1 < VP_PAIRS) v_load3(pp + 1);
                     }
+                    proj_bases();
                     wp_load3(0, wa0[0], wa2[0]);
-                    if (NT & 1) {
+                    if (NT & 1) {        // the odd last key chunk, folded (vt_bf3.h): three more instructions on each chain
                         __builtin_amdgcn_sched_barrier(0);
+                        const vt3::odd_x pr = vt3::make_odd_x(po);
 #pragma unroll
-                        for (int e = 0; e < 6; ++e)
+                        for (int t = 0; t < NC; ++t) oA[t] = vt3::mma_odd<0>(vt3::make_odd_w(vh[t]), pr, oA[t]);
 #pragma unroll
-                            for (int t = 0; t < NC; ++t) oB[t] = vt3::mma16(vh[t][TW[e]], po[TX[e]], oB[t]);
+                        for (int t = 0; t < NC; ++t) oA[t] = vt3::mma_odd<1>(vt3::make_odd_w(vh[t]), pr, oA[t]);
+#pragma unroll
+                        for (int t = 0; t < NC; ++t) oA[t] = vt3::mma_odd<2>(vt3::make_odd_w(vh[t]), pr, oA[t]);
                     }
 #pragma unroll
-                    for (int t = 0; t < NC; ++t) o[t] = (oA[t] + oB[t]) * splat4(rden);
+                    for (int t = 0; t < NC; ++t) o[t] = oA[t] * splat4(rden);
                 } else if constexpr (VP2L) {
                     // O^T = V^T P^T pair by pair: a key-chunk pair's exponentials are split where they are produced (12 registers of pieces
                     // alive at a time, not the 120 of all ten pairs) and go straight into the pair's 18 MFMAs; V^T's h / m pieces from LDS, its l
@@ -961,12 +1027,13 @@ __global__ __launch_bounds__(NW * 64, (NW == 5 && !WLDS) ? 3 : 1) void blocks_ke
                 u32x4 ob[3];
                 u32x2 oc[3];
                 split_h3(o, ob, oc);
+                const auto& ox = xrow(oc);
 #pragma unroll
                 for (int ot = 0; ot < NC; ++ot) {
                     if (NWB == 2 && ot + 1 < NC) wp_load3(ot + 1, wa0[(ot + 1) % NWB], wa2[(ot + 1) % NWB]);
                     if (NWB == 1) wp_load3(ot, wa0[0], wa2[0]);
                     __builtin_amdgcn_sched_barrier(0);
-                    x[i][ot] = tile48(std::false_type{}, wa0[ot % NWB], wa2[ot % NWB], ob, oc, x[i][ot] + ld4(S + S_BPROJ + 16 * ot + 4 * q));
+                    x[i][ot] = tile48(std::false_type{}, wa0[ot % NWB], wa2[ot % NWB], ob, ox, x[i][ot] + ld4(S + S_BPROJ + 16 * ot + 4 * q));
                     __builtin_amdgcn_sched_barrier(0);
                 }
             } else if (!A3 && VT_BLK_OWNERS && T - toff < NOWN && T != dbg_skip_tile && !(last_skip_z && 16 * T < len_z)) {
@@ -1089,14 +1156,15 @@ __global__ __launch_bounds__(NW * 64, (NW == 5 && !WLDS) ? 3 : 1) void blocks_ke
                     Mg[(g * 2 + 0) * 64 + lane] = m;
                     Mg[(g * 2 + 1) * 64 + lane] = den;
                 };
-                // A3: the same partial attention on pieces; every key chunk of a guest is a K = 16 product (one chain per feature tile)
+                // A3: the same partial attention on pieces; every key chunk of a guest is a lone 16-deep chunk, folded into three K = 32
+                // instructions (vt_bf3.h mma_odd; one chain per feature tile)
                 auto attn_part3 = [&](auto njc, int J0) {
                     constexpr int NJ = decltype(njc)::value;
-                    constexpr int TW[6] = {2, 0, 1, 1, 0, 0}, TX[6] = {0, 2, 1, 0, 1, 0};
                     u32x4 qb[3];
                     u32x2 qc[3];
                     u32x4 a0[NJ][3];
-                    u32x2 a2[NJ][3];
+                    W2 a2[NJ];
+                    twin(Kp3h2, Kp3h);
 #pragma unroll
                     for (int pc = 0; pc < 3; ++pc) {
                         qb[pc] = reinterpret_cast<const u32x4*>(Qg)[pc * 64 + lane3];
@@ -1104,10 +1172,13 @@ __global__ __launch_bounds__(NW * 64, (NW == 5 && !WLDS) ? 3 : 1) void blocks_ke
                     }
 #pragma unroll
                     for (int j = 0; j < NJ; ++j) k_load3(J0 + j, a0[j], a2[j]);
-                    // V^T pieces of key chunk J0 + j: a half of its pair's 16 bytes, or the odd last chunk
+                    // V^T pieces of key chunk J0 + j: a half of its pair's 16 bytes, or the odd last chunk.  Read ONCE (18 registers a key
+                    // chunk) and made the folded form's two quads where they are used: two v_mov per feature tile.  The first chunk's are
+                    // requested here, with everything the scores need; a further chunk's (guest 3) behind the scores, under the softmax --
+                    // guest 3's burst of two key tiles is the kernel's register peak, and with the folded form's wider operands it no
+                    // longer fits beside all of V^T
                     u32x2 vh[NJ][NC][3];
-#pragma unroll
-                    for (int j = 0; j < NJ; ++j) {
+                    auto vh_load = [&](int j) {
                         const int J = J0 + j;
                         const bool oddc = (NT & 1) && J == NT - 1;
 #pragma unroll
@@ -1117,11 +1188,15 @@ __global__ __launch_bounds__(NW * 64, (NW == 5 && !WLDS) ? 3 : 1) void blocks_ke
                             for (int pc = 0; pc < 3; ++pc)
                                 vh[j][t][pc] = oddc ? base[VP_PAIRS * 3 * 64 * 2 + pc * 64 + lane3] : base[(((J >> 1) * 3 + pc) * 64 + lane3) * 2 + (J & 1)];
                         }
-                    }
+                    };
+                    vh_load(0);
                     __builtin_amdgcn_sched_barrier(0);
                     f4 sc[NJ];
 #pragma unroll
-                    for (int j = 0; j < NJ; ++j) sc[j] = tile48(std::false_type{}, a0[j], a2[j], qb, qc, splat4(0.f));
+                    for (int j = 0; j < NJ; ++j) sc[j] = tile48(std::false_type{}, a0[j], a2[j], qb, xrow(qc), splat4(0.f));
+                    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                    for (int j = 1; j < NJ; ++j) vh_load(j);
                     float m0 = -3.0e38f, m1 = -3.0e38f;
 #pragma unroll
                     for (int j = 0; j < NJ; ++j) {
@@ -1149,11 +1224,15 @@ __global__ __launch_bounds__(NW * 64, (NW == 5 && !WLDS) ? 3 : 1) void blocks_ke
 #pragma unroll
                     for (int t = 0; t < NC; ++t) o[t] = splat4(0.f);
 #pragma unroll
-                    for (int j = 0; j < NJ; ++j)
+                    for (int j = 0; j < NJ; ++j) {
+                        const vt3::odd_x pr = vt3::make_odd_x(pp[j]);
 #pragma unroll
-                        for (int e = 0; e < 6; ++e)
+                        for (int t = 0; t < NC; ++t) o[t] = vt3::mma_odd<0>(vt3::make_odd_w(vh[j][t]), pr, o[t]);
 #pragma unroll
-                            for (int t = 0; t < NC; ++t) o[t] = vt3::mma16(vh[j][t][TW[e]], pp[j][TX[e]], o[t]);
+                        for (int t = 0; t < NC; ++t) o[t] = vt3::mma_odd<1>(vt3::make_odd_w(vh[j][t]), pr, o[t]);
+#pragma unroll
+                        for (int t = 0; t < NC; ++t) o[t] = vt3::mma_odd<2>(vt3::make_odd_w(vh[j][t]), pr, o[t]);
+                    }
 #pragma unroll
                     for (int t = 0; t < NC; ++t) Pg[(g * NC + t) * 64 + lane] = o[t];
                     Mg[(g * 2 + 0) * 64 + lane] = m;
@@ -1197,10 +1276,12 @@ __global__ __launch_bounds__(NW * 64, (NW == 5 && !WLDS) ? 3 : 1) void blocks_ke
                     for (int t = 0; t < NC; ++t) o[t] = o[t] * splat4(rl);
                     if constexpr (A3) {
                         u32x4 ob[3], wa0[3];
-                        u32x2 oc[3], wa2[3];
+                        u32x2 oc[3];
+                        W2 wa2;
+                        proj_bases();
                         wp_load3(g, wa0, wa2);
                         split_h3(o, ob, oc);
-                        Dg[g * 64 + lane] = tile48(std::false_type{}, wa0, wa2, ob, oc, splat4(0.f));
+                        Dg[g * 64 + lane] = tile48(std::false_type{}, wa0, wa2, ob, xrow(oc), splat4(0.f));
                     } else {
                         f4 acc[1] = {splat4(0.f)};
                         gemm_stage<NC, 1, true, true>([&](int c, opnd (&a)[1]) { a[0] = w_proj(g * NC + c); },
@@ -1280,30 +1361,25 @@ __global__ __launch_bounds__(NW * 64, (NW == 5 && !WLDS) ? 3 : 1) void blocks_ke
             fc2(hid[hi], 2, x[i]);
         };
         // ---- BF3: the same MLP as exact three-piece bf16 products (vt_bf3.h).  fc1 walks the 12 hidden tiles in units of two
-        // (two independent accumulator chains; 12 MFMAs per tile: six terms on chunk pair (0, 1), six on chunk 2 with a zero
-        // upper half), the next unit's weight pieces requested ahead, GELU + the split of the previous unit under the current
+        // (9 MFMAs per tile: six terms on chunk pair (0, 1), chunk 2's six folded into three), the next unit's weight pieces requested ahead, GELU + the split of the previous unit under the current
         // unit's MFMAs.  Unit u's two hidden tiles ARE fc2's chunk pair u, so the split results are fc2's B operands as they stand.
-        // N chains x 12 MFMAs: the small terms of both K steps first, then the large ones
-        auto fc1_terms3 = [&](auto nc, const u32x4 (*a0)[3], const u32x2 (*a2)[3], const u32x4 (&hb)[3], const u32x2 (&hc)[3], f4* acc) {
+        // N chains x 9 MFMAs in tile48's order (chunk 2 folded: vt_bf3.h mma_odd; a folded step behind pair terms 1, 3 and 5), term by
+        // term across the chains
+        auto fc1_terms3 = [&](auto nc, const u32x4 (*a0)[3], const vt3::odd_w* a2, const u32x4 (&hb)[3], const u32x2 (&hc)[3], f4* acc) {
             constexpr int N = decltype(nc)::value;
             constexpr int TW[6] = {2, 0, 1, 1, 0, 0}, TX[6] = {0, 2, 1, 0, 1, 0};
-            f4 accB[N];
+            const vt3::odd_x xr = vt3::make_odd_x(hc);
 #pragma unroll
-            for (int j = 0; j < N; ++j) accB[j] = splat4(0.f);
+            for (int e = 0; e < 6; ++e) {
 #pragma unroll
-            for (int half = 0; half < 2; ++half)
+                for (int j = 0; j < N; ++j) acc[j] = vt3::mma(a0[j][TW[e]], hb[TX[e]], acc[j]);
 #pragma unroll
-                for (int k = 0; k < 2; ++k)
-#pragma unroll
-                    for (int t3 = 0; t3 < 3; ++t3)
-#pragma unroll
-                        for (int j = 0; j < N; ++j) {
-                            const int e = 3 * half + t3;
-                            if (k == 0) accB[j] = vt3::mma16(a2[j][TW[e]], hc[TX[e]], accB[j]);
-                            else acc[j] = vt3::mma(a0[j][TW[e]], hb[TX[e]], acc[j]);
-                        }
-#pragma unroll
-            for (int j = 0; j < N; ++j) acc[j] = acc[j] + accB[j];
+                for (int j = 0; j < N; ++j) {
+                    if (e == 1) acc[j] = vt3::mma_odd<0>(a2[j], xr, acc[j]);
+                    if (e == 3) acc[j] = vt3::mma_odd<1>(a2[j], xr, acc[j]);
+                    if (e == 5) acc[j] = vt3::mma_odd<2>(a2[j], xr, acc[j]);
+                }
+            }
         };
         u32x4 hq[NHID][NH / 2][3];       // GELU(fc1) as pieces: [chunk pair][piece] = {quad of chunk 2 p | quad of chunk 2 p + 1}
         auto mlp_first3 = [&](int i, int hi) {
@@ -1314,17 +1390,24 @@ __global__ __launch_bounds__(NW * 64, (NW == 5 && !WLDS) ? 3 : 1) void blocks_ke
             u32x4 hb[3];
             u32x2 hc[3];
             split_h3(h, hb, hc);
+            const vt3::odd_x hx = vt3::make_odd_x(hc);      // chunk 2's pieces as the folded form's three quads, once for the 12 tiles
+            twin(Wa3h2, Wa3h);
             fstamp();
-            // one hidden tile per step, its 12 MFMAs as two independent chains (chunk pair 0 onto the bias, chunk 2 onto zero) that
-            // are added afterwards: the next tile's 18 weight registers are requested a step ahead (36 in flight, not 72).  GELU + the
-            // split of the PREVIOUS tile (48 VALU instructions) are written out as six stages of ~8, one behind each pair of MFMAs,
-            // with a scheduling barrier per stage: left to itself hipcc issues the 12 MFMAs as one block (the wave then sits on the
+            // one hidden tile per step, its 9 MFMAs (tile48's terms, the folded steps closing stages 1, 3 and 5) as one chain onto the
+            // bias: the next tile's 20 weight registers are requested a step ahead (40 in flight, not 80).  GELU + the split of the
+            // PREVIOUS tile (48 VALU instructions) are written out as six stages of ~8, one behind each one or two MFMAs,
+            // with a scheduling barrier per stage: left to itself hipcc issues the MFMAs as one block (the wave then sits on the
             // accumulator chains for ~190 cycles with nothing else to issue) and the VALU work behind it; sched_group_barrier
             // requests did not change that here, and without the asm pin LLVM sinks the whole chain below the following tiles.
             constexpr int TW[6] = {2, 0, 1, 1, 0, 0}, TX[6] = {0, 2, 1, 0, 1, 0};
             u32x4 a0[2][3];
-            u32x2 a2[2][3];
-            w1_load3(0, a0[0], a2[0]);
+            vt3::odd_w a2[2];
+            auto w1_ld = [&](int t, u32x4 (&a)[3], vt3::odd_w& ao) {      // w1_load3 (this lambda is compiled in every form; the staged form alone calls it)
+#pragma unroll
+                for (int pc = 0; pc < 3; ++pc) a[pc] = Wa3[t * W3_FC1_OT16 + pc * 64];
+                ao = vt3::ld_odd_w(Wa3h, Wa3h2, t * W3_FC1_OT16 * 2);
+            };
+            w1_ld(0, a0[0], a2[0]);
             f4 bias1[2];
             bias1[0] = ld4(S + S_B1 + 4 * q);
             f4 prev = splat4(0.f);
@@ -1407,20 +1490,22 @@ __global__ __launch_bounds__(NW * 64, (NW == 5 && !WLDS) ? 3 : 1) void blocks_ke
 #pragma unroll
             for (int t = 0; t <= NH; ++t) {
                 if (t == 4 || t == 8) fstamp();
-                f4 accA = splat4(0.f), accB = splat4(0.f);
+                f4 accA = splat4(0.f);
                 if (t < NH) {
                     accA = bias1[t & 1];
                     if (t + 1 < NH) {       // the next tile's pieces AND its bias, a tile ahead (see the qkv loop)
-                        w1_load3(t + 1, a0[(t + 1) & 1], a2[(t + 1) & 1]);
+                        w1_ld(t + 1, a0[(t + 1) & 1], a2[(t + 1) & 1]);
                         bias1[(t + 1) & 1] = ld4(S + S_B1 + 16 * (t + 1) + 4 * q);
                     }
                 }
                 __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
                 for (int e = 0; e < 6; ++e) {
-                    if (t < NH) {
-                        accB = vt3::mma16(a2[t & 1][TW[e]], hc[TX[e]], accB);
+                    if (t < NH) {       // tile48's nine terms, spread over the six stages
                         accA = vt3::mma(a0[t & 1][TW[e]], hb[TX[e]], accA);
+                        if (e == 1) accA = vt3::mma_odd<0>(a2[t & 1], hx, accA);
+                        if (e == 3) accA = vt3::mma_odd<1>(a2[t & 1], hx, accA);
+                        if (e == 5) accA = vt3::mma_odd<2>(a2[t & 1], hx, accA);
                     }
                     if (t > 0) {
                         if (e < 5) gstage(e);
@@ -1428,7 +1513,7 @@ __global__ __launch_bounds__(NW * 64, (NW == 5 && !WLDS) ? 3 : 1) void blocks_ke
                     }
                     __builtin_amdgcn_sched_barrier(0);
                 }
-                prev = accA + accB;
+                prev = accA;
             }
         };
         auto mlp_second3 = [&](int i, int hi) {
@@ -1464,8 +1549,9 @@ __global__ __launch_bounds__(NW * 64, (NW == 5 && !WLDS) ? 3 : 1) void blocks_ke
                 u32x4 hb[3];
                 u32x2 hc[3];
                 split_h3(h, hb, hc);
+                twin(Wa3h2, Wa3h);
                 u32x4 a0[NC][3];
-                u32x2 a2[NC][3];
+                W2 a2[NC];
 #pragma unroll
                 for (int j = 0; j < NC; ++j) w1_load3(NC * g + j, a0[j], a2[j]);
                 f4 acc[NC];
@@ -1498,38 +1584,24 @@ __global__ __launch_bounds__(NW * 64, (NW == 5 && !WLDS) ? 3 : 1) void blocks_ke
                     bh[pc] = odd ? gq[0][pc] : gq[2][pc];
                 }
                 u32x4 af[NC][3];
-                u32x2 ah[NC][3];       // the half pair: the weights' quad of this guest's chunk only (K = 16 instruction)
+                vt3::odd_w ah[NC];     // the half pair: the weights' quad of this guest's chunk only (a lone 16-deep chunk: folded)
                 w2_load3(p_full, af);
                 {
                     // chunk 2 p + 1 = the upper quad of the lane's 16 bytes, chunk 2 p the lower; p_half is wave-uniform, not constant
                     const unsigned hoff = 16u * lane3 + (odd ? 8u : 0u) + (unsigned)p_half * (3u * 64u * 16u);
                     const auto Wb3h = lds_lane_base<u32x2>(Wb, hoff);
                     const auto Wk3h = lds_lane_base<u32x2>(Kimg, hoff);
+                    const auto Wb3h2 = again(Wb3h);
+                    const auto Wk3h2 = again(Wk3h);
 #pragma unroll
-                    for (int ot = 0; ot < NC; ++ot)
-#pragma unroll
-                        for (int pc = 0; pc < 3; ++pc)
-                            ah[ot][pc] = ot < 2 ? Wb3h[((ot * (NH / 2)) * 3 + pc) * 64 * 2] : Wk3h[pc * 64 * 2];
+                    for (int ot = 0; ot < NC; ++ot)       // pieces 1 KiB apart
+                        ah[ot] = ot < 2 ? vt3::ld_odd_w(Wb3h, Wb3h2, (ot * (NH / 2)) * 3 * 64 * 2, 128) : vt3::ld_odd_w(Wk3h, Wk3h2, 0, 128);
                 }
-                f4 part[NC], partB[NC];
+                f4 part[NC];
 #pragma unroll
-                for (int ot = 0; ot < NC; ++ot) part[ot] = partB[ot] = splat4(0.f);
+                for (int ot = 0; ot < NC; ++ot) part[ot] = splat4(0.f);
                 __builtin_amdgcn_sched_barrier(0);
-                constexpr int TW[6] = {2, 0, 1, 1, 0, 0}, TX[6] = {0, 2, 1, 0, 1, 0};
-#pragma unroll
-                for (int half = 0; half < 2; ++half)
-#pragma unroll
-                    for (int k = 0; k < 2; ++k)
-#pragma unroll
-                        for (int t3 = 0; t3 < 3; ++t3)
-#pragma unroll
-                            for (int ot = 0; ot < NC; ++ot) {
-                                const int e = 3 * half + t3;
-                                if (k == 0) partB[ot] = vt3::mma16(ah[ot][TW[e]], bh[TX[e]], partB[ot]);
-                                else part[ot] = vt3::mma(af[ot][TW[e]], bf[TX[e]], part[ot]);
-                            }
-#pragma unroll
-                for (int ot = 0; ot < NC; ++ot) part[ot] = part[ot] + partB[ot];
+                fc1_terms3(std::integral_constant<int, NC>{}, af, ah, bf, bh, part);      // the same nine terms per chain: full pair + folded half pair
 #pragma unroll
                 for (int ot = 0; ot < NC; ++ot) Pg2[(g * NC + ot) * 64 + lane] = part[ot];
             }
@@ -1598,7 +1670,7 @@ __global__ __launch_bounds__(NW * 64, (NW == 5 && !WLDS) ? 3 : 1) void blocks_ke
                     const u32x4* const G1 = reinterpret_cast<const u32x4*>(P3);
                     const u32x2* const G1h = reinterpret_cast<const u32x2*>(P3);
                     const u32x4* const G2 = G1 + W3_FC1_TILES * 64;
-                    auto g1_load3 = [&](int t, u32x4 (&a0)[3], u32x2 (&a2)[3]) {
+                    auto g1_load3 = [&](int t, u32x4 (&a0)[3], W2& a2) {
 #pragma unroll
                         for (int pc = 0; pc < 3; ++pc) {
                             a0[pc] = G1[t * W3_FC1_OT16 + pc * 64 + lane3];
@@ -1610,10 +1682,12 @@ __global__ __launch_bounds__(NW * 64, (NW == 5 && !WLDS) ? 3 : 1) void blocks_ke
                     u32x4 hb[3];
                     u32x2 hc[3];
                     split_h3(h, hb, hc);
+                    const auto& hx = xrow(hc);
+                    twin(Wa3h2, Wa3h);
                     u32x4 hq3[NH / 2][3];
                     {
                         u32x4 a0[2][3];
-                        u32x2 a2[2][3];
+                        W2 a2[2];
                         g1_load3(0, a0[0], a2[0]);
                         u32x2 pl[3];
 #pragma unroll
@@ -1621,7 +1695,7 @@ __global__ __launch_bounds__(NW * 64, (NW == 5 && !WLDS) ? 3 : 1) void blocks_ke
                             if (t + 1 < NH) g1_load3(t + 1, a0[(t + 1) & 1], a2[(t + 1) & 1]);
                             const f4 bias = ld4(S + S_B1 + 16 * t + 4 * q);
                             __builtin_amdgcn_sched_barrier(0);
-                            const f4 r = tile48(std::false_type{}, a0[t & 1], a2[t & 1], hb, hc, bias);
+                            const f4 r = tile48(std::false_type{}, a0[t & 1], a2[t & 1], hb, hx, bias);
                             u32x2 pc3[3];
                             vt3::split3(gelu4(r), pc3[0], pc3[1], pc3[2]);
 #pragma unroll
