@@ -260,6 +260,21 @@ int vt_crop_form(void);
 #define VT_GEMM_FC2 16   /* MLP fc2 */
 #define VT_GEMM_HEAD 32  /* head conv1 of the three towers (and conv2, chosen by its own tile count) */
 int vt_gemm_form(const vt_model* m, int32_t B);
+/* The arithmetic of a patch-16 ViT model (vt_create_vit, or the ViT-Base / ViT-Large tuples of vt_create; anything else: VT_ERR_ARG).
+ * VT_PRECISION_BF16 (the default): single-piece bf16 operands.  VT_PRECISION_FP32: every contraction multiplies the exact three-piece bf16
+ * splits of its fp32 operands (six terms, fp32 accumulator) at six times the GEMM depth, activations between kernels are fp32, the
+ * attention and GELU run in fp32: results agree with the reference's fp32 outputs to a few 1e-6 on maps.  Every entry point
+ * of the model works in either mode; vt_gemm_form reports the tiles of the mode's launches (VT_GEMM_QK: the qkv projection, always a GEMM
+ * there); VB_LN_FOLD and VB_FUSED_QKV have no effect in fp32 mode.  Callable before or after vt_load_weights: the weights' piece images are
+ * built at whichever comes second (vt_load_weights keeps the unfolded fp32 tensors of a patch-16 ViT model in host memory for that: the model's
+ * size once more, in either mode).  The mode's workspaces (the largest: max_batch x L x 4 C x 12 bytes) are allocated when it is first selected; a failed allocation leaves the model in bf16 mode (VT_ERR_HIP, the size in the message).  The mode and
+ * candidate elimination exclude each other (VT_ERR_STATE from either call).  Switching drops the template cache.  Synchronises the device;
+ * VT_ERR_STATE while a captured graph of the model is alive.  VB_PRECISION=fp32, read at vt_create, selects the mode from the start. */
+#define VT_PRECISION_BF16 0
+#define VT_PRECISION_FP32 1
+int vt_set_precision(vt_model* m, int32_t precision);
+/* The mode of a patch-16 ViT model.  Any other model: -1 (it has no mode; vt_last_error is left as it is).  NULL: -1, "null model". */
+int vt_precision(const vt_model* m);
 
 /* The tail of Vit_dist.track (lib/test/tracker/vit_dist.py:107-111,150-156; clip_box,
  * lib/utils/box_ops.py:97-106): scale the windowed box back to image pixels, map it to the frame,

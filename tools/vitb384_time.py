@@ -76,10 +76,11 @@ def _split(geom, B, script=None):
             name = r["Name"].split("(")[0].replace("void ", "")
             rows[name] = rows.get(name, 0.0) + float(r["TotalDurationNs"]) * 1e-3
             calls[name] = calls.get(name, 0) + int(r["Calls"])
-    # every step (the capture's eager warm-up and the capture's own replay included) launches conv5 exactly once
-    steps = next((n for name, n in calls.items() if "conv5_kernel" in name), 0)
+    # every step (the capture's eager warm-up and the capture's own replay included) launches conv5 exactly once: vbm::conv5_kernel, in
+    # fp32 mode vbf::conv5_f32_kernel
+    steps = next((n for name, n in calls.items() if "conv5_kernel" in name or "conv5_f32_kernel" in name), 0)
     if not steps:
-        return "no conv5_kernel launch in the trace"
+        return "no conv5 kernel launch in the trace"
     return {k: {"us_per_step": round(v / steps, 1), "launches_per_step": round(calls[k] / steps, 2),
                 "us_per_launch": round(v / calls[k], 1)} for k, v in sorted(rows.items(), key=lambda kv: -kv[1])}
 

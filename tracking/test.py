@@ -21,14 +21,14 @@ sys.path.insert(0, ROOT)
 
 
 def run_tracker(tracker_name, tracker_param, run_id=None, dataset_name="synthetic", sequence=None, debug=0, threads=0,
-                num_gpus=8, batch=0, synthetic_weights=False, frames_per_launch=1, shards=1, continuous=False, ce_form=None):
+                num_gpus=8, batch=0, synthetic_weights=False, frames_per_launch=1, shards=1, continuous=False, ce_form=None, precision=None):
     from vittracker_amd.evaluation import Tracker, get_dataset
     from vittracker_amd.evaluation.running import run_dataset, run_dataset_batched, run_dataset_continuous
     dataset = get_dataset(dataset_name)
     if sequence is not None:
         dataset = type(dataset)([dataset[sequence]])
     tracker = Tracker(tracker_name, tracker_param, dataset_name, run_id)
-    if synthetic_weights or ce_form is not None:
+    if synthetic_weights or ce_form is not None or precision is not None:
         _get = tracker.get_parameters
 
         def get_parameters():
@@ -37,6 +37,8 @@ def run_tracker(tracker_name, tracker_param, run_id=None, dataset_name="syntheti
                 p.allow_synthetic_weights = True
             if ce_form is not None:
                 p.ce_form = ce_form
+            if precision is not None:
+                p.precision = precision
             return p
         tracker.get_parameters = get_parameters
     if batch > 0:
@@ -78,13 +80,17 @@ def main():
     p.add_argument("--ce_form", choices=("masked", "compact"), default=None,
                    help="candidate-elimination models (ostrack *_ce_* YAMLs): key masking, or the kept tokens gathered into shorter "
                         "frames behind every stage; default: the environment variable VB_CE_FORM, else masked")
+    p.add_argument("--precision", choices=("bf16", "fp32"), default=None,
+                   help="patch-16 ViT models (ostrack YAMLs): bf16 operands, or the fp32-equivalent mode on three-piece bf16 operands; "
+                        "default: the environment variable VB_PRECISION, else bf16")
     a = p.parse_args()
     try:
         seq = int(a.sequence)
     except (TypeError, ValueError):
         seq = a.sequence
+    more = {} if a.precision is None else {"precision": a.precision}
     run_tracker(a.tracker_name, a.tracker_param, a.runid, a.dataset_name, seq, a.debug, a.threads, a.num_gpus, a.batch,
-                a.synthetic_weights, a.frames_per_launch, a.shards, a.continuous, a.ce_form)
+                a.synthetic_weights, a.frames_per_launch, a.shards, a.continuous, a.ce_form, **more)
 
 
 if __name__ == "__main__":

@@ -78,7 +78,7 @@ class BatchedVitTracker:
         self.cfg = params.cfg
         self.B = batch
         g = geometry(self.cfg)
-        self.net = build_network(self.cfg, max_batch=batch, ce_form=getattr(params, "ce_form", None))      # vit_48 or ViT-Base OSTrack, by the cfg
+        self.net = build_network(self.cfg, max_batch=batch, ce_form=getattr(params, "ce_form", None), precision=getattr(params, "precision", None))      # vit_48 or ViT-Base OSTrack, by the cfg
         ckpt = getattr(params, "checkpoint", None)
         import os
         if ckpt and os.path.isfile(ckpt):

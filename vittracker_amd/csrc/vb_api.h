@@ -57,6 +57,11 @@ int set_ce_form(VbModel* m, int form, std::string* err);
 int ce_result(VbModel* m, int B, hipStream_t st, uint8_t* removed_stage, float* scores, std::string* err);
 // Which GEMM kinds of a plain forward of B frames run the narrow 128 x 64 tile: the VT_GEMM_* bits of include/vittrack.h (vt_gemm_form)
 int gemm_form(const VbModel* m, int B);
+// The fp32-equivalent mode (include/vittrack.h vt_set_precision; kernels: vb_f32.h): VT_PRECISION_BF16 / VT_PRECISION_FP32.  Selecting fp32
+// allocates the mode's workspaces the first time and builds the weights' piece images if the weights are loaded (else load_weights does);
+// a failure leaves the model in bf16 mode.  Synchronises the device.  Refused with candidate elimination set (and the reverse).
+int set_precision(VbModel* m, int precision, std::string* err);
+int precision(const VbModel* m);
 // blocks[0..nblocks) on the residual stream (tokens_in: optional replacement, copied in first), then the final norm:
 // the search rows go to the head's input map (and to feat_out as f32 (B,Lx,C), optional); resid_out optional copy
 int blocks(VbModel* m, const float* tokens_in, int B, int nblocks, hipStream_t st, float* feat_out, float* resid_out, std::string* err,

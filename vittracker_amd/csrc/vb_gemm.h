@@ -104,6 +104,7 @@ enum Epi {
     EPI_PATCH_ROWS_N = 7, // EPI_PATCH_ROWS for a kind whose rows per frame are no power of two (OSTrack-384: 144 / 576): Args::row_shift
                           // holds the rows per frame themselves, frame = m / rows by a multiply-high with ceil(2^32 / rows), exact
                           // while M * rows < 2^32 (checked by the host).  Its own instantiation: EPI_PATCH_ROWS keeps its code
+    EPI_F32 = 8,     // out[m][n] = acc + bias[n] as f32 (the fp32-equivalent mode, vb_f32.h: q | k | v, the fc1 pre-activation, the head's convs)
 };
 
 struct Args {
@@ -410,6 +411,27 @@ __global__ __launch_bounds__(NWAVES * 64) void gemm_kernel(const Args a) {
                         const float m2 = row16_sum(hsum4(d * d));
                         if (ok && ch == 0) a.stats[(size_t)(tn * WN + wn) * a.ldstats + mo] = f2{s, m2};
                     }
+                }
+                lds_fence();
+            }
+            return;
+        }
+        if constexpr (EPI == EPI_F32) {
+            // f32 rows of `out` (row stride ldo; grouped launches gOut apart): chunk = 16 rows x 256 B through the staging area, as the
+            // residual epilogue's, stores only.  Columns past N (N = 32 under the 64-wide tile) are zero padding
+            lds_fence();
+            float* const obase = static_cast<float*>(a.out) + grp * a.gOut;
+            const int ch = lane & 15, r0 = lane >> 4;
+#pragma unroll
+            for (int j = 0; j < TM; ++j) {
+#pragma unroll
+                for (int i = 0; i < TN; ++i) *reinterpret_cast<f4a*>(ep + l15 * 256 + (((i * 4 + (q4 >> 2)) ^ l15) << 4)) = acc[i][j] + bs[i];
+                lds_fence();
+#pragma unroll
+                for (int t = 0; t < 4; ++t) {
+                    const int row = 4 * t + r0, m = mw + j * 16 + row;
+                    const f4 v = *reinterpret_cast<const f4a*>(ep + row * 256 + ((ch ^ row) << 4));
+                    if ((!CHECK || m < a.M) && nw + ch * 4 < a.N) st4(obase + (size_t)m * a.ldo + nw + ch * 4, v);
                 }
                 lds_fence();
             }

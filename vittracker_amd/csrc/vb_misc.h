@@ -1,6 +1,7 @@
 // vb_misc.h -- the HBM-bound kernels around the GEMMs of the ViT-Base path: patch gathering, LayerNorm, head tail.
 #pragma once
 #include "vb_gemm.h"
+#include "vt_bf3.h"
 
 namespace vbm {
 
@@ -205,6 +206,103 @@ __global__ __launch_bounds__(256) void layernorm_small_kernel(const float* __res
             }
             if (feat) *reinterpret_cast<fv*>(feat + ((size_t)f * (L - Lz) + tt) * C + c) = y;
         }
+    }
+}
+
+// ------------------------------------------------------------------------- the fp32-equivalent mode
+// An fp32 operand of a GEMM is stored as its three exact bf16 pieces x = h + m + l (split3_rne below), laid out along k as the six k-ranges
+// [xm | xh | xl | xh | xm | xh] of an expanded row of 6 K; the weight row is [wm | wl | wh | wm | wh | wh] (vb_f32.h expand_weight_kernel).
+// vbg::gemm_kernel at depth 6 K then sums mm, hl, lh, hm, mh, hh in that order: the small terms meet the accumulator first.
+// split3_rne: h = bf16(x), m = bf16(x - h), l = bf16(x - h - m), each rounded to nearest even (v_cvt_pk_bf16_f32); both subtractions are
+// exact and the last residual has at most 8 significant bits, so x = h + m + l exactly, as with vt3::split3's truncation.  Rounded pieces
+// are half the size of truncated ones and of either sign: the three dropped cross terms (ml, lm, ll) are below 2^-26 of a product and
+// unbiased, where truncation's are up to 2^-24 and all of the product's sign -- measured on three fixtures, the worst ratio of the device's
+// error to the reference's own fp32 error fell from 8.5 to 5.0.  Same pair packing as vt3::split3: element r in the low half first.
+__device__ __forceinline__ void split3_rne(f4 x, vt3::u32x2& h, vt3::u32x2& m, vt3::u32x2& l) {
+#pragma unroll
+    for (int p = 0; p < 2; ++p) {
+        const vbg::f2 v = {x[2 * p], x[2 * p + 1]};
+        const unsigned hu = __builtin_bit_cast(unsigned, __builtin_convertvector(v, vbg::bf16x2));
+        const vbg::f2 r1 = v - vbg::f2{__uint_as_float(hu << 16), __uint_as_float(hu & 0xffff0000u)};
+        const unsigned mu = __builtin_bit_cast(unsigned, __builtin_convertvector(r1, vbg::bf16x2));
+        const vbg::f2 r2 = r1 - vbg::f2{__uint_as_float(mu << 16), __uint_as_float(mu & 0xffff0000u)};
+        h[p] = hu; m[p] = mu; l[p] = __builtin_bit_cast(unsigned, __builtin_convertvector(r2, vbg::bf16x2));
+    }
+}
+// store_split8: eight values at column c (a multiple of 8) of a K-wide row, as six 16-byte stores into the expanded row `row`.
+__device__ __forceinline__ void store_split8(bf16* row, int K, int c, f4 a, f4 b) {
+    vt3::u32x2 ha, ma, la, hb, mb, lb;
+    split3_rne(a, ha, ma, la);
+    split3_rne(b, hb, mb, lb);
+    const vt3::u32x4 h = vt3::cat2(ha, hb), m = vt3::cat2(ma, mb), l = vt3::cat2(la, lb);
+    vt3::u32x4* p = reinterpret_cast<vt3::u32x4*>(row + c);
+    const int s = K / 8;      // a k-range in 16-byte units
+    p[0] = m; p[s] = h; p[2 * s] = l; p[3 * s] = h; p[4 * s] = m; p[5 * s] = h;
+}
+__device__ __forceinline__ void store_split4(bf16* row, int K, int c, f4 a) {      // four values, 8-byte stores
+    vt3::u32x2 h, m, l;
+    split3_rne(a, h, m, l);
+    vt3::u32x2* p = reinterpret_cast<vt3::u32x2*>(row + c);
+    const int s = K / 4;
+    p[0] = m; p[s] = h; p[2 * s] = l; p[3 * s] = h; p[4 * s] = m; p[5 * s] = h;
+}
+
+// LayerNorm over the f32 residual stream with f32 statistics, one wave per row, writing the next GEMM's expanded operand xs [M][6 C]
+// and / or the search rows as f32 feat [B][Lx][C] (the final norm).  Lanes hold float4 slots of 256 columns; at widths that are no multiple
+// of 256 (384, 192) the last slot's upper lanes hold nothing and add zeros to the sums.
+template <int C>
+__global__ __launch_bounds__(256) void layernorm_split_kernel(const float* __restrict__ resid, const float* __restrict__ gamma,
+                                                              const float* __restrict__ beta, float eps, int M, int L, int Lz,
+                                                              bf16* __restrict__ xs, float* __restrict__ feat) {
+    static_assert(C % 4 == 0, "float4 lanes");
+    constexpr int NV = (C + 255) / 256;
+    const int lane = threadIdx.x & 63;
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= M) return;
+    const float* p = resid + (size_t)row * C;
+    f4 v[NV];
+    float s = 0.f;
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+        const int c = i * 256 + lane * 4;
+        v[i] = c < C ? ld4(p + c) : splat4(0.f);
+        s += hsum4(v[i]);
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
+    const float mean = s * (1.0f / C);
+    float ss = 0.f;
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+        if (i * 256 + lane * 4 < C) {
+            v[i] = v[i] - splat4(mean);
+            ss += hsum4(v[i] * v[i]);
+        }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) ss += __shfl_xor(ss, o);
+    const float rstd = 1.0f / sqrtf(ss * (1.0f / C) + eps);
+    const int f = row / L, t = row - f * L;
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+        const int c = i * 256 + lane * 4;
+        if (c >= C) continue;
+        const f4 y = v[i] * splat4(rstd) * ld4(gamma + c) + ld4(beta + c);
+        if (xs) store_split4(xs + (size_t)row * 6 * C, C, c, y);
+        if (feat && t >= Lz) st4(feat + ((size_t)f * (L - Lz) + (t - Lz)) * C + c, y);
+    }
+}
+
+// nn.GELU() in its exact erf form on the f32 pre-activation [rows][N], written as fc2's expanded operand [rows][6 N].  One thread = 8 columns
+__device__ __forceinline__ float gelu_erf(float u) { return 0.5f * u * (1.0f + erff(u * 0.70710678118654752440f)); }
+__global__ __launch_bounds__(256) void gelu_split_kernel(const float* __restrict__ pre, bf16* __restrict__ xs, size_t rows, int N) {
+    const size_t per = (size_t)N / 8, total = rows * per;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
+        const size_t r = i / per;
+        const int c = (int)(i - r * per) * 8;
+        const f4 a = ld4(pre + r * N + c), b = ld4(pre + r * N + c + 4);
+        store_split8(xs + r * 6 * N, N, c, f4{gelu_erf(a.x), gelu_erf(a.y), gelu_erf(a.z), gelu_erf(a.w)},
+                     f4{gelu_erf(b.x), gelu_erf(b.y), gelu_erf(b.z), gelu_erf(b.w)});
     }
 }
 

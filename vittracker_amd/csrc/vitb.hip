@@ -2,6 +2,8 @@
 // weights as [cout][tap][cin], attention scale folded into W_q), workspace, launch sequence.  Kernels: vb_gemm.h, vb_misc.h and the
 // three attention kernels vb_attn.h, vb_qkvattn.h, vb_attn_stream.h (the 384 geometry's), whose shared arithmetic lives in vb_attn.h;
 // vb_ce.h: OSTrack candidate elimination by key masking or compacted (the stages' score / select / gather kernels; vb::blocks routes them).
+// vb_f32.h: the fp32-equivalent mode (vb::set_precision): the same GEMM kernel on operands expanded to six bf16 k-ranges, f32 activations, f32
+// attention and head tail; stem_rows_f32 / blocks_f32 / head_f32 below are its three routes, ModeF32 its workspaces and weight images.
 // Reached through the same C ABI as the vit_48 path (vt_create with channels = 768, or the ViT-Large tuple at channels = 1024; vt_create_vit for
 // those two and for ViT-Small 384 / 6 and ViT-Tiny 192 / 3).  The model points differ in width, head count and hidden width alone (VbModel::C /
 // HEADS / HID); the kernels take them at run time except the three that compile the width in (dispatch_width below).  What the two small
@@ -19,6 +21,7 @@
 #include "vb_attn.h"
 #include "vb_attn_stream.h"
 #include "vb_ce.h"
+#include "vb_f32.h"
 #include "vb_gemm.h"
 #include "vb_misc.h"
 #include "vb_qkvattn.h"
@@ -74,6 +77,29 @@ struct Buf {      // owns its device memory; movable (std::vector<BlockW> is res
 struct BlockW {
     Buf<float> ln1g, ln1b, ln2g, ln2b, bqkv, bproj, b1, b2;
     Buf<bf16> wqkv, wproj, w1, w2;
+};
+
+// The fp32-equivalent mode (vb_f32.h).  Per block: the host's unfolded f32 tensors (q rows and bias times the attention scale),
+// kept from vt_load_weights so that vt_set_precision can come later, and their expanded piece images [N (padded)][6 K] on the device.
+struct BlockF {
+    std::vector<float> h_wqkv, h_bqkv, h_wproj, h_w1, h_b1, h_w2;
+    Buf<bf16> wqkv, wproj, w1, w2;
+    Buf<float> bqkv, b1;
+};
+// What the mode adds to a model: workspaces (allocated when the mode is first selected) and weight images (built when mode and weights meet)
+struct ModeF32 {
+    bool ws = false, weights = false;
+    Buf<bf16> x6;            // [max rows][6 C]: the LayerNorms' and the attention's output, the operand of qkv / fc1 / proj
+    Buf<bf16> hid6;          // [max rows][6 HID]: GELU's output, fc2's operand (and the patch operand of the widths below 768)
+    Buf<float> hid32;        // [max rows][HID]: fc1's pre-activation; q | k | v [rows][3 C] of a slice lives in the same rows
+    Buf<float> feat32;       // [max_batch][LX][C]: the final norm's search rows
+    Buf<float> tmp32;        // [max_batch][LX][768]: a head conv's f32 output, slice by slice
+    Buf<bf16> map6[4];       // the head's zero-bordered maps of expanded pixels (map_split_kernel)
+    Buf<bf16> zop6;          // template cache: [max_batch * LZ][6 x 768]
+    Buf<bf16> wpatch, wpatch_u8, wc[4];
+    Buf<float> bpatch_u8;
+    std::vector<BlockF> blk;
+    std::vector<float> h_wc[4];      // the head's folded conv weights [3 towers][rows][9 cin] as load_weights lays them out
 };
 
 }  // namespace
@@ -138,6 +164,8 @@ struct VbModel {
     Buf<int32_t> ce_index, ce_src, ce_inv;
     std::vector<size_t> ce_index_off;
     int ce_lp(int k) const { return (LZ + ce_keep[k] + 15) / 16 * 16; }
+    int precision = VT_PRECISION_BF16;      // vb::set_precision
+    ModeF32 f32;
 };
 
 namespace {
@@ -232,8 +260,10 @@ int launch_gemm(const vbg::Args& a, int groups, hipStream_t st, const Err& E, in
     const Hooks& H = hooks();
     vbg::Args ad = a;
     ad.dbg = H.dbg;
-    if (H.rb[EPI] >= 0) ad.rb = H.rb[EPI];
-    if (H.desync_us[EPI] > 0) { ad.desync_ticks = H.desync_us[EPI] * 100; ad.desync_groups = H.desync_groups[EPI]; }
+    if constexpr (EPI < 8) {      // (the hooks know the bf16 mode's eight epilogues)
+        if (H.rb[EPI] >= 0) ad.rb = H.rb[EPI];
+        if (H.desync_us[EPI] > 0) { ad.desync_ticks = H.desync_us[EPI] * 100; ad.desync_groups = H.desync_groups[EPI]; }
+    }
     // persistent workgroups: one per CU, each walks tiles blockIdx.x, blockIdx.x + grid, ...
     const int ntiles = ((a.M + BM - 1) / BM) * ((a.N + BN - 1) / BN);
     if (H.max_cus > 0) cus = cus > 0 ? std::min(cus, H.max_cus) : H.max_cus;
@@ -384,6 +414,99 @@ int upload_centring(Buf<float>& d, const std::vector<float>& pos, int C, double 
     return upload_f32(d, cpos.data(), cpos.size(), E);
 }
 
+// ---- the fp32-equivalent mode: weight images and workspaces
+// an f32 tensor [rows][K] as its expanded image [rows + pad_rows zero rows][terms K] (vbf::expand_weight_kernel), through a staging upload
+int expand_upload(Buf<bf16>& d, const float* h, size_t rows, int K, int terms, size_t pad_rows, const Err& E) {
+    const size_t n = (rows + pad_rows) * terms * K;
+    if (!d.p || d.n != n) {
+        d.release();
+        VB_HIP(d.alloc(n));
+    }
+    Buf<float> stage;
+    VB_HIP(stage.alloc(rows * K));
+    VB_HIP(hipMemcpy(stage.p, h, rows * K * sizeof(float), hipMemcpyHostToDevice));
+    if (pad_rows) VB_HIP(hipMemset(d.p + rows * terms * K, 0, pad_rows * terms * K * sizeof(bf16)));
+    hipLaunchKernelGGL(vbf::expand_weight_kernel, dim3(grid256(rows * K / 4)), dim3(256), 0, 0, stage.p, d.p, rows, K, terms);
+    VB_HIP(hipGetLastError());
+    VB_HIP(hipDeviceSynchronize());
+    return VT_OK;
+}
+size_t pad_rows256(int N) { return (size_t)((N + 255) / 256 * 256 - N); }
+
+// Preprocessor.process folded into the uint8 form of the patch weights as fold_patch_u8 does, for the mode: uncentred (the operand is the
+// byte itself, exact in one piece) and kept to fp32 by the three weight pieces
+int build_f32_patch_u8(VbModel* m, const Err& E) {
+    const int C = m->C;
+    std::vector<float> w((size_t)C * PATCH_K), b(C);
+    double k255[3], ms[3];
+    for (int c = 0; c < 3; ++c) { k255[c] = 1.0 / (255.0 * (double)m->norm_std[c]); ms[c] = (double)m->norm_mean[c] / (double)m->norm_std[c]; }
+    for (int n = 0; n < C; ++n) {
+        const float* row = m->h_wpatch.data() + (size_t)n * PATCH_K;
+        double sm = 0;
+        for (int k = 0; k < PATCH_K; ++k) {
+            sm += (double)row[k] * ms[k >> 8];
+            w[(size_t)n * PATCH_K + k] = (float)((double)row[k] * k255[k >> 8]);
+        }
+        b[n] = (float)((double)m->h_bpatch[n] - sm);
+    }
+    if (int rc = expand_upload(m->f32.wpatch_u8, w.data(), C, PATCH_K, 3, pad_rows256(C), E)) return rc;
+    return upload_f32(m->f32.bpatch_u8, b.data(), b.size(), E);
+}
+
+int build_f32_weights(VbModel* m, const Err& E) {
+    ModeF32& f = m->f32;
+    const int C = m->C, HID = m->HID;
+    int rc;
+    f.weights = false;
+    if ((rc = expand_upload(f.wpatch, m->h_wpatch.data(), C, PATCH_K, 6, pad_rows256(C), E)) || (rc = build_f32_patch_u8(m, E))) return rc;
+    for (BlockF& b : f.blk) {
+        if ((rc = expand_upload(b.wqkv, b.h_wqkv.data(), 3 * C, C, 6, pad_rows256(3 * C), E)) || (rc = upload_f32(b.bqkv, b.h_bqkv.data(), b.h_bqkv.size(), E)) ||
+            (rc = expand_upload(b.wproj, b.h_wproj.data(), C, C, 6, pad_rows256(C), E)) ||
+            (rc = expand_upload(b.w1, b.h_w1.data(), HID, C, 6, pad_rows256(HID), E)) || (rc = upload_f32(b.b1, b.h_b1.data(), b.h_b1.size(), E)) ||
+            (rc = expand_upload(b.w2, b.h_w2.data(), C, HID, 6, pad_rows256(C), E)))
+            return rc;
+    }
+    for (int li = 0; li < 4; ++li) {      // [rows][tap][cin] -> [rows][tap][6 cin]: a tap's channels are one expanded row
+        const int cin = m->head_ch(li);
+        if ((rc = expand_upload(f.wc[li], f.h_wc[li].data(), f.h_wc[li].size() / cin, cin, 6, 0, E))) return rc;
+    }
+    f.weights = true;
+    return VT_OK;
+}
+
+// the mode's workspaces, all or none; the new GEMM instantiations' dynamic LDS
+int alloc_f32_ws(VbModel* m, const Err& E) {
+    ModeF32& f = m->f32;
+    if (f.ws) return VT_OK;
+    const size_t B = (size_t)m->maxB, M = B * m->L, C = (size_t)m->C, HID = (size_t)m->HID, LX = (size_t)m->LX, P2 = (size_t)(m->F + 2) * (m->F + 2);
+    const std::pair<Buf<bf16>*, size_t> hb[] = {{&f.x6, M * 6 * C}, {&f.hid6, M * 6 * HID}, {&f.zop6, B * m->LZ * 6 * PATCH_K}, {&f.map6[0], B * P2 * 6 * C},
+                                                {&f.map6[1], 3 * B * P2 * 6 * HEAD_CH[1]}, {&f.map6[2], 3 * B * P2 * 6 * HEAD_CH[2]},
+                                                {&f.map6[3], 3 * B * P2 * 6 * HEAD_CH[3]}};
+    const std::pair<Buf<float>*, size_t> fb[] = {{&f.hid32, M * HID}, {&f.feat32, B * LX * C}, {&f.tmp32, B * LX * 3 * HEAD_CH[1]}};
+    hipError_t e = hipSuccess;
+    size_t bytes = 0;
+    for (const auto& w : hb) { bytes += w.second * 2; if (e == hipSuccess) e = w.first->alloc(w.second); }
+    for (const auto& w : fb) { bytes += w.second * 4; if (e == hipSuccess) e = w.first->alloc(w.second); }
+    for (Buf<bf16>& b : f.map6)      // zero borders; the kernels write interiors only
+        if (e == hipSuccess) e = hipMemset(b.p, 0, b.n * 2);
+    using namespace vbg;
+    const struct { const void* kernel; int lds; } dynamic_lds[] = {
+        {kernel_ptr(gemm_kernel<256, 256, 2, 4, A_PLAIN, EPI_F32>), lds_bytes<256, 256>()},
+        {kernel_ptr(gemm_kernel<128, 64, 8, 1, A_PLAIN, EPI_F32>), lds_bytes<128, 64>()},
+        {kernel_ptr(gemm_kernel<256, 64, 8, 1, A_CONV, EPI_F32>), lds_bytes<256, 64>()},
+        {kernel_ptr(gemm_kernel<128, 64, 8, 1, A_CONV, EPI_F32>), lds_bytes<128, 64>()}};
+    for (const auto& k : dynamic_lds)
+        if (e == hipSuccess) e = hipFuncSetAttribute(k.kernel, hipFuncAttributeMaxDynamicSharedMemorySize, k.lds);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        for (const auto& w : hb) w.first->release();
+        for (const auto& w : fb) w.first->release();
+        return E.fail(VT_ERR_HIP, "fp32 mode: workspaces of " + std::to_string(bytes) + " bytes: " + hipGetErrorString(e));
+    }
+    f.ws = true;
+    return VT_OK;
+}
+
 int fold_patch_u8(VbModel* m, const Err& E) {
     const int C = m->C;
     std::vector<float> w((size_t)C * PATCH_K), b(C);
@@ -405,7 +528,8 @@ int fold_patch_u8(VbModel* m, const Err& E) {
     }
     int rc;
     if ((rc = upload_bf16(m->wpatch_u8, w, E, tile_pad(C, PATCH_K))) || (rc = upload_f32(m->bpatch_u8, b.data(), b.size(), E))) return rc;
-    return upload_centring(m->cpos_u8, m->h_pos, C, bsum, E);
+    if ((rc = upload_centring(m->cpos_u8, m->h_pos, C, bsum, E))) return rc;
+    return m->f32.weights ? build_f32_patch_u8(m, E) : VT_OK;      // (vt_set_normalization in fp32 mode: the mode's image follows)
 }
 
 }  // namespace
@@ -573,6 +697,8 @@ int set_candidate_elimination(VbModel* m, int n, const int32_t* loc, const doubl
     const Err E{err};
     if (int rc = check_ce_args(n, loc, keep_ratio, err)) return rc;
     if (m->C != C_BASE) return E.fail(VT_ERR_ARG, "candidate elimination is implemented for ViT-Base models (channels 768) only");
+    if (m->precision == VT_PRECISION_FP32)
+        return E.fail(VT_ERR_STATE, "candidate elimination and fp32 mode exclude each other: this model is in fp32 mode (vt_set_precision)");
     if (n > m->depth || loc[n - 1] >= m->depth)
         return E.fail(VT_ERR_ARG, "candidate elimination: " + std::to_string(n) + " stages up to block " + std::to_string(loc[n - 1]) + " do not fit depth " +
                                       std::to_string(m->depth) + " (1 <= n <= depth, loc in [0, depth))");
@@ -662,28 +788,38 @@ int load_weights(VbModel* m, const TensorMap& tm, std::string* err) {
     for (int k = 0; k < C; ++k) bsum += bp[k];
     if ((rc = upload_centring(m->cpos, m->h_pos, C, bsum, E)) || (rc = fold_patch_u8(m, E))) return rc;
     const float scale = 1.0f / std::sqrt((float)HD);     // 0.125: a power of two, folding it into W_q / b_q is exact
+    m->f32.blk.resize(m->depth);
+    m->f32.weights = false;
     for (int i = 0; i < m->depth; ++i) {
         BlockW& b = m->blk[i];
+        BlockF& bf = m->f32.blk[i];
         const std::string pre = bb + "blocks." + std::to_string(i) + ".";
         const float *g1, *be1, *g2, *be2;
         if ((rc = load_f32(b.ln1g, tm, pre + "norm1.weight", C, E, &g1)) || (rc = load_f32(b.ln1b, tm, pre + "norm1.bias", C, E, &be1))) return rc;
         if ((rc = load_f32(b.ln2g, tm, pre + "norm2.weight", C, E, &g2)) || (rc = load_f32(b.ln2b, tm, pre + "norm2.bias", C, E, &be2))) return rc;
         if ((rc = load_f32(b.bproj, tm, pre + "attn.proj.bias", C, E)) || (rc = load_f32(b.b2, tm, pre + "mlp.fc2.bias", C, E))) return rc;
         // a Linear behind a LayerNorm: the norm folded in (VB_LN_FOLD), its first `nscaled` output rows times the attention scale
-        auto folded = [&](const std::string& name, int N, const float* g, const float* be, int nscaled, Buf<bf16>& W, Buf<float>& Bv, size_t pad) {
+        auto folded = [&](const std::string& name, int N, const float* g, const float* be, int nscaled, Buf<bf16>& W, Buf<float>& Bv, size_t pad,
+                          std::vector<float>& hw, std::vector<float>& hb) {
             const float *pw, *pb;
             if ((rc = need(tm, pre + name + ".weight", (int64_t)N * C, &pw, E)) || (rc = need(tm, pre + name + ".bias", N, &pb, E))) return rc;
             std::vector<float> w(pw, pw + (size_t)N * C), bias(pb, pb + N);
+            hw = w; hb = bias;      // the fp32-equivalent mode's: unfolded, scaled
+            for (size_t k = 0; k < (size_t)nscaled * C; ++k) hw[k] *= scale;
+            for (int k = 0; k < nscaled; ++k) hb[k] *= scale;
             if (m->fold) fold_layernorm(w, bias, g, be, N, C);
             for (size_t k = 0; k < (size_t)nscaled * C; ++k) w[k] *= scale;
             for (int k = 0; k < nscaled; ++k) bias[k] *= scale;
             if ((rc = upload_bf16(W, w, E, pad))) return rc;
             return upload_f32(Bv, bias.data(), bias.size(), E);
         };
-        if ((rc = folded("attn.qkv", 3 * C, g1, be1, C, b.wqkv, b.bqkv, tile_pad(C, C)))) return rc;      // the v GEMM's N = C rows end the matrix
-        if ((rc = load_bf16(b.wproj, tm, pre + "attn.proj.weight", (int64_t)C * C, E, nullptr, tile_pad(C, C)))) return rc;
-        if ((rc = folded("mlp.fc1", HID, g2, be2, 0, b.w1, b.b1, tile_pad(HID, C)))) return rc;
-        if ((rc = load_bf16(b.w2, tm, pre + "mlp.fc2.weight", (int64_t)HID * C, E, nullptr, tile_pad(C, HID)))) return rc;
+        const float *hproj, *hfc2;
+        if ((rc = folded("attn.qkv", 3 * C, g1, be1, C, b.wqkv, b.bqkv, tile_pad(C, C), bf.h_wqkv, bf.h_bqkv))) return rc;      // the v GEMM's N = C rows end the matrix
+        if ((rc = load_bf16(b.wproj, tm, pre + "attn.proj.weight", (int64_t)C * C, E, &hproj, tile_pad(C, C)))) return rc;
+        if ((rc = folded("mlp.fc1", HID, g2, be2, 0, b.w1, b.b1, tile_pad(HID, C), bf.h_w1, bf.h_b1))) return rc;
+        if ((rc = load_bf16(b.w2, tm, pre + "mlp.fc2.weight", (int64_t)HID * C, E, &hfc2, tile_pad(C, HID)))) return rc;
+        bf.h_wproj.assign(hproj, hproj + (size_t)C * C);
+        bf.h_w2.assign(hfc2, hfc2 + (size_t)HID * C);
     }
     if ((rc = load_f32(m->ng, tm, bb + "norm.weight", C, E)) || (rc = load_f32(m->nb, tm, bb + "norm.bias", C, E))) return rc;
     // ---- head: Conv3x3(+bias) + BatchNorm(eval, eps 1e-5) folded in double (head.py:8-21), weights as [cout][tap][cin]
@@ -712,6 +848,7 @@ int load_weights(VbModel* m, const TensorMap& tm, std::string* err) {
         }
         if ((rc = upload_bf16(m->wc[li], w, E))) return rc;
         if ((rc = upload_f32(m->bc[li], bias.data(), bias.size(), E))) return rc;
+        m->f32.h_wc[li] = std::move(w);
     }
     {
         const int CW = HEAD_CH[4];
@@ -730,6 +867,7 @@ int load_weights(VbModel* m, const TensorMap& tm, std::string* err) {
         if ((rc = upload_f32(m->b5, b5.data(), 5, E))) return rc;
     }
     m->loaded = true;
+    if (m->precision == VT_PRECISION_FP32 && (rc = build_f32_weights(m, E))) { m->loaded = false; return rc; }
     return VT_OK;
 }
 
@@ -745,10 +883,217 @@ static int check_slice(VbModel* m, int B, const Slice* sl, const Err& E) {
     return VT_OK;
 }
 
+// ------------------------------------------------------------------------------ the fp32-equivalent mode
+int precision(const VbModel* m) { return m->precision; }
+
+int set_precision(VbModel* m, int prec, std::string* err) {
+    const Err E{err};
+    if (prec != VT_PRECISION_BF16 && prec != VT_PRECISION_FP32)
+        return E.fail(VT_ERR_ARG, "precision " + std::to_string(prec) + ": VT_PRECISION_BF16 (0) or VT_PRECISION_FP32 (1)");
+    if (prec == VT_PRECISION_FP32 && m->ce_set)
+        return E.fail(VT_ERR_STATE, "fp32 mode and candidate elimination exclude each other: this model has candidate elimination set");
+    VB_HIP(hipDeviceSynchronize());      // no step may be running on the buffers of the other mode
+    if (prec == VT_PRECISION_FP32) {
+        if (int rc = alloc_f32_ws(m, E)) return rc;
+        if (m->loaded && !m->f32.weights)
+            if (int rc = build_f32_weights(m, E)) return rc;
+    }
+    m->precision = prec;
+    return VT_OK;
+}
+
+namespace {
+// the bytes of an expanded operand one GEMM launch of the mode may span: below the 4 GiB its 32-bit byte offsets reach
+constexpr unsigned long long F32_OPERAND_BYTES = (1ull << 32) - (1ull << 20);
+// what an fp32-mode entry addresses for a frame slice (SliceView holds the residual stream and the slice itself)
+struct SliceF32 {
+    bf16 *x6, *hid6, *zop6, *map6[4];
+    float *hid32, *feat32, *tmp32;
+    SliceF32(const VbModel* m, const SliceView& v) {
+        const ModeF32& f = m->f32;
+        const size_t P2 = (size_t)(m->F + 2) * (m->F + 2);
+        x6 = f.x6.p + v.r0 * 6 * m->C; hid6 = f.hid6.p + v.r0 * 6 * m->HID; zop6 = f.zop6.p + v.f0 * m->LZ * 6 * PATCH_K;
+        for (int i = 0; i < 4; ++i) map6[i] = f.map6[i].p + v.f0 * P2 * 6 * m->head_ch(i);
+        hid32 = f.hid32.p + v.r0 * m->HID; feat32 = f.feat32.p + v.f0 * m->LX * m->C; tmp32 = f.tmp32.p + v.f0 * m->LX * 3 * HEAD_CH[1];
+    }
+    // the patch GEMMs' expanded operand rows [rows][6 x 768]: in the width's own rows, or (384, 192) in the hidden rows
+    bf16* patch_operand(const VbModel* m) const { return m->C >= PATCH_K ? x6 : hid6; }
+};
+
+int patchify_split(const float* img, int T, int B, bf16* P, hipStream_t st, const Err& E) {
+    hipLaunchKernelGGL(vbf::patchify_split_kernel, dim3(grid256((size_t)B * (T / 16) * (T / 16) * 96)), dim3(256), 0, st, img, P, B, T);
+    VB_HIP(hipGetLastError());
+    return VT_OK;
+}
+
+int run_layernorm_split(const VbModel* m, const float* resid, const float* g, const float* b, int M, hipStream_t st, bf16* xs, float* feat, const Err& E) {
+    dispatch_width(m->C, [&](auto W) {
+        hipLaunchKernelGGL((vbm::layernorm_split_kernel<decltype(W)::value>), dim3((M + 3) / 4), dim3(256), 0, st, resid, g, b, LN_EPS, M, m->L, m->LZ, xs, feat);
+    });
+    VB_HIP(hipGetLastError());
+    return VT_OK;
+}
+
+// f32 rows -> a zero-bordered map of expanded pixels, `towers` of them (vbf::map_split_kernel)
+int run_map_split(const float* src, size_t src_tower, int ld, bf16* dst, size_t dst_tower, int towers, int B, int F, int C, bool relu, hipStream_t st,
+                  const Err& E) {
+    hipLaunchKernelGGL(vbf::map_split_kernel, dim3(grid256((size_t)B * F * F * (C / 8)), towers), dim3(256), 0, st, src, src_tower, ld, dst, dst_tower, B, F, C,
+                       relu ? 1 : 0);
+    VB_HIP(hipGetLastError());
+    return VT_OK;
+}
+}  // namespace
+
+// vb::stem_rows in fp32 mode: the same two GEMMs on expanded operands (six terms from an fp32 crop, three from a uint8 patch), no bf16
+// copy and no statistics behind them.  vb::stem takes this route too (Z_GIVEN): one arithmetic for the cached and the given template.
+static int stem_rows_f32(VbModel* m, ZSrc zsrc, const float* z, const float* x, const unsigned char* xu8, int B, hipStream_t st, const SliceView& v,
+                         const Err& E) {
+    int rc;
+    const int L = m->L, LZ = m->LZ, LX = m->LX, C = m->C, K6 = 6 * PATCH_K;
+    const SliceF32 w(m, v);
+    bf16* const op = w.patch_operand(m);
+    bf16* const xop = op + (size_t)B * LZ * K6;
+    const bf16* zop = w.zop6;
+    if (zsrc == Z_GIVEN) {
+        if ((rc = patchify_split(z, m->TZ, B, op, st, E))) return rc;
+        zop = op;
+    }
+    if (xu8) {
+        hipLaunchKernelGGL(vbf::patchify_u8_split_kernel, dim3(grid256((size_t)B * LX * 16)), dim3(256), 0, st, xu8, xop, B, m->TX);
+        VB_HIP(hipGetLastError());
+    } else if ((rc = patchify_split(x, m->TX, B, xop, st, E))) return rc;
+    vbg::Args a{};
+    a.resid = v.resid; a.pos = m->pos.p; a.N = C; a.L = L;
+    // whole frames per launch, as many as keep the launch's operand below F32_OPERAND_BYTES (blocks_f32: chunk_rows)
+    auto rows_gemm = [&](const vbg::Args& whole, int rows, int shift) {
+        const int fmax = std::max(1, (int)(F32_OPERAND_BYTES / ((unsigned long long)rows * whole.K * 2)));
+        for (int f0 = 0; f0 < B; f0 += fmax) {
+            vbg::Args g = whole;
+            g.X = whole.X + (size_t)f0 * rows * whole.K; g.resid = whole.resid + (size_t)f0 * L * C; g.M = std::min(fmax, B - f0) * rows;
+            g.row_shift = shift < 0 ? rows : shift;
+            if (int r = shift < 0 ? launch_tile<vbg::A_PLAIN, vbg::EPI_PATCH_ROWS_N>(m, g, 1, st, E, v.cus)
+                                  : launch_tile<vbg::A_PLAIN, vbg::EPI_PATCH_ROWS>(m, g, 1, st, E, v.cus)) return r;
+        }
+        return (int)VT_OK;
+    };
+    if (zsrc != Z_NONE) {
+        vbg::Args az = a;
+        az.X = zop; az.W = m->f32.wpatch.p; az.bias = m->bpatch.p; az.M = B * LZ; az.K = K6; az.row_o0 = 0;
+        if ((rc = rows_gemm(az, LZ, m->zshift))) return rc;
+    }
+    a.X = xop; a.M = B * LX; a.row_o0 = LZ;
+    a.W = xu8 ? m->f32.wpatch_u8.p : m->f32.wpatch.p;
+    a.bias = xu8 ? m->f32.bpatch_u8.p : m->bpatch.p;
+    a.K = xu8 ? 3 * PATCH_K : K6;
+    return rows_gemm(a, LX, m->xshift);
+}
+
+// vb::blocks in fp32 mode: LayerNorm -> expanded operand -> qkv GEMM (f32 rows) -> f32 attention -> expanded operand -> proj (f32
+// read-modify-write) -> LayerNorm -> fc1 (f32 pre-activation) -> exact GELU -> expanded operand -> fc2; the final norm writes f32 features
+static int blocks_f32(VbModel* m, const float* tokens_in, int B, int nblocks, hipStream_t st, float* feat_out, float* resid_out, const SliceView& v,
+                      const Err& E) {
+    int rc;
+    const int C = m->C, HID = m->HID, L = m->L, M = B * L;
+    const SliceF32 w(m, v);
+    if (tokens_in && tokens_in != v.resid) VB_HIP(hipMemcpyAsync(v.resid, tokens_in, (size_t)M * C * 4, hipMemcpyDeviceToDevice, st));
+    float* const qkv = w.hid32;      // [M][3 C] in the hidden rows, idle until fc1
+    const int qtiles = (L + vbf::AQ - 1) / vbf::AQ;
+    // The GEMMs address an operand by 32-bit byte offsets from its base (vb_gemm.h), and an expanded operand of a whole batch can pass 4 GiB
+    // (fc2's: rows x 6 HID x 2 bytes -- 9.1 GB for ViT-Large at 192 / 384 with 256 frames): a GEMM of the mode runs as launches of at most
+    // chunk_rows(K) rows, each with its operand, residual and output based at its first row.  Every output element keeps its whole sum in
+    // one workgroup in the same order wherever its tile lies, so the chunking changes no bit (tests: B = 66 against frames one at a time).
+    auto chunk_rows = [](int K) { return std::max(256, (int)((F32_OPERAND_BYTES / ((unsigned long long)K * 2)) / 256 * 256)); };
+    auto resid_gemm = [&](const bf16* X, const bf16* W, const float* bias, int K) {
+        for (int r0 = 0, step = chunk_rows(K); r0 < M; r0 += step) {
+            vbg::Args p{};
+            p.X = X + (size_t)r0 * K; p.W = W; p.bias = bias; p.resid = v.resid + (size_t)r0 * C; p.M = std::min(step, M - r0); p.N = C; p.K = K;
+            if (int r = launch_tile<vbg::A_PLAIN, vbg::EPI_RESID>(m, p, 1, st, E, v.cus)) return r;
+        }
+        return (int)VT_OK;
+    };
+    auto f32_gemm = [&](const bf16* W, const float* bias, float* out, int N) {
+        const int K = 6 * C;
+        for (int r0 = 0, step = chunk_rows(K); r0 < M; r0 += step) {
+            vbg::Args a{};
+            a.X = w.x6 + (size_t)r0 * K; a.W = W; a.bias = bias; a.out = out + (size_t)r0 * N; a.M = std::min(step, M - r0); a.N = N; a.K = K; a.ldo = N; a.rb = 4;
+            if (int r = launch_tile<vbg::A_PLAIN, vbg::EPI_F32>(m, a, 1, st, E, v.cus)) return r;
+        }
+        return (int)VT_OK;
+    };
+    for (int i = 0; i < nblocks; ++i) {
+        const BlockW& b = m->blk[i];
+        const BlockF& bf = m->f32.blk[i];
+        if ((rc = run_layernorm_split(m, v.resid, b.ln1g.p, b.ln1b.p, M, st, w.x6, nullptr, E))) return rc;
+        if ((rc = f32_gemm(bf.wqkv.p, bf.bqkv.p, qkv, 3 * C))) return rc;
+        hipLaunchKernelGGL(vbf::attn_f32_kernel, dim3(B * m->HEADS * qtiles), dim3(256), 0, st, qkv, w.x6, C, m->HEADS, L, qtiles);
+        VB_HIP(hipGetLastError());
+        if ((rc = resid_gemm(w.x6, bf.wproj.p, b.bproj.p, 6 * C))) return rc;
+        if ((rc = run_layernorm_split(m, v.resid, b.ln2g.p, b.ln2b.p, M, st, w.x6, nullptr, E))) return rc;
+        if ((rc = f32_gemm(bf.w1.p, bf.b1.p, w.hid32, HID))) return rc;
+        hipLaunchKernelGGL(vbm::gelu_split_kernel, dim3(grid256((size_t)M * (HID / 8))), dim3(256), 0, st, w.hid32, w.hid6, (size_t)M, HID);
+        VB_HIP(hipGetLastError());
+        if ((rc = resid_gemm(w.hid6, bf.w2.p, b.b2.p, 6 * HID))) return rc;
+    }
+    if (resid_out) VB_HIP(hipMemcpyAsync(resid_out, v.resid, (size_t)M * C * 4, hipMemcpyDeviceToDevice, st));
+    if ((rc = run_layernorm_split(m, v.resid, m->ng.p, m->nb.p, M, st, nullptr, w.feat32, E))) return rc;
+    if (feat_out) VB_HIP(hipMemcpyAsync(feat_out, w.feat32, (size_t)B * m->LX * C * 4, hipMemcpyDeviceToDevice, st));
+    return run_map_split(w.feat32, 0, C, w.map6[0], 0, 1, B, m->F, C, false, st, E);
+}
+
+// vb::head in fp32 mode: the towers as A_CONV GEMMs on maps of expanded pixels (six k-ranges per tap) with f32 outputs; a conv's ReLU is
+// applied where its output is expanded for the next one (conv4's: in the 1 x 1 tail)
+static int head_f32(VbModel* m, const float* feat_in, int B, hipStream_t st, float* score, float* size, float* offset, const SliceView& v, const Err& E) {
+    int rc;
+    const int LX = m->LX, F = m->F, M = B * LX, C = m->C;
+    const SliceF32 w(m, v);
+    const long long Bt = v.Bt, P2 = (long long)(F + 2) * (F + 2);
+    // (a map of expanded pixels is addressed by 32-bit element offsets from the slice's first frame: launches of at most `fmax` frames, each
+    // based at its first frame; the tile is chosen for the whole call, as vt_gemm_form reports it)
+    auto conv = [&](const vbg::Args& whole, int groups) {
+        const bool narrow = narrow_pick(m, whole.M, whole.N, groups, v.cus);
+        const int fmax = std::max(1, (int)((1ull << 31) / ((unsigned long long)P2 * whole.C) - 1));
+        for (int f0 = 0; f0 < B; f0 += fmax) {
+            vbg::Args a = whole;
+            a.X = whole.X + (size_t)f0 * P2 * whole.C; a.M = std::min(fmax, B - f0) * LX;
+            a.out = static_cast<float*>(whole.out) + (size_t)f0 * LX * whole.ldo;
+            if (int r = narrow ? launch_gemm<128, 64, 8, 1, vbg::A_CONV, vbg::EPI_F32>(a, groups, st, E, v.cus)
+                               : launch_gemm<256, 64, 8, 1, vbg::A_CONV, vbg::EPI_F32>(a, groups, st, E, v.cus)) return r;
+        }
+        return (int)VT_OK;
+    };
+    if (feat_in && (rc = run_map_split(feat_in, 0, C, w.map6[0], 0, 1, B, F, C, false, st, E))) return rc;
+    {   // conv1 of the three towers as one GEMM: N = 3 x 256 dense f32 columns, K = 9 taps x 6 C
+        vbg::Args a{};
+        a.X = w.map6[0]; a.W = m->f32.wc[0].p; a.bias = m->bc[0].p; a.out = w.tmp32;
+        a.M = M; a.N = 3 * HEAD_CH[1]; a.K = 9 * 6 * C; a.ldo = 3 * HEAD_CH[1]; a.C = 6 * C; a.F = F;
+        if ((rc = conv(a, 1))) return rc;
+        if ((rc = run_map_split(w.tmp32, HEAD_CH[1], 3 * HEAD_CH[1], w.map6[1], (size_t)(Bt * P2 * 6 * HEAD_CH[1]), 3, B, F, HEAD_CH[1], true, st, E))) return rc;
+    }
+    for (int li = 1; li < 4; ++li) {   // conv2..4: blockIdx.y = tower, f32 outputs [tower][the slice's pixels][cout]
+        const int cin = HEAD_CH[li], cout = HEAD_CH[li + 1], rows = li == 1 ? 256 : (cout < 64 ? 64 : cout);
+        vbg::Args a{};
+        a.X = w.map6[li]; a.W = m->f32.wc[li].p; a.bias = m->bc[li].p; a.out = w.tmp32;
+        a.M = M; a.N = cout; a.K = 9 * 6 * cin; a.ldo = cout; a.C = 6 * cin; a.F = F;
+        a.gX = Bt * P2 * 6 * cin; a.gW = (long long)rows * 9 * 6 * cin; a.gBias = cout; a.gOut = (long long)M * cout;
+        if ((rc = conv(a, 3))) return rc;
+        if (li < 3 && (rc = run_map_split(w.tmp32, (size_t)M * cout, cout, w.map6[li + 1], (size_t)(Bt * P2 * 6 * cout), 3, B, F, cout, true, st, E))) return rc;
+    }
+    hipLaunchKernelGGL((vbf::conv5_f32_kernel<32>), dim3((M + 255) / 256), dim3(256), 0, st, w.tmp32, m->w5.p, m->b5.p, M, LX, (size_t)M * HEAD_CH[4], score, size,
+                       offset);
+    VB_HIP(hipGetLastError());
+    return VT_OK;
+}
+
 int stem(VbModel* m, const float* z, const float* x, int B, hipStream_t st, float* tokens_out, std::string* err, const Slice* sl) {
     const Err E{err};
     int rc = check(m, B, E);
     if (rc || (rc = check_slice(m, B, sl, E))) return rc;
+    if (m->precision == VT_PRECISION_FP32) {
+        const SliceView v(m, B, sl);
+        if ((rc = stem_rows_f32(m, Z_GIVEN, z, x, nullptr, B, st, v, E))) return rc;
+        if (tokens_out) VB_HIP(hipMemcpyAsync(tokens_out, v.resid, (size_t)B * m->L * m->C * 4, hipMemcpyDeviceToDevice, st));
+        return VT_OK;
+    }
     const int L = m->L, M = B * L, C = m->C;
     const SliceView v(m, B, sl);
     bf16* const patches = patch_operand(m, v);
@@ -777,11 +1122,14 @@ int set_template(VbModel* m, const float* z, int n, const int32_t* slots, hipStr
     int rc = check(m, n, E);
     if (rc) return rc;
     const int TZ = m->TZ;
-    const size_t zrow = (size_t)m->LZ * PATCH_K;
-    if (!slots) return patchify_dense(z, TZ, n, m->zop.p, st, E);
+    const bool f32 = m->precision == VT_PRECISION_FP32;      // the mode caches the expanded operand rows (vb_f32.h)
+    const size_t zrow = (size_t)m->LZ * PATCH_K * (f32 ? 6 : 1);
+    bf16* const zop = f32 ? m->f32.zop6.p : m->zop.p;
+    auto dense = [&](const float* img, int nf, bf16* P) { return f32 ? patchify_split(img, TZ, nf, P, st, E) : patchify_dense(img, TZ, nf, P, st, E); };
+    if (!slots) return dense(z, n, zop);
     for (int i = 0; i < n; ++i) {      // a frame's operand rows depend on that frame alone: straight into place
         if (slots[i] < 0 || slots[i] >= m->maxB) return E.fail(VT_ERR_ARG, "template slot outside the batch");
-        if ((rc = patchify_dense(z + (size_t)i * 3 * TZ * TZ, TZ, 1, m->zop.p + (size_t)slots[i] * zrow, st, E))) return rc;
+        if ((rc = dense(z + (size_t)i * 3 * TZ * TZ, 1, zop + (size_t)slots[i] * zrow))) return rc;
     }
     return VT_OK;
 }
@@ -795,6 +1143,13 @@ int stem_rows(VbModel* m, ZSrc zsrc, const float* z, const float* x, const unsig
     if (xu8 && (reinterpret_cast<uintptr_t>(xu8) & 15)) return E.fail(VT_ERR_ARG, "the uint8 patch must be 16-byte aligned on the ViT-Base path");
     const int L = m->L, LZ = m->LZ, LX = m->LX, C = m->C;
     const SliceView v(m, B, sl);
+    if (m->precision == VT_PRECISION_FP32) {
+        if ((rc = stem_rows_f32(m, zsrc, z, x, xu8, B, st, v, E))) return rc;
+        if (x_tokens_out)
+            VB_HIP(hipMemcpy2DAsync(x_tokens_out + (size_t)LZ * C, (size_t)L * C * 4, v.resid + (size_t)LZ * C, (size_t)L * C * 4, (size_t)LX * C * 4, B,
+                                    hipMemcpyDeviceToDevice, st));
+        return VT_OK;
+    }
     // B * LX dense rows inside the slice's B * L (as vb::stem's operand); in the hidden rows (narrow models) behind the B * LZ rows of a given template
     bf16* const xop = patch_operand(m, v) + (m->C >= PATCH_K ? (size_t)0 : (size_t)B * LZ * PATCH_K);
     const bf16* zop = m->zop.p + v.f0 * LZ * PATCH_K;
@@ -1014,6 +1369,8 @@ int blocks(VbModel* m, const float* tokens_in, int B, int nblocks, hipStream_t s
     if (rc || (rc = check_slice(m, B, sl, E))) return rc;
     const int C = m->C, HID = m->HID;
     const SliceView v(m, B, sl);
+    if (m->precision == VT_PRECISION_FP32)
+        return blocks_f32(m, tokens_in, B, (nblocks < 0 || nblocks > m->depth) ? m->depth : nblocks, st, feat_out, resid_out, v, E);
     CeWalk ce(m, v, B);      // ce.M: the slice's residual rows, B frames of L; behind a compacting stage, B frames of ce.Lc
     if (nblocks < 0 || nblocks > m->depth) nblocks = m->depth;
     if (tokens_in && tokens_in != v.resid)
@@ -1050,6 +1407,14 @@ int blocks(VbModel* m, const float* tokens_in, int B, int nblocks, hipStream_t s
 int gemm_form(const VbModel* m, int B) {
     const int M = B * m->L, C = m->C;
     int form = 0;
+    if (m->precision == VT_PRECISION_FP32) {      // the mode's launches: the qkv projection is always one GEMM of 3 C columns; conv1 of 768
+        if (narrow_pick(m, B * m->LX, C, 1, 0)) form |= VT_GEMM_PATCH;
+        if (narrow_pick(m, M, C, 1, 0)) form |= VT_GEMM_PROJ | VT_GEMM_FC2;
+        if (narrow_pick(m, M, 3 * C, 1, 0)) form |= VT_GEMM_QK;
+        if (narrow_pick(m, M, m->HID, 1, 0)) form |= VT_GEMM_FC1;
+        if (narrow_pick(m, B * m->LX, 3 * HEAD_CH[1], 1, 0)) form |= VT_GEMM_HEAD;
+        return form;
+    }
     if (narrow_pick(m, M, C, 1, 0)) form |= VT_GEMM_PATCH | VT_GEMM_PROJ | VT_GEMM_FC2;
     // the q | k projection is a GEMM of its own only outside the fused qkv + attention kernel (run_attention)
     if ((!m->fused_qkv || m->g384 || m->ce_first >= 0) && narrow_pick(m, M, 2 * C, 1, 0)) form |= VT_GEMM_QK;
@@ -1065,6 +1430,7 @@ int head(VbModel* m, const float* feat_in, int B, hipStream_t st, float* score, 
     if (rc || (rc = check_slice(m, B, sl, E))) return rc;
     const int LX = m->LX, F = m->F, M = B * LX, C = m->C;
     const SliceView v(m, B, sl);
+    if (m->precision == VT_PRECISION_FP32) return head_f32(m, feat_in, B, st, score, size, offset, v, E);
     const long long Bt = v.Bt, P2 = (long long)(F + 2) * (F + 2);              // tower-major buffers: [tower][Bt frames]...
     if (feat_in) {
         hipLaunchKernelGGL(vbm::feat_to_map_kernel, dim3(grid256((size_t)B * LX * (C / 4))), dim3(256), 0, st, feat_in, v.map[0], B, F, C);

@@ -1208,6 +1208,11 @@ int create_vitb(const vt_config* cfg, vt_model** out, bool family_vit = false) {
     vt_model* m = new vt_model();
     m->vb = vbm;
     if ((rc = init_model(m, cfg, true))) { vt_destroy(m); return rc; }
+    if (const char* p = std::getenv("VB_PRECISION"); p && *p) {      // the mode from the start, where no call chooses one (vt_set_precision)
+        const std::string v(p);
+        if (v != "fp32" && v != "bf16") { vt_destroy(m); return fail(VT_ERR_ARG, "VB_PRECISION=" + v + ": bf16 or fp32"); }
+        if (v == "fp32" && (rc = vb::set_precision(m->vb, VT_PRECISION_FP32, &err))) { vt_destroy(m); return fail(rc, err); }
+    }
     *out = m;
     return VT_OK;
 }
@@ -1603,6 +1608,27 @@ int vt_set_open_loop(vt_model* m, int32_t on) {
 int vt_gemm_form(const vt_model* m, int32_t B) {
     if (!m) return (void)fail(VT_ERR_ARG, "null model"), -1;
     return m->vb ? vb::gemm_form(m->vb, B) : 0;
+}
+
+static const char* const PRECISION_MODELS =
+    "the fp32-equivalent mode is implemented for the patch-16 ViT models: vt_create_vit, or the ViT-Base (768, 12) / ViT-Large (1024, 16) tuples of vt_create";
+
+int vt_set_precision(vt_model* m, int32_t precision) {
+    if (!m) return fail(VT_ERR_ARG, "null model");
+    if (!m->vb) return fail(VT_ERR_ARG, PRECISION_MODELS);
+    if (m->graphs_captured > 0)
+        return fail(VT_ERR_STATE, "captured graphs hold the routes and workspaces of their capture: set the precision before capturing");
+    std::string err;
+    const int before = vb::precision(m->vb);
+    if (int rc = vb::set_precision(m->vb, precision, &err)) return fail(rc, err);
+    if (before != precision) m->tmpl_frames = 0;      // the template cache holds the other mode's operand rows
+    return VT_OK;
+}
+
+int vt_precision(const vt_model* m) {
+    if (!m) return (void)fail(VT_ERR_ARG, "null model"), -1;
+    if (!m->vb) return -1;      // a query: another model family has no mode, and asking is no error
+    return vb::precision(m->vb);
 }
 
 int vt_crop_form(void) {

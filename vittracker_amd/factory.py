@@ -23,12 +23,15 @@ def network_builder(cfg):
     return build_ostrack_dist
 
 
-def build_network(cfg, max_batch: int = 1, ce_form=None):
-    """ce_form: the form a candidate-elimination backbone runs in (model_vitb.build_ostrack); the vit_48 family has none."""
+def build_network(cfg, max_batch: int = 1, ce_form=None, precision=None):
+    """ce_form: the form a candidate-elimination backbone runs in (model_vitb.build_ostrack); the vit_48 family has none.
+    precision: "bf16" | "fp32", the arithmetic mode of a patch-16 ViT model (model_vitb.build_ostrack); the vit_48 family has none."""
     from .model_vitb import build_ostrack
     builder = network_builder(cfg)
     if builder is build_ostrack:
-        return builder(cfg, max_batch=max_batch, ce_form=ce_form)
+        return builder(cfg, max_batch=max_batch, ce_form=ce_form, precision=precision)
+    if precision is not None:
+        raise ValueError(f"precision={precision!r}: the vit_48 family has no bf16 / fp32 mode (its library is chosen by native.Model(precision=))")
     if ce_form is not None:
         raise ValueError(f"ce_form={ce_form!r}: the vit_48 family has no candidate elimination")
     return builder(cfg, max_batch=max_batch)

@@ -64,14 +64,17 @@ def ce_template_rows(template_range: str, feat_sz_z: int):
 class OSTrack(OstrackDist):
     family = "vit"      # vt_create_vit: 384 / 6 and 192 / 3 are LeViT-stem vit_dist models under vt_create
 
-    def __init__(self, cfg, depth=None, max_batch=1, ce_form=None, small=False):
-        """small: build_small_ostrack's model -- TYPE vit_base_patch16_224_ce at depth 3 with the YAML's CHANNELS / HEADS, CE_LOC may be empty."""
+    def __init__(self, cfg, depth=None, max_batch=1, ce_form=None, small=False, precision=None):
+        """small: build_small_ostrack's model -- TYPE vit_base_patch16_224_ce at depth 3 with the YAML's CHANNELS / HEADS, CE_LOC may be empty.
+        precision: "bf16" | "fp32" (native.Model.set_precision: the fp32-equivalent mode on three-piece bf16 operands); None:
+        the environment variable VB_PRECISION, else "bf16".  The fp32 mode and a candidate-elimination backbone exclude each other."""
         g = geometry(cfg)
         if g["head_type"] != "CENTER":
             raise ValueError("HEAD TYPE %s is not supported." % g["head_type"])
         bb_type = str(cfg.MODEL.BACKBONE.TYPE)
         self.ce_loc, self.ce_keep_ratio, self.ce_rows = [], [], None
         self.ce_form = native.ce_form_name(ce_form)      # "masked" | "compact"; read by a candidate-elimination backbone only
+        self.precision = native.vit_precision_name(precision)
         if small:
             if bb_type != "vit_base_patch16_224_ce":
                 raise NotImplementedError(f"build_small_ostrack: backbone {cfg.MODEL.BACKBONE.TYPE!r}: only vit_base_patch16_224_ce (depth 3, CHANNELS / HEADS "
@@ -107,6 +110,9 @@ class OSTrack(OstrackDist):
         else:
             raise NotImplementedError(f"backbone {cfg.MODEL.BACKBONE.TYPE!r}: only vit_base_patch16_224, vit_base_patch16_224_ce, "
                                       "vit_large_patch16_224, vit_small_patch16_224 and vit_tiny_patch16_224 are implemented")
+        if self.precision == "fp32" and self.ce_loc:
+            raise NotImplementedError("precision 'fp32' and candidate elimination (CE_LOC %s) exclude each other: the fp32 mode ranks no tokens; "
+                                      "use TYPE vit_base_patch16_224 or precision 'bf16'" % self.ce_loc)
         if str(cfg.MODEL.BACKBONE.CAT_MODE) != "direct":
             raise NotImplementedError("only CAT_MODE 'direct' (template tokens first) is implemented")
         self.geom, self.depth, self.mode, self.head_type, self.max_batch = g, depth, "eval", "CENTER", max_batch
@@ -119,6 +125,8 @@ class OSTrack(OstrackDist):
     def _native(self) -> native.Model:
         fresh = self._nat is None
         nat = OstrackDist._native(self)
+        if fresh and nat.precision != self.precision:      # (VB_PRECISION has chosen at vt_create already; an explicit argument overrides it)
+            nat.set_precision(self.precision)
         if fresh and self.ce_loc:      # every entry point of the native model (forward, forward_u8, track_step*, captures) then runs with it
             nat.set_candidate_elimination(self.ce_loc, self.ce_keep_ratio, self.ce_rows, form=self.ce_form)
         return nat
@@ -174,18 +182,19 @@ class OSTrack(OstrackDist):
     __call__ = forward
 
 
-def build_ostrack(cfg, training=False, max_batch=1, ce_form=None):
-    """ce_form: "masked" | "compact", the form a candidate-elimination backbone runs in; None: VB_CE_FORM, else "masked"."""
+def build_ostrack(cfg, training=False, max_batch=1, ce_form=None, precision=None):
+    """ce_form: "masked" | "compact", the form a candidate-elimination backbone runs in; None: VB_CE_FORM, else "masked".
+    precision: "bf16" | "fp32" (the fp32-equivalent mode); None: VB_PRECISION, else "bf16"."""
     if training:
         raise NotImplementedError("inference graph only")
-    return OSTrack(cfg, max_batch=max_batch, ce_form=ce_form)
+    return OSTrack(cfg, max_batch=max_batch, ce_form=ce_form, precision=precision)
 
 
-def build_small_ostrack(cfg, training=False, max_batch=1, ce_form=None):
+def build_small_ostrack(cfg, training=False, max_batch=1, ce_form=None, precision=None):
     """The reference's build_small_ostrack (lib/models/ostrack/ostrack.py:288-342; its tracking/profile_model*.py and onnxexport.py build exactly
     this): TYPE vit_base_patch16_224_ce at depth 3, width / heads from MODEL.BACKBONE.CHANNELS / HEADS -- (192, 3), (384, 6) or (768, 12).  An
     empty CE_LOC is the plain depth-3 model; a non-empty one runs at width 768 through build_ostrack's candidate-elimination machinery and
     raises NotImplementedError at the small widths."""
     if training:
         raise NotImplementedError("inference graph only")
-    return OSTrack(cfg, max_batch=max_batch, ce_form=ce_form, small=True)
+    return OSTrack(cfg, max_batch=max_batch, ce_form=ce_form, small=True, precision=precision)

@@ -81,6 +81,8 @@ ABI = {
     "vt_set_candidate_elimination": (C.c_int, [_vp, _i32, C.POINTER(_i32), C.POINTER(C.c_double), _vp]),
     "vt_set_ce_form": (C.c_int, [_vp, _i32]),
     "vt_ce_result": (C.c_int, [_vp, _i32, _vp, _vp, _vp]),
+    "vt_set_precision": (C.c_int, [_vp, _i32]),
+    "vt_precision": (C.c_int, [_vp]),
 }
 # the three frame sources of the crops and of the step: a dense (B,H,W,3) batch (frames, H, W), a vt_frame table, a vt_image table
 for _sfx, _src in (("", [_vp, _i32, _i32]), ("_frames", [_vp]), ("_images", [_vp])):
@@ -333,6 +335,19 @@ def ce_form_name(form=None) -> str:
     return form
 
 
+#: the arithmetic modes of a patch-16 ViT model (include/vittrack.h VT_PRECISION_BF16 / VT_PRECISION_FP32)
+VIT_PRECISIONS = {"bf16": 0, "fp32": 1}
+
+
+def vit_precision_name(precision=None) -> str:
+    """The mode's name: `precision`, or without one the environment variable VB_PRECISION, or "bf16"."""
+    if precision is None:
+        precision = os.environ.get("VB_PRECISION") or "bf16"
+    if precision not in VIT_PRECISIONS:
+        raise VtError(f"ViT precision {precision!r}: one of {sorted(VIT_PRECISIONS)}")
+    return precision
+
+
 def ce_compact_lengths(len_z: int, len_x: int, keep_ratio):
     """Rows of a frame behind each stage in the compact form: template rows + kept search tokens, rounded up to 16
     (0.7, 0.7, 0.7: 256 / 192 / 160 at 64 + 256 tokens, 560 / 432 / 352 at 144 + 576)."""
@@ -417,7 +432,7 @@ class Model:
         (192, 3) ViT-Tiny, (384, 6) ViT-Small, (768, 12), (1024, 16), anything else refused."""
         if family not in (None, "vit"):
             raise ValueError(f"family={family!r}: None (vt_create's choice) or 'vit'")
-        self.precision, self.family = precision, family
+        self.contractions, self.family = precision, family      # the library: 'f32' | 'f16'
         self._L = lib(precision)
         self.cfg = VtConfig(template_size, search_size, channels, heads, depth, head_channels, stride, max_batch)
         h = C.c_void_p()
@@ -434,6 +449,24 @@ class Model:
         # the reference's torch float32 window, bit for bit (vt_create's libm one differs by ulps at F = 14, 16, 24)
         from .host_ops import hann2d
         self.set_window(hann2d((self.feat_sz, self.feat_sz)).numpy())
+
+    @property
+    def precision(self) -> str:
+        """A patch-16 ViT model: the arithmetic mode, "bf16" | "fp32" (vt_precision).  Any other model: the library's contractions,
+        'f32' | 'f16', as the constructor took them."""
+        v = int(self._L.vt_precision(self._h)) if getattr(self, "_h", None) else -1
+        return self.contractions if v < 0 else ("bf16", "fp32")[v]
+
+    def set_precision(self, precision: str):
+        """vt_set_precision: "bf16" (single-piece bf16 operands, the default) or "fp32" (three-piece bf16 operands, six terms per product,
+        fp32 activations: the reference's fp32 outputs to a few 1e-6).  Patch-16 ViT models only; not with candidate elimination; before
+        any capture.  Allocates the mode's workspaces the first time; drops the template cache."""
+        if precision not in VIT_PRECISIONS:
+            raise VtError(f"ViT precision {precision!r}: one of {sorted(VIT_PRECISIONS)}")
+        before = self.precision
+        _check(self._L.vt_set_precision(self._h, VIT_PRECISIONS[precision]), "vt_set_precision", self._L)
+        if before != precision:
+            self._tmpl_B = 0      # the cache held the other mode's operand rows
 
     def live_graphs(self) -> int:
         return sum(1 for g in self._graphs if g._valid)

@@ -25,4 +25,6 @@ def parameters(yaml_name: str, env=None):
     params.save_all_boxes = False
     #: candidate-elimination YAMLs: "masked" | "compact" (model_vitb.build_ostrack); None: the environment variable VB_CE_FORM, else "masked"
     params.ce_form = None
+    #: "bf16" | "fp32", the fp32-equivalent mode of the patch-16 ViT models (model_vitb.build_ostrack); None: VB_PRECISION, else "bf16"
+    params.precision = None
     return params

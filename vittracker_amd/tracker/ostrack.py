@@ -13,7 +13,8 @@ The candidate-elimination backbone (``vit_base_patch16_224_ce``, every published
 vitb_256_mae_ce_32x4_ep300.yaml`` / ``vitb_384_mae_ce_32x4_ep300.yaml``) runs through the same class: its ``box_mask_z``
 (``generate_mask_cond``, :57-62) is fixed per model from ``CE_TEMPLATE_RANGE`` when the network is built, so ``initialize()`` has nothing
 to generate.  ``params.ce_form`` (``"masked"`` | ``"compact"``, ``None``: the environment variable ``VB_CE_FORM``, else masked) picks the form the
-stages run in -- removed tokens as absent keys, or the kept tokens gathered into shorter frames -- with the same results.  Not implemented, as in :mod:`vittracker_amd.model_vitb`: ViT-Large CE, ``CE_TEMPLATE_RANGE: GT_BOX``, ``ce_keep_rate``,
+stages run in -- removed tokens as absent keys, or the kept tokens gathered into shorter frames -- with the same results.
+``params.precision`` (``"bf16"`` | ``"fp32"``, ``None``: ``VB_PRECISION``, else bf16) selects the fp32-equivalent mode of the plain backbones.  Not implemented, as in :mod:`vittracker_amd.model_vitb`: ViT-Large CE, ``CE_TEMPLATE_RANGE: GT_BOX``, ``ce_keep_rate``,
 ``MODEL.PROCESS.*`` and the debug visualisation (``removed_indexes_s`` is returned by the model's ``forward``; nothing draws it)."""
 from __future__ import annotations
 

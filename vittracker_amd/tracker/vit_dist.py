@@ -67,7 +67,7 @@ class Vit_dist(BaseTracker):
             # to the next one (initialize() resets all per-sequence state); objects alive at the same time get their own.
             key = (getattr(params, "checkpoint", None), bool(getattr(params, "allow_synthetic_weights", False)),
                    params.template_size, params.search_size, float(params.template_factor), float(params.search_factor),
-                   getattr(params, "yaml_name", None), getattr(params, "ce_form", None))
+                   getattr(params, "yaml_name", None), getattr(params, "ce_form", None), getattr(params, "precision", None))
             pool = _PIPELINES.setdefault(key, [])
             bt = pool.pop() if pool else BatchedVitTracker(params, 1)   # builds the network, loads the checkpoint, sets the Hann window
             bt.params = params
@@ -77,7 +77,7 @@ class Vit_dist(BaseTracker):
             self.network = self._bt.net
             self.output_window = hann2d(torch.tensor([self.feat_sz, self.feat_sz]).long(), centered=True).cuda()
             return
-        network = build_network(params.cfg, ce_form=getattr(params, "ce_form", None))
+        network = build_network(params.cfg, ce_form=getattr(params, "ce_form", None), precision=getattr(params, "precision", None))
         ckpt_path = getattr(params, "checkpoint", None)
         if ckpt_path and os.path.isfile(ckpt_path):
             network.load_state_dict(torch.load(ckpt_path, map_location="cpu")["net"], strict=False)  # :25
