@@ -9,7 +9,7 @@
 VARIANTS in tests/test_gpu_variants.py, VT_TRACK_U8=0, VT_GRAPH_CHAINS=2 and 3, and the crop forms tests/test_gpu_patch_u8.py forces
 (crop_bytes, crop_fast_off, crop_band_off, crop_band4, crop_band2, crop_band4_unaligned), and the ViT-Base attention routes the default never
 takes: vb_unfused (attn_kernel<320, 64>), vb_stream (attn_stream_kernel<320>), vb_nofold.  Configs: g128, g256, generic (112, 224), f16 (the f16
-build at G128, needs --f16), vitb, vitb384 (192 / 384, depth 12), vitbce, vitbce384 (candidate elimination, below).  Batches 1, 5, 7, 96, 256
+build at G128, needs --f16), vitb, vitb384 (192 / 384, depth 12), vitbce, vitbce384 (candidate elimination, below), vitpoints (below).  Batches 1, 5, 7, 96, 256
 (vitb 1, 96; vitb384 1, 5; vitbce, vitbce384 1, 5).  Entries: forward, forward on the cached template, forward_u8,
 capture + replay, track_step, track_step_frames, track_step_images (NV12, and I420 under BT.709: the other body of the band image kernel)
 -- four steps each for the tracker entries, so the state
@@ -18,7 +18,14 @@ refuses the case: both libraries must refuse with the same code.  Children run o
 
 vitbce / vitbce384: a depth-4 ViT-Base model with CE_LOC [0, 1, 2] and keep ratios 0.7 at either geometry, in the masked and the compact
 form, under CE_TEMPLATE_RANGE CTR_POINT (the plain score loop), ALL (the MFMA score) and ALL with VB_CE_SCORE_PLAIN=1 (the plain loop at 64 /
-144 rows); entries forward and capture + replay.  The hash covers the six outputs and both arrays of ce_result as bytes, NaN scores included."""
+144 rows); entries forward and capture + replay.  The hash covers the six outputs and both arrays of ce_result as bytes, NaN scores included.
+
+vitpoints: the patch-16 ViT at every model point -- shallow models (depth 2) at each of the four widths (192 / 3, 384 / 6, 768 / 12,
+1024 / 16), both geometries, both precisions (bf16, fp32), batches 1 and 3 (whatever --batches says).  Not among the default --configs (256
+cases per environment, and only the ViT path's own environments touch it): ask for it by name.  Entries: forward, forward_u8 with a
+given template, forward and forward_u8 on the cached template, set_template_slots followed by forward(None, x), capture + two replays, and the
+stage API stem -> blocks(tokens, nblocks=1, want_resid=True) -> blocks(resid) -> head(feat), every tensor it returns in the hash: that chain
+runs the LayerNorm kernels on outside tokens, the feature-to-map kernels on outside features and the final norm alone."""
 import argparse, json, os, subprocess, sys
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 KEYS = ("score_map", "size_map", "offset_map", "pred_boxes", "hann_boxes", "conf")
@@ -26,6 +33,8 @@ VITB_BATCHES = {"vitb": (1, 96), "vitb384": (1, 5), "vitbce": (1, 5), "vitbce384
 CE_GEOMS = {"vitbce": (128, 256), "vitbce384": (192, 384)}      # the candidate-elimination configs
 CE_LOC, CE_RATIO, CE_DEPTH = [0, 1, 2], [0.7, 0.7, 0.7], 4
 CE_RANGES = (("CTR_POINT", "0"), ("ALL", "0"), ("ALL", "1"))      # (CE_TEMPLATE_RANGE, VB_CE_SCORE_PLAIN: read when the model is created)
+# the vitpoints config: (channels, heads) of the four model points, the two geometries, the two precisions, its depth and batches
+POINTS, POINT_GEOMS, POINT_PRECISIONS, POINT_DEPTH, POINT_BATCHES = ((192, 3), (384, 6), (768, 12), (1024, 16)), ((128, 256), (192, 384)), ("bf16", "fp32"), 2, (1, 3)
 
 VITB_CHILD = r"""
 import sys, json, hashlib
@@ -113,9 +122,52 @@ def child(configs, batches):
                     case(tag + "capture", captured)
         os.environ.pop("VB_CE_SCORE_PLAIN", None)
 
+    def point_cases():
+        for (ch, heads), (tz, tx), prec in ((p, g, q) for p in POINTS for g in POINT_GEOMS for q in POINT_PRECISIONS):
+            sd = synth.synth_vitb_state_dict(26, C=ch, depth=POINT_DEPTH, heads=heads, len_z=(tz // 16) ** 2, len_x=(tx // 16) ** 2)
+            for B in POINT_BATCHES:
+                m = native.Model(tz, tx, channels=ch, heads=heads, depth=POINT_DEPTH, head_channels=256, max_batch=B, family="vit")
+                m.load_state_dict(sd)
+                m.set_precision(prec)
+                z, x = synth.synth_inputs(60 + B, B, tz, tx)
+                z2 = synth.synth_inputs(80 + B, B, tz, tx)[0]
+                zd, xd, z2d = torch.from_numpy(z).cuda(), torch.from_numpy(x).cuda(), torch.from_numpy(z2).cuda()
+                xp = torch.from_numpy(synth.synth_patches(9 + B, B, tx)).cuda()
+                tag = f"vitpoints/{ch}/{tz}-{tx}/{prec}/B{B}/"
+                case(tag + "forward", lambda: digest(m.forward(zd, xd)))
+                case(tag + "forward_u8_given", lambda: digest(m.forward_u8(zd, xp)))
+                case(tag + "set_template", lambda: m.set_template(zd) or "ok")
+                case(tag + "forward_cached", lambda: digest(m.forward(None, xd)))
+                case(tag + "forward_u8", lambda: digest(m.forward_u8(None, xp)))
+
+                def slots():      # the last slot alone takes another template
+                    m.set_template_slots(z2d[B - 1:], [B - 1])
+                    return digest(m.forward(None, xd))
+                case(tag + "template_slots", slots)
+
+                def stages():
+                    tok = m.stem(zd, xd)
+                    feat1, resid = m.blocks(tok, nblocks=1, want_resid=True)
+                    feat = m.blocks(resid)
+                    return digest(m.head(feat), tok, feat1, resid, feat)
+                case(tag + "stages", stages)
+
+                def captured():
+                    g, out = m.capture(zd, xd)
+                    g.launch()
+                    g.launch()
+                    h = digest(out)
+                    del g
+                    return h
+                case(tag + "capture", captured)
+                m.close()
+
     for cfg in configs:
         if cfg in CE_GEOMS:
             ce_cases(cfg)
+            continue
+        if cfg == "vitpoints":
+            point_cases()
             continue
         tz, tx = {"g128": (64, 128), "g256": (128, 256), "generic": (112, 224), "f16": (64, 128), "vitb": (128, 256), "vitb384": (192, 384)}[cfg]
         if cfg in VITB_BATCHES:

@@ -29,6 +29,7 @@
 // chain or two.
 #pragma once
 #include "vb_attn.h"
+#include "vb_misc.h"
 
 namespace vbc {
 
@@ -282,7 +283,7 @@ __global__ __launch_bounds__(256) void ce_select_kernel(const float* __restrict_
 // zeros.  Grid-stride over (frame, search token, 4 channels).
 __global__ __launch_bounds__(256) void ce_zero_rows_kernel(const uint32_t* __restrict__ bits, bf16* __restrict__ map, float* __restrict__ feat, int B, int L,
                                                            int Lz, int F, int C) {
-    const int Lx = L - Lz, W = (L + 31) / 32, C4 = C / 4, P = F + 2;
+    const int Lx = L - Lz, W = (L + 31) / 32, C4 = C / 4;
     const size_t total = (size_t)B * Lx * C4;
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
         const int c = (int)(i % C4) * 4;
@@ -290,7 +291,7 @@ __global__ __launch_bounds__(256) void ce_zero_rows_kernel(const uint32_t* __res
         const int t = (int)(row % Lx), f = (int)(row / Lx);
         if (key_present(bits + (size_t)f * W, Lz + t)) continue;
         const int y = t / F, x = t - y * F;
-        *reinterpret_cast<bf16x4*>(map + ((size_t)(f * P + y + 1) * P + x + 1) * C + c) = bf16x4{(bf16)0.f, (bf16)0.f, (bf16)0.f, (bf16)0.f};
+        *reinterpret_cast<bf16x4*>(map + vbm::map_px(f, y, x, F, C) + c) = bf16x4{(bf16)0.f, (bf16)0.f, (bf16)0.f, (bf16)0.f};
         if (feat) st4(feat + row * C + c, splat4(0.f));
     }
 }
@@ -413,7 +414,7 @@ template <int C>
 __global__ __launch_bounds__(256) void ce_final_norm_kernel(const float* __restrict__ resid, const float* __restrict__ gamma, const float* __restrict__ beta,
                                                             float eps, const int32_t* __restrict__ inv, int B, int Lp, int Lz, int Lx, int F,
                                                             bf16* __restrict__ map, float* __restrict__ feat) {
-    constexpr int NV = C / 256;
+    constexpr int NV = vbm::ln_slots<C, 4>();
     const int lane = threadIdx.x & 63;
     const long long o = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (o >= (long long)B * Lx) return;
@@ -421,39 +422,18 @@ __global__ __launch_bounds__(256) void ce_final_norm_kernel(const float* __restr
     const int p = inv[o];
     f4 y[NV];
     if (p >= 0) {
-        const float* r = resid + ((size_t)f * Lp + Lz + p) * C;
-        float s = 0.f;
+        const vbm::LnStats st = vbm::ln_row<C, 4, false>(resid + ((size_t)f * Lp + Lz + p) * C, lane, eps, y, [](int, int, f4) {});
 #pragma unroll
-        for (int i = 0; i < NV; ++i) {
-            y[i] = ld4(r + i * 256 + lane * 4);
-            s += hsum4(y[i]);
-        }
-#pragma unroll
-        for (int k = 32; k > 0; k >>= 1) s += __shfl_xor(s, k);
-        const float mean = s * (1.0f / C);
-        float ss = 0.f;
-#pragma unroll
-        for (int i = 0; i < NV; ++i) {
-            y[i] = y[i] - splat4(mean);
-            ss += hsum4(y[i] * y[i]);
-        }
-#pragma unroll
-        for (int k = 32; k > 0; k >>= 1) ss += __shfl_xor(ss, k);
-        const float rstd = 1.0f / sqrtf(ss * (1.0f / C) + eps);
-#pragma unroll
-        for (int i = 0; i < NV; ++i) {
-            const int c = i * 256 + lane * 4;
-            y[i] = y[i] * splat4(rstd) * ld4(gamma + c) + ld4(beta + c);
-        }
+        for (int i = 0; i < NV; ++i) y[i] = vbm::ln_affine<4>(y[i], st.rstd, gamma, beta, vbm::ln_col<4>(i, lane));
     } else {
 #pragma unroll
         for (int i = 0; i < NV; ++i) y[i] = splat4(0.f);
     }
-    const int yy = tt / F, xx = tt - yy * F, P = F + 2;
+    const int yy = tt / F, xx = tt - yy * F;
 #pragma unroll
     for (int i = 0; i < NV; ++i) {
-        const int c = i * 256 + lane * 4;
-        *reinterpret_cast<bf16x4*>(map + ((size_t)(f * P + yy + 1) * P + xx + 1) * C + c) = vbg::to_bf16x4(y[i]);
+        const int c = vbm::ln_col<4>(i, lane);
+        *reinterpret_cast<bf16x4*>(map + vbm::map_px(f, yy, xx, F, C) + c) = vbg::to_bf16x4(y[i]);
         if (feat) st4(feat + (size_t)o * C + c, y[i]);
     }
 }

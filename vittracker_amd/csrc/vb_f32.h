@@ -36,8 +36,7 @@ __global__ __launch_bounds__(256) void patchify_split_kernel(const float* __rest
         const int ch = (int)(i % 96);
         const size_t m = i / 96;
         const int t = (int)(m % Lk), f = (int)(m / Lk);
-        const int c = ch >> 5, r = (ch >> 1) & 15, s0 = (ch & 1) * 8, py = t / g, px = t - py * g;
-        const float* src = img + (((size_t)f * 3 + c) * T + py * 16 + r) * T + px * 16 + s0;
+        const float* src = vbm::crop_patch_src(img, T, g, f, t, ch);
         vbm::store_split8(P + m * (6 * 768), 768, ch * 8, ld4(src), ld4(src + 4));
     }
 }
@@ -45,38 +44,19 @@ __global__ __launch_bounds__(256) void patchify_split_kernel(const float* __rest
 // vbm::patchify_u8_kernel's operand for the mode: P[m][3 x 768] = [b | b | b], b = bf16(byte) (exact, uncentred: the weights' three pieces
 // carry Preprocessor.process to fp32 accuracy, so there is no rounding for a common mode to meet).  Same thread layout.
 __global__ __launch_bounds__(256) void patchify_u8_split_kernel(const unsigned char* __restrict__ xp, bf16* __restrict__ P, int B, int T) {
-    typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
     const int g = T / 16, Lx = g * g;
     const size_t total = (size_t)B * Lx * 16;
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
         const int r = (int)(i & 15);
         const size_t m = i >> 4;
-        const int t = (int)(m % Lx), py = t / g, px = t - py * g;
-        const size_t f = m / Lx;
-        const u32x4* src = reinterpret_cast<const u32x4*>(xp + ((f * T + py * 16 + r) * T + px * 16) * 3);
-        unsigned w[12];
-#pragma unroll
-        for (int j = 0; j < 3; ++j) {
-            const u32x4 v = __builtin_nontemporal_load(src + j);
-            w[4 * j] = v.x; w[4 * j + 1] = v.y; w[4 * j + 2] = v.z; w[4 * j + 3] = v.w;
-        }
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            unsigned o[8];
-#pragma unroll
-            for (int s = 0; s < 16; s += 2) {
-                const int k0 = 3 * s + c, k1 = k0 + 3;
-                const float v0 = (float)((w[k0 >> 2] >> (8 * (k0 & 3))) & 255u);
-                const float v1 = (float)((w[k1 >> 2] >> (8 * (k1 & 3))) & 255u);
-                o[s >> 1] = __builtin_amdgcn_perm(__float_as_uint(v1), __float_as_uint(v0), 0x07060302u);
-            }
+        vbm::u8_row_unpack(xp, T, g, Lx, m, r, 0.f, [&](int c, vbg::u32x4 lo, vbg::u32x4 hi) {
 #pragma unroll
             for (int seg = 0; seg < 3; ++seg) {
-                u32x4* dst = reinterpret_cast<u32x4*>(P + m * (3 * 768) + seg * 768 + c * 256 + r * 16);
-                dst[0] = u32x4{o[0], o[1], o[2], o[3]};
-                dst[1] = u32x4{o[4], o[5], o[6], o[7]};
+                vbg::u32x4* dst = reinterpret_cast<vbg::u32x4*>(P + m * (3 * 768) + seg * 768 + c * 256 + r * 16);
+                dst[0] = lo;
+                dst[1] = hi;
             }
-        }
+        });
     }
 }
 
@@ -194,13 +174,13 @@ __global__ __launch_bounds__(256) void map_split_kernel(const float* __restrict_
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
         const int c = (int)(i % per) * 8;
         const size_t px = i / per;
-        const int x = (int)(px % F), y = (int)((px / F) % F), b = (int)(px / ((size_t)F * F)), P = F + 2;
+        const int x = (int)(px % F), y = (int)((px / F) % F), b = (int)(px / ((size_t)F * F));
         f4 u = ld4(src + px * ld + c), v = ld4(src + px * ld + c + 4);
         if (relu) {
             u = f4{fmaxf(u.x, 0.f), fmaxf(u.y, 0.f), fmaxf(u.z, 0.f), fmaxf(u.w, 0.f)};
             v = f4{fmaxf(v.x, 0.f), fmaxf(v.y, 0.f), fmaxf(v.z, 0.f), fmaxf(v.w, 0.f)};
         }
-        vbm::store_split8(dst + ((size_t)(b * P + y + 1) * P + x + 1) * 6 * C, C, c, u, v);
+        vbm::store_split8(dst + vbm::map_px(b, y, x, F, 6 * C), C, c, u, v);
     }
 }
 
@@ -209,36 +189,7 @@ template <int CW>
 __global__ __launch_bounds__(256) void conv5_f32_kernel(const float* __restrict__ t4, const float* __restrict__ w5, const float* __restrict__ b5,
                                                         int npix_total, int FF, size_t tower_stride, float* __restrict__ score,
                                                         float* __restrict__ size, float* __restrict__ offset) {
-    __shared__ float sw[5 * CW + 5];
-    for (int i = threadIdx.x; i < 5 * CW + 5; i += 256) sw[i] = i < 5 * CW ? w5[i] : b5[i - 5 * CW];
-    __syncthreads();
-    const int p = blockIdx.x * 256 + threadIdx.x;
-    if (p >= npix_total) return;
-    float o[5];
-#pragma unroll
-    for (int j = 0; j < 5; ++j) o[j] = sw[5 * CW + j];
-#pragma unroll
-    for (int tw = 0; tw < 3; ++tw) {
-        const float* src = t4 + (size_t)tw * tower_stride + (size_t)p * CW;
-#pragma unroll
-        for (int c4 = 0; c4 < CW / 4; ++c4) {
-            const f4 v = ld4(src + c4 * 4);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const float a = fmaxf(v[e], 0.f);
-                const int c = c4 * 4 + e;
-                if (tw == 0) o[0] = fmaf(a, sw[0 * CW + c], o[0]);
-                if (tw == 1) { o[1] = fmaf(a, sw[1 * CW + c], o[1]); o[2] = fmaf(a, sw[2 * CW + c], o[2]); }
-                if (tw == 2) { o[3] = fmaf(a, sw[3 * CW + c], o[3]); o[4] = fmaf(a, sw[4 * CW + c], o[4]); }
-            }
-        }
-    }
-    const int b = p / FF, px = p - b * FF;
-    score[p] = sigmoid_clamped(o[0]);
-    offset[((size_t)b * 2 + 0) * FF + px] = o[1];
-    offset[((size_t)b * 2 + 1) * FF + px] = o[2];
-    size[((size_t)b * 2 + 0) * FF + px] = sigmoid_clamped(o[3]);
-    size[((size_t)b * 2 + 1) * FF + px] = sigmoid_clamped(o[4]);
+    vbm::conv5_body<CW, float, true>(t4, w5, b5, npix_total, FF, tower_stride, score, size, offset);
 }
 
 }  // namespace vbf

@@ -3,13 +3,15 @@
 // three attention kernels vb_attn.h, vb_qkvattn.h, vb_attn_stream.h (the 384 geometry's), whose shared arithmetic lives in vb_attn.h;
 // vb_ce.h: OSTrack candidate elimination by key masking or compacted (the stages' score / select / gather kernels; vb::blocks routes them).
 // vb_f32.h: the fp32-equivalent mode (vb::set_precision): the same GEMM kernel on operands expanded to six bf16 k-ranges, f32 activations, f32
-// attention and head tail; stem_rows_f32 / blocks_f32 / head_f32 below are its three routes, ModeF32 its workspaces and weight images.
+// attention and head tail; blocks_f32 / head_f32 below are its routes (the stem shares run_stem_rows with the bf16 mode: StemRoute holds what
+// differs), ModeF32 its workspaces and weight images, for_chunks its launches below the GEMMs' 32-bit operand offsets.
 // Reached through the same C ABI as the vit_48 path (vt_create with channels = 768, or the ViT-Large tuple at channels = 1024; vt_create_vit for
 // those two and for ViT-Small 384 / 6 and ViT-Tiny 192 / 3).  The model points differ in width, head count and hidden width alone (VbModel::C /
-// HEADS / HID); the kernels take them at run time except the three that compile the width in (dispatch_width below).  What the two small
+// HEADS / HID, a row of POINTS); the kernels take them at run time except the three that compile the width in (dispatch_width below).  What the two small
 // widths need beyond that: launch_wide (an odd number of k-tiles), tile_pad (N no multiple of 256), patch_operand (rows shorter than 768).
 // Layout of this file: Buf owns device memory (a model is freed by deleting it); Hooks holds the experiment switches, read once;
-// SliceView holds what a frame slice addresses, built once per entry; run_attention launches one of the four attention forms.
+// SliceView holds what a frame slice addresses, built once per entry; run_attention launches one of the four attention forms;
+// alloc_workspaces allocates a model's (or the fp32 mode's) workspaces, all or none.
 #include "vb_api.h"
 
 #include <algorithm>
@@ -31,10 +33,26 @@ using vbg::bf16;
 namespace {
 
 constexpr int HD = 64, PATCH_K = 768, HW = 256 /* head width */;
-// the two model points (lib/models/ostrack/vit.py:393-400): width, heads of 64, MLP width = 4 x width
-constexpr int C_BASE = 768, HEADS_BASE = 12, C_LARGE = 1024, HEADS_LARGE = 16;
-// the small patch-16 students (build_small_ostrack, lib/models/ostrack/ostrack.py:288-342; timm's DeiT-Small / DeiT-Tiny): vb::create_vit only
-constexpr int C_SMALL = 384, HEADS_SMALL = 6, C_TINY = 192, HEADS_TINY = 3;
+// The model points: width, heads of 64 (the MLP width is 4 x width), the deepest model admitted, the heads the fused qkv + attention kernel
+// walks together, and the name the refusals use.  ViT-Base / ViT-Large: lib/models/ostrack/vit.py:393-400, the two vt_create knows.  The
+// small patch-16 students (build_small_ostrack, lib/models/ostrack/ostrack.py:288-342; timm's DeiT-Small / DeiT-Tiny): vb::create_vit only.
+// hgroup: 6 of 12 heads measured best at width 768 (vb_qkvattn.h); 16 heads of width 1024 take 4, the divisor whose group of weight rows
+// (4 x 384 KiB) is nearest to that one's (6 x 288 KiB); ViT-Small / ViT-Tiny all 6 / 3 heads of a frame together -- their whole qkv matrix,
+// 864 / 216 KiB, is smaller than one such group.  max_depth is what the refusals check, and vt_create's ViT-Base tuple is refused by no
+// depth of its own (vb::create): that row's 24 is what build_model admits for any model.
+struct ModelPoint {
+    int C, heads, max_depth, hgroup;
+    bool vt_create;
+    const char* name;
+};
+constexpr ModelPoint POINTS[] = {{768, 12, 24, 6, true, "ViT-Base"}, {1024, 16, 24, 4, true, "ViT-Large"}, {384, 6, 12, 6, false, "ViT"}, {192, 3, 12, 3, false, "ViT"}};
+constexpr int NPOINTS = sizeof(POINTS) / sizeof(POINTS[0]);
+constexpr int C_BASE = POINTS[0].C, C_LARGE = POINTS[1].C, C_SMALL = POINTS[2].C, C_TINY = POINTS[3].C;      // (names for the kernel lists below)
+const ModelPoint* model_point(int C) {
+    for (const ModelPoint& p : POINTS)
+        if (p.C == C) return &p;
+    return nullptr;
+}
 // The two geometries (template / search crop -> tokens at stride 16): OSTrack-256 = 128 / 256 -> 64 + 256 = 320, OSTrack-384 = 192 / 384 ->
 // 144 + 576 = 720.  The model carries its own (VbModel::L, LZ, LX, F, TZ, TX); the token counts below are the attention kernels' template arguments.
 constexpr int L256 = 320, L384 = 720;
@@ -43,6 +61,11 @@ constexpr float LN_EPS = 1e-6f;
 // (the sweep of tools/vitb_latency.py)
 constexpr int NARROW_FILL = 33;
 constexpr int HEAD_CH[5] = {0 /* the model's width: VbModel::head_ch */, 256, 128, 64, 32};
+// Weight rows per tower of the head's conv li + 1 (cout output channels).  conv1: towers along N (K = 9 x the model's width), no padding.
+// conv2 (N = 128 per tower, K = 2304) runs on the 256 x 256 software-pipelined tile, one group per tower, with its weight rows zero-padded
+// to 256 (half of every MFMA column block is padding, and it still beats the two-buffer 256 x 64 loop: 268 -> ~180 us, round 5); conv3 /
+// conv4 keep the narrow tile (BN = 64: rows padded to 64)
+constexpr int head_rows(int li, int cout) { return li == 0 ? cout : (li == 1 ? 256 : (cout < 64 ? 64 : cout)); }
 
 struct Err {
     std::string* e;
@@ -73,6 +96,44 @@ struct Buf {      // owns its device memory; movable (std::vector<BlockW> is res
     hipError_t alloc(size_t count) { n = count; return hipMalloc(reinterpret_cast<void**>(&p), count * sizeof(T)); }
     void release() { if (p) (void)hipFree(p); p = nullptr; }
 };
+
+// One workspace of a list (alloc_workspaces): a Buf of any element type, its element count, whether it starts zero-filled
+struct WsBuf {
+    void** p;
+    size_t* n;
+    size_t count, elem;
+    bool zero;
+    template <typename T>
+    WsBuf(Buf<T>& b, size_t count, bool zero = false) : p(reinterpret_cast<void**>(&b.p)), n(&b.n), count(count), elem(sizeof(T)), zero(zero) {}
+};
+struct KernelLds { const void* kernel; int lds; };      // a kernel and the dynamic LDS it is launched with
+template <typename K>
+const void* kernel_ptr(K kernel) { return reinterpret_cast<const void*>(kernel); }
+
+// Allocates every workspace of the list, zero-fills the marked ones and raises the kernels' dynamic LDS limit.  All or none: the first
+// error is returned, with every buffer of the list released.  *bytes (optional): the bytes asked for.
+hipError_t alloc_workspaces(std::initializer_list<WsBuf> bufs, std::initializer_list<KernelLds> kernels, size_t* bytes = nullptr) {
+    hipError_t e = hipSuccess;
+    for (const WsBuf& w : bufs) {
+        if (bytes) *bytes += w.count * w.elem;
+        if (e == hipSuccess) {
+            *w.n = w.count;
+            e = hipMalloc(w.p, w.count * w.elem);
+        }
+    }
+    for (const WsBuf& w : bufs)
+        if (w.zero && e == hipSuccess) e = hipMemset(*w.p, 0, w.count * w.elem);
+    for (const KernelLds& k : kernels)
+        if (e == hipSuccess) e = hipFuncSetAttribute(k.kernel, hipFuncAttributeMaxDynamicSharedMemorySize, k.lds);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        for (const WsBuf& w : bufs) {
+            if (*w.p) (void)hipFree(*w.p);
+            *w.p = nullptr;
+        }
+    }
+    return e;
+}
 
 struct BlockW {
     Buf<float> ln1g, ln1b, ln2g, ln2b, bqkv, bproj, b1, b2;
@@ -107,7 +168,7 @@ struct ModeF32 {
 struct VbModel {
     vt_config cfg{};
     int depth = 12, maxB = 0;
-    int C = C_BASE, HEADS = HEADS_BASE, HID = 4 * C_BASE;      // width, heads, MLP width: ViT-Base, or 1024 / 16 / 4096 (ViT-Large)
+    int C = POINTS[0].C, HEADS = POINTS[0].heads, HID = 4 * POINTS[0].C;      // width, heads, MLP width: a row of POINTS
     int head_ch(int i) const { return i ? HEAD_CH[i] : C; }    // channels of the head's map i
     int stat_p() const { return C / 64; }      // (sum, M2) pairs per residual row: one per 64-column wave slice of the 256-wide GEMM tiles
     int TZ = 128, TX = 256, LZ = 64, LX = 256, L = 320, F = 16;      // crop sides, template / search / all tokens per frame, head map side
@@ -180,12 +241,18 @@ int need(const vb::TensorMap& tm, const std::string& name, int64_t numel, const 
     return VT_OK;
 }
 
+// d holds `count` elements afterwards: reallocated if its size was another
 template <typename T>
-int upload(Buf<T>& d, const void* h, size_t count, const Err& E) {
+int ensure(Buf<T>& d, size_t count, const Err& E) {
     if (!d.p || d.n != count) {
         d.release();
         VB_HIP(d.alloc(count));
     }
+    return VT_OK;
+}
+template <typename T>
+int upload(Buf<T>& d, const void* h, size_t count, const Err& E) {
+    if (int rc = ensure(d, count, E)) return rc;
     VB_HIP(hipMemcpy(d.p, h, count * sizeof(T), hipMemcpyHostToDevice));
     return VT_OK;
 }
@@ -275,13 +342,13 @@ int launch_gemm(const vbg::Args& a, int groups, hipStream_t st, const Err& E, in
 }
 
 // The kernels that compile the width in (vbm::layernorm_kernel<C>, vbm::ln_finalize_kernel<C / 64>, the fused qkv + attention kernel): f
-// is called with the model's width as a std::integral_constant.  vb::create / vb::create_vit admit no fifth width.
-template <typename F>
+// is called with the model's width as a std::integral_constant: the row of POINTS with that width.  vb::create / vb::create_vit admit no other
+// (a width outside the table would run the last row's instantiation).
+template <int I = 0, typename F>
 void dispatch_width(int C, F&& f) {
-    if (C == C_LARGE) f(std::integral_constant<int, C_LARGE>{});
-    else if (C == C_SMALL) f(std::integral_constant<int, C_SMALL>{});
-    else if (C == C_TINY) f(std::integral_constant<int, C_TINY>{});
-    else f(std::integral_constant<int, C_BASE>{});
+    if constexpr (I + 1 < NPOINTS)
+        if (C != POINTS[I].C) return dispatch_width<I + 1>(C, f);
+    f(std::integral_constant<int, POINTS[I].C>{});
 }
 
 // The kernels that compile the frame length in (the streaming attention and the candidate-elimination scores on full frames): f is called
@@ -322,9 +389,6 @@ int launch_tile(const VbModel* m, const vbg::Args& a, int groups, hipStream_t st
     // 256 x 64 on the two-buffer loop -- measured SLOWER, 6.94 against 6.42 ms and 3.37 against 3.02 ms per step of 256 frames: NOTES.md)
     return launch_wide<AMODE, EPI>(a, groups, st, E, cus);
 }
-
-template <typename K>
-const void* kernel_ptr(K kernel) { return reinterpret_cast<const void*>(kernel); }
 
 // rows: the residual rows when they are not B frames of L (the compact form of candidate elimination; then no map / feat)
 int run_layernorm(const VbModel* m, const float* resid, const float* g, const float* b, int B, hipStream_t st, bf16* xn, bf16* map, float* feat,
@@ -396,12 +460,35 @@ void fold_layernorm(std::vector<float>& w, std::vector<float>& b, const float* g
 }
 
 // Preprocessor.process (lib/test/tracker/data_utils.py:11-17: / 255, - mean, / std) folded into the patch embedding of the uint8 search
-// patch, in double.  The operand is the CENTRED byte p - ctr (vbm::patchify_u8_kernel, ctr = 128):
-//     W'[n][c,r,s] = W[n][c,r,s] / (255 std_c),      b'[n] = b[n] - sum W mean_c / std_c + ctr sum W'
-// with the bias from the UNROUNDED W'.  What the bf16 rounding of W' then multiplies is p - 128 instead of p: uncentred, the rounding
-// errors of a row of W' meet a common mode of ~2 sigma of the patch and the tokens leave the 3.2e-3 the stage is held to (3.3e-3 on
-// noise patches; centred 1.7e-3; the fp32 route 2.3-2.6e-3: NOTES R7-1, tests/test_vitb_track_host.py).  Compensating with the ROUNDED
-// weights instead is algebraically the uncentred form again.  The centring table of the search rows (Args::cm) follows b'.
+// patch, in double: against the byte p itself
+//     W'[n][c,r,s] = W[n][c,r,s] / (255 std_c),      b'[n] = b[n] - sum W mean_c / std_c
+// and wsum[n] = sum W'[n][.] from the UNROUNDED W': what an operand p - ctr adds to the bias, ctr wsum[n].  Both images of the uint8 patch
+// weights are built from it (fold_patch_u8: bf16, centred; build_f32_patch_u8: three pieces, uncentred).
+struct PatchFold {
+    std::vector<float> w;              // W' [C][PATCH_K]
+    std::vector<double> bias, wsum;    // [C]
+};
+PatchFold fold_preprocessor(const VbModel* m) {
+    const int C = m->C;
+    PatchFold f{std::vector<float>((size_t)C * PATCH_K), std::vector<double>(C), std::vector<double>(C)};
+    double k255[3], ms[3];
+    for (int c = 0; c < 3; ++c) { k255[c] = 1.0 / (255.0 * (double)m->norm_std[c]); ms[c] = (double)m->norm_mean[c] / (double)m->norm_std[c]; }
+    for (int n = 0; n < C; ++n) {
+        const float* row = m->h_wpatch.data() + (size_t)n * PATCH_K;
+        double sm = 0, sw = 0;
+        for (int k = 0; k < PATCH_K; ++k) {
+            const int c = k >> 8;
+            const double wd = (double)row[k] * k255[c];
+            sm += (double)row[k] * ms[c];
+            sw += wd;
+            f.w[(size_t)n * PATCH_K + k] = (float)wd;
+        }
+        f.bias[n] = (double)m->h_bpatch[n] - sm;
+        f.wsum[n] = sw;
+    }
+    return f;
+}
+
 // The patch GEMM's centring constants, [L]: a token row is patches W^T + bias + pos row; what is known of its mean before the GEMM runs is
 // mean(bias) + mean(pos row) (the projection of a normalised patch is zero-mean over channels to first order).  bias_sum: over channels
 int upload_centring(Buf<float>& d, const std::vector<float>& pos, int C, double bias_sum, const Err& E) {
@@ -417,14 +504,9 @@ int upload_centring(Buf<float>& d, const std::vector<float>& pos, int C, double 
 // ---- the fp32-equivalent mode: weight images and workspaces
 // an f32 tensor [rows][K] as its expanded image [rows + pad_rows zero rows][terms K] (vbf::expand_weight_kernel), through a staging upload
 int expand_upload(Buf<bf16>& d, const float* h, size_t rows, int K, int terms, size_t pad_rows, const Err& E) {
-    const size_t n = (rows + pad_rows) * terms * K;
-    if (!d.p || d.n != n) {
-        d.release();
-        VB_HIP(d.alloc(n));
-    }
     Buf<float> stage;
-    VB_HIP(stage.alloc(rows * K));
-    VB_HIP(hipMemcpy(stage.p, h, rows * K * sizeof(float), hipMemcpyHostToDevice));
+    int rc;
+    if ((rc = ensure(d, (rows + pad_rows) * terms * K, E)) || (rc = upload(stage, h, rows * K, E))) return rc;
     if (pad_rows) VB_HIP(hipMemset(d.p + rows * terms * K, 0, pad_rows * terms * K * sizeof(bf16)));
     hipLaunchKernelGGL(vbf::expand_weight_kernel, dim3(grid256(rows * K / 4)), dim3(256), 0, 0, stage.p, d.p, rows, K, terms);
     VB_HIP(hipGetLastError());
@@ -433,23 +515,12 @@ int expand_upload(Buf<bf16>& d, const float* h, size_t rows, int K, int terms, s
 }
 size_t pad_rows256(int N) { return (size_t)((N + 255) / 256 * 256 - N); }
 
-// Preprocessor.process folded into the uint8 form of the patch weights as fold_patch_u8 does, for the mode: uncentred (the operand is the
-// byte itself, exact in one piece) and kept to fp32 by the three weight pieces
+// The uint8 form of the patch weights for the mode: uncentred (the operand is the byte itself, exact in one piece) and kept to fp32 by the
+// three weight pieces
 int build_f32_patch_u8(VbModel* m, const Err& E) {
-    const int C = m->C;
-    std::vector<float> w((size_t)C * PATCH_K), b(C);
-    double k255[3], ms[3];
-    for (int c = 0; c < 3; ++c) { k255[c] = 1.0 / (255.0 * (double)m->norm_std[c]); ms[c] = (double)m->norm_mean[c] / (double)m->norm_std[c]; }
-    for (int n = 0; n < C; ++n) {
-        const float* row = m->h_wpatch.data() + (size_t)n * PATCH_K;
-        double sm = 0;
-        for (int k = 0; k < PATCH_K; ++k) {
-            sm += (double)row[k] * ms[k >> 8];
-            w[(size_t)n * PATCH_K + k] = (float)((double)row[k] * k255[k >> 8]);
-        }
-        b[n] = (float)((double)m->h_bpatch[n] - sm);
-    }
-    if (int rc = expand_upload(m->f32.wpatch_u8, w.data(), C, PATCH_K, 3, pad_rows256(C), E)) return rc;
+    const PatchFold f = fold_preprocessor(m);
+    const std::vector<float> b(f.bias.begin(), f.bias.end());
+    if (int rc = expand_upload(m->f32.wpatch_u8, f.w.data(), m->C, PATCH_K, 3, pad_rows256(m->C), E)) return rc;
     return upload_f32(m->f32.bpatch_u8, b.data(), b.size(), E);
 }
 
@@ -479,55 +550,39 @@ int alloc_f32_ws(VbModel* m, const Err& E) {
     ModeF32& f = m->f32;
     if (f.ws) return VT_OK;
     const size_t B = (size_t)m->maxB, M = B * m->L, C = (size_t)m->C, HID = (size_t)m->HID, LX = (size_t)m->LX, P2 = (size_t)(m->F + 2) * (m->F + 2);
-    const std::pair<Buf<bf16>*, size_t> hb[] = {{&f.x6, M * 6 * C}, {&f.hid6, M * 6 * HID}, {&f.zop6, B * m->LZ * 6 * PATCH_K}, {&f.map6[0], B * P2 * 6 * C},
-                                                {&f.map6[1], 3 * B * P2 * 6 * HEAD_CH[1]}, {&f.map6[2], 3 * B * P2 * 6 * HEAD_CH[2]},
-                                                {&f.map6[3], 3 * B * P2 * 6 * HEAD_CH[3]}};
-    const std::pair<Buf<float>*, size_t> fb[] = {{&f.hid32, M * HID}, {&f.feat32, B * LX * C}, {&f.tmp32, B * LX * 3 * HEAD_CH[1]}};
-    hipError_t e = hipSuccess;
-    size_t bytes = 0;
-    for (const auto& w : hb) { bytes += w.second * 2; if (e == hipSuccess) e = w.first->alloc(w.second); }
-    for (const auto& w : fb) { bytes += w.second * 4; if (e == hipSuccess) e = w.first->alloc(w.second); }
-    for (Buf<bf16>& b : f.map6)      // zero borders; the kernels write interiors only
-        if (e == hipSuccess) e = hipMemset(b.p, 0, b.n * 2);
     using namespace vbg;
-    const struct { const void* kernel; int lds; } dynamic_lds[] = {
-        {kernel_ptr(gemm_kernel<256, 256, 2, 4, A_PLAIN, EPI_F32>), lds_bytes<256, 256>()},
-        {kernel_ptr(gemm_kernel<128, 64, 8, 1, A_PLAIN, EPI_F32>), lds_bytes<128, 64>()},
-        {kernel_ptr(gemm_kernel<256, 64, 8, 1, A_CONV, EPI_F32>), lds_bytes<256, 64>()},
-        {kernel_ptr(gemm_kernel<128, 64, 8, 1, A_CONV, EPI_F32>), lds_bytes<128, 64>()}};
-    for (const auto& k : dynamic_lds)
-        if (e == hipSuccess) e = hipFuncSetAttribute(k.kernel, hipFuncAttributeMaxDynamicSharedMemorySize, k.lds);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        for (const auto& w : hb) w.first->release();
-        for (const auto& w : fb) w.first->release();
-        return E.fail(VT_ERR_HIP, "fp32 mode: workspaces of " + std::to_string(bytes) + " bytes: " + hipGetErrorString(e));
-    }
+    size_t bytes = 0;
+    const hipError_t e = alloc_workspaces(      // the maps: zero borders; the kernels write interiors only
+        {{f.x6, M * 6 * C}, {f.hid6, M * 6 * HID}, {f.zop6, B * m->LZ * 6 * PATCH_K}, {f.map6[0], B * P2 * 6 * C, true},
+         {f.map6[1], 3 * B * P2 * 6 * HEAD_CH[1], true}, {f.map6[2], 3 * B * P2 * 6 * HEAD_CH[2], true}, {f.map6[3], 3 * B * P2 * 6 * HEAD_CH[3], true},
+         {f.hid32, M * HID}, {f.feat32, B * LX * C}, {f.tmp32, B * LX * 3 * HEAD_CH[1]}},
+        {{kernel_ptr(gemm_kernel<256, 256, 2, 4, A_PLAIN, EPI_F32>), lds_bytes<256, 256>()},
+         {kernel_ptr(gemm_kernel<128, 64, 8, 1, A_PLAIN, EPI_F32>), lds_bytes<128, 64>()},
+         {kernel_ptr(gemm_kernel<256, 64, 8, 1, A_CONV, EPI_F32>), lds_bytes<256, 64>()},
+         {kernel_ptr(gemm_kernel<128, 64, 8, 1, A_CONV, EPI_F32>), lds_bytes<128, 64>()}},
+        &bytes);
+    if (e != hipSuccess) return E.fail(VT_ERR_HIP, "fp32 mode: workspaces of " + std::to_string(bytes) + " bytes: " + hipGetErrorString(e));
     f.ws = true;
     return VT_OK;
 }
 
+// The bf16 image.  Its operand is the CENTRED byte p - ctr (vbm::patchify_u8_kernel, ctr = 128): b'[n] + ctr wsum[n] is the bias.  What the
+// bf16 rounding of W' then multiplies is p - 128 instead of p: uncentred, the rounding errors of a row of W' meet a common mode of ~2 sigma
+// of the patch and the tokens leave the 3.2e-3 the stage is held to (3.3e-3 on noise patches; centred 1.7e-3; the fp32 route 2.3-2.6e-3:
+// NOTES R7-1, tests/test_vitb_track_host.py).  Compensating with the ROUNDED weights instead is algebraically the uncentred form again.
+// The centring table of the search rows (Args::cm) follows the bias.
 int fold_patch_u8(VbModel* m, const Err& E) {
     const int C = m->C;
-    std::vector<float> w((size_t)C * PATCH_K), b(C);
-    double k255[3], ms[3], bsum = 0;
-    for (int c = 0; c < 3; ++c) { k255[c] = 1.0 / (255.0 * (double)m->norm_std[c]); ms[c] = (double)m->norm_mean[c] / (double)m->norm_std[c]; }
+    const PatchFold f = fold_preprocessor(m);
+    std::vector<float> b(C);
+    double bsum = 0;
     for (int n = 0; n < C; ++n) {
-        const float* row = m->h_wpatch.data() + (size_t)n * PATCH_K;
-        double sm = 0, sw = 0;
-        for (int k = 0; k < PATCH_K; ++k) {
-            const int c = k >> 8;
-            const double wd = (double)row[k] * k255[c];
-            sm += (double)row[k] * ms[c];
-            sw += wd;
-            w[(size_t)n * PATCH_K + k] = (float)wd;
-        }
-        const double bd = (double)m->h_bpatch[n] - sm + (double)m->u8_centre * sw;
+        const double bd = f.bias[n] + (double)m->u8_centre * f.wsum[n];
         b[n] = (float)bd;
         bsum += bd;
     }
     int rc;
-    if ((rc = upload_bf16(m->wpatch_u8, w, E, tile_pad(C, PATCH_K))) || (rc = upload_f32(m->bpatch_u8, b.data(), b.size(), E))) return rc;
+    if ((rc = upload_bf16(m->wpatch_u8, f.w, E, tile_pad(C, PATCH_K))) || (rc = upload_f32(m->bpatch_u8, b.data(), b.size(), E))) return rc;
     if ((rc = upload_centring(m->cpos_u8, m->h_pos, C, bsum, E))) return rc;
     return m->f32.weights ? build_f32_patch_u8(m, E) : VT_OK;      // (vt_set_normalization in fp32 mode: the mode's image follows)
 }
@@ -552,16 +607,23 @@ static std::string got_config(const vt_config* cfg, bool depth) {
            " stride=" + std::to_string(cfg->stride) + " template=" + std::to_string(cfg->template_size) + " search=" + std::to_string(cfg->search_size);
 }
 
+// whether a configuration is model point p at one of the two geometries (depth: within the point's range too)
+static bool admits(const ModelPoint& p, const vt_config* cfg, bool depth) {
+    const bool g256 = cfg->template_size == 128 && cfg->search_size == 256, g384 = cfg->template_size == 192 && cfg->search_size == 384;
+    return cfg->channels == p.C && cfg->heads == p.heads && cfg->head_channels == HW && cfg->stride == 16 && (g256 || g384) &&
+           (!depth || (cfg->depth >= 1 && cfg->depth <= p.max_depth));
+}
+
 int create(const vt_config* cfg, VbModel** out, std::string* err) {
     const Err E{err};
-    const bool g256 = cfg->template_size == 128 && cfg->search_size == 256, g384 = cfg->template_size == 192 && cfg->search_size == 384;
     const bool large = cfg->channels == C_LARGE;
-    if (large) {       // vt_create sends only the exact ViT-Large tuple here; the depth is what is left to refuse
-        if (cfg->heads != HEADS_LARGE || cfg->head_channels != HW || cfg->stride != 16 || !(g256 || g384) || cfg->depth < 1 || cfg->depth > 24)
-            return E.fail(VT_ERR_ARG, "unsupported ViT-Large configuration: this build implements CHANNELS=1024, HEADS=16, HEAD.NUM_CHANNELS=256, "
-                                      "STRIDE=16, 1 <= depth <= 24, template 128 / search 256 or template 192 / search 384; " + got_config(cfg, true));
-    } else if (cfg->channels != C_BASE || cfg->heads != HEADS_BASE || cfg->head_channels != HW || cfg->stride != 16 || !(g256 || g384))
-        return E.fail(VT_ERR_ARG, "unsupported ViT-Base configuration: this build implements CHANNELS=768, HEADS=12, "
+    const ModelPoint& p = POINTS[large ? 1 : 0];
+    const std::string unsupported = std::string("unsupported ") + p.name + " configuration: this build implements ";
+    if (large && !admits(p, cfg, true))       // vt_create sends only the exact ViT-Large tuple here; the depth is what is left to refuse
+        return E.fail(VT_ERR_ARG, unsupported + "CHANNELS=1024, HEADS=16, HEAD.NUM_CHANNELS=256, "
+                                  "STRIDE=16, 1 <= depth <= 24, template 128 / search 256 or template 192 / search 384; " + got_config(cfg, true));
+    if (!large && !admits(p, cfg, false))
+        return E.fail(VT_ERR_ARG, unsupported + "CHANNELS=768, HEADS=12, "
                                   "HEAD.NUM_CHANNELS=256, STRIDE=16, template 128 / search 256 (OSTrack-256) or template 192 / search 384 "
                                   "(OSTrack-384); " + got_config(cfg, false));
     return build_model(cfg, out, E);
@@ -569,11 +631,9 @@ int create(const vt_config* cfg, VbModel** out, std::string* err) {
 
 int create_vit(const vt_config* cfg, VbModel** out, std::string* err) {
     const Err E{err};
-    const bool base = cfg->channels == C_BASE && cfg->heads == HEADS_BASE, large = cfg->channels == C_LARGE && cfg->heads == HEADS_LARGE;
-    if (base || large) return create(cfg, out, err);      // the two tuples vt_create knows: its checks, its messages
-    const bool g256 = cfg->template_size == 128 && cfg->search_size == 256, g384 = cfg->template_size == 192 && cfg->search_size == 384;
-    const bool small = (cfg->channels == C_SMALL && cfg->heads == HEADS_SMALL) || (cfg->channels == C_TINY && cfg->heads == HEADS_TINY);
-    if (!small || cfg->head_channels != HW || cfg->stride != 16 || !(g256 || g384) || cfg->depth < 1 || cfg->depth > 12)
+    const ModelPoint* p = model_point(cfg->channels);
+    if (p && p->vt_create && cfg->heads == p->heads) return create(cfg, out, err);      // the two tuples vt_create knows: its checks, its messages
+    if (!p || p->vt_create || !admits(*p, cfg, true))
         return E.fail(VT_ERR_ARG, "unsupported ViT configuration: this build implements (CHANNELS, HEADS) = (192, 3), (384, 6) with 1 <= depth <= 12, "
                                   "(768, 12), (1024, 16) with 1 <= depth <= 24, HEAD.NUM_CHANNELS=256, STRIDE=16, template 128 / search 256 or "
                                   "template 192 / search 384; " + got_config(cfg, true));
@@ -615,60 +675,46 @@ static int build_model(const vt_config* cfg, VbModel** out, const Err& E) {
     m->attn_stream = env_int("VB_ATTN_STREAM", 0) != 0;
     m->ce_plain = env_int("VB_CE_SCORE_PLAIN", 0) != 0;
     const size_t B = (size_t)cfg->max_batch, M = B * L, P2 = (size_t)(F + 2) * (F + 2);
-    hipError_t e = hipSuccess;
     // the streaming attention kernel's last key chunk reads up to PAD_TOKENS rows (qk) / elements (vt) past a frame's last token: the
     // workspaces carry that tail so the reads stay inside them, and are zero-filled ONCE, here.  Nothing read there is used: the kernel
     // masks those keys' scores and zeroes their V^T columns in registers (vb_attn_stream.h)
     constexpr size_t PAD = vbs::PAD_TOKENS;
-    auto alloc_all = [&](auto list) {
-        for (const auto& w : list)
-            if (e == hipSuccess) e = w.first->alloc(w.second);
-    };
-    alloc_all(std::initializer_list<std::pair<Buf<bf16>*, size_t>>{
-        {&m->xn, M * C}, {&m->qk, (M + PAD) * 2 * C}, {&m->vt, M * C + PAD}, {&m->ao, M * C}, {&m->hid, M * HID}, {&m->map[0], B * P2 * (size_t)C},
-        {&m->map[1], 3 * B * P2 * HEAD_CH[1]}, {&m->map[2], 3 * B * P2 * HEAD_CH[2]}, {&m->map[3], 3 * B * P2 * HEAD_CH[3]},
-        {&m->t4, 3 * B * LX * HEAD_CH[4]}, {&m->zop, B * LZ * PATCH_K}});
-    alloc_all(std::initializer_list<std::pair<Buf<float>*, size_t>>{{&m->resid, M * C}, {&m->rstd, M}, {&m->rmean, M}});
-    alloc_all(std::initializer_list<std::pair<Buf<vbg::f2>*, size_t>>{{&m->stats, (size_t)m->stat_p() * M}});
-    // zero borders of the padded maps (kernels only ever write interiors), and the two tails
-    Buf<bf16>* const zeroed[] = {&m->map[0], &m->map[1], &m->map[2], &m->map[3], &m->qk, &m->vt};
-    for (Buf<bf16>* b : zeroed)
-        if (e == hipSuccess) e = hipMemset(b->p, 0, b->n * 2);
     using namespace vbg;
-    const struct { const void* kernel; int lds; } dynamic_lds[] = {
-        {kernel_ptr(gemm_kernel<256, 256, 2, 4, A_PLAIN, EPI_PATCH>), lds_bytes<256, 256>()},
-        {kernel_ptr(gemm_kernel<256, 256, 2, 4, A_PLAIN, EPI_PATCH_ROWS>), lds_bytes<256, 256>()},
-        {kernel_ptr(gemm_kernel<256, 256, 2, 4, A_PLAIN, EPI_PATCH_ROWS_N>), lds_bytes<256, 256>()},
-        {kernel_ptr(gemm_kernel<256, 256, 2, 4, A_PLAIN, EPI_BF16>), lds_bytes<256, 256>()},
-        {kernel_ptr(gemm_kernel<256, 256, 2, 4, A_PLAIN, EPI_VT>), lds_bytes<256, 256>()},
-        {kernel_ptr(gemm_kernel<256, 256, 2, 4, A_PLAIN, EPI_RESID>), lds_bytes<256, 256>()},
-        {kernel_ptr(gemm_kernel<256, 256, 2, 4, A_PLAIN, EPI_GELU>), lds_bytes<256, 256>()},
-        {kernel_ptr(gemm_kernel<256, 256, 2, 4, A_CONV, EPI_CONV>), lds_bytes<256, 256>()},
-        {kernel_ptr(gemm_kernel<256, 64, 8, 1, A_CONV, EPI_CONV>), lds_bytes<256, 64>()},
-        {kernel_ptr(gemm_kernel<128, 64, 8, 1, A_PLAIN, EPI_PATCH>), lds_bytes<128, 64>()},
-        {kernel_ptr(gemm_kernel<128, 64, 8, 1, A_PLAIN, EPI_PATCH_ROWS>), lds_bytes<128, 64>()},
-        {kernel_ptr(gemm_kernel<128, 64, 8, 1, A_PLAIN, EPI_PATCH_ROWS_N>), lds_bytes<128, 64>()},
-        {kernel_ptr(gemm_kernel<128, 64, 8, 1, A_PLAIN, EPI_BF16>), lds_bytes<128, 64>()},
-        {kernel_ptr(gemm_kernel<128, 64, 8, 1, A_PLAIN, EPI_RESID>), lds_bytes<128, 64>()},
-        {kernel_ptr(gemm_kernel<128, 64, 8, 1, A_PLAIN, EPI_GELU>), lds_bytes<128, 64>()},
-        {kernel_ptr(gemm_kernel<128, 64, 8, 1, A_CONV, EPI_CONV>), lds_bytes<128, 64>()},
-        {kernel_ptr(vba::attn_kernel<L256, HD>), vba::Geo<L256, HD>::LDS_BYTES},
-        {kernel_ptr(vbs::attn_stream_kernel<L256>), vbs::LDS_BYTES},
-        {kernel_ptr(vbs::attn_stream_kernel<L384>), vbs::LDS_BYTES},
-        {kernel_ptr(vbs::attn_stream_masked_kernel<L256>), vbs::LDS_BYTES},
-        {kernel_ptr(vbs::attn_stream_masked_kernel<L384>), vbs::LDS_BYTES},
-        {kernel_ptr(vbs::attn_stream_rt_kernel), vbs::LDS_BYTES},
-        {kernel_ptr(vbc::ce_score_all_rt_kernel), 16 * L384 * 4},
-        {kernel_ptr(vbq::qkv_attn_kernel), vbq::LDS_BYTES},
-        {kernel_ptr(vbq::qkv_attn_wide_kernel<C_LARGE>), vbq::LDS_BYTES},
-        {kernel_ptr(vbq::qkv_attn_wide_kernel<C_SMALL>), vbq::LDS_BYTES},
-        {kernel_ptr(vbq::qkv_attn_wide_kernel<C_TINY>), vbq::LDS_BYTES},
-        {kernel_ptr(gemm_kernel<256, 256, 2, 4, A_PLAIN | A_ANYK, EPI_BF16>), lds_bytes<256, 256>()},
-        {kernel_ptr(gemm_kernel<256, 256, 2, 4, A_PLAIN | A_ANYK, EPI_VT>), lds_bytes<256, 256>()},
-        {kernel_ptr(gemm_kernel<256, 256, 2, 4, A_PLAIN | A_ANYK, EPI_RESID>), lds_bytes<256, 256>()},
-        {kernel_ptr(gemm_kernel<256, 256, 2, 4, A_PLAIN | A_ANYK, EPI_GELU>), lds_bytes<256, 256>()}};
-    for (const auto& k : dynamic_lds)
-        if (e == hipSuccess) e = hipFuncSetAttribute(k.kernel, hipFuncAttributeMaxDynamicSharedMemorySize, k.lds);
+    const hipError_t e = alloc_workspaces(      // zero-filled: the borders of the padded maps (kernels only ever write interiors), and the two tails
+        {{m->xn, M * C}, {m->qk, (M + PAD) * 2 * C, true}, {m->vt, M * C + PAD, true}, {m->ao, M * C}, {m->hid, M * HID}, {m->map[0], B * P2 * (size_t)C, true},
+         {m->map[1], 3 * B * P2 * HEAD_CH[1], true}, {m->map[2], 3 * B * P2 * HEAD_CH[2], true}, {m->map[3], 3 * B * P2 * HEAD_CH[3], true},
+         {m->t4, 3 * B * LX * HEAD_CH[4]}, {m->zop, B * LZ * PATCH_K}, {m->resid, M * C}, {m->rstd, M}, {m->rmean, M}, {m->stats, (size_t)m->stat_p() * M}},
+        {{kernel_ptr(gemm_kernel<256, 256, 2, 4, A_PLAIN, EPI_PATCH>), lds_bytes<256, 256>()},
+         {kernel_ptr(gemm_kernel<256, 256, 2, 4, A_PLAIN, EPI_PATCH_ROWS>), lds_bytes<256, 256>()},
+         {kernel_ptr(gemm_kernel<256, 256, 2, 4, A_PLAIN, EPI_PATCH_ROWS_N>), lds_bytes<256, 256>()},
+         {kernel_ptr(gemm_kernel<256, 256, 2, 4, A_PLAIN, EPI_BF16>), lds_bytes<256, 256>()},
+         {kernel_ptr(gemm_kernel<256, 256, 2, 4, A_PLAIN, EPI_VT>), lds_bytes<256, 256>()},
+         {kernel_ptr(gemm_kernel<256, 256, 2, 4, A_PLAIN, EPI_RESID>), lds_bytes<256, 256>()},
+         {kernel_ptr(gemm_kernel<256, 256, 2, 4, A_PLAIN, EPI_GELU>), lds_bytes<256, 256>()},
+         {kernel_ptr(gemm_kernel<256, 256, 2, 4, A_CONV, EPI_CONV>), lds_bytes<256, 256>()},
+         {kernel_ptr(gemm_kernel<256, 64, 8, 1, A_CONV, EPI_CONV>), lds_bytes<256, 64>()},
+         {kernel_ptr(gemm_kernel<128, 64, 8, 1, A_PLAIN, EPI_PATCH>), lds_bytes<128, 64>()},
+         {kernel_ptr(gemm_kernel<128, 64, 8, 1, A_PLAIN, EPI_PATCH_ROWS>), lds_bytes<128, 64>()},
+         {kernel_ptr(gemm_kernel<128, 64, 8, 1, A_PLAIN, EPI_PATCH_ROWS_N>), lds_bytes<128, 64>()},
+         {kernel_ptr(gemm_kernel<128, 64, 8, 1, A_PLAIN, EPI_BF16>), lds_bytes<128, 64>()},
+         {kernel_ptr(gemm_kernel<128, 64, 8, 1, A_PLAIN, EPI_RESID>), lds_bytes<128, 64>()},
+         {kernel_ptr(gemm_kernel<128, 64, 8, 1, A_PLAIN, EPI_GELU>), lds_bytes<128, 64>()},
+         {kernel_ptr(gemm_kernel<128, 64, 8, 1, A_CONV, EPI_CONV>), lds_bytes<128, 64>()},
+         {kernel_ptr(vba::attn_kernel<L256, HD>), vba::Geo<L256, HD>::LDS_BYTES},
+         {kernel_ptr(vbs::attn_stream_kernel<L256>), vbs::LDS_BYTES},
+         {kernel_ptr(vbs::attn_stream_kernel<L384>), vbs::LDS_BYTES},
+         {kernel_ptr(vbs::attn_stream_masked_kernel<L256>), vbs::LDS_BYTES},
+         {kernel_ptr(vbs::attn_stream_masked_kernel<L384>), vbs::LDS_BYTES},
+         {kernel_ptr(vbs::attn_stream_rt_kernel), vbs::LDS_BYTES},
+         {kernel_ptr(vbc::ce_score_all_rt_kernel), 16 * L384 * 4},
+         {kernel_ptr(vbq::qkv_attn_kernel), vbq::LDS_BYTES},
+         {kernel_ptr(vbq::qkv_attn_wide_kernel<C_LARGE>), vbq::LDS_BYTES},
+         {kernel_ptr(vbq::qkv_attn_wide_kernel<C_SMALL>), vbq::LDS_BYTES},
+         {kernel_ptr(vbq::qkv_attn_wide_kernel<C_TINY>), vbq::LDS_BYTES},
+         {kernel_ptr(gemm_kernel<256, 256, 2, 4, A_PLAIN | A_ANYK, EPI_BF16>), lds_bytes<256, 256>()},
+         {kernel_ptr(gemm_kernel<256, 256, 2, 4, A_PLAIN | A_ANYK, EPI_VT>), lds_bytes<256, 256>()},
+         {kernel_ptr(gemm_kernel<256, 256, 2, 4, A_PLAIN | A_ANYK, EPI_RESID>), lds_bytes<256, 256>()},
+         {kernel_ptr(gemm_kernel<256, 256, 2, 4, A_PLAIN | A_ANYK, EPI_GELU>), lds_bytes<256, 256>()}});
     if (e != hipSuccess) {
         destroy(m);
         return E.fail(VT_ERR_HIP, std::string("ViT workspace: ") + hipGetErrorString(e));
@@ -826,10 +872,7 @@ int load_weights(VbModel* m, const TensorMap& tm, std::string* err) {
     const char* towers[3] = {"ctr", "offset", "size"};
     for (int li = 0; li < 4; ++li) {
         const int cin = m->head_ch(li), cout = HEAD_CH[li + 1], K = 9 * cin;
-        // conv1: towers along N (K = 9 x the model's width).  conv2 (N = 128 per tower, K = 2304) runs on the 256 x 256 software-pipelined tile, one group per tower, with
-        // its weight rows zero-padded to 256 (half of every MFMA column block is padding, and it still beats the two-buffer 256 x 64 loop:
-        // 268 -> ~180 us, round 5); conv3 / conv4 keep the narrow tile (BN = 64: rows padded to 64)
-        const int rows = li == 0 ? cout : (li == 1 ? 256 : (cout < 64 ? 64 : cout));
+        const int rows = head_rows(li, cout);
         std::vector<float> w((size_t)3 * rows * K, 0.f), bias((size_t)3 * cout);
         for (int t = 0; t < 3; ++t) {
             const std::string cn = std::string("box_head.conv") + std::to_string(li + 1) + "_" + towers[t];
@@ -905,6 +948,17 @@ int set_precision(VbModel* m, int prec, std::string* err) {
 namespace {
 // the bytes of an expanded operand one GEMM launch of the mode may span: below the 4 GiB its 32-bit byte offsets reach
 constexpr unsigned long long F32_OPERAND_BYTES = (1ull << 32) - (1ull << 20);
+// The GEMMs address an operand by 32-bit offsets from its base (vb_gemm.h), and an expanded operand of a whole batch can pass 4 GiB (fc2's:
+// rows x 6 HID x 2 bytes -- 9.1 GB for ViT-Large at 192 / 384 with 256 frames): a GEMM of the mode runs as launches of at most `most` units
+// (rows or frames), each with its operand, residual and output based at its first unit.  body(first, count) is one launch.  Every output
+// element keeps its whole sum in one workgroup in the same order wherever its tile lies, so the chunking changes no bit (tests: B = 66
+// against frames one at a time).
+template <typename Body>
+int for_chunks(int units, int most, Body&& body) {
+    for (int u0 = 0; u0 < units; u0 += most)
+        if (int rc = body(u0, std::min(most, units - u0))) return rc;
+    return VT_OK;
+}
 // what an fp32-mode entry addresses for a frame slice (SliceView holds the residual stream and the slice itself)
 struct SliceF32 {
     bf16 *x6, *hid6, *zop6, *map6[4];
@@ -920,8 +974,20 @@ struct SliceF32 {
     bf16* patch_operand(const VbModel* m) const { return m->C >= PATCH_K ? x6 : hid6; }
 };
 
-int patchify_split(const float* img, int T, int B, bf16* P, hipStream_t st, const Err& E) {
-    hipLaunchKernelGGL(vbf::patchify_split_kernel, dim3(grid256((size_t)B * (T / 16) * (T / 16) * 96)), dim3(256), 0, st, img, P, B, T);
+// one token kind's rows of an fp32 crop batch (B, 3, T, T) as a dense operand: bf16 [rows][PATCH_K] (patchify_kernel with no template, Tz = 0,
+// walks the crops alone) or, in fp32 mode, expanded [rows][6 PATCH_K]
+int patchify_crop(const VbModel* m, const float* img, int T, int B, bf16* P, hipStream_t st, const Err& E) {
+    const dim3 grid(grid256((size_t)B * (T / 16) * (T / 16) * 96));
+    if (m->precision == VT_PRECISION_FP32) hipLaunchKernelGGL(vbf::patchify_split_kernel, grid, dim3(256), 0, st, img, P, B, T);
+    else hipLaunchKernelGGL(vbm::patchify_kernel, grid, dim3(256), 0, st, nullptr, img, P, B, 0, T);
+    VB_HIP(hipGetLastError());
+    return VT_OK;
+}
+// the search rows from the uint8 patch: bf16 [rows][PATCH_K] of centred bytes, or [rows][3 PATCH_K] of the bytes themselves
+int patchify_u8(const VbModel* m, const unsigned char* xu8, int B, bf16* P, hipStream_t st, const Err& E) {
+    const dim3 grid(grid256((size_t)B * m->LX * 16));
+    if (m->precision == VT_PRECISION_FP32) hipLaunchKernelGGL(vbf::patchify_u8_split_kernel, grid, dim3(256), 0, st, xu8, P, B, m->TX);
+    else hipLaunchKernelGGL(vbm::patchify_u8_kernel, grid, dim3(256), 0, st, xu8, P, B, m->TX, m->u8_centre);
     VB_HIP(hipGetLastError());
     return VT_OK;
 }
@@ -942,83 +1008,104 @@ int run_map_split(const float* src, size_t src_tower, int ld, bf16* dst, size_t 
     VB_HIP(hipGetLastError());
     return VT_OK;
 }
-}  // namespace
 
-// vb::stem_rows in fp32 mode: the same two GEMMs on expanded operands (six terms from an fp32 crop, three from a uint8 patch), no bf16
-// copy and no statistics behind them.  vb::stem takes this route too (Z_GIVEN): one arithmetic for the cached and the given template.
-static int stem_rows_f32(VbModel* m, ZSrc zsrc, const float* z, const float* x, const unsigned char* xu8, int B, hipStream_t st, const SliceView& v,
-                         const Err& E) {
-    int rc;
-    const int L = m->L, LZ = m->LZ, LX = m->LX, C = m->C, K6 = 6 * PATCH_K;
-    const SliceF32 w(m, v);
-    bf16* const op = w.patch_operand(m);
-    bf16* const xop = op + (size_t)B * LZ * K6;
-    const bf16* zop = w.zop6;
-    if (zsrc == Z_GIVEN) {
-        if ((rc = patchify_split(z, m->TZ, B, op, st, E))) return rc;
-        zop = op;
+// The stem on dense operands of one token kind each: the z GEMM, then the x GEMM, onto the token rows of the residual stream.  What the
+// two precisions differ in:
+struct StemRoute {
+    bf16 *zop_given, *xop;         // where a given template's / the search crops' operand rows are written
+    const bf16* zop_cached;        // vt_set_template's rows
+    int Kz, Kx;                    // operand depth: PATCH_K in bf16; six terms from an fp32 crop, three from a uint8 patch in fp32 mode
+    const bf16 *Wz, *Wx;
+    const float *bz, *bx;
+    const float *cmz, *cmx;        // the rows' centring constants (folded LayerNorm, VB_LN_CENTER), or nullptr
+    bool stats;                    // the GEMMs leave the rows' bf16 copy and statistics, ln_finalize follows (folded LayerNorm)
+    bool chunked;                  // launches of whole frames below F32_OPERAND_BYTES (no bf16 copy and no statistics behind them)
+};
+StemRoute stem_route(const VbModel* m, const SliceView& v, int B, bool u8) {
+    const size_t zrows = (size_t)B * m->LZ;
+    StemRoute r{};
+    r.bz = m->bpatch.p;
+    if (m->precision == VT_PRECISION_FP32) {
+        const SliceF32 w(m, v);
+        const ModeF32& f = m->f32;
+        r.zop_given = w.patch_operand(m);
+        r.xop = r.zop_given + zrows * 6 * PATCH_K;
+        r.zop_cached = w.zop6;
+        r.Kz = 6 * PATCH_K; r.Kx = u8 ? 3 * PATCH_K : 6 * PATCH_K;
+        r.Wz = f.wpatch.p; r.Wx = u8 ? f.wpatch_u8.p : f.wpatch.p;
+        r.bx = u8 ? f.bpatch_u8.p : m->bpatch.p;
+        r.chunked = true;
+        return r;
     }
-    if (xu8) {
-        hipLaunchKernelGGL(vbf::patchify_u8_split_kernel, dim3(grid256((size_t)B * LX * 16)), dim3(256), 0, st, xu8, xop, B, m->TX);
-        VB_HIP(hipGetLastError());
-    } else if ((rc = patchify_split(x, m->TX, B, xop, st, E))) return rc;
+    // B * LX dense rows inside the slice's B * L (as vb::stem's operand); in the hidden rows (narrow models) behind the B * LZ rows of a given
+    // template.  A given template goes to the hidden rows, not through the cache: such a call leaves vt_set_template's rows alone
+    r.zop_given = v.hid;
+    r.xop = patch_operand(m, v) + (m->C >= PATCH_K ? (size_t)0 : zrows * PATCH_K);
+    r.zop_cached = m->zop.p + v.f0 * m->LZ * PATCH_K;
+    r.Kz = r.Kx = PATCH_K;
+    r.Wz = m->wpatch.p; r.Wx = u8 ? m->wpatch_u8.p : m->wpatch.p;
+    r.bx = u8 ? m->bpatch_u8.p : m->bpatch.p;
+    if (m->fold && m->center) { r.cmz = m->cpos.p; r.cmx = u8 ? m->cpos_u8.p : m->cpos.p; }
+    r.stats = m->fold;
+    return r;
+}
+
+int run_stem_rows(VbModel* m, ZSrc zsrc, const float* z, const float* x, const unsigned char* xu8, int B, hipStream_t st, const SliceView& v, const Err& E) {
+    int rc;
+    const int L = m->L, LZ = m->LZ, LX = m->LX, C = m->C;
+    const StemRoute r = stem_route(m, v, B, xu8 != nullptr);
+    if (zsrc == Z_GIVEN && (rc = patchify_crop(m, z, m->TZ, B, r.zop_given, st, E))) return rc;
+    if ((rc = xu8 ? patchify_u8(m, xu8, B, r.xop, st, E) : patchify_crop(m, x, m->TX, B, r.xop, st, E))) return rc;
     vbg::Args a{};
     a.resid = v.resid; a.pos = m->pos.p; a.N = C; a.L = L;
-    // whole frames per launch, as many as keep the launch's operand below F32_OPERAND_BYTES (blocks_f32: chunk_rows)
+    if (r.stats) v.stats_of(a);
+    // operand rows -> (frame, token): a shift at 64 / 256 rows per frame, the rows themselves at 144 / 576 (EPI_PATCH_ROWS_N)
     auto rows_gemm = [&](const vbg::Args& whole, int rows, int shift) {
-        const int fmax = std::max(1, (int)(F32_OPERAND_BYTES / ((unsigned long long)rows * whole.K * 2)));
-        for (int f0 = 0; f0 < B; f0 += fmax) {
+        const int fmax = r.chunked ? std::max(1, (int)(F32_OPERAND_BYTES / ((unsigned long long)rows * whole.K * 2))) : B;
+        return for_chunks(B, fmax, [&](int f0, int nf) {
             vbg::Args g = whole;
-            g.X = whole.X + (size_t)f0 * rows * whole.K; g.resid = whole.resid + (size_t)f0 * L * C; g.M = std::min(fmax, B - f0) * rows;
+            g.X = whole.X + (size_t)f0 * rows * whole.K; g.resid = whole.resid + (size_t)f0 * L * C; g.M = nf * rows;
             g.row_shift = shift < 0 ? rows : shift;
-            if (int r = shift < 0 ? launch_tile<vbg::A_PLAIN, vbg::EPI_PATCH_ROWS_N>(m, g, 1, st, E, v.cus)
-                                  : launch_tile<vbg::A_PLAIN, vbg::EPI_PATCH_ROWS>(m, g, 1, st, E, v.cus)) return r;
-        }
-        return (int)VT_OK;
+            return shift < 0 ? launch_tile<vbg::A_PLAIN, vbg::EPI_PATCH_ROWS_N>(m, g, 1, st, E, v.cus)
+                             : launch_tile<vbg::A_PLAIN, vbg::EPI_PATCH_ROWS>(m, g, 1, st, E, v.cus);
+        });
     };
     if (zsrc != Z_NONE) {
         vbg::Args az = a;
-        az.X = zop; az.W = m->f32.wpatch.p; az.bias = m->bpatch.p; az.M = B * LZ; az.K = K6; az.row_o0 = 0;
+        az.X = zsrc == Z_GIVEN ? r.zop_given : r.zop_cached; az.W = r.Wz; az.bias = r.bz; az.cm = r.cmz; az.K = r.Kz; az.row_o0 = 0;
         if ((rc = rows_gemm(az, LZ, m->zshift))) return rc;
     }
-    a.X = xop; a.M = B * LX; a.row_o0 = LZ;
-    a.W = xu8 ? m->f32.wpatch_u8.p : m->f32.wpatch.p;
-    a.bias = xu8 ? m->f32.bpatch_u8.p : m->bpatch.p;
-    a.K = xu8 ? 3 * PATCH_K : K6;
-    return rows_gemm(a, LX, m->xshift);
+    a.X = r.xop; a.W = r.Wx; a.bias = r.bx; a.cm = r.cmx; a.K = r.Kx; a.row_o0 = LZ;
+    if ((rc = rows_gemm(a, LX, m->xshift))) return rc;
+    return r.stats ? run_finalize(m, v, B * L, st, E) : (int)VT_OK;
 }
+}  // namespace
 
 // vb::blocks in fp32 mode: LayerNorm -> expanded operand -> qkv GEMM (f32 rows) -> f32 attention -> expanded operand -> proj (f32
 // read-modify-write) -> LayerNorm -> fc1 (f32 pre-activation) -> exact GELU -> expanded operand -> fc2; the final norm writes f32 features
-static int blocks_f32(VbModel* m, const float* tokens_in, int B, int nblocks, hipStream_t st, float* feat_out, float* resid_out, const SliceView& v,
+static int blocks_f32(VbModel* m, int B, int nblocks, hipStream_t st, float* feat_out, float* resid_out, const SliceView& v,
                       const Err& E) {
     int rc;
     const int C = m->C, HID = m->HID, L = m->L, M = B * L;
     const SliceF32 w(m, v);
-    if (tokens_in && tokens_in != v.resid) VB_HIP(hipMemcpyAsync(v.resid, tokens_in, (size_t)M * C * 4, hipMemcpyDeviceToDevice, st));
     float* const qkv = w.hid32;      // [M][3 C] in the hidden rows, idle until fc1
     const int qtiles = (L + vbf::AQ - 1) / vbf::AQ;
-    // The GEMMs address an operand by 32-bit byte offsets from its base (vb_gemm.h), and an expanded operand of a whole batch can pass 4 GiB
-    // (fc2's: rows x 6 HID x 2 bytes -- 9.1 GB for ViT-Large at 192 / 384 with 256 frames): a GEMM of the mode runs as launches of at most
-    // chunk_rows(K) rows, each with its operand, residual and output based at its first row.  Every output element keeps its whole sum in
-    // one workgroup in the same order wherever its tile lies, so the chunking changes no bit (tests: B = 66 against frames one at a time).
+    // launches of at most chunk_rows(K) rows (for_chunks)
     auto chunk_rows = [](int K) { return std::max(256, (int)((F32_OPERAND_BYTES / ((unsigned long long)K * 2)) / 256 * 256)); };
     auto resid_gemm = [&](const bf16* X, const bf16* W, const float* bias, int K) {
-        for (int r0 = 0, step = chunk_rows(K); r0 < M; r0 += step) {
+        return for_chunks(M, chunk_rows(K), [&](int r0, int rows) {
             vbg::Args p{};
-            p.X = X + (size_t)r0 * K; p.W = W; p.bias = bias; p.resid = v.resid + (size_t)r0 * C; p.M = std::min(step, M - r0); p.N = C; p.K = K;
-            if (int r = launch_tile<vbg::A_PLAIN, vbg::EPI_RESID>(m, p, 1, st, E, v.cus)) return r;
-        }
-        return (int)VT_OK;
+            p.X = X + (size_t)r0 * K; p.W = W; p.bias = bias; p.resid = v.resid + (size_t)r0 * C; p.M = rows; p.N = C; p.K = K;
+            return launch_tile<vbg::A_PLAIN, vbg::EPI_RESID>(m, p, 1, st, E, v.cus);
+        });
     };
     auto f32_gemm = [&](const bf16* W, const float* bias, float* out, int N) {
         const int K = 6 * C;
-        for (int r0 = 0, step = chunk_rows(K); r0 < M; r0 += step) {
+        return for_chunks(M, chunk_rows(K), [&](int r0, int rows) {
             vbg::Args a{};
-            a.X = w.x6 + (size_t)r0 * K; a.W = W; a.bias = bias; a.out = out + (size_t)r0 * N; a.M = std::min(step, M - r0); a.N = N; a.K = K; a.ldo = N; a.rb = 4;
-            if (int r = launch_tile<vbg::A_PLAIN, vbg::EPI_F32>(m, a, 1, st, E, v.cus)) return r;
-        }
-        return (int)VT_OK;
+            a.X = w.x6 + (size_t)r0 * K; a.W = W; a.bias = bias; a.out = out + (size_t)r0 * N; a.M = rows; a.N = N; a.K = K; a.ldo = N; a.rb = 4;
+            return launch_tile<vbg::A_PLAIN, vbg::EPI_F32>(m, a, 1, st, E, v.cus);
+        });
     };
     for (int i = 0; i < nblocks; ++i) {
         const BlockW& b = m->blk[i];
@@ -1052,14 +1139,13 @@ static int head_f32(VbModel* m, const float* feat_in, int B, hipStream_t st, flo
     auto conv = [&](const vbg::Args& whole, int groups) {
         const bool narrow = narrow_pick(m, whole.M, whole.N, groups, v.cus);
         const int fmax = std::max(1, (int)((1ull << 31) / ((unsigned long long)P2 * whole.C) - 1));
-        for (int f0 = 0; f0 < B; f0 += fmax) {
+        return for_chunks(B, fmax, [&](int f0, int nf) {
             vbg::Args a = whole;
-            a.X = whole.X + (size_t)f0 * P2 * whole.C; a.M = std::min(fmax, B - f0) * LX;
+            a.X = whole.X + (size_t)f0 * P2 * whole.C; a.M = nf * LX;
             a.out = static_cast<float*>(whole.out) + (size_t)f0 * LX * whole.ldo;
-            if (int r = narrow ? launch_gemm<128, 64, 8, 1, vbg::A_CONV, vbg::EPI_F32>(a, groups, st, E, v.cus)
-                               : launch_gemm<256, 64, 8, 1, vbg::A_CONV, vbg::EPI_F32>(a, groups, st, E, v.cus)) return r;
-        }
-        return (int)VT_OK;
+            return narrow ? launch_gemm<128, 64, 8, 1, vbg::A_CONV, vbg::EPI_F32>(a, groups, st, E, v.cus)
+                          : launch_gemm<256, 64, 8, 1, vbg::A_CONV, vbg::EPI_F32>(a, groups, st, E, v.cus);
+        });
     };
     if (feat_in && (rc = run_map_split(feat_in, 0, C, w.map6[0], 0, 1, B, F, C, false, st, E))) return rc;
     {   // conv1 of the three towers as one GEMM: N = 3 x 256 dense f32 columns, K = 9 taps x 6 C
@@ -1070,7 +1156,7 @@ static int head_f32(VbModel* m, const float* feat_in, int B, hipStream_t st, flo
         if ((rc = run_map_split(w.tmp32, HEAD_CH[1], 3 * HEAD_CH[1], w.map6[1], (size_t)(Bt * P2 * 6 * HEAD_CH[1]), 3, B, F, HEAD_CH[1], true, st, E))) return rc;
     }
     for (int li = 1; li < 4; ++li) {   // conv2..4: blockIdx.y = tower, f32 outputs [tower][the slice's pixels][cout]
-        const int cin = HEAD_CH[li], cout = HEAD_CH[li + 1], rows = li == 1 ? 256 : (cout < 64 ? 64 : cout);
+        const int cin = HEAD_CH[li], cout = HEAD_CH[li + 1], rows = head_rows(li, cout);
         vbg::Args a{};
         a.X = w.map6[li]; a.W = m->f32.wc[li].p; a.bias = m->bc[li].p; a.out = w.tmp32;
         a.M = M; a.N = cout; a.K = 9 * 6 * cin; a.ldo = cout; a.C = 6 * cin; a.F = F;
@@ -1090,7 +1176,7 @@ int stem(VbModel* m, const float* z, const float* x, int B, hipStream_t st, floa
     if (rc || (rc = check_slice(m, B, sl, E))) return rc;
     if (m->precision == VT_PRECISION_FP32) {
         const SliceView v(m, B, sl);
-        if ((rc = stem_rows_f32(m, Z_GIVEN, z, x, nullptr, B, st, v, E))) return rc;
+        if ((rc = run_stem_rows(m, Z_GIVEN, z, x, nullptr, B, st, v, E))) return rc;      // one arithmetic for the cached and the given template
         if (tokens_out) VB_HIP(hipMemcpyAsync(tokens_out, v.resid, (size_t)B * m->L * m->C * 4, hipMemcpyDeviceToDevice, st));
         return VT_OK;
     }
@@ -1110,13 +1196,6 @@ int stem(VbModel* m, const float* z, const float* x, int B, hipStream_t st, floa
     return VT_OK;
 }
 
-// one token kind's rows of a crop batch as a dense operand: patchify_kernel with no template (Tz = 0) walks (B, 3, T, T) alone
-static int patchify_dense(const float* img, int T, int B, bf16* P, hipStream_t st, const Err& E) {
-    hipLaunchKernelGGL(vbm::patchify_kernel, dim3(grid256((size_t)B * (T / 16) * (T / 16) * 96)), dim3(256), 0, st, nullptr, img, P, B, 0, T);
-    VB_HIP(hipGetLastError());
-    return VT_OK;
-}
-
 int set_template(VbModel* m, const float* z, int n, const int32_t* slots, hipStream_t st, std::string* err) {
     const Err E{err};
     int rc = check(m, n, E);
@@ -1125,11 +1204,10 @@ int set_template(VbModel* m, const float* z, int n, const int32_t* slots, hipStr
     const bool f32 = m->precision == VT_PRECISION_FP32;      // the mode caches the expanded operand rows (vb_f32.h)
     const size_t zrow = (size_t)m->LZ * PATCH_K * (f32 ? 6 : 1);
     bf16* const zop = f32 ? m->f32.zop6.p : m->zop.p;
-    auto dense = [&](const float* img, int nf, bf16* P) { return f32 ? patchify_split(img, TZ, nf, P, st, E) : patchify_dense(img, TZ, nf, P, st, E); };
-    if (!slots) return dense(z, n, zop);
+    if (!slots) return patchify_crop(m, z, TZ, n, zop, st, E);
     for (int i = 0; i < n; ++i) {      // a frame's operand rows depend on that frame alone: straight into place
         if (slots[i] < 0 || slots[i] >= m->maxB) return E.fail(VT_ERR_ARG, "template slot outside the batch");
-        if ((rc = dense(z + (size_t)i * 3 * TZ * TZ, 1, zop + (size_t)slots[i] * zrow))) return rc;
+        if ((rc = patchify_crop(m, z + (size_t)i * 3 * TZ * TZ, TZ, 1, zop + (size_t)slots[i] * zrow, st, E))) return rc;
     }
     return VT_OK;
 }
@@ -1143,45 +1221,7 @@ int stem_rows(VbModel* m, ZSrc zsrc, const float* z, const float* x, const unsig
     if (xu8 && (reinterpret_cast<uintptr_t>(xu8) & 15)) return E.fail(VT_ERR_ARG, "the uint8 patch must be 16-byte aligned on the ViT-Base path");
     const int L = m->L, LZ = m->LZ, LX = m->LX, C = m->C;
     const SliceView v(m, B, sl);
-    if (m->precision == VT_PRECISION_FP32) {
-        if ((rc = stem_rows_f32(m, zsrc, z, x, xu8, B, st, v, E))) return rc;
-        if (x_tokens_out)
-            VB_HIP(hipMemcpy2DAsync(x_tokens_out + (size_t)LZ * C, (size_t)L * C * 4, v.resid + (size_t)LZ * C, (size_t)L * C * 4, (size_t)LX * C * 4, B,
-                                    hipMemcpyDeviceToDevice, st));
-        return VT_OK;
-    }
-    // B * LX dense rows inside the slice's B * L (as vb::stem's operand); in the hidden rows (narrow models) behind the B * LZ rows of a given template
-    bf16* const xop = patch_operand(m, v) + (m->C >= PATCH_K ? (size_t)0 : (size_t)B * LZ * PATCH_K);
-    const bf16* zop = m->zop.p + v.f0 * LZ * PATCH_K;
-    if (zsrc == Z_GIVEN) {      // not through the cache: a call with its own template leaves vt_set_template's rows alone
-        if ((rc = patchify_dense(z, m->TZ, B, v.hid, st, E))) return rc;
-        zop = v.hid;
-    }
-    if (xu8) {
-        hipLaunchKernelGGL(vbm::patchify_u8_kernel, dim3(grid256((size_t)B * LX * 16)), dim3(256), 0, st, xu8, xop, B, m->TX, m->u8_centre);
-        VB_HIP(hipGetLastError());
-    } else if ((rc = patchify_dense(x, m->TX, B, xop, st, E))) return rc;
-    vbg::Args a{};
-    a.resid = v.resid; a.pos = m->pos.p; a.N = C; a.K = PATCH_K; a.L = L;
-    if (m->fold) v.stats_of(a);
-    // operand rows -> (frame, token): a shift at 64 / 256 rows per frame, the rows themselves at 144 / 576 (EPI_PATCH_ROWS_N)
-    auto rows_gemm = [&](vbg::Args& g, int rows, int shift) {
-        g.row_shift = shift < 0 ? rows : shift;
-        return shift < 0 ? launch_tile<vbg::A_PLAIN, vbg::EPI_PATCH_ROWS_N>(m, g, 1, st, E, v.cus)
-                       : launch_tile<vbg::A_PLAIN, vbg::EPI_PATCH_ROWS>(m, g, 1, st, E, v.cus);
-    };
-    if (zsrc != Z_NONE) {
-        vbg::Args az = a;
-        az.X = zop; az.W = m->wpatch.p; az.bias = m->bpatch.p; az.M = B * LZ; az.row_o0 = 0;
-        if (m->fold && m->center) az.cm = m->cpos.p;
-        if ((rc = rows_gemm(az, LZ, m->zshift))) return rc;
-    }
-    a.X = xop; a.M = B * LX; a.row_o0 = LZ;
-    a.W = xu8 ? m->wpatch_u8.p : m->wpatch.p;
-    a.bias = xu8 ? m->bpatch_u8.p : m->bpatch.p;
-    if (m->fold && m->center) a.cm = xu8 ? m->cpos_u8.p : m->cpos.p;
-    if ((rc = rows_gemm(a, LX, m->xshift))) return rc;
-    if (m->fold && (rc = run_finalize(m, v, B * L, st, E))) return rc;
+    if ((rc = run_stem_rows(m, zsrc, z, x, xu8, B, st, v, E))) return rc;
     if (x_tokens_out)
         VB_HIP(hipMemcpy2DAsync(x_tokens_out + (size_t)LZ * C, (size_t)L * C * 4, v.resid + (size_t)LZ * C, (size_t)L * C * 4, (size_t)LX * C * 4, B,
                                 hipMemcpyDeviceToDevice, st));
@@ -1203,11 +1243,8 @@ static int run_attention(const VbModel* m, const SliceView& v, const BlockW& b, 
     if (m->fused_qkv && !m->g384 && !ce) {
         vbq::Args qa{};
         qa.X = v.xn; qa.W = b.wqkv.p; qa.bias = b.bqkv.p; qa.rstd = rstd; qa.out = v.ao; qa.B = B; qa.heads = HEADS;
-        // heads walked together: 6 of 12 measured best at width 768 (vb_qkvattn.h); 16 heads of width 1024 take 4, the divisor whose group of
-        // weight rows (4 x 384 KiB) is nearest to that one's (6 x 288 KiB)
-        static const int hgv = env_int("VB_QA_HGROUP", -1);
-        // (ViT-Small / ViT-Tiny: all 6 / 3 heads of a frame together -- their whole qkv matrix, 864 / 216 KiB, is smaller than one such group)
-        const int hg = hgv < 0 ? (C == C_LARGE ? 4 : 6) : hgv;
+        static const int hgv = env_int("VB_QA_HGROUP", -1);      // heads walked together: the model point's, or the experiment's where it divides
+        const int hg = hgv < 0 ? model_point(C)->hgroup : hgv;
         qa.hgroup = (hg > 0 && HEADS % hg == 0) ? hg : HEADS;
         dispatch_width(C, [&](auto W) {      // width 768: the non-template kernel
             constexpr int CW = decltype(W)::value;
@@ -1369,12 +1406,11 @@ int blocks(VbModel* m, const float* tokens_in, int B, int nblocks, hipStream_t s
     if (rc || (rc = check_slice(m, B, sl, E))) return rc;
     const int C = m->C, HID = m->HID;
     const SliceView v(m, B, sl);
-    if (m->precision == VT_PRECISION_FP32)
-        return blocks_f32(m, tokens_in, B, (nblocks < 0 || nblocks > m->depth) ? m->depth : nblocks, st, feat_out, resid_out, v, E);
-    CeWalk ce(m, v, B);      // ce.M: the slice's residual rows, B frames of L; behind a compacting stage, B frames of ce.Lc
     if (nblocks < 0 || nblocks > m->depth) nblocks = m->depth;
     if (tokens_in && tokens_in != v.resid)
-        VB_HIP(hipMemcpyAsync(v.resid, tokens_in, (size_t)ce.M * C * 4, hipMemcpyDeviceToDevice, st));
+        VB_HIP(hipMemcpyAsync(v.resid, tokens_in, (size_t)B * m->L * C * 4, hipMemcpyDeviceToDevice, st));
+    if (m->precision == VT_PRECISION_FP32) return blocks_f32(m, B, nblocks, st, feat_out, resid_out, v, E);
+    CeWalk ce(m, v, B);      // ce.M: the slice's residual rows, B frames of L; behind a compacting stage, B frames of ce.Lc
     const bool fold = m->fold;
     float* const rstd = fold ? v.rstd : nullptr;
     // folded LayerNorms: a residual stream from outside has no bf16 copy / rstd yet (vb::stem leaves both behind its GEMM)
@@ -1444,7 +1480,7 @@ int head(VbModel* m, const float* feat_in, int B, hipStream_t st, float* score, 
         if ((rc = launch_tile<vbg::A_CONV, vbg::EPI_CONV>(m, a, 1, st, E, v.cus))) return rc;
     }
     for (int li = 1; li < 4; ++li) {   // conv2..4: one launch per layer, blockIdx.y = tower
-        const int cin = HEAD_CH[li], cout = HEAD_CH[li + 1], rows = li == 1 ? 256 : (cout < 64 ? 64 : cout);
+        const int cin = HEAD_CH[li], cout = HEAD_CH[li + 1], rows = head_rows(li, cout);
         vbg::Args a{};
         a.X = v.map[li]; a.W = m->wc[li].p; a.bias = m->bc[li].p; a.out = v.map[li + 1];
         a.M = M; a.N = cout; a.K = 9 * cin; a.ldo = cout; a.C = cin; a.F = F; a.out_padded = li < 3;
